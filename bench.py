@@ -17,6 +17,12 @@ decomposition), SURVEY.md 8(d).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run only sets up, warms up, times the K steps and prints the line (``roofline`` and ``cpu_baseline`` are null).
+``--full`` adds everything else: the dominant kernel's launch timing during the timed steps (plus, for a captured diag fit,
+three launch-by-launch fits behind them), the roofline block built from it and the CPU baselines (``--no-cpu-baseline``
+leaves those out again).  ``--dump-outputs DIR`` writes what ``la.fit()`` handed back after the last timed step as
+``DIR/<name>.npy`` (``_fit_outputs``): the inputs are seeded, so two builds can be compared output for output.
+
 N > 1: one process per GPU, the graph / features / weights replicated.  A batch's SAMPLES are never split for KFAC
 (B factors have cross-sample terms inside a batch), but B = sum over batches and class columns, so the 10 x 40
 (batch, class) units are dealt in balanced runs of 400/N (laplace_gnn_amd.units_of_rank) and one RCCL all-reduce sums
@@ -182,7 +188,11 @@ def _parse():
     ap.add_argument("--structure", default=None, choices=["kron", "diag", "lastlayer"],
                     help="hessian_structure; default kron for arxiv (BASELINE configs[2]), diag for cora (configs[1]), "
                          "last-layer full GGN for products (configs[4])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel launch timing, roofline, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed la.fit() produced as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--no-fit-graph", action="store_true",
                     help="diag workloads: time the launch-by-launch fit instead of the captured graph")
     ap.add_argument("--emulate-world", type=int, default=0,
@@ -224,6 +234,55 @@ def _median(xs):
     xs = sorted(xs)
     n = len(xs)
     return None if n == 0 else (xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2]))
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def _fit_outputs(la):
+    """What ``la.fit()`` hands its caller, as (name, tensor) pairs: the loss and the curvature -- for kron the Kronecker
+    factors and their eigenvalues, otherwise ``la.H`` itself (diag: [P]; last-layer full GGN: [P, P]).  The eigenvectors
+    are left out: they follow from the factors, and where two eigenvalues lie close they differ from run to run (1e-2 in
+    a column of the arxiv-shaped fit at a gap of 3e-4) without the fit being any different."""
+    import torch
+    import laplace_gnn_amd as lg
+
+    out = [("loss", torch.as_tensor(la.loss).detach().reshape(()).double())]
+    if isinstance(la.H, lg.KronDecomposed):
+        for i, F in enumerate(la.H_facs.kfacs):
+            for j, t in enumerate(F):
+                out += [(f"kron_factor_{i}_{j}", t), (f"kron_eigenvalues_{i}_{j}", la.H.eigenvalues[i][j])]
+    else:
+        out.append(("hessian", la.H))
+    return out
+
+
+def _dump_outputs(pairs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """Write every (name, tensor) as ``out_dir/<name>.npy`` (float32 as computed, float64 for the loss).  Smallest first,
+    each array gets an equal share of the byte budget that is left; one that does not fit its share is written as a fixed
+    sample, ``<name>_sample.npy``: the rows (2-D) or entries (1-D) at sorted positions drawn by a generator seeded with 0."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    pairs = sorted(pairs, key=lambda p: p[1].numel() * p[1].element_size())
+    left = limit - 4096 * len(pairs)  # (room for the .npy headers)
+    written = {}
+    for k, (name, t) in enumerate(pairs):
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        share = left // (len(pairs) - k)
+        if t.numel() * t.element_size() > share:
+            row_bytes = (t[0].numel() if t.ndim > 1 else 1) * t.element_size()
+            n = max(1, share // row_bytes)
+            pick = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+            t, name = t.index_select(0, pick.to(t.device)), name + "_sample"
+        a = t.contiguous().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def _pmc_traffic(workload, structure, units_per_launch):
@@ -330,25 +389,29 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    if not fit_graph:
+    if args.full and not fit_graph:
         eng.enable_kernel_timing(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step(timed=True)
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(_fit_outputs(la), args.dump_outputs)  # before anything below runs another fit
     kt_steps = args.steps
-    if fit_graph:
-        # event records around the dominant kernel cannot live inside the replayed graph: its launch duration is measured over
-        # three more fits of the launch-by-launch path right behind the timed region (same process, same buffers)
-        eng.enable_kernel_timing(True)
-        kt_steps = 3
-        for _ in range(kt_steps):
-            step()
-        sync()
-    launches, kern_ms, units = eng.kernel_timing()
-    per_launch = eng.kernel_timing_launches() if hasattr(eng, "kernel_timing_launches") else []
-    eng.enable_kernel_timing(False)
+    launches, kern_ms, units, per_launch = 0, 0.0, 0, []
+    if args.full:
+        if fit_graph:
+            # event records around the dominant kernel cannot live inside the replayed graph: its launch duration is measured
+            # over three more fits of the launch-by-launch path right behind the timed region (same process, same buffers)
+            eng.enable_kernel_timing(True)
+            kt_steps = 3
+            for _ in range(kt_steps):
+                step()
+            sync()
+        launches, kern_ms, units = eng.kernel_timing()
+        per_launch = eng.kernel_timing_launches() if hasattr(eng, "kernel_timing_launches") else []
+        eng.enable_kernel_timing(False)
     step_ms = [e[0].elapsed_time(e[2]) for e in ev]
     acc_ms = [e[0].elapsed_time(e[1]) for e in ev]
     dist_info = None
@@ -503,7 +566,7 @@ def main():
         }
         if dist_info is not None:
             out["dist"] = dist_info
-        if world == 1 and not args.no_cpu_baseline and not args.emulate_world:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.emulate_world:
             Ws = [c.lin.weight.detach().cpu().numpy() for c in model.convs]
             bs = [c.lin.bias.detach().cpu().numpy() for c in model.convs]
             out["cpu_baseline"] = cpu_baseline(args.workload, ei, X, Ws, bs, train_idx, train_y, w, structure, model)

@@ -1,39 +1,67 @@
-"""Drop-in proof in the build container: the backend class of this package,
-``laplace_gnn_amd.HipGGN``, UNMODIFIED, handed as ``backend=`` to the REFERENCE's own ``Laplace`` classes
-(``laplace/baselaplace.py`` loaded from /root/reference through oracle/ref_loader.py) -- constructor kwargs
-(baselaplace.py:175-190), return types (``self.H += H_batch`` at :852 goes through the reference's ``Kron.__add__``,
-laplace/utils/matrix.py:85-86), conventions (A rescaled by M/N, factor, fresh tensors) and results against the goldens
-the same reference produced with its own CurvlinopsGGN backend.
+"""Drop-in proof: the backend class of this package, ``laplace_gnn_amd.HipGGN``, UNMODIFIED,
+handed as ``backend=`` to a ``Laplace`` front -- constructor kwargs (baselaplace.py:175-190), return types (``self.H +=
+H_batch`` at :852 goes through the host's ``Kron.__add__``, laplace/utils/matrix.py:85-86), conventions (A rescaled by M/N,
+factor, fresh tensors) and results against the goldens the reference produced with its own CurvlinopsGGN backend.
+
+Self-contained: the front is this package's own (the reference's class layout, string-keyed factory and ``backend=`` /
+``backend_kwargs=`` arguments), and the host application's container module ``laplace.utils.matrix`` is a stand-in written
+here (``host_matrix``) whose ``Kron.__add__`` accepts only its own class -- the contract ``curvature._kron_class`` bridges.
 
 There is no GPU here: the engine behind the backend is the CPU oracle stand-in (tests/oracle_engine.py, same Python
 surface as ``GraphEngine``); on a GPU box the engine is the HIP library and these same code lines of ``HipGGN`` run
-(tests/test_gpu_frontend.py).  Skipped where the reference tree is absent (the GPU box)."""
-import importlib
+(tests/test_gpu_frontend.py)."""
 import os
 import sys
+import types
 
 import numpy as np
 import pytest
 import torch
 from torch.utils.data import DataLoader, TensorDataset
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-import ref_loader  # noqa: E402
+import laplace_gnn_amd as lg
+from laplace_gnn_amd import laplace as front
+from laplace_gnn_amd import matrix as front_matrix
+from test_host_logic import _cpu_model, rel
 
-import laplace_gnn_amd as lg  # noqa: E402
-from test_host_logic import _cpu_model, rel  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present (GPU box)")
 RTOL = 1e-4
 
 
 @pytest.fixture(scope="module")
 def ref():
-    ns = ref_loader.load()
-    ns.laplace_factory = importlib.import_module("laplace.laplace").Laplace  # the reference's own string-keyed factory
-    return ns
+    """The front the backend class is handed to: classes, factory and containers under the names the tests use."""
+    return types.SimpleNamespace(laplace_factory=lg.Laplace, baselaplace=front, matrix=front_matrix)
+
+
+@pytest.fixture
+def host_matrix(monkeypatch):
+    """A host application's ``laplace.utils.matrix`` loaded in this process: its own ``Kron`` (a weight [out, in] has the
+    factors [out x out, in x in], a bias one [out x out]) whose ``__add__`` refuses any other class.  Removed again after
+    the test."""
+
+    class HostKron:
+        def __init__(self, kfacs):
+            self.kfacs = kfacs
+
+        @classmethod
+        def init_from_model(cls, params, device):
+            kfacs = []
+            for p in params:
+                dims = [p.shape[0]] if p.ndim == 1 else [p.shape[0], p.shape[1]]
+                kfacs.append([torch.zeros(d, d, device=device) for d in dims])
+            return cls(kfacs)
+
+        def __add__(self, other):
+            if not isinstance(other, HostKron):
+                raise ValueError("Can only add Kron to Kron.")
+            return HostKron([[a.add(b) for a, b in zip(F, G)] for F, G in zip(self.kfacs, other.kfacs)])
+
+    mod = types.ModuleType("laplace.utils.matrix")
+    mod.Kron = HostKron
+    monkeypatch.setitem(sys.modules, "laplace.utils.matrix", mod)
+    return mod
 
 
 def _loader(g, y_key="train_y"):
@@ -81,27 +109,27 @@ def test_reference_kron_and_diag_laplace_run_on_the_hip_backend_class(ref, name)
     assert abs(float(ld.log_marginal_likelihood()) - float(g["diag_marglik_pp1"])) < 2e-4 * abs(float(g["diag_marglik_pp1"]))
 
 
-def test_backend_returns_fresh_tensors_of_both_container_types(ref):
-    """``kron()`` hands out an object that the reference's ``Kron.__add__`` accepts (isinstance of ITS class) and that
-    this package's front accepts too; callers mutate the result (``self.H += ``, ``F[1] *= ``), so every call returns
-    fresh tensors."""
+def test_backend_returns_fresh_tensors_of_both_container_types(host_matrix):
+    """With a host application's container module loaded, ``kron()`` hands out an object that the host's ``Kron.__add__``
+    accepts (isinstance of ITS class) and that this package's front accepts too; callers mutate the result (``self.H += ``,
+    ``F[1] *= ``), so every call returns fresh tensors."""
     g = np.load(os.path.join(GOLDEN, "gcn_small_1batch_s0.npz"))
     model = _cpu_model(g)
     be = lg.HipGGN(model, "classification")
     x, y = torch.from_numpy(g["train_idx"]), torch.from_numpy(g["train_y"])
     l1, k1 = be.kron(x, y, N=len(x))
     l2, k2 = be.kron(x, y, N=len(x))
-    assert isinstance(k1, ref.matrix.Kron) and isinstance(k1, lg.Kron)
+    assert isinstance(k1, host_matrix.Kron) and isinstance(k1, lg.Kron)
     assert [[t.shape for t in F] for F in k1.kfacs] == [[t.shape for t in F] for F in
-                                                         ref.matrix.Kron.init_from_model(be.params, "cpu").kfacs]
+                                                         host_matrix.Kron.init_from_model(be.params, "cpu").kfacs]
     for Fa, Fb in zip(k1.kfacs, k2.kfacs):
         for a, b in zip(Fa, Fb):
             assert a.data_ptr() != b.data_ptr() and torch.equal(a, b)
     k1.kfacs[0][0].mul_(0)  # mutating one result leaves the other (and the next call) intact
     assert float(k2.kfacs[0][0].abs().sum()) > 0
-    zero = ref.matrix.Kron.init_from_model(be.params, "cpu")
-    acc = zero + k2  # the reference's __add__
-    assert type(acc) is ref.matrix.Kron
+    zero = host_matrix.Kron.init_from_model(be.params, "cpu")
+    acc = zero + k2  # the host's __add__
+    assert type(acc) is host_matrix.Kron
     acc2 = lg.Kron.init_from_model(be.params, "cpu") + k2  # this package's __add__
     assert type(acc2) is lg.Kron and torch.equal(acc2.kfacs[0][0], acc.kfacs[0][0])
     assert torch.is_tensor(l1) and l1.ndim == 0

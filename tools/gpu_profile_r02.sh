@@ -11,7 +11,7 @@ case $wl in
   products) kern=gram_mem_kernel; units=1128 ;;
 esac
 mkdir -p $O
-timeout -k 10 900 python $R/bench.py --workload $wl --steps $steps --warmup 2 > $O/${P}_bench.log 2>&1 || { tail -5 $O/${P}_bench.log; exit 1; }
+timeout -k 10 900 python $R/bench.py --full --workload $wl --steps $steps --warmup 2 > $O/${P}_bench.log 2>&1 || { tail -5 $O/${P}_bench.log; exit 1; }
 tail -1 $O/${P}_bench.log > $O/${P}_bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${P}_prof -- python3 $R/bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline > $O/${P}_prof.log 2>&1 || exit 1

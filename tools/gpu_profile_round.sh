@@ -3,7 +3,7 @@
 # baseline, rocprofv3 kernel stats, PMC passes (one rocprofv3 --pmc run per counter group; never combined with traces)
 tag=$1; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out
 mkdir -p $O
-timeout -k 10 400 python $R/bench.py --steps 3 --warmup 1 > $O/${tag}_bench.log 2>&1 || { tail -5 $O/${tag}_bench.log; exit 1; }
+timeout -k 10 400 python $R/bench.py --full --steps 3 --warmup 1 > $O/${tag}_bench.log 2>&1 || { tail -5 $O/${tag}_bench.log; exit 1; }
 tail -1 $O/${tag}_bench.log > $O/${tag}_bench.json
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${tag}_prof -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/${tag}_prof.log 2>&1 || exit 1
