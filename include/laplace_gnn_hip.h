@@ -357,6 +357,41 @@ LGNN_API int lgnn_diag_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const f
                              float* grad_adj, const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand,
                              float* grad_cand, float* grad_cand_adj, void* stream);
 
+/* ---- the adjacency gradient on ALL N x N pairs (LoRASTEGCN, gnn/models/models.py:186-235) --------------------------------
+ * LoRA parameterises the whole adjacency, adj0 + scaling * (adj_lora_B @ adj_lora_A) (models.py:226-232), so the gradient
+ * that neg_marglik.backward() leaves in A and B (gnn/marglik_training.py:197-216) needs d(-marglik)/d adj on every pair.
+ * The same chains as lgnn_kfac_adjgrad_batch / lgnn_adjgrad_finish and lgnn_diag_adjgrad_batch / _finish, but the caller's
+ * grad_adj_dense [N, N] (fp32, row major, zeroed before the first batch) takes the place of grad_P, candidates and grad_adj:
+ * every per-pair term becomes a tile GEMM on the full grid (fp32 MFMA, lora.hip), the _finish call turns it in place into
+ * grad_adj_dense[i, j] = d(-marglik)/d adj[i, j]: normalize_adj backward (gnn/models/utils.py:106-112), the STE as identity
+ * (gnn/models/utils.py:42-86), a symmetric model's (i, j) / (j, i) average, the diagonal 0 (fill_diagonal_(1)).  Between the
+ * calls the buffer holds d/dP on the grid.  Plain 2-layer GCN (no res / norm), N^2 < 2^31.  Workspace: the same as the
+ * sparse chains; the Kronecker batch runs all N rows (as with candidates).                                                  */
+LGNN_API int lgnn_kfac_adjgrad_batch_dense(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags,
+                                  const float* const* gamma_B /* host array of 2 device ptrs */, float loss_scale,
+                                  float* out_bar, float* grad_adj_dense, void* stream);
+LGNN_API int lgnn_adjgrad_finish_dense(lgnn_ctx* h, const float* out_bar, const float* const* gamma_A, float a_scale,
+                              float* grad_adj_dense, void* stream);
+LGNN_API int lgnn_diag_adjgrad_batch_dense(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma,
+                                  float loss_scale, float* out_bar, float* h1_bar, float* e_bar, float* grad_adj_dense,
+                                  void* stream);
+LGNN_API int lgnn_diag_adjgrad_finish_dense(lgnn_ctx* h, const float* out_bar, const float* h1_bar, const float* e_bar,
+                                   float* grad_adj_dense, void* stream);
+
+/* ---- LoRA structure learning (LoRASTEGCN) -----------------------------------------------------------------------------
+ * lgnn_lora_threshold: re-binarise the LoRA adjacency (gnn/models/models.py:226-230) against the stored pattern and edit it
+ * in place (lgnn_update_adjacency).  For every off-diagonal pair: t = (B @ A)[i, j] * scaling, m = adj0[i, j] + t, symmetric
+ * models (m_ij + m_ji) / 2; stored afterwards iff m > threshold.  base_rowptr / base_col: int32 CSR of adj0's 0/1 pattern
+ * (sorted columns); lora_A [r, N], lora_B [N, r] fp32.  The flips are compacted on the device; only their number reaches the
+ * host (*num_flips; synchronises the stream).  The diagonal is never edited (the GCN's self loops).
+ * lgnn_lora_grad: grad_A [r, N] = scaling B^T G and grad_B [N, r] = scaling G A^T (overwritten) from the dense gradient G of
+ * lgnn_*_finish_dense; one pass over row tiles of G, grad_A's partials summed in a fixed order.  1 <= r <= 64.           */
+LGNN_API int lgnn_lora_threshold(lgnn_ctx* h, const int32_t* base_rowptr, const int32_t* base_col, const float* lora_A,
+                                 const float* lora_B, int64_t r, float scaling, float threshold, int symmetric,
+                                 int64_t* num_flips, void* stream);
+LGNN_API int lgnn_lora_grad(lgnn_ctx* h, const float* grad_adj_dense, const float* lora_A, const float* lora_B, int64_t r,
+                            float scaling, float* grad_A, float* grad_B, void* stream);
+
 /* ---- matrix-free GLM predictive ("next" row 8(f)-3 at scale) -------------------------------------------------------
  * Replaces the Jacobian route of the default la(x) (laplace/baselaplace.py:1123-1158 + laplace/utils/matrix.py:396-451 resp.
  * baselaplace.py:1901-1903) for 2-layer GCN and GraphSAGE models: f_mu [M, C] = logits and f_var_diag [M, C] = diag(J P^-1 J^T) per

@@ -62,6 +62,12 @@ SIGNATURES = {
     "lgnn_adjgrad_finish": (_i32, [_vp, _vp, _pp, C.c_float, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_diag_adjgrad_batch": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "lgnn_diag_adjgrad_finish": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_kfac_adjgrad_batch_dense": (_i32, [_vp, _vp, _vp, _i64, _u32, _pp, C.c_float, _vp, _vp, _vp]),
+    "lgnn_adjgrad_finish_dense": (_i32, [_vp, _vp, _pp, C.c_float, _vp, _vp]),
+    "lgnn_diag_adjgrad_batch_dense": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_diag_adjgrad_finish_dense": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_lora_threshold": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_float, _i32, C.POINTER(_i64), _vp]),
+    "lgnn_lora_grad": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_float, _vp, _vp, _vp]),
     "lgnn_glm_variance": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgnn_glm_variance_mapped": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgnn_symeig_batched": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp]),

@@ -615,6 +615,19 @@ int sgemm_rm(hipStream_t s, int64_t R, int64_t Nout, int64_t K, float alpha, con
   return 0;
 }
 
+// first occurrences of the batch's nodes: orows[t] = idx[m], lrows[t] = m for every m with pos[idx[m]] == m (the seed term's
+// rows on the dense route; any order -- the rows are distinct)
+__global__ void first_rows_kernel(const int64_t* __restrict__ idx, int64_t M, int64_t N, const int32_t* __restrict__ pos,
+                                  int32_t* __restrict__ orows, int32_t* __restrict__ lrows, int32_t* __restrict__ count) {
+  const int64_t m = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const int64_t a = idx[m];
+  if (a < 0 || a >= N || pos[a] != int32_t(m)) return;
+  const int32_t t = atomicAdd(count, 1);
+  orows[t] = int32_t(a);
+  lrows[t] = int32_t(m);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // GraphSAGE
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1588,9 +1601,19 @@ int diag_adjgrad_batch_sage(lgnn_ctx* h, const int64_t* idx, const void* y, int6
 }
 }  // namespace
 
+int launch_gp_rowcol(lgnn_ctx* h, const float* gP, float* rs, float* cs, hipStream_t s) {
+  hipLaunchKernelGGL(gp_rowcol_kernel, dim3(unsigned(cdiv(h->N, 256))), dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, gP,
+                     h->N, rs, cs);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// dense != null (plain 2-layer GCN, lgnn_kfac_adjgrad_batch_dense): every candidate-pair term is also added on the full grid,
+// dense[a * N + b] += d/dP[a, b] (lora.hip's tile GEMMs); everything is then defined on all N rows as with candidates.
 int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags, const float* gamma_B0,
                        const float* gamma_B1, const float* gamma_Br, float loss_scale, float* grad_P, float* out_bar,
-                       const int32_t* cand_a, const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s) {
+                       const int32_t* cand_a, const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s,
+                       float* dense = nullptr) {
   LGNN_REQUIRE(K == 0 || (cand_a && cand_b && grad_cand), "candidate pairs without their buffers");
   LGNN_REQUIRE(M > 0 && idx && y && gamma_B0 && gamma_B1 && grad_P && out_bar, "empty batch or null pointers");
   if (h->extras())
@@ -1611,7 +1634,7 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
   // fit's own top-layer kernel writes just those rows (0.3 ms instead of 3.5 ms over all N rows) and the backward GEMM runs
   // over the compacted list (0.9 ms instead of 4.4 ms): rows that are not active hold whatever the buffers held and are
   // never looked at.  Candidate pairs can name any row: then everything is defined on all N rows as before.
-  const bool compact = K == 0 && H == 256 && h->fc.mask_bits[0].p != nullptr && backgemm_supported(C, H, true) &&
+  const bool compact = K == 0 && dense == nullptr && H == 256 && h->fc.mask_bits[0].p != nullptr && backgemm_supported(C, H, true) &&
                        (N + 1) * H * 4 < (int64_t(1) << 31) && getenv("LGNN_ADJ_ALL_ROWS") == nullptr &&
                        getenv("LGNN_ADJ_CHUNKED") == nullptr;
   const int64_t u_stride = compact ? (N + 1) * H : N * H;  // the compacted backward GEMM wants a spare row per plane
@@ -1631,6 +1654,15 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
   }
   LGNN_CALL(h->ws.jac.reserve(size_t(M) * CC * 4));  // Vbar [M][C][C]
   float* vbar = h->ws.jac.as<float>();
+  int32_t* first_rows = nullptr;
+  if (dense) {  // the seed term's rows: the first occurrence of every batch node
+    LGNN_CALL(h->ws.dense_rows.reserve(size_t(2 * M + 1) * 4));
+    first_rows = h->ws.dense_rows.as<int32_t>();
+    LGNN_HIP_CHECK(hipMemsetAsync(first_rows + 2 * M, 0, 4, s));
+    hipLaunchKernelGGL(first_rows_kernel, dim3(unsigned(cdiv(M, 256))), dim3(256), 0, s, idx, M, N, h->ws.pos.as<int32_t>(),
+                       first_rows, first_rows + M, first_rows + 2 * M);
+    LGNN_HIP_CHECK(hipGetLastError());
+  }
   // values of P^T with the columns of inactive (all-zero) source rows removed
   LGNN_CALL(h->ws.val_act.reserve(size_t(std::max<int64_t>(h->nnz, 1)) * 4));
   float* val_act = h->ws.val_act.as<float>();
@@ -1682,9 +1714,16 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
     // gradP[(a,b)] += sum_c <u_c[a], g0bar_c[b]> and ubar = mask * (P g0bar) (overwrites u), both over the active rows only
     // (u, hence ubar's consumers, vanish elsewhere); candidates first: they read u before it is overwritten
     LGNN_CALL(launch_sddmm_coo(cand_a, cand_b, K, U, H, N * H, G0B, H, N * H, H, cc, h->ws.active.as<uint8_t>(), grad_cand, s));
+    if (dense) {  // sum_c <u_c[a], g0bar_c[b]> over the active rows a (u vanishes elsewhere), all b
+      DenseNtArgs dn;
+      dn.out = dense; dn.ldo = N; dn.ncols = N; dn.nrows = N; dn.nrows_dev = h->ws.act_count.as<int32_t>();
+      dn.orows = h->ws.act_list.as<int32_t>();
+      dn.L = U; dn.l_ld = H; dn.l_stride = u_stride; dn.R = G0B; dn.r_ld = H; dn.r_stride = N * H; dn.width = H; dn.nplanes = cc;
+      LGNN_CALL(launch_dense_nt(dn, s));
+    }
     if (H % 4 == 0 && H <= 256) {
       // (candidate pairs reach g1bar at arbitrary rows, so ubar is then needed everywhere, not on the active rows only)
-      const int32_t* rows = K > 0 ? nullptr : h->ws.act_list.as<int32_t>();
+      const int32_t* rows = (K > 0 || dense) ? nullptr : h->ws.act_list.as<int32_t>();
       static const bool chunked = getenv("LGNN_ADJ_CHUNKED") != nullptr;  // dev: the 8-planes-per-wave kernel
       if (!chunked && cc < 65536)
         hipLaunchKernelGGL(sddmm_spmm_pm_kernel, dim3(unsigned(cdiv(N, 4)), unsigned(cc)), dim3(256), 0, s, h->P.rowptr, h->P.col,
@@ -1719,12 +1758,21 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
     }
     LGNN_CALL(sgemm_rm(s, cc * N, C, C, 2.f, g1c, C, gamma_B1, C, 1.f, G1B, C));
     // gradP[(a,b)] += sum_c <G_c[a], g1bar_c[b]> for the batch rows a;  Vbar = (P g1bar)[batch rows]
-    hipLaunchKernelGGL(sddmm_seed_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, h->P.rowptr, h->P.col, idx, M, N, C,
-                       h->ws.pos.as<int32_t>(), h->ws.seeds.as<float>(), G1B, c0, cc, grad_P);
+    if (!dense)  // (the dense route takes the same term on the full grid below)
+      hipLaunchKernelGGL(sddmm_seed_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, h->P.rowptr, h->P.col, idx, M, N, C,
+                         h->ws.pos.as<int32_t>(), h->ws.seeds.as<float>(), G1B, c0, cc, grad_P);
     LGNN_HIP_CHECK(hipGetLastError());
     if (K > 0)
       hipLaunchKernelGGL(sddmm_coo_seed_kernel, dim3(unsigned(cdiv(K, 4))), dim3(256), 0, s, cand_a, cand_b, K, N, C,
                          h->ws.pos.as<int32_t>(), h->ws.seeds.as<float>(), G1B, c0, cc, grad_cand);
+    if (dense) {  // sum_c <G_c[a], g1bar_c[b]>: the seed rows of the batch nodes a, all b
+      DenseNtArgs dn;
+      dn.out = dense; dn.ldo = N; dn.ncols = N; dn.nrows = M; dn.nrows_dev = first_rows + 2 * M;
+      dn.orows = first_rows; dn.lrows = first_rows + M;
+      dn.L = h->ws.seeds.as<float>() + c0 * C; dn.l_ld = CC; dn.l_stride = C;
+      dn.R = G1B; dn.r_ld = C; dn.r_stride = N * C; dn.width = C; dn.nplanes = cc;
+      LGNN_CALL(launch_dense_nt(dn, s));
+    }
     hipLaunchKernelGGL(seed_adjoint_gather_kernel, dim3(unsigned(cdiv(M * cc * C, 256))), dim3(256), 0, s, h->P.rowptr,
                        h->P.col, h->P.val, idx, M, N, C, G1B, c0, cc, vbar);
     LGNN_HIP_CHECK(hipGetLastError());
@@ -2091,7 +2139,7 @@ __global__ __launch_bounds__(256) void dadj_cand_kernel(const int32_t* __restric
 
 int diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, float loss_scale,
                        float* grad_P, float* out_bar, float* h1_bar, float* e_bar, const int32_t* cand_a, const int32_t* cand_b,
-                       int64_t K, float* grad_cand, hipStream_t s) {
+                       int64_t K, float* grad_cand, hipStream_t s, float* dense = nullptr) {
   LGNN_REQUIRE(K == 0 || (cand_a && cand_b && grad_cand), "candidate pairs without their buffers");
   if (h->kind == LGNN_KIND_SAGE)  // (e_bar [N, F + 1] carries the adjoint of P X in its first F columns)
     return diag_adjgrad_batch_sage(h, idx, y, M, gamma, loss_scale, grad_P, out_bar, h1_bar, e_bar, cand_a, cand_b, K, grad_cand,
@@ -2137,6 +2185,9 @@ int diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
                          h->ws.pos.as<int32_t>(), h->ws.mult.as<int32_t>(), m0, mc, mask, H, PX, ldx, rowsum, F,
                          h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, grad_cand);
     LGNN_HIP_CHECK(hipGetLastError());
+    if (dense)
+      LGNN_CALL(launch_dense_diag_pair(idx, m0, mc, N, h->ws.pos.as<int32_t>(), h->ws.mult.as<int32_t>(), mask, H, PX, ldx, rowsum,
+                                       F, h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, dense, s));
   }
   LGNN_CALL(batch_epilogue(h, idx, M, s));
   return 0;
@@ -2146,7 +2197,7 @@ int diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
 // that take the place of the Kronecker posterior's 2 a_scale H_1 Gamma_A1 (gamma_A1 is null then)
 int adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float* gamma_A0, const float* gamma_A1, float a1_scale,
                    float* grad_P, float* grad_adj, const int32_t* cand_a, const int32_t* cand_b, int64_t K, float* grad_cand,
-                   float* grad_cand_adj, hipStream_t s, const float* h1_bar, const float* e_bar) {
+                   float* grad_cand_adj, hipStream_t s, const float* h1_bar, const float* e_bar, float* dense = nullptr) {
   LGNN_REQUIRE(K == 0 || (cand_a && cand_b && grad_cand && grad_cand_adj), "candidate pairs without their buffers");
   if (h->extras()) LGNN_CALL(check_model_ext(h));
   else LGNN_CALL(check_model(h));
@@ -2172,8 +2223,14 @@ int adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float* gamma_A0, con
   GemmEpilogue eb1;
   eb1.bias = h->b[1];
   LGNN_CALL(launch_gemm(h->fc.hact_p[0], h->fc.hact_ld[0], h->Wt[1].as<float>(), C, Z, C, N, H, C, eb1, s));
-  LGNN_CALL(launch_sddmm(h->P, N, nullptr, nullptr, out_bar, C, 0, Z, C, 0, C, 1, grad_P, s));
+  if (!dense) LGNN_CALL(launch_sddmm(h->P, N, nullptr, nullptr, out_bar, C, 0, Z, C, 0, C, 1, grad_P, s));
   LGNN_CALL(launch_sddmm_coo(cand_a, cand_b, K, out_bar, C, 0, Z, C, 0, C, 1, nullptr, grad_cand, s));
+  DenseNtArgs dn;  // (the full-grid forms of the terms: dense route only)
+  dn.out = dense; dn.ldo = N; dn.ncols = N; dn.nrows = N;
+  if (dense) {
+    dn.L = out_bar; dn.l_ld = C; dn.R = Z; dn.r_ld = C; dn.width = C;
+    LGNN_CALL(launch_dense_nt(dn, s));
+  }
   // Z1bar = P^T outbar;  H1bar = Z1bar W1 + 2 a1_scale H1 Gamma_A1;  P0bar = mask * H1bar
   LGNN_CALL(launch_spmm(h->PT, N, out_bar, C, Zb, C, C, 0, s));
   LGNN_CALL(sgemm_rm(s, N, H, C, 1.f, Zb, C, h->W[1], H, 0.f, Hb, H));
@@ -2193,19 +2250,31 @@ int adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float* gamma_A0, con
   GemmEpilogue eb0;
   eb0.bias = h->b[0];
   LGNN_CALL(launch_gemm(h->fc.lin_in_p[0], h->fc.lin_in_ld[0], h->Wt[0].as<float>(), H, Z, H, N, F, H, eb0, s));
-  LGNN_CALL(launch_sddmm(h->P, N, nullptr, nullptr, Hb, H, 0, Z, H, 0, H, 1, grad_P, s));
+  if (!dense) LGNN_CALL(launch_sddmm(h->P, N, nullptr, nullptr, Hb, H, 0, Z, H, 0, H, 1, grad_P, s));
   LGNN_CALL(launch_sddmm_coo(cand_a, cand_b, K, Hb, H, 0, Z, H, 0, H, 1, nullptr, grad_cand, s));
+  if (dense) {
+    dn.L = Hb; dn.l_ld = H; dn.R = Z; dn.r_ld = H; dn.width = H;
+    LGNN_CALL(launch_dense_nt(dn, s));
+  }
   if (e_bar) {
     // P X = sum_u P[v, u] X[u]: gradP[(v, u)] += <e_bar[v, :F], X[u]>;  rowsum(P)[v] = sum_u P[v, u]: += e_bar[v, F]
     const int64_t F1 = F + 1;
     LGNN_CALL(forward_input_view(h, s));
-    LGNN_CALL(launch_sddmm(h->P, N, nullptr, nullptr, e_bar, F1, 0, h->fc.lin_in_p[0], h->fc.lin_in_ld[0], 0, F, 1, grad_P, s));
-    LGNN_CALL(launch_sddmm_coo(cand_a, cand_b, K, e_bar, F1, 0, h->fc.lin_in_p[0], h->fc.lin_in_ld[0], 0, F, 1, nullptr,
-                               grad_cand, s));
-    hipLaunchKernelGGL(row_const_kernel, dim3(unsigned(cdiv(N, 4))), dim3(256), 0, s, h->P.rowptr, N, e_bar + F, F1, grad_P,
-                       cand_a, K, grad_cand);
-    LGNN_HIP_CHECK(hipGetLastError());
+    if (!dense) {
+      LGNN_CALL(launch_sddmm(h->P, N, nullptr, nullptr, e_bar, F1, 0, h->fc.lin_in_p[0], h->fc.lin_in_ld[0], 0, F, 1, grad_P, s));
+      LGNN_CALL(launch_sddmm_coo(cand_a, cand_b, K, e_bar, F1, 0, h->fc.lin_in_p[0], h->fc.lin_in_ld[0], 0, F, 1, nullptr,
+                                 grad_cand, s));
+      hipLaunchKernelGGL(row_const_kernel, dim3(unsigned(cdiv(N, 4))), dim3(256), 0, s, h->P.rowptr, N, e_bar + F, F1, grad_P,
+                         cand_a, K, grad_cand);
+      LGNN_HIP_CHECK(hipGetLastError());
+    }
+    if (dense) {  // <e_bar[a, :F], X[b]> + e_bar[a, F] on every pair
+      dn.L = e_bar; dn.l_ld = F1; dn.R = h->fc.lin_in_p[0]; dn.r_ld = h->fc.lin_in_ld[0]; dn.width = F;
+      dn.rowc = e_bar + F; dn.rowc_ld = F1;
+      LGNN_CALL(launch_dense_nt(dn, s));
+    }
   }
+  if (dense) return dense_adj_finish(h, dense, s);  // normalize_adj backward, symmetrisation, diagonal on the full grid
   // normalize_adj backward + the straight-through binarisation
   LGNN_CALL(h->ws.misc.reserve(size_t(2) * N * 4 + size_t(h->nnz) * 4));
   float* rs = h->ws.misc.as<float>();
@@ -2262,4 +2331,63 @@ extern "C" int lgnn_diag_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const
   if (!h1_bar || !e_bar) { lgnn::set_error("lgnn_diag_adjgrad_finish: null adjoint buffers"); return 2; }
   return lgnn::adjgrad_finish(h, out_bar, nullptr, nullptr, 0.f, grad_P, grad_adj, cand_a, cand_b, num_cand, grad_cand,
                               grad_cand_adj, static_cast<hipStream_t>(stream), h1_bar, e_bar);
+}
+
+// ---- the dense [N, N] route (plain 2-layer GCN; LoRASTEGCN, lora.hip) ---------------------------------------------------------
+namespace {
+// The dense route reads nothing of the stored-entry accumulator: the kernels that only add into it are skipped, those whose
+// other outputs are needed (the fused SDDMM + SpMM that also forms ubar; the diagonal posterior's entry kernel that also
+// scatters h1_bar / e_bar) write into this zeroed scratch, which is never read.
+int dense_scope(lgnn_ctx* h, const char* what, hipStream_t s) {
+  using namespace lgnn;
+  if (h->kind != LGNN_KIND_GCN || h->L != 2 || h->extras()) {
+    set_error(std::string(what) + ": the dense adjacency gradient covers plain 2-layer GCN models (no res / norm)");
+    return 2;
+  }
+  if (h->N * h->N >= (int64_t(1) << 31)) {
+    set_error(std::string(what) + ": N^2 exceeds int32 indexing of the dense gradient");
+    return 2;
+  }
+  LGNN_CALL(h->ws.dense_stored.reserve(size_t(std::max<int64_t>(h->nnz, 1)) * 4));
+  LGNN_HIP_CHECK(hipMemsetAsync(h->ws.dense_stored.p, 0, size_t(std::max<int64_t>(h->nnz, 1)) * 4, s));
+  return 0;
+}
+}  // namespace
+
+extern "C" int lgnn_kfac_adjgrad_batch_dense(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags,
+                                             const float* const* gamma_B, float loss_scale, float* out_bar,
+                                             float* grad_adj_dense, void* stream) {
+  if (!h || !gamma_B || !grad_adj_dense) { lgnn::set_error("null argument"); return 2; }
+  LGNN_CALL(dense_scope(h, "lgnn_kfac_adjgrad_batch_dense", static_cast<hipStream_t>(stream)));
+  return lgnn::kfac_adjgrad_batch(h, idx, y, M, flags, gamma_B[0], gamma_B[1], nullptr, loss_scale,
+                                  h->ws.dense_stored.as<float>(), out_bar, nullptr, nullptr, 0, nullptr,
+                                  static_cast<hipStream_t>(stream), grad_adj_dense);
+}
+
+extern "C" int lgnn_adjgrad_finish_dense(lgnn_ctx* h, const float* out_bar, const float* const* gamma_A, float a_scale,
+                                         float* grad_adj_dense, void* stream) {
+  if (!h || !gamma_A || !grad_adj_dense) { lgnn::set_error("null argument"); return 2; }
+  LGNN_CALL(dense_scope(h, "lgnn_adjgrad_finish_dense", static_cast<hipStream_t>(stream)));
+  float* scratch = h->ws.dense_stored.as<float>();
+  return lgnn::adjgrad_finish(h, out_bar, gamma_A[0], gamma_A[1], a_scale, scratch, scratch, nullptr, nullptr, 0, nullptr,
+                              nullptr, static_cast<hipStream_t>(stream), nullptr, nullptr, grad_adj_dense);
+}
+
+extern "C" int lgnn_diag_adjgrad_batch_dense(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma,
+                                             float loss_scale, float* out_bar, float* h1_bar, float* e_bar,
+                                             float* grad_adj_dense, void* stream) {
+  if (!h || !grad_adj_dense) { lgnn::set_error("null argument"); return 2; }
+  LGNN_CALL(dense_scope(h, "lgnn_diag_adjgrad_batch_dense", static_cast<hipStream_t>(stream)));
+  return lgnn::diag_adjgrad_batch(h, idx, y, M, gamma, loss_scale, h->ws.dense_stored.as<float>(), out_bar, h1_bar, e_bar,
+                                  nullptr, nullptr, 0, nullptr, static_cast<hipStream_t>(stream), grad_adj_dense);
+}
+
+extern "C" int lgnn_diag_adjgrad_finish_dense(lgnn_ctx* h, const float* out_bar, const float* h1_bar, const float* e_bar,
+                                              float* grad_adj_dense, void* stream) {
+  if (!h || !grad_adj_dense) { lgnn::set_error("null argument"); return 2; }
+  if (!h1_bar || !e_bar) { lgnn::set_error("lgnn_diag_adjgrad_finish_dense: null adjoint buffers"); return 2; }
+  LGNN_CALL(dense_scope(h, "lgnn_diag_adjgrad_finish_dense", static_cast<hipStream_t>(stream)));
+  float* scratch = h->ws.dense_stored.as<float>();
+  return lgnn::adjgrad_finish(h, out_bar, nullptr, nullptr, 0.f, scratch, scratch, nullptr, nullptr, 0, nullptr, nullptr,
+                              static_cast<hipStream_t>(stream), h1_bar, e_bar, grad_adj_dense);
 }

@@ -124,6 +124,11 @@ struct Workspace {
   DevBuf planes_c;  // GCN with res, >= 3 layers: u_l Wr_l of the level being computed; adjacency gradient (diag, res / norm): tangent planes
   DevBuf adj_z0;    // adjacency gradient of res / norm models: Z0 = X W0^T + b0 [N, H]
   DevBuf adj_dir;   // the same, diagonal posterior: parameter directions R [chunk, C, P]
+  // LoRA (lora.hip): compacted flips of lgnn_lora_threshold (rows, cols int64, state uint8), their counter, and the
+  // per-row-tile partials of grad_A in lgnn_lora_grad
+  DevBuf lora_rows, lora_cols, lora_state, lora_count, lora_part;
+  DevBuf dense_stored;  // fp32 [nnz]: scratch accumulator of the stored-entry terms on the dense route
+  DevBuf dense_rows;    // int32 [2 M + 1]: output / operand rows of the seed term on the dense route
 };
 
 }  // namespace lgnn
@@ -268,6 +273,31 @@ int exclusive_scan_i32(int32_t* in, int32_t* out, int64_t n, DevBuf& tmp, hipStr
 int graph_build(lgnn_ctx* h, const int64_t* edge_index, int64_t E, hipStream_t s);
 int graph_values(lgnn_ctx* h, bool same, hipStream_t s);
 int graph_update(lgnn_ctx* h, const int64_t* fi, const int64_t* fj, const uint8_t* st, int64_t K, hipStream_t s);
+
+// ---- dense [N, N] adjacency gradient (lora.hip) -----------------------------------------------------------------------------
+// out[orow(t) * ldo + b] += sum_c sum_k L[c * l_stride + lrow(t) * l_ld + k] * R[c * r_stride + b * r_ld + k]  (+ rowc[orow * rowc_ld])
+// for list entries t < nrows (or *nrows_dev), b < ncols; orow(t) = orows ? orows[t] : t, lrow(t) = lrows ? lrows[t] : orow(t).
+// Output rows must be distinct within a launch.
+struct DenseNtArgs {
+  float* out = nullptr;
+  int64_t ldo = 0, ncols = 0, nrows = 0;
+  const int32_t* nrows_dev = nullptr;
+  const int32_t* orows = nullptr;
+  const int32_t* lrows = nullptr;
+  const float* L = nullptr;
+  int64_t l_ld = 0, l_stride = 0;
+  const float* R = nullptr;
+  int64_t r_ld = 0, r_stride = 0;
+  int64_t width = 0, nplanes = 1;
+  const float* rowc = nullptr;
+  int64_t rowc_ld = 0;
+};
+int launch_dense_nt(const DenseNtArgs& g, hipStream_t s);
+int launch_dense_diag_pair(const int64_t* idx, int64_t m0, int64_t mc, int64_t N, const int32_t* pos, const int32_t* mult,
+                           const float* mask, int64_t H, const float* PX, int64_t ldx, const float* rowsum, int64_t F,
+                           const float* H1p, int64_t ldh, const float* T, const float* phibar, float* out, hipStream_t s);
+int launch_gp_rowcol(lgnn_ctx* h, const float* gP, float* rs, float* cs, hipStream_t s);  // adjgrad.hip
+int dense_adj_finish(lgnn_ctx* h, float* G, hipStream_t s);
 
 // ---- kernels (launchers) -------------------------------------------------------------
 // out[r, 0:width) = sum_j val[j] * in[col[j], 0:width)   for r in [0, nrows)

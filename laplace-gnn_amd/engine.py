@@ -582,6 +582,83 @@ class GraphEngine:
         _lib.check(rc, "lgnn_diag_adjgrad_finish")
         return out if cand is None else (out, cout)
 
+    # -- the same gradient on all N x N pairs (LoRASTEGCN: lgnn_*_dense, csrc/lora.hip) ---------------------------------
+    def adjgrad_batch_dense(self, idx, y, gammas_B, out_bar: torch.Tensor, grad_dense: torch.Tensor, fork_exact: bool = True,
+                            loss_scale: float = 1.0):
+        """Add one batch's terms to ``out_bar`` [N, C] and to ``grad_dense`` [N, N] (d/dP on the full grid until the finish)."""
+        self._sync_versions()
+        idx, y = idx.contiguous(), y.contiguous()
+        self._keep = [g.contiguous() for g in gammas_B]
+        gb = _lib.ptr_array([_dev_ptr(g, torch.float32, "gamma_B").value for g in self._keep])
+        rc = self.lib.lgnn_kfac_adjgrad_batch_dense(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
+            _lib.FLAG_FORK_EXACT_SEED if fork_exact else 0, gb, float(loss_scale), _dev_ptr(out_bar, torch.float32, "out_bar"),
+            _dev_ptr(grad_dense, torch.float32, "grad_dense"), _stream(self.device))
+        _lib.check(rc, "lgnn_kfac_adjgrad_batch_dense")
+
+    def adjgrad_finish_dense(self, out_bar: torch.Tensor, gammas_A, a_scale: float, grad_dense: torch.Tensor):
+        """Forward-pass terms + normalize_adj / STE backward, in place: ``grad_dense[i, j] = d / d adj[i, j]``."""
+        self._sync_versions()
+        keep = [g.contiguous() for g in gammas_A]
+        ga = _lib.ptr_array([_dev_ptr(g, torch.float32, "gamma_A").value for g in keep])
+        rc = self.lib.lgnn_adjgrad_finish_dense(self._h, _dev_ptr(out_bar, torch.float32, "out_bar"), ga, float(a_scale),
+                                                _dev_ptr(grad_dense, torch.float32, "grad_dense"), _stream(self.device))
+        _lib.check(rc, "lgnn_adjgrad_finish_dense")
+        return grad_dense
+
+    def diag_adjgrad_batch_dense(self, idx, y, gamma: torch.Tensor, out_bar: torch.Tensor, h1_bar: torch.Tensor,
+                                 e_bar: torch.Tensor, grad_dense: torch.Tensor, loss_scale: float = 1.0):
+        """Diagonal posterior: as ``diag_adjgrad_batch`` with the full grid ``grad_dense`` [N, N] in place of the stored entries."""
+        self._sync_versions()
+        idx, y = idx.contiguous(), y.contiguous()
+        self._keep = gamma.contiguous()
+        rc = self.lib.lgnn_diag_adjgrad_batch_dense(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
+            _dev_ptr(self._keep, torch.float32, "gamma"), float(loss_scale), _dev_ptr(out_bar, torch.float32, "out_bar"),
+            _dev_ptr(h1_bar, torch.float32, "h1_bar"), _dev_ptr(e_bar, torch.float32, "e_bar"),
+            _dev_ptr(grad_dense, torch.float32, "grad_dense"), _stream(self.device))
+        _lib.check(rc, "lgnn_diag_adjgrad_batch_dense")
+
+    def diag_adjgrad_finish_dense(self, out_bar: torch.Tensor, h1_bar: torch.Tensor, e_bar: torch.Tensor,
+                                  grad_dense: torch.Tensor):
+        self._sync_versions()
+        rc = self.lib.lgnn_diag_adjgrad_finish_dense(self._h, _dev_ptr(out_bar, torch.float32, "out_bar"),
+                                                     _dev_ptr(h1_bar, torch.float32, "h1_bar"),
+                                                     _dev_ptr(e_bar, torch.float32, "e_bar"),
+                                                     _dev_ptr(grad_dense, torch.float32, "grad_dense"), _stream(self.device))
+        _lib.check(rc, "lgnn_diag_adjgrad_finish_dense")
+        return grad_dense
+
+    # -- LoRA (lgnn_lora_threshold / lgnn_lora_grad) ------------------------------------------------------------------
+    def lora_threshold(self, base_rowptr: torch.Tensor, base_col: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
+                       scaling: float, threshold: float, symmetric: bool) -> int:
+        """Re-binarise ``adj0 + scaling B A`` (symmetrised for symmetric models) into the stored graph; returns the flips."""
+        A, B = A.detach().contiguous(), B.detach().contiguous()
+        r = A.shape[0]
+        if A.shape != (r, self.num_nodes) or B.shape != (self.num_nodes, r):
+            raise ValueError("lora_A must be [r, N] and lora_B [N, r]")
+        n = C.c_int64(0)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.lgnn_lora_threshold(
+                self._h, _dev_ptr(base_rowptr, torch.int32, "base_rowptr"), _dev_ptr(base_col, torch.int32, "base_col"),
+                _dev_ptr(A, torch.float32, "lora_A"), _dev_ptr(B, torch.float32, "lora_B"), r, float(scaling),
+                float(threshold), int(bool(symmetric)), C.byref(n), _stream(self.device)), "lgnn_lora_threshold")
+        if n.value:
+            self._graph_edits = getattr(self, "_graph_edits", 0) + 1
+        return int(n.value)
+
+    def lora_grad(self, grad_dense: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scaling: float):
+        """``(scaling B^T G, scaling G A^T)`` from the dense adjacency gradient G [N, N]."""
+        A, B = A.detach().contiguous(), B.detach().contiguous()
+        r = A.shape[0]
+        gA = torch.empty_like(A)
+        gB = torch.empty_like(B)
+        _lib.check(self.lib.lgnn_lora_grad(self._h, _dev_ptr(grad_dense, torch.float32, "grad_dense"),
+                                           _dev_ptr(A, torch.float32, "lora_A"), _dev_ptr(B, torch.float32, "lora_B"), r,
+                                           float(scaling), gA.data_ptr(), gB.data_ptr(), _stream(self.device)),
+                   "lgnn_lora_grad")
+        return gA, gB
+
     def glm_variance(self, idx: torch.Tensor, S0, S1, kappa, QA0=None, QB0=None, QA1=None, QB1sq=None, out_map=None):
         """Matrix-free GLM predictive of a 2-layer GCN / GraphSAGE: (f_mu [M, C], diag(J P^-1 J^T) [M, C]) from the closed-form
         Jacobian (see include/laplace_gnn_hip.h lgnn_glm_variance for the operand conventions).  ``out_map`` = E [Cm, C]:

@@ -156,6 +156,18 @@ def _adjacency_candidates(eng, candidates, sym: bool):
             torch.zeros(ci.shape[0], dtype=torch.float32, device=eng.device))
 
 
+def _dense_scope(eng, what: str):
+    """``dense=True`` of ``neg_marglik_adj_grad``: the all-pairs gradient (LoRASTEGCN) covers plain 2-layer GCN models on the
+    HIP backend, and N x N floats must fit the workspace limit and int32 indexing."""
+    if eng is None or getattr(eng, "kind", None) != "gcn" or eng.num_layers != 2 or eng.has_extras:
+        raise NotImplementedError(f"{what}(dense=True): plain 2-layer GCN models (no res / norm) on the HIP backend")
+    N = eng.num_nodes
+    limit = getattr(eng, "_ws_limit", None) or (32 << 30)
+    if N * N >= 2 ** 31 or 4 * N * N > limit:
+        raise NotImplementedError(f"{what}(dense=True): an N x N gradient of {N} nodes exceeds the workspace limit "
+                                  f"({limit} bytes) or int32 indexing")
+
+
 class ParametricLaplace(BaseLaplace):
     def _init_H(self):
         raise NotImplementedError
@@ -862,7 +874,7 @@ class KronLaplace(ParametricLaplace):
             gA.append(((QA * cA) @ QA.T).float())
         return gB, gA
 
-    def neg_marglik_adj_grad(self, train_loader, prior_precision=None, process_group=None, candidates=None):
+    def neg_marglik_adj_grad(self, train_loader, prior_precision=None, process_group=None, candidates=None, dense=False):
         """``-log_marginal_likelihood()`` of this fit and its gradient w.r.t. the adjacency the model propagates with --
         what ``neg_marglik.backward()`` leaves in ``model.adj.grad`` in the reference's structure-learning loop
         (gnn/marglik_training.py:197-216), here on the stored sparsity pattern: returns ``(neg_marglik, edge_index [2, nnz],
@@ -873,7 +885,11 @@ class KronLaplace(ParametricLaplace):
 
         ``candidates`` (int64 [2, K], pairs (i, j) that are NOT stored): the reference's dense ``adj.grad`` also has an
         entry for every non-edge -- that is how its structure learning proposes new edges.  With candidates a fourth value
-        is returned: ``d(-marglik) / d adj[i, j]`` for each listed pair."""
+        is returned: ``d(-marglik) / d adj[i, j]`` for each listed pair.
+
+        ``dense=True`` (plain 2-layer GCN; LoRASTEGCN, gnn/models/models.py:186-235): returns ``(neg_marglik, grad [N, N])``,
+        ``d(-marglik) / d adj[i, j]`` for EVERY pair (symmetrised for symmetric models, diagonal 0) -- the dense ``adj.grad`` of
+        the reference, from tile GEMMs on the full grid (csrc/lora.hip)."""
         if self.H_facs is None:
             raise AttributeError("Laplace not fitted. Run fit() first.")
         if prior_precision is not None:
@@ -881,10 +897,28 @@ class KronLaplace(ParametricLaplace):
         if self.likelihood != "classification":
             raise NotImplementedError("adjacency gradient: classification likelihood")
         eng = self.backend.engine
+        if dense:
+            if candidates is not None:
+                raise ValueError("dense=True covers every pair: no candidates")
+            _dense_scope(eng, "KronLaplace.neg_marglik_adj_grad")
         value = -self._log_marginal_likelihood64()
         gB, gA = self._logdet_factor_gradients()
         gB = [0.5 * g for g in gB]  # neg marglik = H_factor * loss + 1/2 (logdet P - logdet P_0 + scatter)
         gA = [0.5 * g for g in gA]
+        if dense:
+            N = eng.num_nodes
+            G = torch.zeros(N, N, dtype=torch.float32, device=eng.device)
+            out_bar = torch.zeros(N, eng.dims[-1], dtype=torch.float32, device=eng.device)
+            rank, world = _dist_info(process_group)
+            for t, (X, y) in enumerate(train_loader):
+                if t % world != rank:
+                    continue
+                eng.adjgrad_batch_dense(X.to(eng.device), y.to(eng.device), gB, out_bar, G,
+                                        fork_exact=getattr(self.backend, "fork_exact_seed", True), loss_scale=self._H_factor)
+            if world > 1:
+                all_reduce_flat_([G, out_bar], process_group)
+            a_scale = len(train_loader) / len(train_loader.dataset)
+            return value, eng.adjgrad_finish_dense(out_bar, gA, a_scale, G)
         grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
         out_bar = torch.zeros(eng.num_nodes, eng.dims[-1], dtype=torch.float32, device=eng.device)
         rank, world = _dist_info(process_group)
@@ -1109,14 +1143,15 @@ class DiagLaplace(ParametricLaplace):
             w1, b1 = E2 @ w1, E2 @ b1
         return dict(S0=torch.cat([w0, b0], dim=1), S1=w1, kappa=b1)
 
-    def neg_marglik_adj_grad(self, train_loader, prior_precision=None, process_group=None, candidates=None):
+    def neg_marglik_adj_grad(self, train_loader, prior_precision=None, process_group=None, candidates=None, dense=False):
         """``-log_marginal_likelihood()`` of this fit and its gradient w.r.t. the adjacency -- what ``neg_marglik.backward()``
         leaves in ``model.adj.grad`` when the structure-learning loop runs with ``hessian_structure="diag"``, the shipped
         STE-GCN configuration (gnn/configs/original/stegcn_config.yaml:7; gnn/marglik_training.py:197-216; the fork's
         Jacobians keep the graph, laplace/curvature/curvature.py:89-130).  Same return values and candidate pairs as
         ``KronLaplace.neg_marglik_adj_grad``.  2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE (STEGraphSAGE),
         classification; the diagonal GGN is a sum over samples, so
-        the loader's batch boundaries do not matter and the ranks of a job split every batch by samples."""
+        the loader's batch boundaries do not matter and the ranks of a job split every batch by samples.  ``dense=True``: as
+        ``KronLaplace.neg_marglik_adj_grad`` (plain 2-layer GCN, ``(neg_marglik, grad [N, N])``)."""
         if self.H is None or not self.n_data:
             raise AttributeError("Laplace not fitted. Run fit() first.")
         if prior_precision is not None:
@@ -1126,6 +1161,10 @@ class DiagLaplace(ParametricLaplace):
         eng = getattr(self.backend, "engine", None)
         if eng is None or not hasattr(eng, "diag_adjgrad_batch") or eng.kind not in ("gcn", "sage"):
             raise NotImplementedError("adjacency gradient under a diagonal posterior: 2-layer GCN / GraphSAGE on the HIP backend")
+        if dense:
+            if candidates is not None:
+                raise ValueError("dense=True covers every pair: no candidates")
+            _dense_scope(eng, "DiagLaplace.neg_marglik_adj_grad")
         value = -self.log_marginal_likelihood()
         f = self._H_factor
         gamma = (0.5 * f / self.posterior_precision).to(torch.float32).contiguous()  # d(1/2 logdet P) / dH_p
@@ -1138,6 +1177,17 @@ class DiagLaplace(ParametricLaplace):
         sym = bool(getattr(self.model, "symmetric", False))
         cand = _adjacency_candidates(eng, candidates, sym)
         eng.set_likelihood("classification")
+        if dense:
+            G = torch.zeros(N, N, dtype=torch.float32, device=eng.device)
+            for X, y in train_loader:
+                M = X.shape[0]
+                lo, hi = M * rank // world, M * (rank + 1) // world
+                if hi > lo:
+                    eng.diag_adjgrad_batch_dense(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), gamma, out_bar, h1_bar,
+                                                 e_bar, G, loss_scale=f)
+            if world > 1:
+                all_reduce_flat_([G, out_bar, h1_bar, e_bar], process_group)
+            return value, eng.diag_adjgrad_finish_dense(out_bar, h1_bar, e_bar, G)
         for X, y in train_loader:
             # every term is a sum over samples: inside a job every rank takes its slice of every batch (a Cora-shaped loader has
             # ONE batch); a candidate pair sees a repeated node id through each slice's own multiplicity

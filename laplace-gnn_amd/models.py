@@ -10,6 +10,7 @@ Neighbour sampling (``num_sampled_nodes_per_hop``) needs an explicit ``sample_se
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -388,3 +389,146 @@ class STEGCN(GCN):
             eng.update_adjacency(self.adj_index[0][flip], self.adj_index[1][flip], want[flip])
             self.edge_index = eng.adj_to_edge_index()
         return n
+
+
+class LoRASTEGCN(GCN):
+    """The reference's low-rank structure-learning GCN (gnn/models/models.py:186-235) with the graph held by the HIP engine.
+
+    The reference propagates with ``normalize_adj(fill_diagonal_(BinarizeSTE(M, threshold), 1))``,
+    ``M = adj + (adj_lora_B @ adj_lora_A) * scaling`` (symmetric models: ``(M + M^T) / 2``), ``scaling = lora_alpha / r``.
+    Here ``adj`` is the base pattern (``adj_index`` [2, n] names its entries, values 1; ``requires_grad=False``, never
+    stepped -- the driver only insists that it exists, gnn/marglik_training.py:78) and lives on the device as a CSR pattern;
+    the engine's graph is always the binarisation of the current A, B (set when the engine is built, kept by ``apply_adj``).
+    Both LoRA names contain ``adj``: the Laplace parameter filter and the driver's weight optimizer drop them.
+
+        la.fit(loader)
+        model.adj_backward(la, loader)        # adj_lora_A.grad / adj_lora_B.grad <- neg_marglik.backward()
+        adj_opt.step(); model.apply_adj()     # adj_opt = SGD([adj_lora_A, adj_lora_B], lr=lr_adj, weight_decay=weight_decay_adj)
+        la.fit(loader)                        # the loop of gnn/marglik_training.py:97-100, 197-224
+
+    The driver's optimizer has no momentum (marglik_training.py:97-100) and its ``clip_grad_norm_(model.adj)`` does not touch A
+    and B.  The base ``adj`` is the given pattern as it is (the reference's ``reset_parameters`` copies the unsymmetrised
+    ``init_adj`` back, base_gnn.py:120-122); a symmetric model averages ``M`` and ``M^T`` before the threshold, so a one-sided
+    base edge enters at 0.5 + the averaged LoRA term.  Random draws: the convs are drawn at construction and A, B after them,
+    once; the reference re-draws the convs in its ``reset_parameters`` before A and B, so one seed gives different values
+    (goldens store the initial weights, A and B).  The gradient needs d(-marglik)/d adj on all N^2 pairs (``neg_marglik_adj_grad(..., dense=True)``), so graphs are
+    limited to a few tens of thousands of nodes -- the reference holds several dense N x N tensors itself."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, X, edge_index, r, lora_alpha,
+                 dropout_p: float = 0.5, act="relu", threshold: float = 0.5, symmetric: bool = False, **kwargs):
+        if kwargs.get("res") or kwargs.get("norm") not in (None, "none"):
+            raise NotImplementedError("LoRASTEGCN: res / norm are not supported (plain 2-layer GCN)")
+        if num_layers != 2:
+            raise NotImplementedError("LoRASTEGCN: num_layers must be 2 (the all-pairs adjacency gradient is 2-layer)")
+        if int(r) < 1:
+            raise ValueError("LoRASTEGCN: the rank r must be >= 1")
+        if int(r) > 64:
+            raise NotImplementedError("LoRASTEGCN: ranks above 64 are not supported (lgnn_lora_grad)")
+        kwargs.pop("update_adj", None)
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, X, edge_index, dropout_p=dropout_p, act=act,
+                         symmetric=symmetric, **kwargs)
+        self.threshold = float(threshold)
+        self.r = int(r)
+        self.lora_alpha = lora_alpha
+        self.scaling = self.lora_alpha / self.r
+        N = self.num_nodes
+        self._set_base(self.edge_index.cpu())
+        self.adj_lora_A = nn.Parameter(torch.zeros(self.r, N))
+        self.adj_lora_B = nn.Parameter(torch.zeros(N, self.r))
+        self.reset_lora_parameters()
+
+    def reset_lora_parameters(self):
+        nn.init.kaiming_uniform_(self.adj_lora_A, a=math.sqrt(5))  # models.py:211-225
+        nn.init.normal_(self.adj_lora_B)
+        self._engine = None
+
+    def _set_base(self, ei: torch.Tensor):
+        """The base pattern adj0 (``init_adj`` as given, models.py:205-209 + base_gnn.py:120-122): ``adj_index``, ``adj`` and
+        the int32 CSR the threshold kernel reads."""
+        N = self.num_nodes
+        keys = torch.unique(ei[0] * N + ei[1])
+        rows, cols = keys // N, keys % N
+        dev = getattr(self, "adj", None).device if isinstance(getattr(self, "adj", None), torch.Tensor) else torch.device("cpu")
+        self.register_buffer("adj_index", torch.stack([rows, cols]).to(dev))
+        self.adj = nn.Parameter(torch.ones(keys.numel(), device=dev), requires_grad=False)
+        rowptr = torch.zeros(N + 1, dtype=torch.int64)
+        rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=N), 0)
+        self.register_buffer("base_rowptr", rowptr.to(torch.int32).to(dev), persistent=False)
+        self.register_buffer("base_col", cols.to(torch.int32).contiguous().to(dev), persistent=False)
+        self.edge_index = torch.stack([rows, cols]).to(self.edge_index.device)
+        self._engine = None
+
+    @property
+    def engine(self) -> GraphEngine:
+        """The HIP context; a new one starts from the base graph and is re-thresholded at once (the initial A, B already push
+        pairs over the threshold: 17 % of the non-edges at N = 64, r = 4, lora_alpha = 16)."""
+        fresh = self._engine is None
+        eng = BaseGNN.engine.fget(self)
+        if fresh:
+            self._fresh_flips = self._threshold(eng)  # (against the base graph the engine was built from)
+        return eng
+
+    def _threshold(self, eng) -> int:
+        return eng.lora_threshold(self.base_rowptr, self.base_col, self.adj_lora_A, self.adj_lora_B, self.scaling,
+                                  self.threshold, self.symmetric)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """A reference checkpoint's dense 0/1 ``adj`` [N, N] becomes the base pattern; A and B load as they are.  The engine is
+        rebuilt (and re-thresholded) on next use.  This module's own checkpoints (1-D ``adj`` + ``adj_index``) rebuild the base
+        pattern from ``adj_index``."""
+        key = prefix + "adj"
+        adj = state_dict.get(key)
+        own_index = state_dict.get(prefix + "adj_index")
+        if adj is not None and adj.dim() == 1 and own_index is not None:
+            self._set_base(own_index.detach().cpu().to(torch.int64))
+        elif adj is not None and adj.dim() == 2:
+            if tuple(adj.shape) != (self.num_nodes, self.num_nodes):
+                error_msgs.append(f"adj has shape {tuple(adj.shape)}, expected ({self.num_nodes}, {self.num_nodes})")
+            elif not bool(((adj == 0) | (adj == 1)).all()):
+                error_msgs.append("LoRASTEGCN: the base adj must be binary (gnn/models/base_gnn.py:73)")
+            else:
+                self._set_base(adj.detach().cpu().nonzero().t().to(torch.int64))
+                state_dict[key] = self.adj.detach().clone()
+            if prefix + "adj_index" not in state_dict:
+                state_dict[prefix + "adj_index"] = self.adj_index
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+        self._engine = None
+
+    def full_adj(self) -> torch.Tensor:
+        """What the reference returns: the base adjacency (gnn/models/base_gnn.py:133-134), dense, small graphs only."""
+        out = torch.zeros(self.num_nodes, self.num_nodes, device=self.adj.device)
+        out[self.adj_index[0], self.adj_index[1]] = self.adj.detach()
+        return out
+
+    def binarized_adj(self) -> torch.Tensor:
+        """The graph the model currently propagates with (dense 0/1 with the self loops), small graphs only."""
+        return BaseGNN.full_adj(self)
+
+    @torch.no_grad()
+    def adj_backward(self, la, train_loader, process_group=None):
+        """``neg_marglik.backward()`` of the loop: ``adj_lora_A.grad += scaling B^T G``, ``adj_lora_B.grad += scaling G A^T`` with
+        G = d(-marglik)/d adj on all pairs (``neg_marglik_adj_grad(..., dense=True)``; lgnn_lora_grad).  Returns the negative
+        log marginal likelihood."""
+        eng = self.engine
+        N = self.num_nodes
+        part = 4 * self.r * N * ((N + 63) // 64)  # lgnn_lora_grad's partials of grad_A
+        limit = getattr(eng, "_ws_limit", None) or (32 << 30)
+        if part > limit:
+            raise NotImplementedError(f"LoRASTEGCN.adj_backward: {part} bytes of grad_A partials exceed the workspace limit "
+                                      f"({limit} bytes)")
+        value, G = la.neg_marglik_adj_grad(train_loader, process_group=process_group, dense=True)
+        gA, gB = eng.lora_grad(G, self.adj_lora_A, self.adj_lora_B, self.scaling)
+        for p, g in ((self.adj_lora_A, gA), (self.adj_lora_B, gB)):
+            p.grad = g if p.grad is None else p.grad + g
+        return value
+
+    @torch.no_grad()
+    def apply_adj(self) -> int:
+        """After the optimizer step (or any change of A / B): re-binarise and flip the engine's entries that changed side
+        (lgnn_lora_threshold).  Returns the number of directed entries flipped; a second call returns 0.  Without an engine (a
+        new model, after ``load_state_dict`` or ``.to()``) one is built from the base graph and thresholded: the flips are
+        counted against the base graph."""
+        if self._engine is None:
+            _ = self.engine
+            return int(self.__dict__.pop("_fresh_flips", 0))
+        return self._threshold(self._engine)
