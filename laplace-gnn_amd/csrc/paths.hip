@@ -198,6 +198,7 @@ struct YArgs {
   int debug;                // LGNN_FUSED_DEBUG (timing experiments only, results are wrong with bits 0 / 1): 1 no Gram, 2 no
                             // products, 4 product waves at priority 3, 8 Gram waves at priority 3, 16 all operand loads from sample 0 / node 0
   int no_bg;                // regression / nothing but the diagonal term: the beta / gamma products vanish
+  int gram_f32;             // LGNN_GRAM_F32: paths_fused_kernel's Gram on fp32 MFMAs instead of the bf16 pieces
 };
 
 // Paths staged per window.  26.6 % of the arxiv-shaped nodes have more than 16 paths, 12 % more than 20 (mean 13.7): every
@@ -924,6 +925,120 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
       }
 }
 
+// The same Gram on v_mfma_f32_32x32x16_bf16 (the default; LGNN_GRAM_F32=1 runs gram_role above).  Every fp32 tile value y is
+// split into three bf16 pieces, each rounded to nearest:  y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y - y0 - y1) = y - y0 - y1
+// (both differences are exact; each piece carries 8 of the 24 significand bits).  A product y z keeps six of the nine piece
+// products, y0 z0 + y0 z1 + y1 z0 + y0 z2 + y1 z1 + y2 z0: the three dropped ones are at most 2^-23 |y z| together and of either
+// sign (fp32 rounding level).  The K slots of an MFMA are (piece pair, class): lane half h holds the classes k0 + h + 2 m,
+// m = 0 .. 3, of a chunk of 8 tile rows, two slots per class in one register, and each column block is kept in three forms
+// (low half | high half):  U = (y0 | y1),  V = (y1 | y0),  S = (y0 | y2).  Per chunk and sub-tile (si, sj) three MFMAs:
+//     U[si] x U[sj] = y0 z0 + y1 z1,   S[si] x V[sj] = y0 z1 + y2 z0,   V[si] x S[sj] = y1 z0 + y0 z2
+// (A and B of one lane share the slot map, see the operand layout: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and
+// B[k = 8 (l >> 5) + j][col l & 31]).  Each register of the three forms is one v_cvt_pk_bf16_f32 of two fp32 values, so the
+// operands need no register moves: 7.5 vector instructions per value.  Rounding can take only a value above 3.39e38 to
+// infinity (its square overflows in fp32 anyway); a NaN or an infinity turns into NaN pieces (inf - inf): a non-finite input
+// gives a non-finite factor, as the fp32 role does.
+// 27 MFMAs of 32 cycles per chunk of 8 tile rows against gram_role's 68 of 16x16x4 fp32 (32 cycles each): 0.4x the matrix cycles.
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
+
+__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest, NaN stays NaN)
+  using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+  const bf16x2 v = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
+  return __builtin_bit_cast(uint32_t, v);
+}
+struct SplitBlk { u32x4v u, v, s; };  // the three forms of a column block for the lane's 4 classes of a chunk
+
+// the lane's four values of column block b in a chunk: rows 2 m (the lane half's row offset is in `p`)
+template <int W>
+__device__ __forceinline__ void split_load(const float* __restrict__ p, float (&x)[8][4]) {
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) x[b][m] = tiles256_uses<W>(b) ? p[2 * m * kYStride + b * 32] : 0.f;
+}
+__device__ __forceinline__ void split_block(const float (&y)[4], SplitBlk& o) {
+#pragma unroll
+  for (int m = 0; m < 4; m += 2) {
+    uint32_t p0 = pk_bf16(y[m], y[m + 1]);
+    asm("" : "+v"(p0));  // (keeps the two values' y0 in one cvt: hipcc otherwise converts and widens each on its own)
+    const float r1a = y[m] - __uint_as_float(p0 << 16), r1b = y[m + 1] - __uint_as_float(p0 & 0xffff0000u);
+    o.u[m] = pk_bf16(y[m], r1a);
+    o.u[m + 1] = pk_bf16(y[m + 1], r1b);
+    const float r2a = r1a - __uint_as_float(o.u[m] & 0xffff0000u), r2b = r1b - __uint_as_float(o.u[m + 1] & 0xffff0000u);
+    o.v[m] = pk_bf16(r1a, y[m]);
+    o.v[m + 1] = pk_bf16(r1b, y[m + 1]);
+    o.s[m] = pk_bf16(y[m], r2a);
+    o.s[m + 1] = pk_bf16(y[m + 1], r2b);
+  }
+}
+__device__ __forceinline__ f32x16 mfma_bf16(u32x4v a, u32x4v b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+template <int W>
+__device__ __forceinline__ void split_chunk(const float (&x)[8][4], f32x16 (&acc)[9]) {
+  SplitBlk f[8];
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+    if (tiles256_uses<W>(b)) split_block(x[b], f[b]);
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const SplitBlk &A = f[Tiles256<W>::si[s]], &B = f[Tiles256<W>::sj[s]];
+    acc[s] = mfma_bf16(A.u, B.u, acc[s]);
+    acc[s] = mfma_bf16(A.s, B.v, acc[s]);
+    acc[s] = mfma_bf16(A.v, B.s, acc[s]);
+  }
+}
+template <int W, bool LIST>
+__device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
+                                                FusedShared& sh, int64_t cnt, float* __restrict__ scratch) {
+  const int lane = threadIdx.x & 63;
+  f32x16 acc[9];
+#pragma unroll
+  for (int s = 0; s < 9; ++s)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+  const int nch = (a.R + 7) >> 3;  // chunks of 8 tile rows (rows past R are zero; 8 nch <= kYRows)
+  int32_t p0, p1;
+  node_range<LIST>(pptr, list, a.n0, cnt, 0, p0, p1);
+  PH_DECL;
+  if (a.debug & 8) __builtin_amdgcn_s_setprio(3);
+  const bool gwork = !(a.debug & 1);
+  for (int64_t i = 0; i < cnt; ++i) {
+    int32_t q0, q1;
+    node_range<LIST>(pptr, list, a.n0, cnt, i + 1, q0, q1);
+    while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
+    PH_MARK(6);
+    if (p1 > p0 && gwork) {
+      const float* __restrict__ base = &sh.y[i & 1][0][0] + (lane >> 5) * kYStride + (lane & 31);
+      float x[8][4];
+      split_load<W>(base, x);
+      for (int ck = 0; ck < nch; ++ck) {  // (wave-uniform trip count, straight-line body)
+        split_chunk<W>(x, acc);
+        // the next chunk's values are read while this chunk's MFMAs run (split_chunk has consumed x)
+        if (ck + 1 < nch) split_load<W>(base + (ck + 1) * 8 * kYStride, x);
+      }
+    }
+    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
+    PH_MARK(5);
+    p0 = q0; p1 = q1;
+  }
+  PH_FLUSH(4 + W, lane);
+  // accumulator layout of 32x32x16 (gram256.h's): column l & 31, rows (r & 3) + 8 (r >> 2) + 4 (l >> 5).  The part below the
+  // diagonal of a diagonal sub-tile is left out, as gram_role leaves it out (the symmetrising pass rewrites it)
+  const int64_t D = a.H;
+  const int l31 = lane & 31, lhi = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int64_t j = Tiles256<W>::sj[s] * 32 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t ii = Tiles256<W>::si[s] * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+      if (ii < D && j < D && (Tiles256<W>::si[s] != Tiles256<W>::sj[s] || ii <= j)) atomicAdd(&scratch[ii * D + j], acc[s][r]);
+    }
+  }
+}
+
 // LIST: the node loop runs over a device-side list of the nodes that have a path
 template <bool LIST>
 __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int32_t* __restrict__ pptr,
@@ -948,10 +1063,11 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   // (which half is which matters: see the kernel's header -- LGNN_FUSED_DEBUG bit 5 swaps them for the A/B run)
   const int role = (a.debug & 32) ? (hw ^ 4) : hw;
   switch (role) {
-    case 4: gram_role<0, LIST>(a, pptr, list, sh, cnt, scratch); break;
-    case 5: gram_role<1, LIST>(a, pptr, list, sh, cnt, scratch); break;
-    case 6: gram_role<2, LIST>(a, pptr, list, sh, cnt, scratch); break;
-    case 7: gram_role<3, LIST>(a, pptr, list, sh, cnt, scratch); break;
+    // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
+    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, cnt, scratch); break;
+    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<1, LIST>(a, pptr, list, sh, cnt, scratch); break;
+    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<2, LIST>(a, pptr, list, sh, cnt, scratch); break;
+    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<3, LIST>(a, pptr, list, sh, cnt, scratch); break;
     default:
       if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
         if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, cnt, role);
@@ -1280,6 +1396,10 @@ static int fused_debug() {  // timing experiments (see YArgs::debug); read per c
   const char* e = getenv("LGNN_FUSED_DEBUG");
   return e ? atoi(e) : 0;
 }
+static int gram_f32() {  // LGNN_GRAM_F32=1: the fused kernel's Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
+  const char* e = getenv("LGNN_GRAM_F32");
+  return e && atoi(e) != 0 ? 1 : 0;
+}
 // persistent workgroups of paths_fused_kernel: one per CU (149 KB of LDS each); LGNN_FUSED_WGS (dev) leaves CUs to other streams
 static int64_t fused_workgroups() {
   static const int64_t n = getenv("LGNN_FUSED_WGS") ? std::max<int64_t>(1, atoll(getenv("LGNN_FUSED_WGS"))) : 256;
@@ -1370,7 +1490,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     y.coef = ws.path_coef.as<float>(); y.bg = ws.path_bg.as<float>(); y.zeros = ws.path_zeros.as<float>();
     y.mask = h->fc.mask_bits[0].as<uint32_t>(); y.mask_words = int(cdiv(H, 32));
     y.W1 = h->W[1]; y.w1_ld = int(H); y.Y = nullptr; y.N = N; y.n0 = nb; y.n1 = ne; y.M = M; y.H = int(H); y.c0 = int(c0); y.R = int(R);
-    y.cb = int(cb); y.n_coef = M; y.no_bg = no_bg ? 1 : 0; y.debug = fused_debug();
+    y.cb = int(cb); y.n_coef = M; y.no_bg = no_bg ? 1 : 0; y.debug = fused_debug(); y.gram_f32 = gram_f32();
     if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel(s) of the KFAC path (bench.py roofline)
     if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
     else hipLaunchKernelGGL(paths_fused_kernel<false>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
@@ -1471,7 +1591,7 @@ int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int 
     y.W1 = h->W[1] + H; y.w1_ld = int(2 * H);  // the neighbour half: the alpha term of the neighbour paths
     y.Y = nullptr; y.N = N; y.n0 = nb; y.n1 = ne; y.M = T; y.H = int(H); y.c0 = int(c0); y.R = int(R);
     y.cb = int(cb); y.n_coef = T; y.no_bg = 0;  // (the one-hot alpha paths go through the beta product: never skipped)
-    y.debug = fused_debug();
+    y.debug = fused_debug(); y.gram_f32 = gram_f32();
     if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the KFAC path (bench.py roofline)
     if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
     else hipLaunchKernelGGL(paths_fused_kernel<false>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
