@@ -103,81 +103,13 @@ int launch_sddmm(const Csr& m, int64_t nrows, const int32_t* rows, const int32_t
 // The two consumers of g0bar's rows in ONE pass over the entries of the active rows a of P (they gather the same rows):
 //     out[(a, b)] += sum_c <u_c[a], R_c[b]>                      (the SDDMM of the step g0 = P^T u)
 //     U_c[a]       = dact[a] * sum_b P[a, b] R_c[b]               (ubar: the SpMM of the step behind it; overwrites u)
-// One wave per row; PC planes at a time: the row's u_c and the running sums stay in registers, every gathered row of R
-// is used for both.  Halves the gather traffic of the two steps and skips the 42 % of rows whose u is zero.
-template <int PC>
-__global__ __launch_bounds__(256) void sddmm_spmm_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                         const float* __restrict__ val, const int32_t* __restrict__ rows,
-                                                         const int32_t* __restrict__ nrows_dev, float* __restrict__ U,
-                                                         const float* __restrict__ R, int64_t N, int64_t width,
-                                                         int64_t nplanes, const float* __restrict__ dact,
-                                                         float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int c0 = lane * 4;
-  const bool col_ok = c0 < width;  // width % 4 == 0, <= 256 (launcher)
-  const bool odd = (lane & 1) != 0;
-  const int64_t total = rows ? int64_t(*nrows_dev) : N;
-  const int64_t plane = N * width;
-  for (int64_t w = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); w < total; w += int64_t(gridDim.x) * 4) {
-    const int64_t a = rows ? int64_t(rows[w]) : w;
-    const int32_t s = rowptr[a], e = rowptr[a + 1];
-    float4 dm = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (col_ok) dm = *reinterpret_cast<const float4*>(dact + a * width + c0);
-    for (int64_t pc0 = 0; pc0 < nplanes; pc0 += PC) {
-      float4 u[PC], acc[PC];
-#pragma unroll
-      for (int c = 0; c < PC; ++c) {
-        acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        u[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (col_ok && pc0 + c < nplanes) u[c] = *reinterpret_cast<const float4*>(U + (pc0 + c) * plane + a * width + c0);
-      }
-      // two entries per step: 2 * PC row slices in flight per wave, and ONE shuffle tree for both dot products (after the
-      // first exchange even lanes carry entry p, odd lanes entry p + 1)
-      for (int32_t p = s; p < e; p += 2) {
-        const bool two = p + 1 < e;
-        const int64_t b0 = col[p], b1 = two ? col[p + 1] : b0;
-        const float v0 = val[p], v1 = two ? val[p + 1] : 0.f;
-        float4 x0[PC], x1[PC];
-#pragma unroll
-        for (int c = 0; c < PC; ++c) {
-          x0[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-          x1[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (col_ok && pc0 + c < nplanes) {
-            x0[c] = *reinterpret_cast<const float4*>(R + (pc0 + c) * plane + b0 * width + c0);
-            x1[c] = *reinterpret_cast<const float4*>(R + (pc0 + c) * plane + b1 * width + c0);
-          }
-        }
-        float d0 = 0.f, d1 = 0.f;
-#pragma unroll
-        for (int c = 0; c < PC; ++c) {
-          acc[c].x = fmaf(v0, x0[c].x, acc[c].x); acc[c].y = fmaf(v0, x0[c].y, acc[c].y);
-          acc[c].z = fmaf(v0, x0[c].z, acc[c].z); acc[c].w = fmaf(v0, x0[c].w, acc[c].w);
-          acc[c].x = fmaf(v1, x1[c].x, acc[c].x); acc[c].y = fmaf(v1, x1[c].y, acc[c].y);
-          acc[c].z = fmaf(v1, x1[c].z, acc[c].z); acc[c].w = fmaf(v1, x1[c].w, acc[c].w);
-          d0 += u[c].x * x0[c].x + u[c].y * x0[c].y + u[c].z * x0[c].z + u[c].w * x0[c].w;
-          d1 += u[c].x * x1[c].x + u[c].y * x1[c].y + u[c].z * x1[c].z + u[c].w * x1[c].w;
-        }
-        float d = (odd ? d1 : d0) + __shfl_xor(odd ? d0 : d1, 1);
-#pragma unroll
-        for (int o = 2; o < 64; o <<= 1) d += __shfl_xor(d, o);
-        if (lane == 0) out[p] += d;
-        if (lane == 1 && two) out[p + 1] += d;
-      }
-#pragma unroll
-      for (int c = 0; c < PC; ++c)
-        if (col_ok && pc0 + c < nplanes)
-          *reinterpret_cast<float4*>(U + (pc0 + c) * plane + a * width + c0) =
-              make_float4(dm.x * acc[c].x, dm.y * acc[c].y, dm.z * acc[c].z, dm.w * acc[c].w);
-    }
-  }
-}
-
-// Plane-major form of the kernel above: grid (row groups, planes), one wave per (row, plane).  The kernel above gathers
-// PC planes at once -- a working set of PC * 173 MB at the arxiv shape, far beyond the 256 MiB Infinity Cache, so its
-// gathers go to HBM (3.3 TB/s measured); here all CUs work on ONE plane at a time (blocks are dispatched x first), which
-// stays cache resident while its rows are gathered ~15 times each.  Eight entries per step; their eight dot products
-// go through one shuffle tree (three halving exchanges leave lane l with entry l % 8, three more finish it); the
-// planes' contributions to out[p] meet through float atomics.
+// Every gathered row of R is used for both: halves the gather traffic of the two steps and skips the 42 % of rows whose u
+// is zero.  Plane major: grid (row groups, planes), one wave per (row, plane).  A wave that gathers k planes at once has a
+// working set of k * 173 MB at the arxiv shape, far beyond the 256 MiB Infinity Cache, so its gathers go to HBM (3.3 TB/s
+// measured); here all CUs work on ONE plane at a time (blocks are dispatched x first), which stays cache resident while its
+// rows are gathered ~15 times each.  Eight entries per step; their eight dot products go through one shuffle tree (three
+// halving exchanges leave lane l with entry l % 8, three more finish it); the planes' contributions to out[p] meet through
+// float atomics.
 __global__ __launch_bounds__(256) void sddmm_spmm_pm_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                             const float* __restrict__ val, const int32_t* __restrict__ rows,
                                                             const int32_t* __restrict__ nrows_dev, float* __restrict__ U,
@@ -1635,8 +1567,7 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
   // over the compacted list (0.9 ms instead of 4.4 ms): rows that are not active hold whatever the buffers held and are
   // never looked at.  Candidate pairs can name any row: then everything is defined on all N rows as before.
   const bool compact = K == 0 && dense == nullptr && H == 256 && h->fc.mask_bits[0].p != nullptr && backgemm_supported(C, H, true) &&
-                       (N + 1) * H * 4 < (int64_t(1) << 31) && getenv("LGNN_ADJ_ALL_ROWS") == nullptr &&
-                       getenv("LGNN_ADJ_CHUNKED") == nullptr;
+                       (N + 1) * H * 4 < (int64_t(1) << 31);
   const int64_t u_stride = compact ? (N + 1) * H : N * H;  // the compacted backward GEMM wants a spare row per plane
   LGNN_CALL(h->ws.top.reserve(size_t(N) * CC * 4 + 16));
   LGNN_CALL(h->ws.active.reserve(size_t(N)));
@@ -1702,7 +1633,7 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
     sa.rowptr = h->PT.rowptr; sa.col = h->PT.col; sa.val = val_act; sa.nrows = N;
     sa.in = U; sa.in_ld = H; sa.in_plane_stride = u_stride; sa.out = G0; sa.out_ld = H; sa.out_plane_stride = N * H;
     sa.width = H; sa.out_act = -1;
-    if (H % 4 == 0 && H <= 256 && N * H * 4 < (int64_t(1) << 32) - (int64_t(1) << 14) && cc < 65536) {
+    if (H % 4 == 0 && H <= 256 && N * H * 4 < (int64_t(1) << 32) - (int64_t(1) << 14)) {
       hipLaunchKernelGGL(spmm256_skip_kernel, dim3(unsigned(cdiv(N, 4)), unsigned(cc)), dim3(256), 0, s, h->PT.rowptr, h->PT.col,
                          val_act, N, U, u_stride, H, G0);
       LGNN_HIP_CHECK(hipGetLastError());
@@ -1724,14 +1655,8 @@ int kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
     if (H % 4 == 0 && H <= 256) {
       // (candidate pairs reach g1bar at arbitrary rows, so ubar is then needed everywhere, not on the active rows only)
       const int32_t* rows = (K > 0 || dense) ? nullptr : h->ws.act_list.as<int32_t>();
-      static const bool chunked = getenv("LGNN_ADJ_CHUNKED") != nullptr;  // dev: the 8-planes-per-wave kernel
-      if (!chunked && cc < 65536)
-        hipLaunchKernelGGL(sddmm_spmm_pm_kernel, dim3(unsigned(cdiv(N, 4)), unsigned(cc)), dim3(256), 0, s, h->P.rowptr, h->P.col,
-                           h->P.val, rows, h->ws.act_count.as<int32_t>(), U, u_stride, G0B, N, H, h->fc.dact0.as<float>(), grad_P);
-      else
-        hipLaunchKernelGGL(sddmm_spmm_kernel<8>, dim3(unsigned(std::min<int64_t>(cdiv(N, 4), 8192))), dim3(256), 0, s,
-                           h->P.rowptr, h->P.col, h->P.val, rows, h->ws.act_count.as<int32_t>(), U, G0B, N, H, cc,
-                           h->fc.dact0.as<float>(), grad_P);
+      hipLaunchKernelGGL(sddmm_spmm_pm_kernel, dim3(unsigned(cdiv(N, 4)), unsigned(cc)), dim3(256), 0, s, h->P.rowptr, h->P.col,
+                         h->P.val, rows, h->ws.act_count.as<int32_t>(), U, u_stride, G0B, N, H, h->fc.dact0.as<float>(), grad_P);
       LGNN_HIP_CHECK(hipGetLastError());
     } else {
       LGNN_CALL(launch_sddmm(h->P, N, h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(), U, H, N * H, G0B, H, N * H,

@@ -308,26 +308,13 @@ __global__ __launch_bounds__(256) void diag_first_layer_kernel(
   }
 }
 
-// ---- the same contraction, rows by LDS-DMA, the wave-uniform operand by v_readlane --------------------------------------
-// diag_first_layer_kernel above stages a chunk of entries, waits for it, computes, and starts over.  Measured at the Cora
-// shape (0.131 ms for a ~10-20 us VALU floor): (1) per chunk one exposed round trip for the entries (row pointer ->
-// column / value) and one for their rows; (2) in the FMA loop every thread reads the 16 act' values of its wave with
-// four ds_read_b128 that all 64 lanes address identically -- 1 KB of LDS bandwidth per instruction for 64 B of data,
-// 3 GB of LDS reads per launch -- and waits for LDS twice per entry (closing mark, then data).  Here
-// (a) ALL entries of a slab are resolved up front, in parallel, into LDS (one chain per workgroup, not one per chunk);
-// (b) the entries' rows -- E for the lanes' 64 input columns, act' (or, for the entry that closes a GCN sample, q) for
-//     the tile's 64 hidden units -- are copied global -> LDS by the DMA path (global_load_lds, one dword per lane: the
-//     [entry][64 lanes] layout, no data registers) into a ring of NBUF slots, NBUF - 1 chunks ahead of the FMAs, behind
-//     counted s_waitcnt vmcnt -- every wave issues the same number of copies per chunk (padding entries copy a zero
-//     word) so that the count is a compile-time constant -- and one raw barrier per chunk;
-// (c) both rows are read ONE dword per lane (conflict free, 512 B per entry and wave instead of 4.3 KB); the hidden-unit
-//     operand, which is the same for all lanes, is taken out of the row register with v_readlane (an SGPR operand of the
-//     FMA): 16 readlanes + 8 packed FMAs per entry, no LDS broadcast, and the next entry's two dwords are loaded while
-//     the current one computes.
-// (Tried and measured slower: the uniform operand through the scalar cache, s_load_dwordx16 per entry -- 0.111 ms: the
-//  scalar data cache has little miss parallelism, and its out-of-order returns force lgkmcnt(0) waits.)
-__device__ float g_diag_consts[2] = {0.f, 1.f};
-
+// ---- staging of the matrix-core kernels below: entries resolved up front, rows by LDS-DMA --------------------------------
+// diag_first_layer_kernel above stages a chunk of entries, waits for it, computes, and starts over: per chunk one exposed
+// round trip for the entries (row pointer -> column / value) and one for their rows.  The kernels below
+// (a) resolve ALL entries of a slab up front, in parallel, into LDS (one chain per workgroup, not one per chunk);
+// (b) copy the entries' rows global -> LDS by the DMA path (global_load_lds, no data registers) into a ring of NBUF slots,
+//     NBUF - 1 chunks ahead of the products, behind counted s_waitcnt vmcnt -- every wave issues the same number of copies
+//     per chunk (padding entries copy zeros) so that the count is a compile-time constant -- and one raw barrier per chunk.
 __device__ __forceinline__ void lds_dma4(const float* src, float* lds_dst) {
   __builtin_amdgcn_global_load_lds(src, reinterpret_cast<__attribute__((address_space(3))) void*>(
                                             reinterpret_cast<uintptr_t>(lds_dst)), 4, 0, 0);
@@ -342,176 +329,16 @@ template <int NI, int MAXA> __device__ __forceinline__ void wait_chunks(int ahea
     else wait_chunks<NI, MAXA - 1>(ahead);
   }
 }
-__device__ __forceinline__ float lane_value(float x, int l) {  // x of lane l (wave uniform l) as a scalar operand
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-}
 
 constexpr int kDiagMaxEntries = 512;  // entries resolved per pass (a slab of 64 Cora samples has ~380)
-
-template <int HAS_SELF, int DCH, int NBUF>
-__global__ __launch_bounds__(256) void diag_first_layer_dma_kernel(
-    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ val,
-    const int64_t* __restrict__ idx, int64_t M, int64_t slab, FeatView E, const float* __restrict__ dact,
-    int64_t H, const float* __restrict__ q, float* __restrict__ diag_w, float* __restrict__ diag_b) {
-  constexpr int ARR = HAS_SELF ? 5 : 2;  // arrays per slot: E rows, act' rows (GCN closing entry: its q row) [, 3 q rows]
-  constexpr int BUF = ARR * DCH * 64;    // floats per ring slot
-  constexpr int NI = (DCH / 4) * ARR;    // DMA instructions per wave and chunk
-  constexpr int MAXE = kDiagMaxEntries;
-  static_assert(NBUF >= 2 && NBUF <= 4 && (NBUF - 2) * NI <= 63 && (DCH & (DCH - 1)) == 0, "ring: vmcnt is a 6-bit counter");
-  // ONE LDS object (hipcc drains vmcnt before reads of a second one): ring | entries {column, weight, closing mark} | slab tables
-  __shared__ float smem[NBUF * BUF + 4 * (MAXE + 2) + 65 + 64 + 64 + 63];
-  float* __restrict__ ring = smem;
-  // (read as scalars: a vector-typed LDS read makes hipcc wait for every LDS-DMA copy in flight)
-  int32_t* __restrict__ smeta = reinterpret_cast<int32_t*>(smem + NBUF * BUF);
-  int32_t* __restrict__ soff = reinterpret_cast<int32_t*>(smem + NBUF * BUF + 4 * (MAXE + 2));
-  int32_t* __restrict__ snode = soff + 65;
-  int32_t* __restrict__ sbase = snode + 64;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int jg = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t i = int64_t(blockIdx.x) * 64 + lane;
-  const int64_t j0 = int64_t(blockIdx.y) * 64;
-  const bool i_ok = i <= E.width, j_ok = j0 + lane < H;
-  const int64_t m_begin = int64_t(blockIdx.z) * slab, m_end = min(M, m_begin + slab);
-  const int ns = int(m_end - m_begin);  // <= 64
-  if (tid < 64) {
-    int32_t len = 0, node = -1, base = 0;
-    if (tid < ns) {
-      const int64_t n = idx[m_begin + tid];
-      if (n >= 0 && n < E.nrows) { node = int32_t(n); base = rowptr[n]; len = rowptr[n + 1] - base + 1; }
-    }
-    snode[tid] = node;
-    sbase[tid] = base;
-    int32_t incl = len;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int32_t t = __shfl_up(incl, o);
-      if (lane >= o) incl += t;
-    }
-    soff[tid + 1] = incl;
-    if (tid == 0) soff[0] = 0;
-  }
-  __syncthreads();
-  const int32_t etot = soff[64];
-  float acc[JPT], T[JPT];
-#pragma unroll
-  for (int jj = 0; jj < JPT; ++jj) { acc[jj] = 0.f; T[jj] = 0.f; }
-  const float* __restrict__ zero = g_diag_consts;
-  // this lane's column of E: a feature column, the bias column (rowsum(P) per node, or the constant 1), or nothing
-  const float* __restrict__ ecol = !i_ok ? nullptr : (i < E.width ? E.base + i : E.bias_col);
-  const int64_t estride = !i_ok ? 0 : (i < E.width ? E.ld : (E.bias_col ? 1 : 0));
-  if (i_ok && i == E.width && !E.bias_col) ecol = g_diag_consts + 1;
-  const float* __restrict__ dcol = dact + j0 + lane;               // this lane's hidden unit of the act' rows ...
-  const float* __restrict__ qcol = q + m_begin * H + j0 + lane;    // ... and of the slab's q rows
-  const int jb = jg * JPT;  // this wave's 16 hidden units sit in lanes jb .. jb + 15 of a row register
-
-  for (int32_t sb0 = 0; sb0 < etot; sb0 += MAXE) {
-    const int ne = min(MAXE, int(etot - sb0));
-    for (int e = tid; e < ne + 2; e += 256) {  // (a) every entry of this pass: sample by bisection, then column / value
-      const int32_t g = sb0 + e;
-      struct { int32_t x, y, z; } m = {0, 0, -1};  // past the end: two entries of weight 0 for the look-ahead
-      if (e < ne) {
-        int lo = 0, hi = ns;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (soff[mid] <= g) lo = mid; else hi = mid; }
-        const int32_t r = g - soff[lo], len = soff[lo + 1] - soff[lo] - 1;
-        m.x = snode[lo]; m.z = lo;  // the virtual entry: the node itself, closes sample lo, weight 0
-        if (r < len) { const int32_t p = sbase[lo] + r; m.x = col[p]; m.y = __builtin_bit_cast(int, val[p]); m.z = -1; }
-      }
-      smeta[4 * e] = m.x; smeta[4 * e + 1] = m.y; smeta[4 * e + 2] = m.z;
-    }
-    __syncthreads();
-    const int nch = (ne + DCH - 1) / DCH;
-    auto issue = [&](int c) {  // (b) chunk c -> ring slot c % NBUF; wave jg copies the rows of entries jg, jg + 4, ...
-      float* __restrict__ slot = ring + (c % NBUF) * BUF;
-#pragma unroll
-      for (int k = 0; k < DCH / 4; ++k) {
-        const int el = jg + 4 * k, e = c * DCH + el, em = min(e, MAXE + 1);
-        const bool ok = e < ne;
-        const int64_t v = smeta[4 * em];
-        const int mk = smeta[4 * em + 2];
-        const bool nb = ok && mk < 0, cl = ok && mk >= 0;
-        lds_dma4(((nb || (HAS_SELF && cl)) && i_ok) ? ecol + v * estride : zero, slot + el * 64);
-        if (HAS_SELF) {
-          lds_dma4((ok && j_ok) ? dcol + v * H : zero, slot + (DCH + el) * 64);
-#pragma unroll
-          for (int z = 0; z < 3; ++z)
-            lds_dma4((cl && j_ok) ? qcol + int64_t(mk) * H + int64_t(z) * M * H : zero, slot + ((2 + z) * DCH + el) * 64);
-        } else {  // the entry that closes a GCN sample reads no act' row: its row is the sample's q row
-          lds_dma4(j_ok ? (nb ? dcol + v * H : (cl ? qcol + int64_t(mk) * H : zero)) : zero, slot + (DCH + el) * 64);
-        }
-      }
-    };
-    for (int c = 0; c < NBUF - 1 && c < nch; ++c) issue(c);
-    // (c) entry g computes while entry g + 1's dwords are on their way from LDS
-    float ev0 = 0.f, r0 = 0.f, a0 = 0.f, ev1 = 0.f, r1 = 0.f, a1 = 0.f;
-    int mk0 = -1, rmk1 = -1, g = 0;
-    auto fetch = [&]() {  // ring step at a chunk's first entry; the next entry's dwords (same chunk) start their way
-      const int el = g & (DCH - 1), c = g / DCH;
-      const float* __restrict__ slot = ring + (c % NBUF) * BUF;
-      if (el == 0) {
-        const int ahead = min(NBUF - 2, nch - 1 - c);  // chunks after c whose copies are in flight
-        if (NBUF >= 4 && ahead >= 2) wait_vmcnt<(NBUF >= 4 ? 2 : 0) * NI>();
-        else if (ahead == 1) wait_vmcnt<NI>();
-        else wait_vmcnt<0>();
-        asm volatile("s_barrier" ::: "memory");  // chunk c has landed for all waves; chunk c - 1 is consumed
-        if (c + NBUF - 1 < nch) issue(c + NBUF - 1);
-        ev0 = slot[lane]; r0 = slot[DCH * 64 + lane];  // (a chunk's first rows are read behind its barrier)
-        a0 = __builtin_bit_cast(float, smeta[4 * g + 1]);
-      }
-      if (el + 1 < DCH) {
-        ev1 = slot[(el + 1) * 64 + lane]; r1 = slot[(DCH + el + 1) * 64 + lane];
-        a1 = __builtin_bit_cast(float, smeta[4 * (g + 1) + 1]);
-      }
-      rmk1 = smeta[4 * (g + 1) + 2];
-      return slot + el * 64 + lane;
-    };
-    auto rotate = [&]() { ev0 = ev1; r0 = r1; a0 = a1; mk0 = __builtin_amdgcn_readfirstlane(rmk1); ++g; };
-    mk0 = __builtin_amdgcn_readfirstlane(smeta[2]);
-    while (g < ne) {
-      while (mk0 < 0 && g < ne) {  // neighbour entries: T += act'(h_1[v]) (x) a E[v]
-        fetch();
-        const float ea = ev0 * a0;
-#pragma unroll
-        for (int jj = 0; jj < JPT; ++jj) T[jj] = fmaf(lane_value(r0, jb + jj), ea, T[jj]);
-        rotate();
-      }
-      if (g < ne) {  // the entry that closes its sample folds the finished T into the accumulator
-        const float* __restrict__ mine = fetch();
-        if (HAS_SELF) {
-          const float q0v = mine[2 * DCH * 64], q1v = mine[3 * DCH * 64], q2v = mine[4 * DCH * 64];
-#pragma unroll
-          for (int jj = 0; jj < JPT; ++jj) {
-            const float sf = lane_value(r0, jb + jj) * ev0;
-            acc[jj] += lane_value(q0v, jb + jj) * T[jj] * T[jj] + 2.f * lane_value(q1v, jb + jj) * sf * T[jj] +
-                       lane_value(q2v, jb + jj) * sf * sf;
-            T[jj] = 0.f;
-          }
-        } else {
-#pragma unroll
-          for (int jj = 0; jj < JPT; ++jj) { acc[jj] = fmaf(lane_value(r0, jb + jj) * T[jj], T[jj], acc[jj]); T[jj] = 0.f; }
-        }
-        rotate();
-      }
-    }
-    __syncthreads();  // the next pass overwrites the entry table and the ring
-  }
-  if (!i_ok) return;
-#pragma unroll
-  for (int jj = 0; jj < JPT; ++jj) {
-    const int64_t j = j0 + jb + jj;
-    if (j < H) {
-      if (i < E.width) atomicAdd(&diag_w[j * E.width + i], acc[jj]);
-      else atomicAdd(&diag_b[j], acc[jj]);
-    }
-  }
-}
 
 // ---- GCN: the per-sample outer products on the matrix cores ---------------------------------------------------------------
 // T_n = sum_v P[n, v] act'(h_1[v]) (x) E[v] is a [64 hidden x 64 input] product with K = the sample's row length: with
 // v_mfma_f32_32x32x2_f32 a pair of entries is one K step, lane l supplying A[j = l & 31][k = l >> 5] = act'(h_1[v_k, j]) and
 // B[k][i = l & 31] = P[n, v_k] E[v_k, i] -- BOTH operands are one dword per lane straight from the staged rows; no operand
-// is wave uniform, so none of the broadcast traffic (LDS b128, scalar cache, v_readlane: see above) exists.  The VALU
-// kernel's counters at the Cora shape (profiles/r03_cora_sq_counters_valu.txt): 30 M VALU instructions for 5.6 M packed
-// FMAs -- 11 M of them v_readlane -- 54 % VALU busy for 0.12 ms; here the VALU only folds a finished sample,
+// is wave uniform, so no broadcast traffic (LDS b128 reads that all lanes address alike, scalar cache, v_readlane) exists.
+// The earlier VALU kernel's counters at the Cora shape (profiles/r03_cora_sq_counters_valu.txt): 30 M VALU instructions
+// for 5.6 M packed FMAs -- 11 M of them v_readlane -- 54 % VALU busy for 0.12 ms; here the VALU only folds a finished sample,
 // acc += q[j] T[j, i]^2 on the accumulator layout, 64 packed instructions per sample.  Measured at the Cora shape
 // (1 299 samples, 42 slabs x 6 column blocks = 252 workgroups): 0.067 ms against 0.131 ms for the round-2 kernel; by
 // switching phases off (DESIGN.md has the table): prologue 8 us, entry resolution + operand reads 21 us, row copies 7 us,
@@ -522,7 +349,7 @@ __global__ __launch_bounds__(256) void diag_first_layer_dma_kernel(
 //   * E = [P X | rowsum(P) | 0] is ONE padded matrix (the bias column sits in the first pad column: context.hip
 //     build_px), so a row's 256-column block is one 16-byte-per-lane LDS-DMA copy;
 //   * samples are padded to an even number of entries (weight 0) so that a K step never straddles two samples;
-//   * entries resolved up front, rows through the NBUF-slot DMA ring with counted vmcnt waits, as in the VALU kernel.
+//   * entries resolved up front, rows through the NBUF-slot DMA ring with counted vmcnt waits (see above).
 __device__ float g_diag_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 using f32x16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
 
@@ -1132,14 +959,13 @@ int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, u
   // (measured at the Cora shape: 1 024 - 2 048 workgroups are the optimum -- fewer lengthen the per-workgroup chain,
   //  more multiply the float atomics of the flush: 0.13 ms at 2 048, 0.26 ms at 8 192)
   int64_t slab = std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, 2048)));
-  // First-layer kernel: 2 = matrix cores (GCN), 1 = LDS-DMA rows + v_readlane operand, 0 = the register-staged kernel of
-  // round 2.  GraphSAGE takes 0: its self path needs three q rows and the node's own rows per closing entry, and at the
-  // arxiv shape the staged kernel is the faster one there (2.02 against 2.21 ms per batch; at the Cora shape 0.131 / 0.122).
-  // LGNN_DIAG_STAGED / LGNN_DIAG_VALU force 0 / 1 for either family (A/B runs, tests).
-  const int route = getenv("LGNN_DIAG_STAGED") != nullptr ? 0
-                    : getenv("LGNN_DIAG_VALU") != nullptr ? 1 : (h->kind == LGNN_KIND_SAGE ? 0 : 2);
-  // the LDS-DMA kernel hides the chain: longer slabs, fewer atomics (~768 workgroups, three per CU)
-  if (route != 0) slab = std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, 768)));
+  // First-layer kernel: the matrix-core kernels for GCN, the register-staged kernel of round 2 for GraphSAGE (its self path
+  // needs three q rows and the node's own rows per closing entry).  LGNN_DIAG_STAGED forces the staged kernel for GCN too
+  // (tests compare the two).
+  const bool staged = getenv("LGNN_DIAG_STAGED") != nullptr || h->kind == LGNN_KIND_SAGE;
+  // the matrix-core kernels size their own slabs; behind them the last-layer kernel takes longer slabs, fewer atomics
+  // (~768 workgroups, three per CU)
+  if (!staged) slab = std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, 768)));
   if (const char* e = getenv("LGNN_DIAG_SLAB")) slab = std::max<int64_t>(1, std::min<int64_t>(64, atoll(e)));
   const unsigned nslab = unsigned(cdiv(M, slab));
 
@@ -1168,25 +994,18 @@ int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, u
       feat_views(h, 0, E);
       const dim3 grid{unsigned(cdiv(E.width + 1, 64)), unsigned(cdiv(H, 64)), nslab};
       if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the diagonal path (bench.py roofline)
-      if (route == 0) {  // the register-staged kernel
+      if (staged) {
         if (has_self)
           hipLaunchKernelGGL(diag_first_layer_kernel<1>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab,
                              E, h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
         else
           hipLaunchKernelGGL(diag_first_layer_kernel<0>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab,
                              E, h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-      } else if (route == 1 || has_self) {
-        if (has_self)
-          hipLaunchKernelGGL((diag_first_layer_dma_kernel<1, 16, 3>), grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val,
-                             idx, M, slab, E, h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-        else
-          hipLaunchKernelGGL((diag_first_layer_dma_kernel<0, 16, 4>), grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val,
-                             idx, M, slab, E, h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
       } else {
         // GCN: the matrix-core kernels; E = [P X | rowsum(P) | 0] is one padded matrix (context.hip build_px)
         LGNN_REQUIRE(E.ld >= E.width + 1 && E.ld % 4 == 0, "internal: P X without its bias column");
         const int64_t ncb = cdiv(E.width + 1, kTileCols);
-        if (ncb >= 4 && H % 4 == 0 && getenv("LGNN_DIAG_ATOMIC") == nullptr) {
+        if (ncb >= 4 && H % 4 == 0) {
           // wide inputs: owned output tiles, long slabs, plain-store partials + a fixed-order reduction (no atomics)
           const int64_t gyt = cdiv(H, 64);
           int64_t nsl = std::max<int64_t>(1, std::min<int64_t>(cdiv(256, ncb * gyt), cdiv(M, 16)));  // ~ one workgroup per CU

@@ -14,8 +14,8 @@
 //   rocsolver_sstedc    divide and conquer on T (eigenvectors of the tridiagonal matrix), one call per factor
 //   backtransform_kernel  y = H_0 H_1 ... H_{n-2} z, one wave per eigenvector, reflectors streamed from L2
 // (The caller pads smaller factors to the common size with a decoupled negative diagonal block, see matrix.py: a column
-// whose off-diagonal part is exactly zero gets tau = 0 and costs one barrier.)  LGNN_EIGH_LIBRARY=1 forces the library
-// path, which larger factors always take.
+// whose off-diagonal part is exactly zero gets tau = 0 and costs one barrier.)  Larger factors take the library path
+// (above 512 rows, or above 256 rows when n % 4 != 0).
 #include <cstdio>
 
 #include <rocsolver/rocsolver.h>
@@ -433,7 +433,7 @@ int stedc_all(int64_t n, int64_t batch, hipStream_t s) {
     if (!g_join[i]) LGNN_HIP_CHECK(hipEventCreateWithFlags(&g_join[i], hipEventDisableTiming));
   }
   if (!g_fork) LGNN_HIP_CHECK(hipEventCreateWithFlags(&g_fork, hipEventDisableTiming));
-  if (branches == 1 || getenv("LGNN_EIGH_ONE_STREAM") != nullptr) {
+  if (branches == 1) {
     for (int i = 0; i < branches; ++i) LGNN_CALL(stedc_branch(i, branches, n, batch, s));
     return 0;
   }
@@ -472,7 +472,7 @@ extern "C" int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W,
   hipStream_t s = static_cast<hipStream_t>(stream);
   // (neither branch touches the shared g_handle: the divide and conquer chains have handles of their own, g_bh, and the
   //  library path g_eig_handle -- queued main-stream work that uses g_handle is never rebound to a side stream from here)
-  if (n <= TN && n >= 2 && getenv("LGNN_EIGH_LIBRARY") == nullptr) {
+  if (n <= TN && n >= 2) {
     LGNN_CALL(g_e.reserve(size_t(batch) * n * 4));
     LGNN_CALL(g_v.reserve(size_t(batch) * n * TN * 4));
     LGNN_CALL(g_tau.reserve(size_t(batch) * n * 4));
@@ -488,7 +488,7 @@ extern "C" int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W,
     LGNN_HIP_CHECK(hipGetLastError());
     return 0;
   }
-  if (n > TN && n <= 2 * TN && n % 4 == 0 && getenv("LGNN_EIGH_LIBRARY") == nullptr) {
+  if (n > TN && n <= 2 * TN && n % 4 == 0) {
     // 256 < n <= 512: n - 256 columns by the streaming kernel, the trailing 256 x 256 block by the register-resident one,
     // divide and conquer on the tridiagonal matrix (library), back-transform: four launches + the library's chain
     LGNN_CALL(g_e.reserve(size_t(batch) * n * 4));

@@ -24,13 +24,6 @@ namespace lgnn {
 
 namespace {
 
-// ablation switches (tools/sweep_fused.py) exist in `make DEV=1` builds only: the production kernels test nothing in their loops
-#ifdef LGNN_DEV
-#define LGNN_DBG(a) ((a).debug)
-#else
-#define LGNN_DBG(a) 0
-#endif
-
 constexpr int KT256 = 32;  // rows per block
 constexpr int UNR = 12;    // neighbour rows in flight per lane and per pipelined row
 constexpr int DEPTH = 3;   // rows whose gathers are in flight per wave
@@ -130,8 +123,8 @@ __device__ __forceinline__ void mfma_wave(const FusedArgs& a, const float* __res
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
   for (int64_t i = 0; i <= nb; ++i) {
-    if (i > 0 && LGNN_DBG(a) != 1) gram256_block<W, KT256 / 2>(tiles + ((i - 1) & 1) * KT256 * 256, lane, acc);
-    if (LGNN_DBG(a) != 4) __syncthreads();
+    if (i > 0) gram256_block<W, KT256 / 2>(tiles + ((i - 1) & 1) * KT256 * 256, lane, acc);
+    __syncthreads();
   }
   gram256_flush<W>(a.scratch, a.width, lane, acc);
 }
@@ -258,7 +251,7 @@ __global__ __launch_bounds__(512, 2) void spmm_gram256_kernel(FusedArgs a) {
     load_block_entries(0, rp_next, re_next, sl_cur, ent);
     rp_next = load_rp(1, re_next);
     for (int64_t i = 0; i <= nb; ++i) {
-      if (i < nb && LGNN_DBG(a) != 2 && LGNN_DBG(a) != 4) {
+      if (i < nb) {
         int64_t plane, rb;
         block_coords(i, plane, rb);
         const float* in = a.in + plane * a.in_plane_stride;
@@ -365,7 +358,7 @@ __global__ __launch_bounds__(512, 2) void spmm_gram256_kernel(FusedArgs a) {
         if constexpr (LIST) nd_cur = nd_next;
         if constexpr (HUB) { sl_cur = sl_next; sl_next = load_slot(i + 2); }
       }
-      if (LGNN_DBG(a) != 4) __syncthreads();
+      __syncthreads();
     }
   } else {
     // ------------------------------------------------ MFMA waves
@@ -381,11 +374,7 @@ __global__ __launch_bounds__(512, 2) void spmm_gram256_kernel(FusedArgs a) {
 
 }  // namespace
 
-int launch_spmm_gram256(const FusedArgs& a_in, hipStream_t s) {
-  FusedArgs a = a_in;
-#ifdef LGNN_DEV  // make DEV=1: ablation switches for tools/sweep_fused.py (1 no MFMA, 2 no gather, 4 no barriers)
-  if (const char* dbg = getenv("LGNN_FUSED_DEBUG")) a.debug = atoi(dbg);
-#endif
+int launch_spmm_gram256(const FusedArgs& a, hipStream_t s) {
   LGNN_REQUIRE(a.nrows * a.in_ld * 4 < (int64_t(1) << 32) - 4096, "plane too large for 32-bit buffer offsets");
   const int64_t nblocks = cdiv(a.nrows, KT256) * a.nplanes;
   const unsigned grid = unsigned(std::min<int64_t>(nblocks, 256));  // one persistent workgroup per CU

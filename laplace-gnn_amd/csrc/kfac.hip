@@ -249,18 +249,12 @@ __global__ __launch_bounds__(1024) void seed_spmm_gram_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ val, int64_t N, int C,
     const int32_t* __restrict__ pos, const float* __restrict__ probs, const float* __restrict__ logits,
     const int32_t* __restrict__ mult, int fork_exact, float* __restrict__ g, const int32_t* __restrict__ act_list,
-    const int32_t* __restrict__ act_count, int cb, int ce, float* __restrict__ scratch, int ldb, int debug_arg,
+    const int32_t* __restrict__ act_count, int cb, int ce, float* __restrict__ scratch, int ldb,
     // hub rows cut into slices (see top_tasks_* below).  mode 0: act_list holds node ids, a node's task is its whole row;
     // mode 1: act_list holds (node or -1 - node, begin, end) triples -- a negative node marks a SLICE of a hub row, whose
     // partial tile is added to hub_tiles[long_slot[node]] instead of being finished here; mode 2: act_list holds the ids of
     // the sliced hubs, their summed tiles are read back from hub_tiles and finished (planes + Gram)
     int mode, const int32_t* __restrict__ long_slot, float* __restrict__ hub_tiles, const uint8_t* __restrict__ active) {
-#ifdef LGNN_DEV  // ablation switches exist in `make DEV=1` builds only
-  const int debug = debug_arg;
-#else
-  (void)debug_arg;
-  constexpr int debug = 0;
-#endif
   constexpr int NT = NBLK * (NBLK + 1) / 2;
   extern __shared__ float sm[];
   const int lane = threadIdx.x & 63;
@@ -411,7 +405,7 @@ __global__ __launch_bounds__(1024) void seed_spmm_gram_kernel(
         __builtin_amdgcn_wave_barrier();  // the next task overwrites the tile
         continue;
       }
-      if (g && debug != 1) {
+      if (g) {
         int r = r0, k = k0;
         float* __restrict__ gn = g + (int64_t(cb) * N + n) * C;
         const int64_t plane = N * C;
@@ -444,7 +438,7 @@ __global__ __launch_bounds__(1024) void seed_spmm_gram_kernel(
         }
       }
       const float* __restrict__ xb = buf + (lane >> 4) * ldb + (lane & 15);
-      for (int kk = 0; kk < (debug == 2 ? 0 : rp); kk += 4) {
+      for (int kk = 0; kk < rp; kk += 4) {
         float x[NBLK];
 #pragma unroll
         for (int b = 0; b < NBLK; ++b) x[b] = colok[b] ? xb[kk * ldb + b * 16] : 0.f;
@@ -478,7 +472,7 @@ __global__ __launch_bounds__(1024) void seed_spmm_gram_kernel(
       tt -= NBLK - bi;
     }
     const int i = bi * 16 + ii, j = bj * 16 + jj;
-    if (i <= j && j < C && debug != 3) atomicAdd(&scratch[int64_t(i) * C + j], red[q]);
+    if (i <= j && j < C) atomicAdd(&scratch[int64_t(i) * C + j], red[q]);
   }
 }
 
@@ -540,18 +534,13 @@ int seed_spmm_gram_launch(lgnn_ctx* h, bool fork_exact, float* g, int64_t cb, in
     attr_set = true;
   }
   const int per_cu = int(std::max<size_t>(1, std::min<size_t>(2048 / (64 * waves), (158 * 1024) / smem)));
-  int debug = 0;
-#ifdef LGNN_DEV  // make DEV=1: ablation switches (1 no plane stores, 2 no MFMA, 3 no global atomics)
-  if (const char* dbg = getenv("LGNN_SEED_DEBUG")) debug = atoi(dbg);
-#endif
   const int fe = h->lik == LGNN_LIK_REGRESSION ? 2 : (fork_exact ? 1 : 0);
   LGNN_CALL(long_rows_ensure(h, s));
-  static const bool no_slices = getenv("LGNN_TOP_NO_SLICES") != nullptr;  // dev: A/B of the sliced hubs
-  if (h->n_top_multi <= 0 || no_slices) {
+  if (h->n_top_multi <= 0) {
     hipLaunchKernelGGL(seed_spmm_gram_kernel<NBLK>, dim3(unsigned(256 * per_cu)), dim3(64 * waves), smem, s, h->PT.rowptr,
                        h->PT.col, h->PT.val, h->N, C, h->ws.pos.as<int32_t>(), h->ws.probs.as<float>(),
                        h->fc.out.as<float>(), h->ws.mult.as<int32_t>(), fe, g, h->ws.act_list.as<int32_t>(),
-                       h->ws.act_count.as<int32_t>(), int(cb), int(ce), scratch, ldb, debug, 0,
+                       h->ws.act_count.as<int32_t>(), int(cb), int(ce), scratch, ldb, 0,
                        static_cast<const int32_t*>(nullptr), static_cast<float*>(nullptr), static_cast<const uint8_t*>(nullptr));
     LGNN_HIP_CHECK(hipGetLastError());
     return 0;
@@ -575,14 +564,14 @@ int seed_spmm_gram_launch(lgnn_ctx* h, bool fork_exact, float* g, int64_t cb, in
   hipLaunchKernelGGL(seed_spmm_gram_kernel<NBLK>, dim3(unsigned(256 * per_cu)), dim3(64 * waves), smem, s, h->PT.rowptr,
                      h->PT.col, h->PT.val, h->N, C, h->ws.pos.as<int32_t>(), h->ws.probs.as<float>(),
                      h->fc.out.as<float>(), h->ws.mult.as<int32_t>(), fe, g, h->top_tasks.as<int32_t>(),
-                     h->top_task_count.as<int32_t>(), int(cb), int(ce), scratch, ldb, debug, 1, h->long_slot.as<int32_t>(),
+                     h->top_task_count.as<int32_t>(), int(cb), int(ce), scratch, ldb, 1, h->long_slot.as<int32_t>(),
                      h->top_hub_tiles.as<float>(), h->ws.active.as<uint8_t>());
   // finishing launch: one wave per sliced hub (its count is a property of the graph: a constant in device memory)
   const unsigned fin_blocks = unsigned(std::min<int64_t>(cdiv(h->n_top_multi, waves), 256 * per_cu));
   hipLaunchKernelGGL(seed_spmm_gram_kernel<NBLK>, dim3(fin_blocks), dim3(64 * waves), smem, s, h->PT.rowptr, h->PT.col,
                      h->PT.val, h->N, C, h->ws.pos.as<int32_t>(), h->ws.probs.as<float>(), h->fc.out.as<float>(),
                      h->ws.mult.as<int32_t>(), fe, g, h->top_multi.as<int32_t>(), h->top_multi.as<int32_t>() + h->n_top_multi, int(cb), int(ce),
-                     scratch, ldb, debug, 2, h->long_slot.as<int32_t>(), h->top_hub_tiles.as<float>(),
+                     scratch, ldb, 2, h->long_slot.as<int32_t>(), h->top_hub_tiles.as<float>(),
                      h->ws.active.as<uint8_t>());
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
@@ -1089,8 +1078,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
             a.self_rows = h->ws.active.as<uint8_t>();
             a.mask_bits = h->fc.mask_bits[l - 1].as<uint32_t>();
             a.mask_words = int(cdiv(d, 32));
-            static const bool no_list = getenv("LGNN_SAGE_NO_ROW_LIST") != nullptr;  // dev: A/B of the row list
-            if (!store && plan.fuse[l] && !no_list) {
+            if (!store && plan.fuse[l]) {
               // g_{l-1} = act' * (dcat_self + P^T dcat_neigh) can be non-zero on the batch nodes and their neighbours only
               // (the columns of the batch nodes' P rows): the fused kernel visits just those rows
               LGNN_CALL(h->ws.out_flags.reserve(size_t(N)));

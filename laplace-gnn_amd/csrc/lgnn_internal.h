@@ -239,7 +239,8 @@ struct FusedArgs {
   const uint8_t* self_rows; const uint32_t* mask_bits; int mask_words;
   int64_t width;     // D <= DT
   float* scratch;    // [D, D]
-  int debug;         // dev experiments: 1 = skip MFMAs, 2 = skip gathers
+  int unused_;       // (keeps the fields below at their kernel-argument offsets: shifted by 8 bytes, hipcc merges the hub
+                     //  instances' scalar argument loads differently and spills SGPRs in spmm_gram256_kernel)
   // 256-wide kernel: rows with more than 64 stored entries arrive finished from long_rows_spmm (longrows.hip):
   // long_slot[row] = slot in hub (-1: ordinary row), hub [plane][n_long][width]
   const int32_t* long_slot; const float* hub; int64_t hub_plane_stride; int64_t n_long;

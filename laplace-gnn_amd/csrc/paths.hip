@@ -41,10 +41,6 @@
 #include "gram256.h"
 #include "lgnn_internal.h"
 
-#ifndef LGNN_PABL
-#define LGNN_PABL 0
-#endif
-
 namespace lgnn {
 
 namespace {
@@ -195,8 +191,8 @@ struct YArgs {
   int H, c0, R;
   int cb;                   // first class of the coefficient table's slots (the call's class range starts there)
   int64_t n_coef;           // rows of the coefficient table
-  int debug;                // LGNN_FUSED_DEBUG (timing experiments only, results are wrong with bits 0 / 1): 1 no Gram, 2 no
-                            // products, 4 product waves at priority 3, 8 Gram waves at priority 3, 16 all operand loads from sample 0 / node 0
+  int unused_;              // (keeps the fields below at their kernel-argument offsets: hipcc merges the argument loads
+                            //  by offset, and shifted by 4 bytes paths_fused_kernel spills more SGPRs)
   int no_bg;                // regression / nothing but the diagonal term: the beta / gamma products vanish
   int gram_f32;             // LGNN_GRAM_F32: paths_fused_kernel's Gram on fp32 MFMAs instead of the bf16 pieces
 };
@@ -484,18 +480,6 @@ __device__ __forceinline__ void lds_publish(int* c, int value, int lane) {
   if (lane == 0) *reinterpret_cast<volatile int*>(c) = value;
 }
 
-#ifdef LGNN_DEV  // make DEV=1: per-wave cycle counts of the fused kernel's phases (s_memtime), printed by paths_phase_report()
-__device__ unsigned long long g_phase[8][8];
-struct Ph { unsigned long long t, acc[8]; };
-#define PH_DECL Ph ph; ph.t = __builtin_amdgcn_s_memtime(); for (int k_ = 0; k_ < 8; ++k_) ph.acc[k_] = 0
-#define PH_MARK(k) do { const unsigned long long ph_n = __builtin_amdgcn_s_memtime(); ph.acc[k] += ph_n - ph.t; ph.t = ph_n; } while (0)
-#define PH_FLUSH(wave, lane) do { if ((lane) == 0) for (int k_ = 0; k_ < 8; ++k_) atomicAdd(&g_phase[wave][k_], ph.acc[k_]); } while (0)
-#else
-#define PH_DECL
-#define PH_MARK(k)
-#define PH_FLUSH(wave, lane)
-#endif
-
 // path range [p0, p1) of the i-th node of this workgroup (entry blockIdx.x + i * gridDim.x of the list of nodes with paths,
 // or of the whole range).  Wave uniform.  `pptr` / `list` are kernel parameters of their own (__restrict__): read through the
 // argument struct hipcc cannot prove them read-only and loads them with VECTOR loads followed by vmcnt(0) -- a drain of
@@ -581,10 +565,6 @@ __device__ __forceinline__ void p_load(const PTables& tb, const PMeta& mt, int s
   const uint32_t oc = uint32_t(__shfl(int(mt.oc), src)) + pl.oc;
   const uint32_t om = uint32_t(__shfl(int(mt.om), src)) + pl.om;
   o.w = __uint_as_float(uint32_t(__shfl(int(mt.w), src)));
-#if LGNN_PABL == 2  // (timing experiment: no operand loads)
-  asm volatile("" :: "v"(oc), "v"(om));
-  return;
-#endif
   bload4<0>(o.ca[0], oc, tb.coef);
   if constexpr (!NOBG) {
     const uint32_t ob = uint32_t(__shfl(int(mt.ob), src)) + pl.ob;
@@ -641,10 +621,6 @@ __device__ __forceinline__ void p_keep(const PCur& c) {
 // the 36 (NOBG: 12) MFMAs of one step;  D: col = i, row = 4 k + r
 template <bool NOBG>
 __device__ __forceinline__ void p_mfma(const PCur& c, f32x4v (&t1)[3][4], f32x4v (&y2)[3][4]) {
-#if LGNN_PABL == 1  // (timing experiment: the step's MFMAs are not issued)
-  p_keep<NOBG>(c);
-  return;
-#endif
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -707,13 +683,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   const int lane = threadIdx.x & 63;
   const int H = a.H;
   const bool path_wave = 64 * cg < H;  // (H <= 192: the last product wave has no columns)
-  PH_DECL;
-  if (a.debug & 4) __builtin_amdgcn_s_setprio(3);
   if (!path_wave) return;  // (its ready counter was set to "everything" at the kernel's top)
-  if (a.debug & 2) {       // (timing experiment: no products)
-    lds_publish(&sh.ready[cg], INT32_MAX, lane);
-    return;
-  }
   PLane pl;
   const int li = lane & 15;
   pl.kq = lane >> 4;
@@ -775,32 +745,21 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       // A's loads: the NL youngest outstanding may be B's (the first pair of a chunk: B's and the three path loads -- there
       // the count also waits for B's first half, issued a whole pair earlier)
       p_wait<NOBG, NL>(A);
-      PH_MARK(4);
       p_xform<NOBG, HI>(A, pl, cA);
       p_keep<NOBG>(cB);  // (cB's MFMAs may still be queued: cA must not be prepared into their operand registers)
-      PH_MARK(0);
       p_load<NOBG>(tb, mx, sx, pl, A);
       p_mfma<NOBG>(cA, t1, y2);
-      PH_MARK(1);
       p_wait<NOBG, NL>(B);  // (younger: A's refill)
-      PH_MARK(4);
       p_xform<NOBG, HI>(B, pl, cB);
       p_keep<NOBG>(cA);  // (likewise)
-      PH_MARK(0);
       p_load<NOBG>(tb, mx, sx + 1, pl, B);
       p_mfma<NOBG>(cB, t1, y2);  // (unconditional: see the role's header)
-      PH_MARK(1);
     }
     if (lastc) {
       // tile i & 1 was last read by the Gram of node i - 2: every Gram wave must have counted i - 1 nodes
       if (i >= 2)
         while (lds_min4(sh.done) < int(i) - 1) __builtin_amdgcn_s_sleep(2);
-      PH_MARK(3);
-#if LGNN_PABL == 3  // (timing experiment: no tile write)
-      if (false) {
-#else
       if (node_has && col_ok) {
-#endif
         // Y[n] = W_1 (.) T1 + Y2.  Rows past the launch's classes come out as the zeros they already are (their coefficients
         // and their rows of W_1 are zero): one branch around twelve unconditional 16-byte stores.
         float (*ytile)[kYStride] = sh.y[i & 1];
@@ -823,7 +782,6 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) { t1[t][ct] = f32x4v{0.f, 0.f, 0.f, 0.f}; y2[t][ct] = f32x4v{0.f, 0.f, 0.f, 0.f}; }
       node_has = false;
-      PH_MARK(2);
     }
     // rotate the chunk stream (the paths issued at the top are older than the 2 NL loads of the last pair's refills)
     meta_finish<2 * NL>(q0f, q1f, lane, row_bytes, mask_bytes, mf2);
@@ -831,7 +789,6 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
     q0n = q0f; q1n = q1f; lastn = lastf; mn = mf2;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the refills past the last chunk
-  PH_FLUSH(cg, lane);
 }
 
 // The Gram wave W: its 9 upper 32 x 32 sub-tiles of gram256.h, each as 2 x 2 tiles of v_mfma_f32_16x16x4_f32 (the lower tile
@@ -875,16 +832,12 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
   const int nk = (a.R + 3) >> 2;  // tile rows four at a time (rows past R are zero)
   int32_t p0, p1;
   node_range<LIST>(pptr, list, a.n0, cnt, 0, p0, p1);
-  PH_DECL;
-  if (a.debug & 8) __builtin_amdgcn_s_setprio(3);
-  const bool gwork = !(a.debug & 1);
   for (int64_t i = 0; i < cnt; ++i) {
     int32_t q0, q1;
     node_range<LIST>(pptr, list, a.n0, cnt, i + 1, q0, q1);
     // node i's tile: every product wave must have published i + 1 nodes
     while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
-    PH_MARK(6);
-    if (p1 > p0 && gwork) {
+    if (p1 > p0) {
       const float* __restrict__ base = &sh.y[i & 1][0][0] + (lane >> 4) * kYStride + (lane & 15);
       float xa[8][2], xb[8][2];
       gram16_load<W>(base, xa);
@@ -902,10 +855,8 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
       }
     }
     lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
-    PH_MARK(5);
     p0 = q0; p1 = q1;
   }
-  PH_FLUSH(4 + W, lane);
   // accumulator layout of 16x16x4: column l & 15, rows 4 (l >> 4) + r
   const int64_t D = a.H;
   const int li = lane & 15, lq = lane >> 4;
@@ -1001,15 +952,11 @@ __device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* _
   const int nch = (a.R + 7) >> 3;  // chunks of 8 tile rows (rows past R are zero; 8 nch <= kYRows)
   int32_t p0, p1;
   node_range<LIST>(pptr, list, a.n0, cnt, 0, p0, p1);
-  PH_DECL;
-  if (a.debug & 8) __builtin_amdgcn_s_setprio(3);
-  const bool gwork = !(a.debug & 1);
   for (int64_t i = 0; i < cnt; ++i) {
     int32_t q0, q1;
     node_range<LIST>(pptr, list, a.n0, cnt, i + 1, q0, q1);
     while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
-    PH_MARK(6);
-    if (p1 > p0 && gwork) {
+    if (p1 > p0) {
       const float* __restrict__ base = &sh.y[i & 1][0][0] + (lane >> 5) * kYStride + (lane & 31);
       float x[8][4];
       split_load<W>(base, x);
@@ -1020,10 +967,8 @@ __device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* _
       }
     }
     lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
-    PH_MARK(5);
     p0 = q0; p1 = q1;
   }
-  PH_FLUSH(4 + W, lane);
   // accumulator layout of 32x32x16 (gram256.h's): column l & 31, rows (r & 3) + 8 (r >> 2) + 4 (l >> 5).  The part below the
   // diagonal of a diagonal sub-tile is left out, as gram_role leaves it out (the symmetrising pass rewrites it)
   const int64_t D = a.H;
@@ -1060,9 +1005,8 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   const int64_t stride = gridDim.x;
   const int64_t nn = LIST ? int64_t(__builtin_amdgcn_readfirstlane(*a.n_list)) : a.n1 - a.n0;
   const int64_t cnt = nn > int64_t(blockIdx.x) ? (nn - blockIdx.x + stride - 1) / stride : 0;
-  // (which half is which matters: see the kernel's header -- LGNN_FUSED_DEBUG bit 5 swaps them for the A/B run)
-  const int role = (a.debug & 32) ? (hw ^ 4) : hw;
-  switch (role) {
+  // (which half is which matters: see the kernel's header)
+  switch (hw) {
     // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
     case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, cnt, scratch); break;
     case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<1, LIST>(a, pptr, list, sh, cnt, scratch); break;
@@ -1070,11 +1014,11 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
     case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<3, LIST>(a, pptr, list, sh, cnt, scratch); break;
     default:
       if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
-        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, cnt, role);
-        else product_role<LIST, false, true>(a, pptr, list, sh, cnt, role);
+        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, cnt, hw);
+        else product_role<LIST, false, true>(a, pptr, list, sh, cnt, hw);
       } else {
-        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, cnt, role);
-        else product_role<LIST, false, false>(a, pptr, list, sh, cnt, role);
+        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, cnt, hw);
+        else product_role<LIST, false, false>(a, pptr, list, sh, cnt, hw);
       }
       break;
   }
@@ -1332,10 +1276,12 @@ int two_hop_ensure(lgnn_ctx* h, hipStream_t s) {
   h->two_hop_max = double(host[1]);
   return 0;
 }
+// The path route pays while a full batch expects at most this many paths per destination node: arxiv's 13.7 take it, the
+// power-law graph's 24x the node count keep the class planes (forced there: 183.7 ms against 107.2 ms with planes)
+constexpr double kPathsPerNodeLimit = 24.0;
 bool paths_pay(const lgnn_ctx* h, int64_t M) {
-  static const double limit = getenv("LGNN_PATHS_PER_NODE") ? atof(getenv("LGNN_PATHS_PER_NODE")) : 24.0;  // dev: move the switch
   const double N = double(h->N);
-  return h->two_hop >= 0 && h->two_hop / N * double(M) / N <= limit;
+  return h->two_hop >= 0 && h->two_hop / N * double(M) / N <= kPathsPerNodeLimit;
 }
 
 bool paths_supported(int kind, int L, const int64_t* dims, int act, int64_t nnz) {
@@ -1361,23 +1307,6 @@ int launch_gram256_stream(const float* Y, int64_t ld, int64_t rows, int64_t widt
   return 0;
 }
 
-#ifdef LGNN_DEV
-// make DEV=1: print and clear the phase counters (called from lgnn_destroy when LGNN_PHASE_REPORT is set)
-void paths_phase_report() {
-  unsigned long long host[8][8];
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_phase), sizeof(host)) != hipSuccess) return;
-  static const char* names[8] = {"P: operand prep", "P: loads + MFMA issue", "P: Y write + publish", "P: drain + wait for tile buffer", "P: operand wait", "G: Gram + publish", "G: wait for tile", "-"};
-  fprintf(stderr, "paths_fused_kernel phase cycles (s_memtime ticks, summed over workgroups and launches)\n");
-  for (int k = 0; k < 8; ++k) {
-    fprintf(stderr, "  %-14s", names[k]);
-    for (int w = 0; w < 8; ++w) fprintf(stderr, " %12llu", host[w][k]);
-    fprintf(stderr, "\n");
-  }
-  unsigned long long zero[8][8] = {};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_phase), zero, sizeof(zero));
-}
-#endif
-
 // The nodes of [nb, ne) that have a path, as a device-side list (GraphSAGE: 65 % of the nodes at the arxiv shape; a short last
 // batch of a GCN: 70 %): the fused kernel's node loop, its barriers and its staging pipeline then only see those.
 static int path_node_list(lgnn_ctx* h, int64_t nb, int64_t ne, hipStream_t s) {
@@ -1392,19 +1321,13 @@ static int path_node_list(lgnn_ctx* h, int64_t nb, int64_t ne, hipStream_t s) {
   return compact_flags(ws.path_flags.as<uint8_t>(), n, ws.path_nodes.as<int32_t>(), ws.path_nnodes.as<int32_t>(), ws.select_tmp, s);
 }
 
-static int fused_debug() {  // timing experiments (see YArgs::debug); read per call
-  const char* e = getenv("LGNN_FUSED_DEBUG");
-  return e ? atoi(e) : 0;
-}
 static int gram_f32() {  // LGNN_GRAM_F32=1: the fused kernel's Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
   const char* e = getenv("LGNN_GRAM_F32");
   return e && atoi(e) != 0 ? 1 : 0;
 }
-// persistent workgroups of paths_fused_kernel: one per CU (149 KB of LDS each); LGNN_FUSED_WGS (dev) leaves CUs to other streams
-static int64_t fused_workgroups() {
-  static const int64_t n = getenv("LGNN_FUSED_WGS") ? std::max<int64_t>(1, atoll(getenv("LGNN_FUSED_WGS"))) : 256;
-  return n;
-}
+// persistent workgroups of paths_fused_kernel: one per CU (149 KB of LDS each).  Leaving CUs to the side stream's eigensolver
+// did not help (252 / 248 / 240 workgroups: 50.6 / 51.5 / 52.4 ms per GraphSAGE fit)
+constexpr int64_t kFusedWorkgroups = 256;
 
 // B_0 scratch += sum over the class columns [cb, ce) of this batch (see the file header).  Needs batch_prologue's
 // probabilities / multiplicities / positions and the cached forward (logits, mask bits).
@@ -1490,10 +1413,10 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     y.coef = ws.path_coef.as<float>(); y.bg = ws.path_bg.as<float>(); y.zeros = ws.path_zeros.as<float>();
     y.mask = h->fc.mask_bits[0].as<uint32_t>(); y.mask_words = int(cdiv(H, 32));
     y.W1 = h->W[1]; y.w1_ld = int(H); y.Y = nullptr; y.N = N; y.n0 = nb; y.n1 = ne; y.M = M; y.H = int(H); y.c0 = int(c0); y.R = int(R);
-    y.cb = int(cb); y.n_coef = M; y.no_bg = no_bg ? 1 : 0; y.debug = fused_debug(); y.gram_f32 = gram_f32();
+    y.cb = int(cb); y.n_coef = M; y.no_bg = no_bg ? 1 : 0; y.gram_f32 = gram_f32();
     if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel(s) of the KFAC path (bench.py roofline)
-    if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
-    else hipLaunchKernelGGL(paths_fused_kernel<false>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, dim3(unsigned(std::min<int64_t>(ne - nb, kFusedWorkgroups))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    else hipLaunchKernelGGL(paths_fused_kernel<false>, dim3(unsigned(std::min<int64_t>(ne - nb, kFusedWorkgroups))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
     LGNN_HIP_CHECK(hipGetLastError());
     if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += R; }
   }
@@ -1591,10 +1514,10 @@ int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int 
     y.W1 = h->W[1] + H; y.w1_ld = int(2 * H);  // the neighbour half: the alpha term of the neighbour paths
     y.Y = nullptr; y.N = N; y.n0 = nb; y.n1 = ne; y.M = T; y.H = int(H); y.c0 = int(c0); y.R = int(R);
     y.cb = int(cb); y.n_coef = T; y.no_bg = 0;  // (the one-hot alpha paths go through the beta product: never skipped)
-    y.debug = fused_debug(); y.gram_f32 = gram_f32();
+    y.gram_f32 = gram_f32();
     if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the KFAC path (bench.py roofline)
-    if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
-    else hipLaunchKernelGGL(paths_fused_kernel<false>, dim3(unsigned(std::min<int64_t>(ne - nb, fused_workgroups()))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, dim3(unsigned(std::min<int64_t>(ne - nb, kFusedWorkgroups))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    else hipLaunchKernelGGL(paths_fused_kernel<false>, dim3(unsigned(std::min<int64_t>(ne - nb, kFusedWorkgroups))), dim3(512), 0, s, y, y.pptr, y.list, scratch);
     LGNN_HIP_CHECK(hipGetLastError());
     if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += R; }
   }

@@ -740,7 +740,6 @@ class KronLaplace(ParametricLaplace):
         self._side_stream = getattr(self, "_side_stream", None)
         # (see _snapshot_large_input_factors; single process, fresh factors, and no exact-key cache for the same factor)
         self._early_ok = (override and rank_world[1] == 1 and self.cache_decompositions and self._inplace_backend()
-                          and os.environ.get("LGNN_NO_EARLY_EIG", "") in ("", "0")
                           and self._decompose_cache(train_loader, override)[0] is None)
         if override:
             self.H_facs = None
