@@ -440,7 +440,7 @@ __device__ __forceinline__ void part_mfma(const float (&x)[8], f32x16 (&acc)[HI 
 // The headline route (round 4): everything of a node on one CU, ONE persistent 512-thread workgroup per CU whose eight waves
 // have two ROLES.  The hardware deals a workgroup's waves round-robin to the CU's four SIMDs, so hardware waves g and g + 4
 // share a SIMD -- and its one matrix pipe:
-//   waves 4 .. 7, the PRODUCT waves (one per SIMD): wave 4 + cg owns the columns [64 cg, 64 cg + 64) of Y[n] for all <= 48
+//   waves 0 .. 3, the PRODUCT waves (one per SIMD): wave cg owns the columns [64 cg, 64 cg + 64) of Y[n] for all <= 48
 //       classes of the launch.  Per step of FOUR paths: three 16-byte loads of the paths' coefficient rows (A operands: lane
 //       (i, k) = class slot i of path k, the four class tiles of a slot side by side in the table row), two 16-byte loads of
 //       the table rows b_m, g_m (B operands: lane (i, k) = columns 64 cg + 4 i .. + 3 of path k -- the four 16-column MFMA
@@ -448,25 +448,46 @@ __device__ __forceinline__ void part_mfma(const float (&x)[8], f32x16 (&acc)[HI 
 //       (3 class tiles x 4 column tiles x (alpha, beta, gamma)).  No LDS staging, no window, no restaging of hubs: the
 //       operands of step s + 1 are in flight while the MFMAs of step s issue, across node boundaries (a node's triples
 //       (m, v, w) arrive with ONE coalesced load a node ahead and are handed to the lanes with ds_bpermute).
-//       Y[n] = W_1 (.) T1 + Y2 goes to one of TWO LDS tiles [40][256] with 16-byte stores.
-//   waves 0 .. 3, the GRAM waves: S += Y[n - 1]^T Y[n - 1] from the other tile into register-resident upper-triangular
-//       accumulators (the 36 sub-tiles of gram256.h, 9 per wave, 144 accumulator registers), nothing else.
-// ONE barrier per node.  The product wave of a SIMD needs the matrix pipe for ~4 400 of a node's ~16 000 cycles and sleeps on
-// memory the rest of the time; the Gram wave is a dense MFMA stream that takes every slot the product wave leaves: the two
-// phases that round 3 ran back to back in every wave (7.7 ms per arxiv batch, matrix pipes 57 % busy) now overlap.
-constexpr int kYRows = 48;  // classes per launch: three 16-class MFMA tiles (LDS: two 48 KiB tiles + W_1's 48 rows)
+//       Y[n] = W_1 (.) T1 + Y2 (W_1's rows straight from L2) is split into three bf16 pieces HERE, once per value, and the
+//       pieces go to one of TWO LDS tiles (FusedShared; 18 16-byte stores per node) -- under LGNN_GRAM_F32 the fp32 values.
+//   waves 4 .. 7, the GRAM waves: S += Y[n - 1]^T Y[n - 1] from the other tile into register-resident upper-triangular
+//       accumulators (the 36 sub-tiles of gram256.h, 9 per wave, 144 accumulator registers), nothing else: their loop is LDS
+//       reads and MFMAs.
+// ONE hand-off per node (LDS counters).  The product wave of a SIMD needs the matrix pipe for about a third of a node's cycles
+// and sleeps on memory part of the rest; the Gram wave is a dense MFMA stream that takes every slot the product wave leaves: the
+// two phases that round 3 ran back to back in every wave (7.7 ms per arxiv batch, matrix pipes 57 % busy) now overlap.
+constexpr int kYRows = 48;  // classes per launch: three 16-class MFMA tiles
 
 using f32x4v = __attribute__((ext_vector_type(4))) float;
 
-constexpr int kYStride = 272;  // floats per tile row: 256 + 16, so that the four rows of a Gram operand read (lanes 16 k ..
-                               // 16 k + 15 read row k0 + k) fall on disjoint banks
+constexpr int kYStride = 272;  // floats per row of the fp32 tile: 256 + 16, so that the four rows of a Gram operand read (lanes
+                               // 16 k .. 16 k + 15 read row k0 + k) fall on disjoint banks
+// The tile as bf16 PIECES (the default Gram role): a tile value y is y0 + y1 + y2, y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y -
+// y0 - y1) (see gram_split_role).  A dword holds the same piece of two tile rows (row r in the low half, r + 1 in the high
+// half); the tile rows come in GROUPS of four, g = row / 4, i.e. (chunk of 8 rows, lane half of the Gram's MFMA operand), and a
+// group is three PLANES (y2, y0, y1) of 256 columns x 2 dwords (rows 4 g, 4 g + 1 | rows 4 g + 2, 4 g + 3): 2 KiB each.  A Gram
+// lane reads the 8 bytes of its column from each plane (ds_read_b64; 32 lanes: 256 contiguous bytes); a product lane writes
+// the 32 bytes of its four columns to each plane (two ds_write_b128).  The 8 lanes one ds_write_b128 cycle serves are 32 bytes
+// apart, which would put them on 16 of the 32 banks twice: the two 16-byte halves of a lane's 32 bytes swap places in the lanes
+// piece_swap() names, and the 8 lanes cover the 32 banks once.  The reads stay permutations of one 256-byte bank row.
+constexpr int kPlaneDwords = 512;             // one plane: 256 columns x 2 dwords
+constexpr int kGroupDwords = 3 * kPlaneDwords;
+constexpr int kYGroups = kYRows / 4;
+// whether the four-column group q (columns 4 q .. 4 q + 3) stores its column pairs in swapped order
+__device__ __forceinline__ int piece_swap(int q) { return (q ^ (q >> 2)) & 1; }
+// dword offset inside a plane of column c's two dwords
+__device__ __forceinline__ int piece_col(int c) { return 8 * (c >> 2) + 4 * (((c >> 1) & 1) ^ piece_swap(c >> 2)) + 2 * (c & 1); }
+
 struct alignas(16) FusedShared {
-  float y[2][kYRows][kYStride];  // the node tiles (double buffered)
-  float w1[kYRows][256];    // W_1's rows of the launch (zero past R / H)
+  union {  // the node tiles (double buffered), in the form the launch's Gram role reads
+    uint32_t pc[2][kYGroups][3][kPlaneDwords];  // bf16 pieces: 2 x 72 KiB
+    float y[2][kYRows][kYStride];               // fp32 (LGNN_GRAM_F32)
+  };
   // hand-off counters (one writer each): ready[p] = nodes whose tile columns product wave p has published, done[g] = nodes
   // Gram wave g has contracted
   int ready[4], done[4];
 };
+static_assert(sizeof(FusedShared) <= 160 * 1024, "the CU's LDS");
 
 // min over the four counters of a hand-off array (one 16-byte LDS read; wave uniform)
 __device__ __forceinline__ int lds_min4(const int* c) {
@@ -519,6 +540,26 @@ __device__ __forceinline__ void bload4(f32x4v& d, uint32_t voff, const i32x4& rs
 __device__ __forceinline__ void bload1(uint32_t& d, uint32_t voff, const i32x4& rsrc) {
   asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rsrc) : "memory");
 }
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
+using u32x2v = __attribute__((ext_vector_type(2))) uint32_t;
+
+__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest, NaN stays NaN)
+  using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+  const bf16x2 v = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
+  return __builtin_bit_cast(uint32_t, v);
+}
+// The three bf16 pieces of two tile values (ya in the low halves, yb in the high halves), each rounded to nearest:
+// q0 = bf16(y), q1 = bf16(y - q0), q2 = bf16(y - q0 - q1) = y - q0 - q1 (see gram_split_role).  11 vector instructions.
+__device__ __forceinline__ void split_pair(float ya, float yb, uint32_t& q0, uint32_t& q1, uint32_t& q2) {
+  q0 = pk_bf16(ya, yb);
+  asm("" : "+v"(q0));  // (keeps the two values in one cvt: hipcc otherwise converts and widens each on its own)
+  const float r1a = ya - __uint_as_float(q0 << 16), r1b = yb - __uint_as_float(q0 & 0xffff0000u);
+  q1 = pk_bf16(r1a, r1b);
+  asm("" : "+v"(q1));
+  q2 = pk_bf16(r1a - __uint_as_float(q1 << 16), r1b - __uint_as_float(q1 & 0xffff0000u));
+}
+
 struct PTables {  // descriptors of what the role reads
   i32x4 coef, b, g, mask, pm, pv, pw;
 };
@@ -702,6 +743,12 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   tb.pm = make_rsrc(a.pm, uint64_t(a.cap) * 4);
   tb.pv = make_rsrc(a.pv, uint64_t(a.cap) * 4);
   tb.pw = make_rsrc(a.pw, uint64_t(a.cap) * 4);
+  // W_1's rows of the launch, read at the tile write (48 KB that every workgroup reads: L2 resident)
+  const uint32_t w1_row_bytes = uint32_t(a.w1_ld) * 4u;
+  const i32x4 w1rs = make_rsrc(a.W1 + int64_t(a.c0) * a.w1_ld, uint64_t(a.R - 1) * w1_row_bytes + row_bytes);
+  const uint32_t w1_off = col_ok ? uint32_t(4 * pl.kq) * w1_row_bytes + 4u * uint32_t(col) : 0x7ff00000u;
+  // the lane's two 16-byte stores inside a piece plane (dword offsets: columns col, col + 1 and col + 2, col + 3)
+  const int pc_lo = 8 * (col >> 2) + 4 * piece_swap(col >> 2), pc_hi = pc_lo ^ 4;
   constexpr int NL = kStepLoads<NOBG>;
   ChunkGen<LIST> gen;
   gen.init(pptr, list, a.n0, cnt);
@@ -756,24 +803,62 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       p_mfma<NOBG>(cB, t1, y2);  // (unconditional: see the role's header)
     }
     if (lastc) {
+      // W_1's 48 x 4 values of the lane: twelve 16-byte loads, the YOUNGEST vector-memory operations of the wave from here to
+      // the vmcnt(0) below (older, in order: the three path loads of the loop's top, the refills of A and B).  A row past the
+      // launch's classes lies outside the descriptor and reads zeros; so does every row of a lane past H (w1_off).
+      f32x4v w1[3][4];
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bload4<0>(w1[t][r], w1_off + uint32_t(16 * t + r) * w1_row_bytes, w1rs);
       // tile i & 1 was last read by the Gram of node i - 2: every Gram wave must have counted i - 1 nodes
       if (i >= 2)
         while (lds_min4(sh.done) < int(i) - 1) __builtin_amdgcn_s_sleep(2);
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(w1[t][0]), "+v"(w1[t][1]), "+v"(w1[t][2]), "+v"(w1[t][3]) :: "memory");
       if (node_has && col_ok) {
         // Y[n] = W_1 (.) T1 + Y2.  Rows past the launch's classes come out as the zeros they already are (their coefficients
-        // and their rows of W_1 are zero): one branch around twelve unconditional 16-byte stores.
-        float (*ytile)[kYStride] = sh.y[i & 1];
+        // and their rows of W_1 are zero): one branch around unconditional 16-byte stores.
+        if (a.gram_f32) {  // the fp32 tile: twelve stores
+          float (*ytile)[kYStride] = sh.y[i & 1];
 #pragma unroll
-        for (int t = 0; t < 3; ++t)
+          for (int t = 0; t < 3; ++t)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = 16 * t + 4 * pl.kq + r;
-            const f32x4v w1 = *reinterpret_cast<const f32x4v*>(&sh.w1[row][col]);
-            f32x4v o;
+            for (int r = 0; r < 4; ++r) {
+              f32x4v o;
 #pragma unroll
-            for (int ct = 0; ct < 4; ++ct) o[ct] = w1[ct] * t1[t][ct][r] + y2[t][ct][r];
-            *reinterpret_cast<f32x4v*>(&ytile[row][col]) = o;
+              for (int ct = 0; ct < 4; ++ct) o[ct] = w1[t][r][ct] * t1[t][ct][r] + y2[t][ct][r];
+              *reinterpret_cast<f32x4v*>(&ytile[16 * t + 4 * pl.kq + r][col]) = o;
+            }
+        } else {
+          // the pieces: the lane's rows 16 t + 4 kq + 0 .. 3 are group 4 t + kq, its columns two 16-byte stores per plane
+          uint32_t* __restrict__ grp = &sh.pc[i & 1][pl.kq][0][0];
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            u32x4v pz[3][2];  // [piece y0, y1, y2][column pair]: (rows 0 1 | rows 2 3) of the pair's two columns
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+              for (int rp = 0; rp < 2; ++rp) {
+                const float ya = w1[t][2 * rp][ct] * t1[t][ct][2 * rp] + y2[t][ct][2 * rp];
+                const float yb = w1[t][2 * rp + 1][ct] * t1[t][ct][2 * rp + 1] + y2[t][ct][2 * rp + 1];
+                uint32_t q0, q1, q2;
+                split_pair(ya, yb, q0, q1, q2);
+                pz[0][ct >> 1][2 * (ct & 1) + rp] = q0;
+                pz[1][ct >> 1][2 * (ct & 1) + rp] = q1;
+                pz[2][ct >> 1][2 * (ct & 1) + rp] = q2;
+              }
+            uint32_t* __restrict__ g = grp + 4 * t * kGroupDwords;
+            // planes in the order (y2, y0, y1)
+            *reinterpret_cast<u32x4v*>(g + pc_lo) = pz[2][0];
+            *reinterpret_cast<u32x4v*>(g + pc_hi) = pz[2][1];
+            *reinterpret_cast<u32x4v*>(g + kPlaneDwords + pc_lo) = pz[0][0];
+            *reinterpret_cast<u32x4v*>(g + kPlaneDwords + pc_hi) = pz[0][1];
+            *reinterpret_cast<u32x4v*>(g + 2 * kPlaneDwords + pc_lo) = pz[1][0];
+            *reinterpret_cast<u32x4v*>(g + 2 * kPlaneDwords + pc_hi) = pz[1][1];
           }
+        }
       }
       ++i;
       lds_publish(&sh.ready[cg], int(i), lane);
@@ -880,64 +965,43 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
 // split into three bf16 pieces, each rounded to nearest:  y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y - y0 - y1) = y - y0 - y1
 // (both differences are exact; each piece carries 8 of the 24 significand bits).  A product y z keeps six of the nine piece
 // products, y0 z0 + y0 z1 + y1 z0 + y0 z2 + y1 z1 + y2 z0: the three dropped ones are at most 2^-23 |y z| together and of either
-// sign (fp32 rounding level).  The K slots of an MFMA are (piece pair, class): lane half h holds the classes k0 + h + 2 m,
-// m = 0 .. 3, of a chunk of 8 tile rows, two slots per class in one register, and each column block is kept in three forms
-// (low half | high half):  U = (y0 | y1),  V = (y1 | y0),  S = (y0 | y2).  Per chunk and sub-tile (si, sj) three MFMAs:
-//     U[si] x U[sj] = y0 z0 + y1 z1,   S[si] x V[sj] = y0 z1 + y2 z0,   V[si] x S[sj] = y1 z0 + y0 z2
+// sign (fp32 rounding level).  The product waves form the pieces (split_pair) and store them in the layout of FusedShared: this
+// role only reads them.  The K slots of an MFMA are (piece, class): lane half h holds the classes 8 ck + 4 h + 0 .. 3 of chunk
+// ck, two classes of one piece per register, six registers per column block (y2a y2b y0a y0b y1a y1b; a = classes 0 1, b =
+// classes 2 3), in two operand forms that overlap:  T = (y2a y2b y0a y0b),  U = (y0a y0b y1a y1b).  Per chunk and sub-tile
+// (si, sj) three MFMAs:
+//     U[si] x U[sj] = y0 z0 + y1 z1,   T[si] x U[sj] = y2 z0 + y0 z1,   U[si] x T[sj] = y0 z2 + y1 z0
 // (A and B of one lane share the slot map, see the operand layout: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and
-// B[k = 8 (l >> 5) + j][col l & 31]).  Each register of the three forms is one v_cvt_pk_bf16_f32 of two fp32 values, so the
-// operands need no register moves: 7.5 vector instructions per value.  Rounding can take only a value above 3.39e38 to
-// infinity (its square overflows in fp32 anyway); a NaN or an infinity turns into NaN pieces (inf - inf): a non-finite input
-// gives a non-finite factor, as the fp32 role does.
+// B[k = 8 (l >> 5) + j][col l & 31]).  hipcc keeps T and U in registers of their own: two moves per column block and chunk.
+// Rounding can take only a value above 3.39e38 to infinity (its square overflows in fp32 anyway); a NaN or an infinity turns
+// into NaN pieces (inf - inf): a non-finite input gives a non-finite factor, as the fp32 role does.
 // 27 MFMAs of 32 cycles per chunk of 8 tile rows against gram_role's 68 of 16x16x4 fp32 (32 cycles each): 0.4x the matrix cycles.
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
+struct PieceBlk { u32x2v y2, y0, y1; };  // a column block's pieces of the lane's 4 classes of a chunk: (rows 0 1 | rows 2 3)
 
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest, NaN stays NaN)
-  using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-  const bf16x2 v = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
-  return __builtin_bit_cast(uint32_t, v);
-}
-struct SplitBlk { u32x4v u, v, s; };  // the three forms of a column block for the lane's 4 classes of a chunk
-
-// the lane's four values of column block b in a chunk: rows 2 m (the lane half's row offset is in `p`)
+// the lane's pieces of its column in every column block the wave uses (`p`: the chunk's group of the lane half + piece_col)
 template <int W>
-__device__ __forceinline__ void split_load(const float* __restrict__ p, float (&x)[8][4]) {
+__device__ __forceinline__ void piece_load(const uint32_t* __restrict__ p, PieceBlk (&x)[8]) {
 #pragma unroll
   for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int m = 0; m < 4; ++m) x[b][m] = tiles256_uses<W>(b) ? p[2 * m * kYStride + b * 32] : 0.f;
-}
-__device__ __forceinline__ void split_block(const float (&y)[4], SplitBlk& o) {
-#pragma unroll
-  for (int m = 0; m < 4; m += 2) {
-    uint32_t p0 = pk_bf16(y[m], y[m + 1]);
-    asm("" : "+v"(p0));  // (keeps the two values' y0 in one cvt: hipcc otherwise converts and widens each on its own)
-    const float r1a = y[m] - __uint_as_float(p0 << 16), r1b = y[m + 1] - __uint_as_float(p0 & 0xffff0000u);
-    o.u[m] = pk_bf16(y[m], r1a);
-    o.u[m + 1] = pk_bf16(y[m + 1], r1b);
-    const float r2a = r1a - __uint_as_float(o.u[m] & 0xffff0000u), r2b = r1b - __uint_as_float(o.u[m + 1] & 0xffff0000u);
-    o.v[m] = pk_bf16(r1a, y[m]);
-    o.v[m + 1] = pk_bf16(r1b, y[m + 1]);
-    o.s[m] = pk_bf16(y[m], r2a);
-    o.s[m + 1] = pk_bf16(y[m + 1], r2b);
-  }
+    if (tiles256_uses<W>(b)) {
+      x[b].y2 = *reinterpret_cast<const u32x2v*>(p + b * 64);
+      x[b].y0 = *reinterpret_cast<const u32x2v*>(p + kPlaneDwords + b * 64);
+      x[b].y1 = *reinterpret_cast<const u32x2v*>(p + 2 * kPlaneDwords + b * 64);
+    }
 }
 __device__ __forceinline__ f32x16 mfma_bf16(u32x4v a, u32x4v b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 template <int W>
-__device__ __forceinline__ void split_chunk(const float (&x)[8][4], f32x16 (&acc)[9]) {
-  SplitBlk f[8];
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-    if (tiles256_uses<W>(b)) split_block(x[b], f[b]);
+__device__ __forceinline__ void piece_mfma(const PieceBlk (&x)[8], f32x16 (&acc)[9]) {
 #pragma unroll
   for (int s = 0; s < 9; ++s) {
-    const SplitBlk &A = f[Tiles256<W>::si[s]], &B = f[Tiles256<W>::sj[s]];
-    acc[s] = mfma_bf16(A.u, B.u, acc[s]);
-    acc[s] = mfma_bf16(A.s, B.v, acc[s]);
-    acc[s] = mfma_bf16(A.v, B.s, acc[s]);
+    const PieceBlk &A = x[Tiles256<W>::si[s]], &B = x[Tiles256<W>::sj[s]];
+    const u32x4v ua = {A.y0[0], A.y0[1], A.y1[0], A.y1[1]}, ta = {A.y2[0], A.y2[1], A.y0[0], A.y0[1]};
+    const u32x4v ub = {B.y0[0], B.y0[1], B.y1[0], B.y1[1]}, tb = {B.y2[0], B.y2[1], B.y0[0], B.y0[1]};
+    acc[s] = mfma_bf16(ua, ub, acc[s]);
+    acc[s] = mfma_bf16(ta, ub, acc[s]);
+    acc[s] = mfma_bf16(ua, tb, acc[s]);
   }
 }
 template <int W, bool LIST>
@@ -957,13 +1021,21 @@ __device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* _
     node_range<LIST>(pptr, list, a.n0, cnt, i + 1, q0, q1);
     while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
     if (p1 > p0) {
-      const float* __restrict__ base = &sh.y[i & 1][0][0] + (lane >> 5) * kYStride + (lane & 31);
-      float x[8][4];
-      split_load<W>(base, x);
-      for (int ck = 0; ck < nch; ++ck) {  // (wave-uniform trip count, straight-line body)
-        split_chunk<W>(x, acc);
-        // the next chunk's values are read while this chunk's MFMAs run (split_chunk has consumed x)
-        if (ck + 1 < nch) split_load<W>(base + (ck + 1) * 8 * kYStride, x);
+      // chunk ck, lane half h: group 2 ck + h
+      const uint32_t* __restrict__ base = &sh.pc[i & 1][lane >> 5][0][0] + piece_col(lane & 31);
+      PieceBlk xa[8], xb[8];
+      piece_load<W>(base, xa);
+      for (int ck = 0; ck < nch; ck += 2) {  // (wave-uniform trip count; the next chunk's pieces are read while this one's MFMAs run)
+        if (ck + 1 < nch) piece_load<W>(base + (ck + 1) * 2 * kGroupDwords, xb);
+        __builtin_amdgcn_sched_barrier(0);
+        piece_mfma<W>(xa, acc);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ck + 1 < nch) {
+          if (ck + 2 < nch) piece_load<W>(base + (ck + 2) * 2 * kGroupDwords, xa);
+          __builtin_amdgcn_sched_barrier(0);
+          piece_mfma<W>(xb, acc);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
     }
     lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
@@ -990,12 +1062,8 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
                                                              const int32_t* __restrict__ list, float* __restrict__ scratch) {
   __shared__ FusedShared sh;  // ONE LDS object
   if (int64_t(pptr[a.N]) > a.cap) return;  // the path list overflowed its buffer: the enumerating route takes over
-  // the tiles are zero where nobody writes: columns >= H, the odd row out
-  for (int q = threadIdx.x; q < 2 * kYRows * kYStride; q += 512) (&sh.y[0][0][0])[q] = 0.f;
-  for (int q = threadIdx.x; q < kYRows * 256; q += 512) {
-    const int row = q >> 8, colq = q & 255;
-    sh.w1[row][colq] = (row < a.R && colq < a.H) ? a.W1[int64_t(a.c0 + row) * a.w1_ld + colq] : 0.f;
-  }
+  // the tiles are zero where nobody writes: columns >= H, the odd row out (zero bits are zero pieces)
+  for (int q = threadIdx.x; q < int(sizeof(sh.pc) / 16); q += 512) reinterpret_cast<u32x4v*>(&sh.pc[0][0][0][0])[q] = u32x4v{0u, 0u, 0u, 0u};
   if (threadIdx.x < 4) {
     sh.ready[threadIdx.x] = 64 * int(threadIdx.x) < a.H ? 0 : INT32_MAX;  // (H <= 192: the last product wave has no columns)
     sh.done[threadIdx.x] = 0;
@@ -1005,7 +1073,7 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   const int64_t stride = gridDim.x;
   const int64_t nn = LIST ? int64_t(__builtin_amdgcn_readfirstlane(*a.n_list)) : a.n1 - a.n0;
   const int64_t cnt = nn > int64_t(blockIdx.x) ? (nn - blockIdx.x + stride - 1) / stride : 0;
-  // (which half is which matters: see the kernel's header)
+  // (hardware waves g and g + 4 share a SIMD: one product wave and one Gram wave on each, see the kernel's header)
   switch (hw) {
     // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
     case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, cnt, scratch); break;
@@ -1325,7 +1393,7 @@ static int gram_f32() {  // LGNN_GRAM_F32=1: the fused kernel's Gram role on fp3
   const char* e = getenv("LGNN_GRAM_F32");
   return e && atoi(e) != 0 ? 1 : 0;
 }
-// persistent workgroups of paths_fused_kernel: one per CU (149 KB of LDS each).  Leaving CUs to the side stream's eigensolver
+// persistent workgroups of paths_fused_kernel: one per CU (144 KB of LDS each).  Leaving CUs to the side stream's eigensolver
 // did not help (252 / 248 / 240 workgroups: 50.6 / 51.5 / 52.4 ms per GraphSAGE fit)
 constexpr int64_t kFusedWorkgroups = 256;
 
