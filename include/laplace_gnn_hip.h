@@ -151,7 +151,9 @@ LGNN_API int lgnn_bind_extras(lgnn_ctx* h, const float* const* res_weights, cons
                      const float* const* norm_weight, const float* const* norm_bias, const float* const* norm_mean,
                      const float* const* norm_var, float norm_eps);
 LGNN_API int lgnn_invalidate(lgnn_ctx* h);
-/* bytes currently held by the context (graph + caches + workspace).  host value. */
+/* bytes currently held by the context (graph + caches + workspace).  host value.  What the first fit sizes and later fits of
+ * the same shape leave alone; the entries of the batch-structure cache are NOT in this figure -- the second fit over a
+ * loader allocates them, bounded by LGNN_BATCH_CACHE_MB, and lgnn_batch_cache_stats reports their bytes. */
 LGNN_API int64_t lgnn_device_bytes(const lgnn_ctx* h);
 /* cap for the backward workspace (chunks over classes are sized to fit); default 32 GiB */
 LGNN_API int lgnn_set_workspace_limit(lgnn_ctx* h, int64_t bytes);
@@ -278,6 +280,24 @@ LGNN_API int lgnn_check_async_errors(lgnn_ctx* h, void* stream);
  * (a replayed hipGraph of a whole fit, DiagLaplace.fit_graph) and must not stall the stream once per fit; the reference's own
  * index errors on a CUDA / HIP device are asynchronous device-side asserts as well.                                          */
 LGNN_API int lgnn_peek_async_errors(lgnn_ctx* h);
+
+/* ---- batch-structure cache -----------------------------------------------------------------------
+ * Part of what lgnn_kfac_accumulate* prepares per batch depends on the graph and the batch's node ids only, not on the
+ * weights: the GCN top layer's active-row list and the path route's two-hop path list.  A caller that runs the same batches
+ * fit after fit (gnn/marglik_training.py:125-127 builds its loader once, shuffle=False) names each batch with a non-zero tag
+ * right before the accumulate call; the tag is consumed and cleared by that call.  The first accumulate under a tag runs
+ * unchanged and only remembers the tag; the second builds an entry (one stream synchronisation: two counts size it); from
+ * then on none of the list-building kernels is launched for that batch, for whole-batch, class-range and share calls alike.
+ * The caller guarantees that one tag always names the same ids of the same length; as a guard every entry keeps a copy of
+ * its ids, compared on the device on every use (lgnn_check_async_errors reports a difference).  Entries are dropped when
+ * the graph changes (lgnn_update_adjacency), not by lgnn_invalidate.  LGNN_BATCH_CACHE_MB (read per call, default 2048;
+ * 0 = off) bounds the device memory: least recently used entries go first, a batch larger than the budget is not cached.
+ * Tag 0 / no call: nothing is cached.  Host-only calls.                                                              */
+LGNN_API int lgnn_kfac_batch_tag(lgnn_ctx* h, uint64_t tag);
+/* Forget a tag's entry (tag 0: every entry and every remembered tag). */
+LGNN_API int lgnn_batch_cache_drop(lgnn_ctx* h, uint64_t tag);
+/* out[5] = entries, device bytes, hits, misses, builds (accumulate calls under a tag on a route that uses the cache) */
+LGNN_API int lgnn_batch_cache_stats(const lgnn_ctx* h, int64_t* out);
 
 /* ---- timing hook (bench.py roofline) -----------------------------------------------------------
  * While enabled, every launch of the dominant kernel of the path in use -- KFAC: the fused SpMM^T -> Gram kernel of

@@ -55,6 +55,9 @@ SIGNATURES = {
     "lgnn_lastlayer_pairs_place": (_i32, [_vp, _vp, _vp, _vp, _vp]),
     "lgnn_check_async_errors": (_i32, [_vp, _vp]),
     "lgnn_peek_async_errors": (_i32, [_vp]),
+    "lgnn_kfac_batch_tag": (_i32, [_vp, C.c_uint64]),
+    "lgnn_batch_cache_drop": (_i32, [_vp, C.c_uint64]),
+    "lgnn_batch_cache_stats": (_i32, [_vp, C.POINTER(_i64)]),
     "lgnn_enable_kernel_timing": (_i32, [_vp, _i32]),
     "lgnn_kernel_timing_read": (_i32, [_vp, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "lgnn_kernel_timing_launches": (_i32, [_vp, _vp, _i64, _vp]),

@@ -343,6 +343,7 @@ extern "C" void lgnn_destroy(lgnn_ctx* h) {
     h->ws.gram_scratch_res[l].release();
   }
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+  batch_cache_clear(h);
   delete h;
 }
 
@@ -417,7 +418,7 @@ extern "C" int64_t lgnn_device_bytes(const lgnn_ctx* h) {
     t += h->Wt[l].bytes + h->fc.lin_in[l].bytes + h->fc.act_out[l].bytes + h->fc.gram_raw[l].bytes +
          h->fc.prop_in[l].bytes + h->ws.gram_scratch[l].bytes + h->fc.mask_bits[l].bytes + h->Wrt[l].bytes +
          h->Wcomb[l].bytes + h->bcomb[l].bytes + h->fc.xhat[l].bytes + h->fc.rstd[l].bytes + h->ws.gram_scratch_res[l].bytes;
-  return int64_t(t);
+  return int64_t(t);  // (the batch-structure cache reports its own bytes: lgnn_batch_cache_stats)
 }
 
 extern "C" int lgnn_forward_all(lgnn_ctx* h, float* out, void* stream) {
@@ -448,6 +449,8 @@ extern "C" int lgnn_check_async_errors(lgnn_ctx* h, void* stream) {
   for (int i = 0; i < 4; ++i) { flags[i] = dev[i]; dev[i] = 0; }
   LGNN_REQUIRE(flags[1] == 0 && flags[0] != 1 && flags[2] == 0, "a batch contained a node index outside [0, num_nodes)");
   LGNN_REQUIRE(flags[0] != 2, "a batch contained a label outside [0, num_classes)");
+  LGNN_REQUIRE(flags[3] == 0, "a batch's node ids differ from the ids its cached structure was built from (the index tensor "
+                              "was written without a version bump): drop the batch cache or pass a fresh tensor");
   return 0;
 }
 
@@ -458,10 +461,12 @@ extern "C" int lgnn_peek_async_errors(lgnn_ctx* h) {
   volatile int* dev = h->ws.flags.as<int>();
   int flags[4];
   for (int i = 0; i < 4; ++i) flags[i] = dev[i];
-  if (flags[0] == 0 && flags[1] == 0 && flags[2] == 0) return 0;
+  if (flags[0] == 0 && flags[1] == 0 && flags[2] == 0 && flags[3] == 0) return 0;
   for (int i = 0; i < 4; ++i) dev[i] = 0;
   LGNN_REQUIRE(flags[1] == 0 && flags[0] != 1 && flags[2] == 0, "a batch contained a node index outside [0, num_nodes)");
   LGNN_REQUIRE(flags[0] != 2, "a batch contained a label outside [0, num_classes)");
+  LGNN_REQUIRE(flags[3] == 0, "a batch's node ids differ from the ids its cached structure was built from (the index tensor "
+                              "was written without a version bump): drop the batch cache or pass a fresh tensor");
   return 0;
 }
 

@@ -18,11 +18,14 @@ namespace lgnn {
 
 namespace {
 
+// guard (optional): the ids a batch-structure cache entry was built from.  A difference means the batch's memory was changed
+// behind the caller's version counter: sticky flag word 3 (the cached lists would give a wrong factor without any sign)
 __global__ void mark_batch_kernel(const int64_t* __restrict__ idx, int64_t M, int64_t N, int32_t* __restrict__ pos,
-                                  int* __restrict__ bad) {
+                                  int* __restrict__ bad, const int64_t* __restrict__ guard) {
   const int64_t m = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (m >= M) return;
   const int64_t n = idx[m];
+  if (guard && guard[m] != n) bad[3] = 1;
   if (n < 0 || n >= N) { bad[1] = 1; return; }  // sticky flag word 1: node id out of range
   atomicMin(&pos[n], int32_t(m));  // duplicates: the first occurrence owns the accumulated seed row
 }
@@ -517,7 +520,9 @@ __global__ void top_tasks_fill_kernel(const int32_t* __restrict__ list, const in
 
 template <int NBLK>
 int seed_spmm_gram_launch(lgnn_ctx* h, bool fork_exact, float* g, int64_t cb, int64_t ce, float* scratch,
-                          hipStream_t s) {
+                          hipStream_t s, const int32_t* act_list, const int32_t* act_count, const uint8_t* active) {
+  // act_list / act_count / active: the batch's active rows -- the workspace's (ws.act_list, ws.act_count, ws.active) or a
+  // batch-structure cache entry's
   const int C = int(h->dims[h->L]);
   constexpr int NT = NBLK * (NBLK + 1) / 2;
   const int rp = (int(ce - cb) + 3) & ~3;
@@ -539,8 +544,8 @@ int seed_spmm_gram_launch(lgnn_ctx* h, bool fork_exact, float* g, int64_t cb, in
   if (h->n_top_multi <= 0) {
     hipLaunchKernelGGL(seed_spmm_gram_kernel<NBLK>, dim3(unsigned(256 * per_cu)), dim3(64 * waves), smem, s, h->PT.rowptr,
                        h->PT.col, h->PT.val, h->N, C, h->ws.pos.as<int32_t>(), h->ws.probs.as<float>(),
-                       h->fc.out.as<float>(), h->ws.mult.as<int32_t>(), fe, g, h->ws.act_list.as<int32_t>(),
-                       h->ws.act_count.as<int32_t>(), int(cb), int(ce), scratch, ldb, 0,
+                       h->fc.out.as<float>(), h->ws.mult.as<int32_t>(), fe, g, act_list,
+                       act_count, int(cb), int(ce), scratch, ldb, 0,
                        static_cast<const int32_t*>(nullptr), static_cast<float*>(nullptr), static_cast<const uint8_t*>(nullptr));
     LGNN_HIP_CHECK(hipGetLastError());
     return 0;
@@ -555,24 +560,24 @@ int seed_spmm_gram_launch(lgnn_ctx* h, bool fork_exact, float* g, int64_t cb, in
   LGNN_CALL(h->top_hub_tiles.reserve(size_t(h->n_long) * nrows * C * 4));
   LGNN_HIP_CHECK(hipMemsetAsync(h->top_task_count.p, 0, 4, s));
   LGNN_HIP_CHECK(hipMemsetAsync(h->top_hub_tiles.p, 0, size_t(h->n_long) * nrows * C * 4, s));
-  hipLaunchKernelGGL(top_tasks_count_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, h->ws.act_list.as<int32_t>(),
-                     h->ws.act_count.as<int32_t>(), h->PT.rowptr, N, h->top_cnt.as<int32_t>());
+  hipLaunchKernelGGL(top_tasks_count_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, act_list,
+                     act_count, h->PT.rowptr, N, h->top_cnt.as<int32_t>());
   LGNN_CALL(exclusive_scan_i32(h->top_cnt.as<int32_t>(), h->top_offs.as<int32_t>(), N, h->ws.select_tmp, s));
-  hipLaunchKernelGGL(top_tasks_fill_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, h->ws.act_list.as<int32_t>(),
-                     h->ws.act_count.as<int32_t>(), h->PT.rowptr, h->top_cnt.as<int32_t>(), h->top_offs.as<int32_t>(),
+  hipLaunchKernelGGL(top_tasks_fill_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, act_list,
+                     act_count, h->PT.rowptr, h->top_cnt.as<int32_t>(), h->top_offs.as<int32_t>(),
                      h->top_tasks.as<int32_t>(), h->top_task_count.as<int32_t>());
   hipLaunchKernelGGL(seed_spmm_gram_kernel<NBLK>, dim3(unsigned(256 * per_cu)), dim3(64 * waves), smem, s, h->PT.rowptr,
                      h->PT.col, h->PT.val, h->N, C, h->ws.pos.as<int32_t>(), h->ws.probs.as<float>(),
                      h->fc.out.as<float>(), h->ws.mult.as<int32_t>(), fe, g, h->top_tasks.as<int32_t>(),
                      h->top_task_count.as<int32_t>(), int(cb), int(ce), scratch, ldb, 1, h->long_slot.as<int32_t>(),
-                     h->top_hub_tiles.as<float>(), h->ws.active.as<uint8_t>());
+                     h->top_hub_tiles.as<float>(), active);
   // finishing launch: one wave per sliced hub (its count is a property of the graph: a constant in device memory)
   const unsigned fin_blocks = unsigned(std::min<int64_t>(cdiv(h->n_top_multi, waves), 256 * per_cu));
   hipLaunchKernelGGL(seed_spmm_gram_kernel<NBLK>, dim3(fin_blocks), dim3(64 * waves), smem, s, h->PT.rowptr, h->PT.col,
                      h->PT.val, h->N, C, h->ws.pos.as<int32_t>(), h->ws.probs.as<float>(), h->fc.out.as<float>(),
                      h->ws.mult.as<int32_t>(), fe, g, h->top_multi.as<int32_t>(), h->top_multi.as<int32_t>() + h->n_top_multi, int(cb), int(ce),
                      scratch, ldb, 2, h->long_slot.as<int32_t>(), h->top_hub_tiles.as<float>(),
-                     h->ws.active.as<uint8_t>());
+                     active);
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -675,7 +680,7 @@ KfacPlan plan_kfac(int kind, int L, int64_t N, int64_t nnz, const int64_t* dims,
 
 // shared by kfac / diag / last layer: mark the batch, compute seeds/probs/loss.
 int batch_prologue(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, bool want_seeds, bool fork_exact,
-                   float* loss_out, hipStream_t s, const void* y_seed, float resid_scale) {
+                   float* loss_out, hipStream_t s, const void* y_seed, float resid_scale, const int64_t* guard_ids) {
   const int64_t N = h->N, C = h->dims[h->L];
   // y_seed != null: single-column gradient seeds of the empirical / MC Fisher (labels resp. fp32 targets to seed with)
   const int seed_mode = y_seed ? (h->lik == LGNN_LIK_REGRESSION ? 4 : 3)
@@ -683,7 +688,7 @@ int batch_prologue(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, bo
   LGNN_REQUIRE(2 * C * 4 <= 64 * 1024, "too many classes for the seed kernel");
   int* bad = h->ws.flags.as<int>();  // allocated and zeroed by lgnn_create; sticky until lgnn_check_async_errors
   hipLaunchKernelGGL(mark_batch_kernel, dim3(unsigned(cdiv(M, 256))), dim3(256), 0, s, idx, M, N,
-                     h->ws.pos.as<int32_t>(), bad);
+                     h->ws.pos.as<int32_t>(), bad, guard_ids);
   LGNN_CALL(h->ws.probs.reserve(size_t(M) * C * 4));
   LGNN_CALL(h->ws.mult.reserve(size_t(M) * 4));
   LGNN_HIP_CHECK(hipMemsetAsync(h->ws.mult.p, 0, size_t(M) * 4, s));
@@ -728,17 +733,22 @@ int kfac_top_planes(lgnn_ctx* h, const int64_t* idx, int64_t M, bool fork_exact,
   LGNN_CALL(h->ws.gram_scratch[l].reserve(size_t(C) * C * 4));
   LGNN_HIP_CHECK(hipMemsetAsync(h->ws.gram_scratch[l].p, 0, size_t(C) * C * 4, s));
   float* sc = h->ws.gram_scratch[l].as<float>();
+  const int32_t* al = h->ws.act_list.as<int32_t>();
+  const int32_t* ac = h->ws.act_count.as<int32_t>();
+  const uint8_t* af = h->ws.active.as<uint8_t>();
   switch (int(cdiv(C, 16))) {
-    case 1: return seed_spmm_gram_launch<1>(h, fork_exact, g, 0, C, sc, s);
-    case 2: return seed_spmm_gram_launch<2>(h, fork_exact, g, 0, C, sc, s);
-    case 3: return seed_spmm_gram_launch<3>(h, fork_exact, g, 0, C, sc, s);
-    default: return seed_spmm_gram_launch<4>(h, fork_exact, g, 0, C, sc, s);
+    case 1: return seed_spmm_gram_launch<1>(h, fork_exact, g, 0, C, sc, s, al, ac, af);
+    case 2: return seed_spmm_gram_launch<2>(h, fork_exact, g, 0, C, sc, s, al, ac, af);
+    case 3: return seed_spmm_gram_launch<3>(h, fork_exact, g, 0, C, sc, s, al, ac, af);
+    default: return seed_spmm_gram_launch<4>(h, fork_exact, g, 0, C, sc, s, al, ac, af);
   }
 }
 
 int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, int64_t n_train, uint32_t flags,
                     int64_t cb, int64_t ce, float* const* A_out, float* const* B_out, float* loss_out, hipStream_t s,
                     const KfacFisherOpts* fisher, const KfacShare* share) {
+  const uint64_t batch_tag = h->bcache.pending_tag;  // names the batch of THIS call only
+  h->bcache.pending_tag = 0;
   LGNN_REQUIRE(M > 0 && idx && (y || (fisher && !fisher->add_loss_and_A)), "empty batch or null batch pointers");
   LGNN_REQUIRE(h->L > 0, "no model bound");
   // Share mode (lgnn_kfac_accumulate_share): parts [begin, end) of `count` equal parts of the batch's work; HOW a batch is
@@ -796,8 +806,14 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   // GCN, fused path: the top-layer kernel rebuilds each sample's C x C seed block from its probabilities and logits,
   // so the blocks are never written (64 MB per arxiv-shaped batch); every other path reads them from ws.seeds
   const bool seeds_on_the_fly = plan.seeds_on_the_fly && !fisher;  // the on-the-fly rebuild knows the GGN blocks only
+  // batch-structure cache (batchcache.hip): the caller named this batch (lgnn_kfac_batch_tag) and the route builds the lists
+  // an entry holds -- the GCN top layer's active rows, the path route's two-hop paths
+  BatchEntry* be = nullptr;
+  bool be_built = false;
+  const bool be_route = h->kind == LGNN_KIND_GCN && seeds_on_the_fly;
+  if (be_route) LGNN_CALL(batch_cache_lookup(h, batch_tag, idx, M, &be, s));
   LGNN_CALL(batch_prologue(h, idx, y, M, !seeds_on_the_fly, fork_exact, once ? loss_out : nullptr, s,
-                           fisher ? fisher->y_seed : nullptr, fisher ? fisher->resid_scale : 1.0f));
+                           fisher ? fisher->y_seed : nullptr, fisher ? fisher->resid_scale : 1.0f, be ? be->ids : nullptr));
 
   // A_l += in_l^T in_l / n_train   (kfac.py:870 divides by M, curvlinops.py:46-53 multiplies by M/N)
   for (int l = 0; once && l < L; ++l)
@@ -832,6 +848,10 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   }
   LGNN_CALL(h->ws.active.reserve(size_t(N)));
   bool have_act_list = false;
+  // the GCN's active rows as the steps below read them: the workspace's, or the cache entry's on a hit
+  const uint8_t* active_p = nullptr;
+  const int32_t* act_list_p = nullptr;
+  const int32_t* act_count_p = nullptr;
   // GraphSAGE, fused path: the top-level GEMM g W_l runs over the (distinct) batch nodes only -- 6 % of the rows at
   // the arxiv shape -- through the compacted-row backward GEMM; the other rows of its output stay zero (see below)
   const bool sage_compact = plan.sage_compact;
@@ -839,14 +859,24 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
     const int64_t nq = (ce - cb) * C;
     if (seeds_on_the_fly) {
       // active rows first (columns of the batch nodes' P rows), then one pass over those rows only
-      LGNN_HIP_CHECK(hipMemsetAsync(h->ws.active.p, 0, size_t(N), s));
-      hipLaunchKernelGGL(mark_active_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr,
-                         h->P.col, h->ws.active.as<uint8_t>());
-      LGNN_HIP_CHECK(hipGetLastError());
-      LGNN_CALL(h->ws.act_list.reserve(size_t(N) * 4));
-      LGNN_CALL(h->ws.act_count.reserve(64));
-      LGNN_CALL(compact_flags(h->ws.active.as<uint8_t>(), N, h->ws.act_list.as<int32_t>(),
-                              h->ws.act_count.as<int32_t>(), h->ws.select_tmp, s));
+      if (be && be->has_act) {
+        active_p = be->active; act_list_p = be->act_list; act_count_p = be->act_count;
+      } else {
+        LGNN_HIP_CHECK(hipMemsetAsync(h->ws.active.p, 0, size_t(N), s));
+        hipLaunchKernelGGL(mark_active_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr,
+                           h->P.col, h->ws.active.as<uint8_t>());
+        LGNN_HIP_CHECK(hipGetLastError());
+        LGNN_CALL(h->ws.act_list.reserve(size_t(N) * 4));
+        LGNN_CALL(h->ws.act_count.reserve(64));
+        LGNN_CALL(compact_flags(h->ws.active.as<uint8_t>(), N, h->ws.act_list.as<int32_t>(),
+                                h->ws.act_count.as<int32_t>(), h->ws.select_tmp, s));
+        active_p = h->ws.active.as<uint8_t>(); act_list_p = h->ws.act_list.as<int32_t>();
+        act_count_p = h->ws.act_count.as<int32_t>();
+        if (be) {  // (this call goes on with the workspace's copy: the entry may be refused for its size)
+          LGNN_CALL(batch_cache_store_active(h, be, s));
+          be_built = true;
+        }
+      }
       have_act_list = true;
       // a single-layer model needs the Gram only -- and so does the two-hop path route (paths.hip), which never reads planes
       const bool paths_route = plan.paths && !fisher;
@@ -857,10 +887,10 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
         LGNN_HIP_CHECK(hipMemsetAsync(gtop + cb * N * C, 0, size_t(N) * nq * 4, s));
       float* sc = h->ws.gram_scratch[L - 1].as<float>();
       if (top_here) switch (int(cdiv(C, 16))) {
-        case 1: LGNN_CALL(seed_spmm_gram_launch<1>(h, fork_exact, gplanes, cb, ce, sc, s)); break;
-        case 2: LGNN_CALL(seed_spmm_gram_launch<2>(h, fork_exact, gplanes, cb, ce, sc, s)); break;
-        case 3: LGNN_CALL(seed_spmm_gram_launch<3>(h, fork_exact, gplanes, cb, ce, sc, s)); break;
-        default: LGNN_CALL(seed_spmm_gram_launch<4>(h, fork_exact, gplanes, cb, ce, sc, s)); break;
+        case 1: LGNN_CALL(seed_spmm_gram_launch<1>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
+        case 2: LGNN_CALL(seed_spmm_gram_launch<2>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
+        case 3: LGNN_CALL(seed_spmm_gram_launch<3>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
+        default: LGNN_CALL(seed_spmm_gram_launch<4>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
       }
     } else {
       int waves = int(std::max<int64_t>(1, std::min<int64_t>(4, (48 * 1024) / (nq * 4))));
@@ -869,6 +899,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
                          h->PT.rowptr, h->PT.col, h->PT.val, N, C, h->ws.pos.as<int32_t>(), h->ws.seeds.as<float>(),
                          gtop, h->ws.active.as<uint8_t>(), cb, ce);
       LGNN_HIP_CHECK(hipGetLastError());
+      active_p = h->ws.active.as<uint8_t>();
       LGNN_CALL(launch_gram(gtop + cb * N * C, C, (ce - cb) * N, C, h->ws.gram_scratch[L - 1].as<float>(), s));
     }
   } else {
@@ -889,7 +920,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   if (paths_route) {
     const int mode = h->lik == LGNN_LIK_REGRESSION ? 2 : (fork_exact ? 1 : 0);
     if (h->kind == LGNN_KIND_GCN)
-      LGNN_CALL(kfac_paths_first_layer(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne));
+      LGNN_CALL(kfac_paths_first_layer(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne, be, &be_built));
     else LGNN_CALL(kfac_paths_first_layer_sage(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne));
   }
 
@@ -904,7 +935,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
       LGNN_CALL(h->ws.val_act.reserve(size_t(h->nnz) * 4));
       const bool gcn = h->kind == LGNN_KIND_GCN;
       hipLaunchKernelGGL(mask_values_kernel, dim3(unsigned(std::min<int64_t>(cdiv(h->nnz, 256), 4096))), dim3(256), 0, s,
-                         h->PT.col, h->PT.val, h->nnz, gcn ? h->ws.active.as<uint8_t>() : (const uint8_t*)nullptr,
+                         h->PT.col, h->PT.val, h->nnz, gcn ? active_p : (const uint8_t*)nullptr,
                          h->ws.pos.as<int32_t>(), h->ws.val_act.as<float>());
       LGNN_HIP_CHECK(hipGetLastError());
       val_top = h->ws.val_act.as<float>();
@@ -919,12 +950,13 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
                                 h->ws.act_count.as<int32_t>(), h->ws.select_tmp, s));
       }
       if (gcn) {
-        row_active = h->ws.active.as<uint8_t>();
+        row_active = active_p;
         if (!have_act_list) {
           LGNN_CALL(h->ws.act_list.reserve(size_t(N) * 4));
           LGNN_CALL(h->ws.act_count.reserve(64));
           LGNN_CALL(compact_flags(row_active, N, h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(),
                                   h->ws.select_tmp, s));
+          act_list_p = h->ws.act_list.as<int32_t>(); act_count_p = h->ws.act_count.as<int32_t>();
         }
       }
     }
@@ -975,7 +1007,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
             BackGemmArgs bg{};
             bg.u_plane_stride = ping_stride;
             bg.G = g; bg.W = h->W[l]; bg.ldw = d; bg.U = ping; bg.N = N; bg.K = dout; bg.Nout = d; bg.planes = cc;
-            bg.rows = h->ws.act_list.as<int32_t>(); bg.na_dev = h->ws.act_count.as<int32_t>();
+            bg.rows = act_list_p; bg.na_dev = act_count_p;
             if (h->act == LGNN_ACT_RELU) { bg.mask_bits = h->fc.mask_bits[l - 1].as<uint32_t>(); bg.mask_words = cdiv(d, 32); }
             else { bg.hact = ep.hact; bg.hact_ld = ep.hact_ld; bg.act = h->act; }
             LGNN_CALL(launch_backgemm(bg, s));
@@ -1139,6 +1171,13 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
     LGNN_CALL(launch_sym_accumulate((h->kind == LGNN_KIND_GCN ? h->ws.gram_scratch_res[l] : h->ws.gram_scratch[l]).as<float>(),
                                     h->dims[l + 1], b_scale, B_out[L + l], s));
   LGNN_CALL(batch_epilogue(h, idx, M, s));
+  // lgnn_batch_cache_stats: a hit launched none of the list-building kernels, a build filled (part of) an entry, a miss ran
+  // the uncached code under a tag
+  if (be_route && batch_tag != 0 && batch_cache_budget() != 0) {
+    if (!be) ++h->bcache.misses;
+    else if (be_built) ++h->bcache.builds;
+    else ++h->bcache.hits;
+  }
   return 0;
 }
 

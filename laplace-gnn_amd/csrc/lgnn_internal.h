@@ -131,6 +131,50 @@ struct Workspace {
   DevBuf dense_rows;    // int32 [2 M + 1]: output / operand rows of the seed term on the dense route
 };
 
+// ---- batch-structure cache (batchcache.hip) ---------------------------------------------------------------------------
+// What a KFAC accumulate derives from the graph and a batch's node ids alone -- not from the weights: the active-row list
+// of the GCN top layer and the two-hop path list of the path route.  The caller names a batch by a 64-bit tag
+// (lgnn_kfac_batch_tag); a tag seen a second time gets an entry, every later accumulate of that batch launches none of the
+// kernels that build these lists.  Entries own their memory (exact sizes, plain hipMalloc: Workspace buffers move when
+// they grow) and are dropped when the graph changes, never by lgnn_invalidate.
+struct BatchEntry {
+  uint64_t tag = 0;
+  int64_t M = 0;
+  uint64_t last_use = 0;
+  size_t bytes = 0, path_bytes = 0;  // device bytes of the whole entry / of its path part
+  bool refused = false;         // over the budget (or out of memory): the tag stays known, nothing is kept or built again
+  int64_t* ids = nullptr;      // [M] the node ids the entry was built from (compared on every hit by mark_batch_kernel)
+  // active rows: flags [N], sorted list [act_n], count (device int32)
+  bool has_act = false;
+  uint8_t* active = nullptr;
+  int32_t* act_list = nullptr;
+  int32_t* act_count = nullptr;
+  // two-hop paths per destination node (CSR over all N nodes); pm / pv / pw stay null when the list overflowed `cap`
+  bool has_paths = false;
+  int64_t cap = 0;              // the list capacity the build ran with (LGNN_PATH_LIST_CAP): another capacity is a rebuild
+  int32_t* pptr = nullptr;      // [N + 1]
+  int32_t* pm = nullptr;
+  int32_t* pv = nullptr;
+  float* pw = nullptr;
+  // nodes of [0, N) with a path (short batches only): list, count (device int32)
+  bool has_nodes = false;
+  int32_t* nodes = nullptr;
+  int32_t* nnodes = nullptr;
+  // R = P^T[:, batch], kept only where the overflow route can be reached
+  bool has_r = false;
+  int32_t* rptr = nullptr;      // [N + 1]
+  int32_t* r_m = nullptr;
+  float* r_w = nullptr;
+};
+struct BatchCache {
+  std::vector<BatchEntry*> entries;
+  std::vector<uint64_t> seen;   // tags met once and not cached yet (bounded; the oldest goes first)
+  uint64_t pending_tag = 0;     // lgnn_kfac_batch_tag: consumed and cleared by the next accumulate
+  uint64_t clock = 0;
+  size_t bytes = 0;
+  int64_t hits = 0, misses = 0, builds = 0;
+};
+
 }  // namespace lgnn
 
 struct lgnn_ctx {
@@ -195,6 +239,7 @@ struct lgnn_ctx {
   std::vector<hipEvent_t> ev;   // pairs (start, stop), grown on demand
   size_t ev_used = 0;           // events recorded since the last reset
   int64_t ev_planes = 0;
+  lgnn::BatchCache bcache;
 };
 
 namespace lgnn {
@@ -400,18 +445,27 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
                     int64_t class_begin, int64_t class_end, float* const* A_out, float* const* B_out, float* loss_out,
                     hipStream_t s, const KfacFisherOpts* fisher = nullptr, const KfacShare* share = nullptr);
 int batch_prologue(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, bool want_seeds, bool fork_exact,
-                   float* loss_out, hipStream_t s, const void* y_seed = nullptr, float resid_scale = 1.0f);
+                   float* loss_out, hipStream_t s, const void* y_seed = nullptr, float resid_scale = 1.0f,
+                   const int64_t* guard_ids = nullptr);  // guard_ids: the ids a cache entry was built from (compared on the device)
 int batch_epilogue(lgnn_ctx* h, const int64_t* idx, int64_t M, hipStream_t s);
 // timing hook (lgnn_enable_kernel_timing): one HIP event on the launch stream; callers bracket the dominant kernel
 int record_event(lgnn_ctx* h, hipStream_t s);
+// ---- batchcache.hip -----------------------------------------------------------------------
+size_t batch_cache_budget();                 // LGNN_BATCH_CACHE_MB in bytes, read per call (0: off)
+void batch_cache_clear(lgnn_ctx* h);         // the graph changed / the context goes: every entry and every remembered tag
+int batch_cache_lookup(lgnn_ctx* h, uint64_t tag, const int64_t* idx, int64_t M, BatchEntry** out, hipStream_t s);
+int batch_cache_store_active(lgnn_ctx* h, BatchEntry* e, hipStream_t s);   // from ws.active / act_list / act_count
+int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r, bool have_nodes, hipStream_t s);
+void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e);
 // ---- paths.hip ----------------------------------------------------------------------------
 bool paths_supported(int kind, int L, const int64_t* dims, int act, int64_t nnz);
 int two_hop_ensure(lgnn_ctx* h, hipStream_t s);   // h->two_hop = 2-hop paths of the graph, counted once (one synchronisation)
 bool paths_pay(const lgnn_ctx* h, int64_t M);     // expected paths per destination node of a batch of M small enough
 // scratch [H, H] += B_0 of this batch's class columns [cb, ce) (seed_mode: 0 upstream, 1 fork exact, 2 regression)
 // (nb, ne: the destination nodes whose Y_n^T Y_n this call adds -- B_0 is a sum over nodes: the multi-GPU cut of these routes)
+// (entry: the batch's cache entry or null; its path part is used if present and built into it otherwise; *built is set then)
 int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce, float* scratch,
-                           hipStream_t s, int64_t nb = 0, int64_t ne = -1);
+                           hipStream_t s, int64_t nb = 0, int64_t ne = -1, BatchEntry* entry = nullptr, bool* built = nullptr);
 int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce,
                                 float* scratch, hipStream_t s, int64_t nb = 0, int64_t ne = -1);  // GraphSAGE: one-hop paths through the same fused kernel
 // scratch [width, width] (upper 32 x 32 sub-tiles) += Y^T Y for rows of `width` floats (row stride ld), 128 < width <= 256:

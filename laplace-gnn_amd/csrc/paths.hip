@@ -1377,17 +1377,24 @@ int launch_gram256_stream(const float* Y, int64_t ld, int64_t rows, int64_t widt
 
 // The nodes of [nb, ne) that have a path, as a device-side list (GraphSAGE: 65 % of the nodes at the arxiv shape; a short last
 // batch of a GCN: 70 %): the fused kernel's node loop, its barriers and its staging pipeline then only see those.
-static int path_node_list(lgnn_ctx* h, int64_t nb, int64_t ne, hipStream_t s) {
+static int path_node_list(lgnn_ctx* h, const int32_t* pptr, int64_t nb, int64_t ne, hipStream_t s) {
   Workspace& ws = h->ws;
   const int64_t n = ne - nb;
   LGNN_CALL(ws.path_flags.reserve(size_t(h->N)));
   LGNN_CALL(ws.path_nodes.reserve(size_t(h->N) * 4));
   LGNN_CALL(ws.path_nnodes.reserve(64));
-  hipLaunchKernelGGL(path_flag_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, ws.path_pptr.as<int32_t>(), nb, n,
+  hipLaunchKernelGGL(path_flag_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, pptr, nb, n,
                      ws.path_flags.as<uint8_t>());
   LGNN_HIP_CHECK(hipGetLastError());
   return compact_flags(ws.path_flags.as<uint8_t>(), n, ws.path_nodes.as<int32_t>(), ws.path_nnodes.as<int32_t>(), ws.select_tmp, s);
 }
+
+// R, the path list and the node list of a batch as the launches below read them: the workspace's or a cache entry's
+struct PathLists {
+  const int32_t* rptr; const int32_t* r_m; const float* r_w;
+  const int32_t* pptr; const int32_t* pm; const int32_t* pv; const float* pw;
+  const int32_t* nodes; const int32_t* nnodes;
+};
 
 static int gram_f32() {  // LGNN_GRAM_F32=1: the fused kernel's Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
   const char* e = getenv("LGNN_GRAM_F32");
@@ -1400,7 +1407,7 @@ constexpr int64_t kFusedWorkgroups = 256;
 // B_0 scratch += sum over the class columns [cb, ce) of this batch (see the file header).  Needs batch_prologue's
 // probabilities / multiplicities / positions and the cached forward (logits, mask bits).
 int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce, float* scratch,
-                           hipStream_t s, int64_t nb, int64_t ne) {
+                           hipStream_t s, int64_t nb, int64_t ne, BatchEntry* entry, bool* built) {
   const int64_t N = h->N, C = h->dims[2], H = h->dims[1];
   if (ne < 0) ne = N;
   LGNN_REQUIRE(nb >= 0 && nb <= ne && ne <= N, "internal: node range");
@@ -1420,64 +1427,94 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     GemmEpilogue none;
     LGNN_CALL(launch_gemm(ws.path_up.as<float>(), C, h->W[1], H, ws.path_bg.as<float>(), H, 2 * M, C, H, none, s));
   }
-  // ---- R = P^T[:, batch]
-  LGNN_CALL(ws.path_cnt.reserve(size_t(N + 1) * 4));
-  LGNN_CALL(ws.path_rptr.reserve(size_t(N + 1) * 4));
-  LGNN_CALL(ws.path_rm.reserve(size_t(std::max<int64_t>(h->nnz, 1)) * 4));
-  LGNN_CALL(ws.path_rw.reserve(size_t(std::max<int64_t>(h->nnz, 1)) * 4));
-  LGNN_CALL(ws.path_zeros.reserve(1024));
-  if (!ws.path_zeros_set) {
-    LGNN_HIP_CHECK(hipMemsetAsync(ws.path_zeros.p, 0, 1024, s));
-    ws.path_zeros_set = true;
-  }
-  LGNN_HIP_CHECK(hipMemsetAsync(ws.path_cnt.p, 0, size_t(N + 1) * 4, s));
-  hipLaunchKernelGGL(path_r_kernel<false>, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, ws.pos.as<int32_t>(),
-                     ws.mult.as<int32_t>(), h->P.rowptr, h->P.col, h->P.val, ws.path_cnt.as<int32_t>(),
-                     static_cast<const int32_t*>(nullptr), static_cast<int32_t*>(nullptr), static_cast<float*>(nullptr));
-  LGNN_CALL(exclusive_scan_i32(ws.path_cnt.as<int32_t>(), ws.path_rptr.as<int32_t>(), N + 1, ws.select_tmp, s));
-  LGNN_HIP_CHECK(hipMemsetAsync(ws.path_cnt.p, 0, size_t(N + 1) * 4, s));
-  hipLaunchKernelGGL(path_r_kernel<true>, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, ws.pos.as<int32_t>(),
-                     ws.mult.as<int32_t>(), h->P.rowptr, h->P.col, h->P.val, ws.path_cnt.as<int32_t>(),
-                     ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>());
-  LGNN_HIP_CHECK(hipGetLastError());
-  // ---- the paths of every destination node: count (one wave per node), scan, fill -- when they fit the buffer
   // (arxiv shape: 2.2 M paths per batch of 10 000.  LGNN_PATH_LIST_CAP, read per call: tests force the enumerating route)
   int64_t cap = std::max<int64_t>(4 * h->nnz, int64_t(1) << 22);
   if (const char* e = getenv("LGNN_PATH_LIST_CAP")) cap = std::max<int64_t>(1, std::min<int64_t>(cap, atoll(e)));
-  LGNN_CALL(ws.path_pcnt.reserve(size_t(N + 1) * 4));
-  LGNN_CALL(ws.path_pptr.reserve(size_t(N + 1) * 4));
-  LGNN_CALL(ws.path_pm.reserve(size_t(cap) * 4));
-  LGNN_CALL(ws.path_pv.reserve(size_t(cap) * 4));
-  LGNN_CALL(ws.path_pw.reserve(size_t(cap) * 4));
-  LGNN_HIP_CHECK(hipMemsetAsync(ws.path_pcnt.as<int32_t>() + N, 0, 4, s));
-  const dim3 pgrid{unsigned(cdiv(N, 4))};
-  hipLaunchKernelGGL(path_list_kernel<false>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N,
-                     ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>(), ws.path_pcnt.as<int32_t>(),
-                     static_cast<const int32_t*>(nullptr), cap, static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                     static_cast<float*>(nullptr));
-  LGNN_CALL(exclusive_scan_i32(ws.path_pcnt.as<int32_t>(), ws.path_pptr.as<int32_t>(), N + 1, ws.select_tmp, s));
-  hipLaunchKernelGGL(path_list_kernel<true>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N,
-                     ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>(), ws.path_pcnt.as<int32_t>(),
-                     ws.path_pptr.as<int32_t>(), cap, ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>());
-  LGNN_HIP_CHECK(hipGetLastError());
-  // ---- class chunks of <= kYRows: everything of a node on one CU (paths_fused_kernel).  Only if the path list overflowed its
-  // buffer do the two launches behind it run: the enumerating Y builder (planes in HBM, under the workspace cap) and the
-  // streaming Gram over them; otherwise they return at once and no plane is ever allocated.
-  LGNN_REQUIRE(N < (int64_t(1) << 31), "too many nodes for one launch");
+  // the overflow route below is gated on the device (the host cannot know a batch's path count without a synchronisation).
+  // What the host does know is a bound: M times the largest number of paths that start at one node (counted once per graph
+  // beside the graph's total).  If that fits the list, no batch can overflow and R is scratch of the list's build.
+  const bool can_overflow = !(h->two_hop_max >= 0 && double(M) * h->two_hop_max <= double(cap));
   // the list of nodes with paths pays when a good share of the nodes has none: with p expected paths per node that share is
   // about exp(-p) (a full arxiv-shaped batch: p = 13.7, every node has paths -- the list would be pure overhead, measured
   // +0.17 ms per launch; its last batch of 941 samples: p = 1.3, 28 % of the nodes without)
   const double ppn = h->two_hop >= 0 ? h->two_hop / double(N) * double(M) / double(N) : 1e9;
   const bool use_list = ppn < 2.5;
-  if (use_list) LGNN_CALL(path_node_list(h, nb, ne, s));
+  const bool whole = nb == 0 && ne == N;  // (a node share builds its own node list: the cached one covers all N nodes)
+  // ---- R, the path list and the node list depend on the graph and the batch's ids only: a batch-structure cache entry
+  // (batchcache.hip) holds them from the second accumulate of a batch on, and none of the kernels below is launched
+  LGNN_CALL(ws.path_zeros.reserve(1024));
+  if (!ws.path_zeros_set) {
+    LGNN_HIP_CHECK(hipMemsetAsync(ws.path_zeros.p, 0, 1024, s));
+    ws.path_zeros_set = true;
+  }
+  if (entry && entry->refused) entry = nullptr;
+  if (entry && entry->has_paths && (entry->cap != cap || (can_overflow && !entry->has_r))) batch_cache_drop_paths(h, entry);
+  const bool cached = entry && entry->has_paths;
+  PathLists pl{};
+  if (cached) {
+    pl.rptr = entry->rptr; pl.r_m = entry->r_m; pl.r_w = entry->r_w;
+    pl.pptr = entry->pptr; pl.pm = entry->pm; pl.pv = entry->pv; pl.pw = entry->pw;
+  } else {
+    // ---- R = P^T[:, batch]
+    LGNN_CALL(ws.path_cnt.reserve(size_t(N + 1) * 4));
+    LGNN_CALL(ws.path_rptr.reserve(size_t(N + 1) * 4));
+    LGNN_CALL(ws.path_rm.reserve(size_t(std::max<int64_t>(h->nnz, 1)) * 4));
+    LGNN_CALL(ws.path_rw.reserve(size_t(std::max<int64_t>(h->nnz, 1)) * 4));
+    LGNN_HIP_CHECK(hipMemsetAsync(ws.path_cnt.p, 0, size_t(N + 1) * 4, s));
+    hipLaunchKernelGGL(path_r_kernel<false>, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, ws.pos.as<int32_t>(),
+                       ws.mult.as<int32_t>(), h->P.rowptr, h->P.col, h->P.val, ws.path_cnt.as<int32_t>(),
+                       static_cast<const int32_t*>(nullptr), static_cast<int32_t*>(nullptr), static_cast<float*>(nullptr));
+    LGNN_CALL(exclusive_scan_i32(ws.path_cnt.as<int32_t>(), ws.path_rptr.as<int32_t>(), N + 1, ws.select_tmp, s));
+    LGNN_HIP_CHECK(hipMemsetAsync(ws.path_cnt.p, 0, size_t(N + 1) * 4, s));
+    hipLaunchKernelGGL(path_r_kernel<true>, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, ws.pos.as<int32_t>(),
+                       ws.mult.as<int32_t>(), h->P.rowptr, h->P.col, h->P.val, ws.path_cnt.as<int32_t>(),
+                       ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>());
+    LGNN_HIP_CHECK(hipGetLastError());
+    // ---- the paths of every destination node: count (one wave per node), scan, fill -- when they fit the buffer
+    LGNN_CALL(ws.path_pcnt.reserve(size_t(N + 1) * 4));
+    LGNN_CALL(ws.path_pptr.reserve(size_t(N + 1) * 4));
+    LGNN_CALL(ws.path_pm.reserve(size_t(cap) * 4));
+    LGNN_CALL(ws.path_pv.reserve(size_t(cap) * 4));
+    LGNN_CALL(ws.path_pw.reserve(size_t(cap) * 4));
+    LGNN_HIP_CHECK(hipMemsetAsync(ws.path_pcnt.as<int32_t>() + N, 0, 4, s));
+    const dim3 pgrid{unsigned(cdiv(N, 4))};
+    hipLaunchKernelGGL(path_list_kernel<false>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N,
+                       ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>(), ws.path_pcnt.as<int32_t>(),
+                       static_cast<const int32_t*>(nullptr), cap, static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
+                       static_cast<float*>(nullptr));
+    LGNN_CALL(exclusive_scan_i32(ws.path_pcnt.as<int32_t>(), ws.path_pptr.as<int32_t>(), N + 1, ws.select_tmp, s));
+    hipLaunchKernelGGL(path_list_kernel<true>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N,
+                       ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>(), ws.path_pcnt.as<int32_t>(),
+                       ws.path_pptr.as<int32_t>(), cap, ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>());
+    LGNN_HIP_CHECK(hipGetLastError());
+    pl.rptr = ws.path_rptr.as<int32_t>(); pl.r_m = ws.path_rm.as<int32_t>(); pl.r_w = ws.path_rw.as<float>();
+    pl.pptr = ws.path_pptr.as<int32_t>(); pl.pm = ws.path_pm.as<int32_t>(); pl.pv = ws.path_pv.as<int32_t>();
+    pl.pw = ws.path_pw.as<float>();
+  }
+  LGNN_REQUIRE(N < (int64_t(1) << 31), "too many nodes for one launch");
+  if (use_list) {
+    if (cached && whole && entry->has_nodes) {
+      pl.nodes = entry->nodes; pl.nnodes = entry->nnodes;
+    } else {
+      LGNN_CALL(path_node_list(h, pl.pptr, nb, ne, s));
+      pl.nodes = ws.path_nodes.as<int32_t>(); pl.nnodes = ws.path_nnodes.as<int32_t>();
+    }
+  }
+  if (entry && !cached) {  // (this call goes on with the workspace's copy: the entry may be refused for its size)
+    LGNN_CALL(batch_cache_store_paths(h, entry, cap, can_overflow, use_list && whole, s));
+    if (built) *built = true;
+  }
+  // ---- class chunks of <= kYRows: everything of a node on one CU (paths_fused_kernel).  Only if the path list overflowed its
+  // buffer do the two launches behind it run: the enumerating Y builder (planes in HBM, under the workspace cap) and the
+  // streaming Gram over them; otherwise they return at once and no plane is ever allocated.
   for (int64_t c0 = cb; c0 < ce; c0 += kYRows) {
     const int64_t R = std::min<int64_t>(kYRows, ce - c0);
     YArgs y{};
-    if (use_list) { y.list = ws.path_nodes.as<int32_t>(); y.n_list = ws.path_nnodes.as<int32_t>(); }
+    if (use_list) { y.list = pl.nodes; y.n_list = pl.nnodes; }
     y.rowptr = h->PT.rowptr; y.col = h->PT.col; y.val = h->PT.val;
-    y.rptr = ws.path_rptr.as<int32_t>(); y.r_m = ws.path_rm.as<int32_t>(); y.r_w = ws.path_rw.as<float>();
-    y.pptr = ws.path_pptr.as<int32_t>(); y.pm = ws.path_pm.as<int32_t>(); y.pv = ws.path_pv.as<int32_t>();
-    y.pw = ws.path_pw.as<float>(); y.cap = cap;
+    y.rptr = pl.rptr; y.r_m = pl.r_m; y.r_w = pl.r_w;
+    y.pptr = pl.pptr; y.pm = pl.pm; y.pv = pl.pv;
+    y.pw = pl.pw; y.cap = cap;
     y.coef = ws.path_coef.as<float>(); y.bg = ws.path_bg.as<float>(); y.zeros = ws.path_zeros.as<float>();
     y.mask = h->fc.mask_bits[0].as<uint32_t>(); y.mask_words = int(cdiv(H, 32));
     y.W1 = h->W[1]; y.w1_ld = int(H); y.Y = nullptr; y.N = N; y.n0 = nb; y.n1 = ne; y.M = M; y.H = int(H); y.c0 = int(c0); y.R = int(R);
@@ -1488,11 +1525,9 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     LGNN_HIP_CHECK(hipGetLastError());
     if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += R; }
   }
-  // the overflow route: gated on the device (the host cannot know a batch's path count without a synchronisation).  What the
-  // host does know is a bound: M times the largest number of paths that start at one node (counted once per graph beside the
-  // graph's total).  If that fits the list, no batch can overflow: no planes, no launches (arxiv shape: 10 000 x 726 paths
-  // against a cap of 10 M entries -- the 6.9 GB of planes are never reserved).
-  if (h->two_hop_max >= 0 && double(M) * h->two_hop_max <= double(cap)) return 0;
+  // the overflow route: where no batch can overflow (see can_overflow above) no planes, no launches (arxiv shape: 10 000 x 726
+  // paths against a cap of 10 M entries -- the 6.9 GB of planes are never reserved).
+  if (!can_overflow) return 0;
   const int64_t per_class = N * H * 4;
   const int64_t cc_max = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ce - cb, 64),
                                                                 h->ws_limit / std::max<int64_t>(per_class, 1)));
@@ -1502,8 +1537,8 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     const int64_t R = std::min(cc_max, ce - c0);
     YArgs y{};
     y.rowptr = h->PT.rowptr; y.col = h->PT.col; y.val = h->PT.val;
-    y.rptr = ws.path_rptr.as<int32_t>(); y.r_m = ws.path_rm.as<int32_t>(); y.r_w = ws.path_rw.as<float>();
-    y.pptr = ws.path_pptr.as<int32_t>(); y.cap = cap;
+    y.rptr = pl.rptr; y.r_m = pl.r_m; y.r_w = pl.r_w;
+    y.pptr = pl.pptr; y.cap = cap;
     y.coef = ws.path_coef.as<float>(); y.bg = ws.path_bg.as<float>(); y.zeros = ws.path_zeros.as<float>();
     y.mask = h->fc.mask_bits[0].as<uint32_t>(); y.mask_words = int(cdiv(H, 32));
     y.W1 = h->W[1]; y.w1_ld = int(H); y.Y = ws.planes_a.as<float>(); y.N = N; y.n0 = nb; y.n1 = ne; y.M = M; y.H = int(H); y.c0 = int(c0); y.R = int(R);
@@ -1511,7 +1546,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     const unsigned threads = unsigned(64 * cdiv(H, 64) * cdiv(R, 32));  // (column groups) x (32-class row tiles) waves
     hipLaunchKernelGGL(ybuild_kernel, dim3(unsigned(std::min<int64_t>(ne - nb, 1024))), dim3(threads), 0, s, y);
     LGNN_HIP_CHECK(hipGetLastError());
-    LGNN_CALL(launch_gram256_stream(y.Y + nb * R * H, H, (ne - nb) * R, H, scratch, s, ws.path_pptr.as<int32_t>() + N, cap));
+    LGNN_CALL(launch_gram256_stream(y.Y + nb * R * H, H, (ne - nb) * R, H, scratch, s, pl.pptr + N, cap));
   }
   return 0;
 }
@@ -1569,7 +1604,7 @@ int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int 
                      ws.path_pptr.as<int32_t>(), ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>());
   LGNN_HIP_CHECK(hipGetLastError());
   LGNN_REQUIRE(N < (int64_t(1) << 31), "too many nodes for one launch");
-  LGNN_CALL(path_node_list(h, nb, ne, s));
+  LGNN_CALL(path_node_list(h, ws.path_pptr.as<int32_t>(), nb, ne, s));
   for (int64_t c0 = cb; c0 < ce; c0 += kYRows) {
     const int64_t R = std::min<int64_t>(kYRows, ce - c0);
     YArgs y{};

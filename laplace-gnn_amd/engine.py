@@ -75,6 +75,55 @@ class _IdentityKey:
         return isinstance(other, _IdentityKey) and other.obj is self.obj
 
 
+class BatchTagMap:
+    """Names a batch for the library's batch-structure cache (``lgnn_kfac_batch_tag``): index tensor -> non-zero 64-bit tag.
+
+    Two calls get the same tag exactly when they hand over the same elements of the same tensor, unchanged as far as torch
+    can tell: the key is the identity of the tensor's base (held by reference, so its address cannot be recycled while the key
+    lives), the data pointer, storage offset, length and the version counter (shared by a base and its views; every in-place
+    write through torch bumps it).  ``TensorBatchLoader`` yields slices of one index tensor, so its batches repeat their keys
+    fit after fit; a loader that collates fresh tensors never does and only ever runs the uncached code.  Writes through
+    ``.data`` bump no counter -- the library compares the ids on the device and reports such a batch as an error.
+
+    The map is bounded: the least recently used key goes first, and ``on_drop(tag)`` tells the library."""
+
+    def __init__(self, capacity: int = 64, on_drop=None):
+        from collections import OrderedDict
+        self._map = OrderedDict()
+        self._next = 1
+        self.capacity = int(capacity)
+        self.on_drop = on_drop
+
+    @staticmethod
+    def key(idx: torch.Tensor):
+        base = idx._base if idx._base is not None else idx
+        return (_IdentityKey(base), idx.data_ptr(), idx.storage_offset(), tuple(idx.shape), idx._version)
+
+    def tag(self, idx: torch.Tensor, copied: bool = False) -> int:
+        """The batch's tag; 0 (never cached) for a tensor that had to be copied to be handed over."""
+        if copied or idx.dim() != 1 or not idx.is_contiguous():
+            return 0
+        k = self.key(idx)
+        t = self._map.get(k)
+        if t is not None:
+            self._map.move_to_end(k)
+            return t
+        t = self._next
+        self._next += 1
+        self._map[k] = t
+        while len(self._map) > self.capacity:
+            _, old = self._map.popitem(last=False)
+            if self.on_drop is not None:
+                self.on_drop(old)
+        return t
+
+    def clear(self):
+        self._map.clear()
+
+    def __len__(self):
+        return len(self._map)
+
+
 class GraphEngine:
     """Graph ingest + model binding + per-batch curvature accumulation on one GPU."""
     supports_shares = True  # kfac_accumulate(share=...): lgnn_kfac_accumulate_share
@@ -98,6 +147,7 @@ class GraphEngine:
         _lib.check(rc, "lgnn_create")
         self._bound = None  # keeps the bound tensors alive (borrowed pointers)
         self.dims = None
+        self._batch_tags = BatchTagMap(on_drop=self._drop_batch_tag)
 
     # -- lifetime -----------------------------------------------------------------------------
     def close(self):
@@ -110,6 +160,25 @@ class GraphEngine:
             self.close()
         except Exception:
             pass
+
+    # -- batch-structure cache ------------------------------------------------------------------------
+    def _drop_batch_tag(self, tag: int):
+        if getattr(self, "_h", None) is not None and self._h:
+            _lib.check(self.lib.lgnn_batch_cache_drop(self._h, int(tag)), "lgnn_batch_cache_drop")
+
+    def batch_cache_stats(self) -> dict:
+        """Host-only: the library's batch-structure cache (``LGNN_BATCH_CACHE_MB``, 0 = off): entries held, their device
+        bytes, and the tagged KFAC accumulates so far by outcome -- hits (no list-building kernel launched), misses (first
+        sight of a batch, or not cacheable), builds (an entry was filled)."""
+        out = (C.c_int64 * 5)()
+        _lib.check(self.lib.lgnn_batch_cache_stats(self._h, out), "lgnn_batch_cache_stats")
+        return {"entries": int(out[0]), "bytes": int(out[1]), "hits": int(out[2]), "misses": int(out[3]),
+                "builds": int(out[4])}
+
+    def batch_cache_clear(self):
+        """Forget every cached batch structure (the library's entries and the tags handed out so far)."""
+        self._batch_tags.clear()
+        _lib.check(self.lib.lgnn_batch_cache_drop(self._h, 0), "lgnn_batch_cache_drop")
 
     # -- graph ----------------------------------------------------------------------------------
     @property
@@ -376,7 +445,10 @@ class GraphEngine:
         the batch's work, cut the way the route in use splits best (``lgnn_kfac_accumulate_share``: destination-node ranges
         on the path routes, class ranges otherwise) -- what a data-parallel caller deals to its ranks."""
         self._sync_versions()
+        given = idx
         idx = idx.contiguous()
+        # what the library may keep for this batch across fits (lgnn_kfac_batch_tag; consumed by the accumulate call below)
+        tag = self._batch_tags.tag(idx, copied=idx is not given)
         yp = self._labels(y, idx.shape[0])
         # 2-layer GCN: two-hop path route (csrc/paths.hip).  paths=None: the library decides (shape and the batch's expected
         # paths per node; LGNN_NO_PATHS=1 keeps the planes); True / False force one route where the shape allows
@@ -385,17 +457,19 @@ class GraphEngine:
             (_lib.FLAG_NO_PATHS if no_paths else 0) | (_lib.FLAG_FORCE_PATHS if paths else 0)
         A = _lib.ptr_array([a.data_ptr() for a, _ in views])
         B = _lib.ptr_array([b.data_ptr() for _, b in views])
+        ip = _dev_ptr(idx, torch.int64, "idx")
+        if share is not None and classes is not None:
+            raise ValueError("pass either classes or share")
+        _lib.check(self.lib.lgnn_kfac_batch_tag(self._h, tag), "lgnn_kfac_batch_tag")  # (nothing below raises before the call)
         if share is not None:
-            if classes is not None:
-                raise ValueError("pass either classes or share")
             rc = self.lib.lgnn_kfac_accumulate_share(
-                self._h, _dev_ptr(idx, torch.int64, "idx"), yp, idx.shape[0], int(n_train),
+                self._h, ip, yp, idx.shape[0], int(n_train),
                 flags, int(share[0]), int(share[1]), int(share[2]), A, B, loss.data_ptr(), _stream(self.device))
             _lib.check(rc, "lgnn_kfac_accumulate_share")
             return
         cb, ce = (0, self.dims[-1]) if classes is None else (int(classes[0]), int(classes[1]))
         rc = self.lib.lgnn_kfac_accumulate_classes(
-            self._h, _dev_ptr(idx, torch.int64, "idx"), yp, idx.shape[0], int(n_train),
+            self._h, ip, yp, idx.shape[0], int(n_train),
             flags, cb, ce, A, B, loss.data_ptr(), _stream(self.device))
         _lib.check(rc, "lgnn_kfac_accumulate_classes")
 
