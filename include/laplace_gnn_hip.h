@@ -163,6 +163,34 @@ LGNN_API int lgnn_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, float* out
 /* all-node logits [N, C] (what forward() indexes into) */
 LGNN_API int lgnn_forward_all(lgnn_ctx* h, float* out /* [N, C] */, void* stream);
 
+/* ---- training-mode forward and its backward to the parameters --------------------------------------------------------
+ * Replaces what autograd does for the weight update of the driver's loop (gnn/marglik_training.py:165-186: model.train();
+ * f = model(train_indices); loss = criterion(f, train_labels); loss.backward(); optimizer.step()) on BaseGNN.forward in
+ * training mode (gnn/models/base_gnn.py:136-161 with the convs of gnn/models/layers.py:18-46): per hidden layer
+ * s = res_l(x) + conv_l(P, x), norms[l] (Identity or LayerNorm), act, inverted dropout on all N rows; the last conv; rows idx.
+ *   lgnn_train_forward : out [M, C] = logits of the batch.  drop_masks: host array of L-1 device pointers to uint8 keep-masks
+ *                        [N, dims[l+1]] (1 = kept, the caller draws them; borrowed until the backward has run), or NULL / a NULL
+ *                        entry for no dropout; kept activations are multiplied by drop_scale = 1 / (1 - p).  The call writes a
+ *                        tape into buffers of its own: the cached eval-mode forward (lgnn_forward) is neither read nor changed.
+ *   lgnn_train_backward: grad_out [M, C] = d loss / d out.  Every gradient is OVERWRITTEN (autograd accumulates): grad_W[l]
+ *                        [dims[l+1], in_l] / grad_b[l] of convs.{l}.lin, grad_res_W[l] [dims[l+1], dims[l]] / grad_res_b[l] of
+ *                        res.{l}, grad_norm_w[l] / grad_norm_b[l] [dims[l+1]] of norms.{l} (host arrays of device pointers; NULL
+ *                        where the model has none).  A node listed several times in idx receives the sum of its rows (in batch
+ *                        order: one thread per class column walks a node's positions, so a node listed thousands of times is
+ *                        a serial loop of that length); the GCN bias is propagated, db_l = sum_n rowsum(P)[n] d_l[n, :].
+ *                        No product of either call combines partial sums with float atomics: the weight gradients are split-K
+ *                        products over the nodes whose partials are summed in a fixed order, every other dense product runs
+ *                        unsplit, the SpMMs and reductions have a fixed order -- two calls on the same inputs agree bit for bit.
+ *                        The call consumes the tape: without a forward since the last backward, the last lgnn_invalidate /
+ *                        lgnn_bind_model or the last lgnn_update_adjacency it fails with a message.
+ * fp32; relu / tanh; GCN and GraphSAGE of any bound depth; BatchNorm1d in training mode is refused.  Device memory grows with
+ * N * width (the tape and two signal buffers), never with M * P.                                                          */
+LGNN_API int lgnn_train_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const uint8_t* const* drop_masks /* host */,
+                                float drop_scale, float* out /* [M, C] */, void* stream);
+LGNN_API int lgnn_train_backward(lgnn_ctx* h, const float* grad_out /* [M, C] */, float* const* grad_W, float* const* grad_b,
+                                 float* const* grad_res_W, float* const* grad_res_b, float* const* grad_norm_w,
+                                 float* const* grad_norm_b, void* stream);
+
 /* ---- KFAC factors of one mini-batch --------------------------------------------------------
  * Replaces CurvlinopsInterface.kron (laplace/curvature/curvlinops.py:77-108) =
  * KFACLinearOperator._compute_kfac (curvlinops/kfac.py:540-581, 607-661, 777-875) +

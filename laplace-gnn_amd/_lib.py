@@ -41,6 +41,8 @@ SIGNATURES = {
     "lgnn_set_workspace_limit": (_i32, [_vp, _i64]),
     "lgnn_forward": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "lgnn_forward_all": (_i32, [_vp, _vp, _vp]),
+    "lgnn_train_forward": (_i32, [_vp, _vp, _i64, _pp, C.c_float, _vp, _vp]),
+    "lgnn_train_backward": (_i32, [_vp, _vp, _pp, _pp, _pp, _pp, _pp, _pp, _vp]),
     "lgnn_kfac_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _u32, _pp, _pp, _vp, _vp]),
     "lgnn_kfac_accumulate_classes": (_i32, [_vp, _vp, _vp, _i64, _i64, _u32, _i64, _i64, _pp, _pp, _vp, _vp]),
     "lgnn_kfac_accumulate_share": (_i32, [_vp, _vp, _vp, _i64, _i64, _u32, _i64, _i64, _i64, _pp, _pp, _vp, _vp]),

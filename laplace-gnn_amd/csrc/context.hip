@@ -343,6 +343,7 @@ extern "C" void lgnn_destroy(lgnn_ctx* h) {
     h->ws.gram_scratch_res[l].release();
   }
   for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
+  train_release(h->tr);
   batch_cache_clear(h);
   delete h;
 }
@@ -385,6 +386,7 @@ extern "C" int lgnn_bind_model(lgnn_ctx* h, int num_layers, const int64_t* dims,
   h->fc.x_valid = false;  // a new X / new widths: nothing survives
   h->fc.px_valid = false;
   h->fc.gram_valid[0] = false;
+  h->tr.input_valid = false;
   return lgnn_invalidate(h);
 }
 
@@ -395,6 +397,7 @@ extern "C" int lgnn_invalidate(lgnn_ctx* h) {
   h->fc.valid = false;
   h->fc.aux_valid = false;
   h->fc.wt_valid = false;
+  h->tr.tape_valid = false;  // a training forward's tape belongs to the weights it ran with
   const bool keep0 = h->fc.x_valid && h->kind == LGNN_KIND_GCN;
   for (int l = 0; l < kMaxLayers; ++l) h->fc.gram_valid[l] = (l == 0 && keep0) ? h->fc.gram_valid[0] : false;
   return 0;
@@ -418,6 +421,7 @@ extern "C" int64_t lgnn_device_bytes(const lgnn_ctx* h) {
     t += h->Wt[l].bytes + h->fc.lin_in[l].bytes + h->fc.act_out[l].bytes + h->fc.gram_raw[l].bytes +
          h->fc.prop_in[l].bytes + h->ws.gram_scratch[l].bytes + h->fc.mask_bits[l].bytes + h->Wrt[l].bytes +
          h->Wcomb[l].bytes + h->bcomb[l].bytes + h->fc.xhat[l].bytes + h->fc.rstd[l].bytes + h->ws.gram_scratch_res[l].bytes;
+  t += train_bytes(h->tr);
   return int64_t(t);  // (the batch-structure cache reports its own bytes: lgnn_batch_cache_stats)
 }
 

@@ -510,7 +510,8 @@ int launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, float*
   // combine with float atomics.  Only for linear epilogues (bias is added by slice 0).
   const int64_t tiles = cdiv(R, GBM) * cdiv(Nout, GBN);
   unsigned splitk = 1;
-  if (tiles < 128 && K >= 256 && ep.hact == nullptr && ep.out_act < 0 && ep.row_active == nullptr && C != nullptr) {
+  if (tiles < 128 && K >= 256 && ep.hact == nullptr && ep.out_act < 0 && ep.row_active == nullptr && C != nullptr &&
+      !ep.no_atomics) {
     const int64_t want = std::min<int64_t>(cdiv(256, tiles), cdiv(K, 64));
     g.k_chunk = cdiv(cdiv(K, want), GBK) * GBK;
     splitk = unsigned(cdiv(K, g.k_chunk));

@@ -175,6 +175,29 @@ struct BatchCache {
   int64_t hits = 0, misses = 0, builds = 0;
 };
 
+// ---- training-mode forward / backward (train.hip) ---------------------------------------------------------------------
+// The tape of one lgnn_train_forward call and the scratch of its backward.  Nothing here is read by the eval-mode calls:
+// dropped activations never reach ForwardCache.  Every buffer is counted by lgnn_device_bytes (train_bytes).
+struct TrainState {
+  bool tape_valid = false;   // a forward ran, neither parameters nor graph changed since, no backward consumed it yet
+  bool input_valid = false;  // GraphSAGE: in[0] = [X | P X] matches the graph and X
+  int64_t M = 0;
+  float scale = 1.f;                         // 1 / (1 - p)
+  const uint8_t* masks[kMaxLayers] = {};     // borrowed keep-masks [N, dims[l+1]] per hidden layer (null: keep everything)
+  DevBuf in[kMaxLayers];     // what nn.Linear l reads: GCN l >= 1: h_l [N, dims[l]]; GraphSAGE: cat_l = [h_l | P h_l] [N, 2 dims[l]]
+  DevBuf xhat[kMaxLayers];   // LayerNorm: normalised rows [N, dims[l+1]]
+  DevBuf rstd[kMaxLayers];   // LayerNorm: 1 / sigma per row [N]
+  DevBuf out;                // all-node logits [N, C]
+  DevBuf z, res;             // [N, max width]: Z_l = h_l W_l^T + b_l and res_l(h_l) of the layer being computed (GCN)
+  DevBuf ga, gb;             // backward signals, ping / pong [N, 2 max width]
+  DevBuf keys, keys_sorted, ord, ord_sorted, sort_tmp;  // batch ids sorted by node (stable): the gather's backward adds in m order
+  DevBuf part;               // split-K partials of the weight gradient [slabs][rows][cols + 1]
+  DevBuf wstack;             // GCN with res: [W_l ; Wr_l] [2 dims[l+1], dims[l]]
+  DevBuf norm_part;          // per-workgroup partials of d gamma / d beta [blocks][2][width]
+};
+size_t train_bytes(const TrainState& t);
+void train_release(TrainState& t);
+
 }  // namespace lgnn
 
 struct lgnn_ctx {
@@ -240,6 +263,7 @@ struct lgnn_ctx {
   size_t ev_used = 0;           // events recorded since the last reset
   int64_t ev_planes = 0;
   lgnn::BatchCache bcache;
+  lgnn::TrainState tr;
 };
 
 namespace lgnn {
@@ -362,6 +386,8 @@ struct GemmEpilogue {
   int64_t hact_row_mod = 0;     // hact row = r % hact_row_mod (planes are [c][n][w]); 0 -> r
   int out_act = -1;             // apply activation to the result itself (-1 none)
   const uint8_t* row_active = nullptr;  // optional [hact rows]: rows flagged 0 are neither computed on nor written
+  bool no_atomics = false;              // never split K over workgroups that combine with float atomics: the result is the
+                                        // same bits on every run (training path; fewer workgroups at few-tile, long-K shapes)
 };
 int launch_gemm(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t R,
                 int64_t K, int64_t Nout, const GemmEpilogue& ep, hipStream_t s);

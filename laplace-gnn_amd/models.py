@@ -3,8 +3,12 @@ parameter names (``convs.{i}.lin.weight|bias``) and ``forward(x_indices) -> [M, 
 (gnn/models/base_gnn.py:11-161, gnn/models/models.py:14-62, gnn/models/layers.py:5-46), but a
 sparse adjacency held by the HIP engine instead of a dense N x N ``nn.Parameter``.
 
-Inference (eval mode) runs on the GPU through the C ABI; training the weights is outside the
-accelerated path.  ``res=True`` (``res.{i}`` Linears, base_gnn.py:97-113) and
+Inference (eval mode) runs on the GPU through the C ABI, and so does training: in ``train()`` mode with grad enabled
+``forward`` is a ``torch.autograd.Function`` over ``lgnn_train_forward`` / ``lgnn_train_backward`` (csrc/train.hip), so the
+driver's weight update (gnn/marglik_training.py:165-186: ``f = model(idx); loss.backward(); optimizer.step()``) runs
+unchanged with any ``torch.optim`` optimizer.  Dropout masks are drawn with torch on the model's device
+(``torch.manual_seed`` governs them; the reference's random stream is not reproduced) or injected with
+``set_dropout_masks``; ``norm="batch"`` in training mode is not supported.  ``res=True`` (``res.{i}`` Linears, base_gnn.py:97-113) and
 ``norm="layer"|"batch"`` (``norms.{i}``, base_gnn.py:86-95) are part of the HIP forward / backward (csrc/resnorm.hip).
 Neighbour sampling (``num_sampled_nodes_per_hop``) needs an explicit ``sample_seed`` (the reference's sampler is unseeded).
 """
@@ -17,6 +21,25 @@ import torch
 from torch import nn
 
 from .engine import GraphEngine
+
+
+class _TrainForward(torch.autograd.Function):
+    """``BaseGNN.forward`` in training mode: logits from ``lgnn_train_forward``, parameter gradients from
+    ``lgnn_train_backward`` (one tape per engine; no double backward).  ``params`` are the model's bound parameters in
+    ``named_parameters()`` order without the ``adj*`` ones -- the order ``GraphEngine.train_backward`` returns."""
+
+    @staticmethod
+    def forward(ctx, engine, idx, masks, p, *params):
+        out = engine.train_forward(idx, masks, p)
+        ctx.engine, ctx.token = engine, engine._train_token
+        ctx.keep = (idx, masks)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        grads = ctx.engine.train_backward(grad_out, ctx.token)
+        return (None, None, None, None, *grads)
 
 
 class _Conv(nn.Module):
@@ -165,10 +188,61 @@ class BaseGNN(nn.Module):
         r, c, v = self.engine.export_propagation()
         return torch.sparse_coo_tensor(torch.stack([r, c]), v, (self.num_nodes, self.num_nodes))
 
+    def set_dropout_masks(self, masks):
+        """Inject the dropout masks of the NEXT training-mode forward call instead of drawing them: one entry per hidden
+        layer, ``[num_nodes, hidden]`` each, non-zero = kept (bool / uint8 / the 0-1 pattern of a float mask); kept
+        activations are scaled by ``1 / (1 - dropout.p)`` as usual.  Used once, then drawing resumes; ``None`` cancels."""
+        if masks is None:
+            self._next_masks = None
+            return
+        masks = list(masks)
+        if len(masks) != self.num_layers - 1:
+            raise ValueError(f"need one dropout mask per hidden layer ({self.num_layers - 1}), got {len(masks)}")
+        for l, m in enumerate(masks):
+            if not isinstance(m, torch.Tensor) or tuple(m.shape) != (self.num_nodes, self.hidden_channels):
+                raise ValueError(f"dropout mask {l} must be a tensor of shape {(self.num_nodes, self.hidden_channels)}")
+        self._next_masks = [(m != 0).to(torch.uint8) for m in masks]
+
+    def _train_params(self):
+        """The engine's parameters in named_parameters() order (norms, convs, res); ``adj*`` belongs to the graph."""
+        ps = []
+        if self.norm_kind == "layer":
+            for m in self.norms:
+                ps += [m.weight, m.bias]
+        for c in self.convs:
+            ps += [c.lin.weight, c.lin.bias]
+        for m in self.res:
+            ps += [m.weight, m.bias]
+        return ps
+
+    def _dropout_masks(self, dev):
+        """uint8 keep-masks of one training forward: the injected ones, or one draw per hidden layer with keep-probability
+        ``1 - p`` from torch's generator of the model's device; ``None`` when nothing is dropped."""
+        given = getattr(self, "_next_masks", None)
+        self._next_masks = None
+        if given is not None:
+            return [m.to(dev).contiguous() for m in given]
+        p = float(self.dropout.p)
+        if p <= 0.0 or self.num_layers < 2:
+            return None
+        return [(torch.rand(self.num_nodes, self.hidden_channels, device=dev) >= p).to(torch.uint8)
+                for _ in range(self.num_layers - 1)]
+
     def forward(self, x_indices: torch.Tensor) -> torch.Tensor:
+        dev = self.convs[0].lin.weight.device
+        if self.training and torch.is_grad_enabled():
+            if self.norm_kind == "batch":
+                raise NotImplementedError("norm='batch' in training mode (batch statistics, running-stat update) is not "
+                                          "supported on the HIP path")
+            p = float(self.dropout.p)
+            if p >= 1.0:
+                raise NotImplementedError("dropout_p must be below 1")
+            eng = self.engine
+            return _TrainForward.apply(eng, x_indices.to(dev), self._dropout_masks(dev), p, *self._train_params())
         if self.training and (self.dropout.p > 0 or self.norm_kind == "batch"):
-            raise NotImplementedError("only eval-mode forward runs on the HIP path (Laplace.fit calls model.eval())")
-        return self.engine.forward(x_indices.to(self.convs[0].lin.weight.device))
+            raise NotImplementedError("a training-mode forward under no_grad has no HIP path: call model.eval() "
+                                      "(Laplace.fit does) or enable grad")
+        return self.engine.forward(x_indices.to(dev))
 
 
 class GCN(BaseGNN):
