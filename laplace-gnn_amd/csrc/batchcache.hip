@@ -15,11 +15,8 @@ namespace {
 
 constexpr size_t kSeenMax = 256;  // tags remembered after one sighting (8 bytes each)
 
+// reset the entry, keep tag and M (its arrays free themselves; hipFree waits for the device: no kernel in flight still reads them)
 void free_entry_memory(BatchEntry* e) {
-  void* ptrs[] = {e->ids, e->active, e->act_list, e->act_count, e->pptr, e->pm, e->pv, e->pw, e->nodes, e->nnodes,
-                  e->rptr, e->r_m, e->r_w};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);  // (hipFree waits for the device: no kernel in flight still reads the entry)
   const uint64_t tag = e->tag;
   const int64_t M = e->M;
   *e = BatchEntry{};
@@ -30,7 +27,6 @@ void free_entry_memory(BatchEntry* e) {
 void remove_entry(lgnn_ctx* h, BatchEntry* e) {
   BatchCache& c = h->bcache;
   c.bytes -= e->bytes;
-  free_entry_memory(e);
   c.entries.erase(std::find(c.entries.begin(), c.entries.end(), e));
   delete e;
 }
@@ -49,16 +45,19 @@ bool make_room(lgnn_ctx* h, BatchEntry* e, size_t add, size_t budget) {
   return true;
 }
 
+// (exact size, not DevBuf::reserve: no 256-byte floor, and a failure only refuses the entry -- the HIP error is cleared and
+// no message is left for the caller)
 template <class T>
-int alloc_copy(T** dst, const void* src, size_t count, hipStream_t s) {
-  *dst = nullptr;
+int alloc_copy(DevArray<T>& dst, const void* src, size_t count, hipStream_t s) {
+  dst = {};
   const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  if (hipMalloc(reinterpret_cast<void**>(dst), bytes) != hipSuccess) {
+  if (hipMalloc(&dst.buf.p, bytes) != hipSuccess) {
     (void)hipGetLastError();
-    *dst = nullptr;
+    dst.buf.p = nullptr;
     return 1;
   }
-  if (count > 0) LGNN_HIP_CHECK(hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyDeviceToDevice, s));
+  dst.buf.bytes = bytes;
+  if (count > 0) LGNN_HIP_CHECK(hipMemcpyAsync(dst.buf.p, src, count * sizeof(T), hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -81,7 +80,7 @@ size_t batch_cache_budget() {
 
 void batch_cache_clear(lgnn_ctx* h) {
   BatchCache& c = h->bcache;
-  for (BatchEntry* e : c.entries) { free_entry_memory(e); delete e; }
+  for (BatchEntry* e : c.entries) delete e;
   c.entries.clear();
   c.seen.clear();
   c.bytes = 0;
@@ -134,7 +133,7 @@ int batch_cache_lookup(lgnn_ctx* h, uint64_t tag, const int64_t* idx, int64_t M,
   e->last_use = ++c.clock;
   c.entries.push_back(e);
   const size_t add = size_t(M) * 8;
-  if (!make_room(h, e, add, budget) || alloc_copy(&e->ids, idx, size_t(M), s) != 0) { refuse(h, e); return 0; }
+  if (!make_room(h, e, add, budget) || alloc_copy(e->ids, idx, size_t(M), s) != 0) { refuse(h, e); return 0; }
   e->bytes += add;
   c.bytes += add;
   *out = e;
@@ -151,9 +150,9 @@ int batch_cache_store_active(lgnn_ctx* h, BatchEntry* e, hipStream_t s) {
   LGNN_HIP_CHECK(hipStreamSynchronize(s));
   LGNN_REQUIRE(n >= 0 && n <= N, "internal: active-row count out of range");
   const size_t add = size_t(N) + size_t(std::max(n, 1)) * 4 + 4;
-  if (!make_room(h, e, add, batch_cache_budget()) || alloc_copy(&e->active, h->ws.active.p, size_t(N), s) != 0 ||
-      alloc_copy(&e->act_list, h->ws.act_list.p, size_t(n), s) != 0 ||
-      alloc_copy(&e->act_count, h->ws.act_count.p, 1, s) != 0) {
+  if (!make_room(h, e, add, batch_cache_budget()) || alloc_copy(e->active, h->ws.active.p, size_t(N), s) != 0 ||
+      alloc_copy(e->act_list, h->ws.act_list.p, size_t(n), s) != 0 ||
+      alloc_copy(e->act_count, h->ws.act_count.p, 1, s) != 0) {
     refuse(h, e);
     return 0;
   }
@@ -183,13 +182,13 @@ int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r
   if (keep_r) add += size_t(N + 1) * 4 + std::max<size_t>(nr, 1) * 8;
   if (have_nodes) add += std::max<size_t>(nn, 1) * 4 + 4;
   bool ok = make_room(h, e, add, batch_cache_budget());
-  ok = ok && alloc_copy(&e->pptr, ws.path_pptr.p, size_t(N + 1), s) == 0 && alloc_copy(&e->pm, ws.path_pm.p, np, s) == 0 &&
-       alloc_copy(&e->pv, ws.path_pv.p, np, s) == 0 && alloc_copy(&e->pw, ws.path_pw.p, np, s) == 0;
+  ok = ok && alloc_copy(e->pptr, ws.path_pptr.p, size_t(N + 1), s) == 0 && alloc_copy(e->pm, ws.path_pm.p, np, s) == 0 &&
+       alloc_copy(e->pv, ws.path_pv.p, np, s) == 0 && alloc_copy(e->pw, ws.path_pw.p, np, s) == 0;
   if (ok && keep_r)
-    ok = alloc_copy(&e->rptr, ws.path_rptr.p, size_t(N + 1), s) == 0 && alloc_copy(&e->r_m, ws.path_rm.p, nr, s) == 0 &&
-         alloc_copy(&e->r_w, ws.path_rw.p, nr, s) == 0;
+    ok = alloc_copy(e->rptr, ws.path_rptr.p, size_t(N + 1), s) == 0 && alloc_copy(e->r_m, ws.path_rm.p, nr, s) == 0 &&
+         alloc_copy(e->r_w, ws.path_rw.p, nr, s) == 0;
   if (ok && have_nodes)
-    ok = alloc_copy(&e->nodes, ws.path_nodes.p, nn, s) == 0 && alloc_copy(&e->nnodes, ws.path_nnodes.p, 1, s) == 0;
+    ok = alloc_copy(e->nodes, ws.path_nodes.p, nn, s) == 0 && alloc_copy(e->nnodes, ws.path_nnodes.p, 1, s) == 0;
   if (!ok) { refuse(h, e); return 0; }
   e->bytes += add;
   h->bcache.bytes += add;
@@ -204,11 +203,7 @@ int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r
 // another list capacity (LGNN_PATH_LIST_CAP) or an R that is needed now and was not kept: the path part is built again
 void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e) {
   if (!e->has_paths) return;
-  void* ptrs[] = {e->pptr, e->pm, e->pv, e->pw, e->nodes, e->nnodes, e->rptr, e->r_m, e->r_w};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  e->pptr = e->pm = e->pv = e->nodes = e->nnodes = e->rptr = e->r_m = nullptr;
-  e->pw = e->r_w = nullptr;
+  e->pptr = {}; e->pm = {}; e->pv = {}; e->pw = {}; e->nodes = {}; e->nnodes = {}; e->rptr = {}; e->r_m = {}; e->r_w = {};
   e->has_paths = e->has_r = e->has_nodes = false;
   h->bcache.bytes -= e->path_bytes;
   e->bytes -= e->path_bytes;

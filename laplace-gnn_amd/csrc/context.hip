@@ -53,6 +53,20 @@ void DevBuf::release() {
   bytes = 0;
   host = false;
 }
+DevBuf::~DevBuf() { release(); }
+DevBuf::DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), host(o.host) {
+  o.p = nullptr;
+  o.bytes = 0;
+  o.host = false;
+}
+DevBuf& DevBuf::operator=(DevBuf&& o) noexcept {
+  if (this != &o) {
+    release();
+    p = o.p; bytes = o.bytes; host = o.host;
+    o.p = nullptr; o.bytes = 0; o.host = false;
+  }
+  return *this;
+}
 
 // GCN: what the first Linear reads.  X itself, or -- unaligned feature rows -- a zero padded copy made once per binding
 int forward_input_view(lgnn_ctx* h, hipStream_t s) {
@@ -329,22 +343,14 @@ extern "C" int lgnn_create(lgnn_ctx** out, int64_t num_nodes, const int64_t* edg
   return 0;
 }
 
+lgnn_ctx::~lgnn_ctx() {
+  for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  batch_cache_clear(this);
+}
+
 extern "C" void lgnn_destroy(lgnn_ctx* h) {
   if (!h) return;
   (void)hipDeviceSynchronize();
-  DevBuf* bufs[] = {&h->A_rowptr, &h->A_col, &h->AT_rowptr, &h->AT_col, &h->val_fwd, &h->val_bwd, &h->deg_scale,
-                    &h->fc.out, &h->fc.tmp, &h->fc.res_out, &h->fc.pre_norm, &h->ws.planes_c, &h->ws.path_coef, &h->ws.path_up, &h->ws.path_bg, &h->ws.path_alpha, &h->ws.adj_z0, &h->ws.adj_dir, &h->ws.path_cnt, &h->ws.path_rptr, &h->ws.path_rm, &h->ws.path_rw, &h->ws.path_zeros, &h->ws.path_pcnt, &h->ws.path_pptr, &h->ws.path_pm, &h->ws.path_pv, &h->ws.path_pw, &h->ws.path_flags, &h->ws.path_nodes, &h->ws.path_nnodes, &h->fc.rowsum, &h->fc.dact0, &h->fc.Xpad, &h->ws.pos, &h->ws.seeds, &h->ws.probs, &h->ws.mult, &h->ws.planes_a,
-                    &h->ws.planes_b, &h->ws.misc, &h->ws.jac, &h->long_rows, &h->long_slot, &h->long_tasks, &h->hub, &h->long_rows_fwd, &h->top_multi, &h->top_tasks, &h->top_task_count, &h->top_cnt, &h->top_offs, &h->top_hub_tiles, &h->ws.top, &h->ws.flags, &h->ws.out_flags, &h->ws.out_list, &h->ws.out_count, &h->ws.val_act2, &h->ws.active, &h->ws.val_act, &h->ws.act_list, &h->ws.act_count, &h->ws.select_tmp};
-  for (DevBuf* b : bufs) b->release();
-  for (int l = 0; l < kMaxLayers; ++l) {
-    h->Wt[l].release(); h->fc.lin_in[l].release(); h->fc.act_out[l].release(); h->fc.gram_raw[l].release();
-    h->fc.prop_in[l].release(); h->ws.gram_scratch[l].release(); h->fc.mask_bits[l].release();
-    h->Wrt[l].release(); h->Wcomb[l].release(); h->bcomb[l].release(); h->fc.xhat[l].release(); h->fc.rstd[l].release();
-    h->ws.gram_scratch_res[l].release();
-  }
-  for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-  train_release(h->tr);
-  batch_cache_clear(h);
   delete h;
 }
 
@@ -413,15 +419,7 @@ extern "C" int lgnn_set_workspace_limit(lgnn_ctx* h, int64_t bytes) {
 extern "C" int64_t lgnn_device_bytes(const lgnn_ctx* h) {
   if (!h) return -1;
   size_t t = 0;
-  const DevBuf* bufs[] = {&h->A_rowptr, &h->A_col, &h->AT_rowptr, &h->AT_col, &h->val_fwd, &h->val_bwd, &h->deg_scale,
-                          &h->fc.out, &h->fc.tmp, &h->fc.res_out, &h->fc.pre_norm, &h->ws.planes_c, &h->ws.path_coef, &h->ws.path_up, &h->ws.path_bg, &h->ws.path_alpha, &h->ws.adj_z0, &h->ws.adj_dir, &h->ws.path_cnt, &h->ws.path_rptr, &h->ws.path_rm, &h->ws.path_rw, &h->ws.path_zeros, &h->ws.path_pcnt, &h->ws.path_pptr, &h->ws.path_pm, &h->ws.path_pv, &h->ws.path_pw, &h->ws.path_flags, &h->ws.path_nodes, &h->ws.path_nnodes, &h->fc.rowsum, &h->fc.dact0, &h->fc.Xpad, &h->ws.pos, &h->ws.seeds, &h->ws.probs, &h->ws.mult,
-                          &h->ws.planes_a, &h->ws.planes_b, &h->ws.misc, &h->ws.jac, &h->long_rows, &h->long_slot, &h->long_tasks, &h->hub, &h->long_rows_fwd, &h->top_multi, &h->top_tasks, &h->top_task_count, &h->top_cnt, &h->top_offs, &h->top_hub_tiles, &h->ws.top, &h->ws.flags, &h->ws.out_flags, &h->ws.out_list, &h->ws.out_count, &h->ws.val_act2, &h->ws.active, &h->ws.val_act, &h->ws.act_list, &h->ws.act_count, &h->ws.select_tmp};
-  for (const DevBuf* b : bufs) t += b->bytes;
-  for (int l = 0; l < kMaxLayers; ++l)
-    t += h->Wt[l].bytes + h->fc.lin_in[l].bytes + h->fc.act_out[l].bytes + h->fc.gram_raw[l].bytes +
-         h->fc.prop_in[l].bytes + h->ws.gram_scratch[l].bytes + h->fc.mask_bits[l].bytes + h->Wrt[l].bytes +
-         h->Wcomb[l].bytes + h->bcomb[l].bytes + h->fc.xhat[l].bytes + h->fc.rstd[l].bytes + h->ws.gram_scratch_res[l].bytes;
-  t += train_bytes(h->tr);
+  h->each_buf([&](const DevBuf& b) { t += b.bytes; });
   return int64_t(t);  // (the batch-structure cache reports its own bytes: lgnn_batch_cache_stats)
 }
 

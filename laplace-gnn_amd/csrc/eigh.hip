@@ -30,13 +30,20 @@ rocblas_handle g_handle = nullptr;
 // while the caller's stream still executes queued batches that use g_handle (rocBLAS handles are not meant to serve two
 // streams at once: they carry the solver's device workspace).
 rocblas_handle g_eig_handle = nullptr;
-DevBuf g_e_large;  // off-diagonal workspace of the library path [batch, n]
-DevBuf g_e;    // off-diagonal workspace [batch, n]
-DevBuf g_v;    // Householder vectors [batch][n][256]
-DevBuf g_tau;  // [batch][n]
-DevBuf g_d;    // diagonal of T in, eigenvalues out [batch][n]
-DevBuf g_z;    // eigenvectors of T [batch][n][n]
-DevBuf g_info; // [batch]
+struct EighScratch {
+  DevBuf e_large;  // off-diagonal workspace of the library path [batch, n]
+  DevBuf e;    // off-diagonal workspace [batch, n]
+  DevBuf v;    // Householder vectors [batch][n][256]
+  DevBuf tau;  // [batch][n]
+  DevBuf d;    // diagonal of T in, eigenvalues out [batch][n]
+  DevBuf z;    // eigenvectors of T [batch][n][n]
+  DevBuf info; // [batch]
+};
+// never deleted, like the handles: a hipFree at static destruction could run after the HIP runtime is gone
+EighScratch& scratch() {
+  static auto* s = new EighScratch;
+  return *s;
+}
 
 // The divide and conquer calls of the factors are independent chains of ~75 tiny kernels each (0.9 ms per 256 x 256
 // factor, launch after launch on one CU): each factor's chain goes to a side stream of its own (own rocBLAS handle and
@@ -416,15 +423,15 @@ __global__ __launch_bounds__(256) void backtransform512_kernel(const float* __re
 int stedc_branch(int br, int branches, int64_t n, int64_t batch, hipStream_t st) {
   if (rocblas_set_stream(g_bh[br], st) != rocblas_status_success) { set_error("rocblas_set_stream failed"); return 3; }
   for (int64_t b = br; b < batch; b += branches) {
-    const rocblas_status rs = rocsolver_sstedc(g_bh[br], rocblas_evect_tridiagonal, rocblas_int(n), g_d.as<float>() + b * n,
-                                               g_e.as<float>() + b * n, g_z.as<float>() + b * n * n, rocblas_int(n),
-                                               g_info.as<int32_t>() + b);
+    const rocblas_status rs = rocsolver_sstedc(g_bh[br], rocblas_evect_tridiagonal, rocblas_int(n), scratch().d.as<float>() + b * n,
+                                               scratch().e.as<float>() + b * n, scratch().z.as<float>() + b * n * n, rocblas_int(n),
+                                               scratch().info.as<int32_t>() + b);
     if (rs != rocblas_status_success) { set_error("rocsolver_sstedc failed"); return 3; }
   }
   return 0;
 }
 
-// eigenpairs of the tridiagonal matrices in g_d / g_e -> g_d (values), g_z (vectors), g_info; on stream s
+// eigenpairs of the tridiagonal matrices in scratch().d / scratch().e -> scratch().d (values), scratch().z (vectors), scratch().info; on stream s
 int stedc_all(int64_t n, int64_t batch, hipStream_t s) {
   const int branches = int(std::min<int64_t>(batch, kBranches));
   for (int i = 0; i < branches; ++i) {
@@ -473,30 +480,30 @@ extern "C" int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W,
   // (neither branch touches the shared g_handle: the divide and conquer chains have handles of their own, g_bh, and the
   //  library path g_eig_handle -- queued main-stream work that uses g_handle is never rebound to a side stream from here)
   if (n <= TN && n >= 2) {
-    LGNN_CALL(g_e.reserve(size_t(batch) * n * 4));
-    LGNN_CALL(g_v.reserve(size_t(batch) * n * TN * 4));
-    LGNN_CALL(g_tau.reserve(size_t(batch) * n * 4));
-    LGNN_CALL(g_d.reserve(size_t(batch) * n * 4));
-    LGNN_CALL(g_z.reserve(size_t(batch) * n * n * 4));
-    LGNN_CALL(g_info.reserve(size_t(batch) * 4));
-    hipLaunchKernelGGL(tridiag256_kernel, dim3(unsigned(batch)), dim3(1024), 0, s, A, int(n), g_d.as<float>(),
-                       g_e.as<float>(), g_v.as<float>(), g_tau.as<float>(), int(n), 0, TN);
+    LGNN_CALL(scratch().e.reserve(size_t(batch) * n * 4));
+    LGNN_CALL(scratch().v.reserve(size_t(batch) * n * TN * 4));
+    LGNN_CALL(scratch().tau.reserve(size_t(batch) * n * 4));
+    LGNN_CALL(scratch().d.reserve(size_t(batch) * n * 4));
+    LGNN_CALL(scratch().z.reserve(size_t(batch) * n * n * 4));
+    LGNN_CALL(scratch().info.reserve(size_t(batch) * 4));
+    hipLaunchKernelGGL(tridiag256_kernel, dim3(unsigned(batch)), dim3(1024), 0, s, A, int(n), scratch().d.as<float>(),
+                       scratch().e.as<float>(), scratch().v.as<float>(), scratch().tau.as<float>(), int(n), 0, TN);
     LGNN_HIP_CHECK(hipGetLastError());
     LGNN_CALL(stedc_all(n, batch, s));
-    hipLaunchKernelGGL(backtransform_kernel, dim3(unsigned(cdiv(n, 4)), unsigned(batch)), dim3(256), 0, s, g_z.as<float>(),
-                       int(n), g_v.as<float>(), g_tau.as<float>(), g_d.as<float>(), g_info.as<int32_t>(), A, W, info);
+    hipLaunchKernelGGL(backtransform_kernel, dim3(unsigned(cdiv(n, 4)), unsigned(batch)), dim3(256), 0, s, scratch().z.as<float>(),
+                       int(n), scratch().v.as<float>(), scratch().tau.as<float>(), scratch().d.as<float>(), scratch().info.as<int32_t>(), A, W, info);
     LGNN_HIP_CHECK(hipGetLastError());
     return 0;
   }
   if (n > TN && n <= 2 * TN && n % 4 == 0) {
     // 256 < n <= 512: n - 256 columns by the streaming kernel, the trailing 256 x 256 block by the register-resident one,
     // divide and conquer on the tridiagonal matrix (library), back-transform: four launches + the library's chain
-    LGNN_CALL(g_e.reserve(size_t(batch) * n * 4));
-    LGNN_CALL(g_v.reserve(size_t(batch) * n * n * 4));
-    LGNN_CALL(g_tau.reserve(size_t(batch) * n * 4));
-    LGNN_CALL(g_d.reserve(size_t(batch) * n * 4));
-    LGNN_CALL(g_z.reserve(size_t(batch) * n * n * 4));
-    LGNN_CALL(g_info.reserve(size_t(batch) * 4));
+    LGNN_CALL(scratch().e.reserve(size_t(batch) * n * 4));
+    LGNN_CALL(scratch().v.reserve(size_t(batch) * n * n * 4));
+    LGNN_CALL(scratch().tau.reserve(size_t(batch) * n * 4));
+    LGNN_CALL(scratch().d.reserve(size_t(batch) * n * 4));
+    LGNN_CALL(scratch().z.reserve(size_t(batch) * n * n * 4));
+    LGNN_CALL(scratch().info.reserve(size_t(batch) * 4));
     const size_t smem = size_t(2 * SNB * n + SRG * n + 3 * n + 2 * SNB) * 4;
     LGNN_REQUIRE(smem <= 160 * 1024, "symeig: panel does not fit the LDS");
     static bool attr_set = false;
@@ -505,24 +512,24 @@ extern "C" int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set = true;
     }
-    LGNN_HIP_CHECK(hipMemsetAsync(g_v.p, 0, size_t(batch) * n * n * 4, s));  // (the trailing block's reflectors start at column n - 256)
+    LGNN_HIP_CHECK(hipMemsetAsync(scratch().v.p, 0, size_t(batch) * n * n * 4, s));  // (the trailing block's reflectors start at column n - 256)
     hipLaunchKernelGGL(tridiag_stream_kernel, dim3(unsigned(batch)), dim3(1024), smem, s, A, int(n), int(n - TN),
-                       g_d.as<float>(), g_e.as<float>(), g_v.as<float>(), g_tau.as<float>());
-    hipLaunchKernelGGL(tridiag256_kernel, dim3(unsigned(batch)), dim3(1024), 0, s, A, TN, g_d.as<float>(), g_e.as<float>(),
-                       g_v.as<float>(), g_tau.as<float>(), int(n), int(n - TN), int(n));
+                       scratch().d.as<float>(), scratch().e.as<float>(), scratch().v.as<float>(), scratch().tau.as<float>());
+    hipLaunchKernelGGL(tridiag256_kernel, dim3(unsigned(batch)), dim3(1024), 0, s, A, TN, scratch().d.as<float>(), scratch().e.as<float>(),
+                       scratch().v.as<float>(), scratch().tau.as<float>(), int(n), int(n - TN), int(n));
     LGNN_HIP_CHECK(hipGetLastError());
     LGNN_CALL(stedc_all(n, batch, s));
-    hipLaunchKernelGGL(backtransform512_kernel, dim3(unsigned(cdiv(n, 4)), unsigned(batch)), dim3(256), 0, s, g_z.as<float>(),
-                       int(n), g_v.as<float>(), g_tau.as<float>(), g_d.as<float>(), g_info.as<int32_t>(), A, W, info);
+    hipLaunchKernelGGL(backtransform512_kernel, dim3(unsigned(cdiv(n, 4)), unsigned(batch)), dim3(256), 0, s, scratch().z.as<float>(),
+                       int(n), scratch().v.as<float>(), scratch().tau.as<float>(), scratch().d.as<float>(), scratch().info.as<int32_t>(), A, W, info);
     LGNN_HIP_CHECK(hipGetLastError());
     return 0;
   }
   if (!g_eig_handle && rocblas_create_handle(&g_eig_handle) != rocblas_status_success) { set_error("rocBLAS handle"); return 3; }
   if (rocblas_set_stream(g_eig_handle, s) != rocblas_status_success) { set_error("rocBLAS stream setup failed"); return 3; }
-  LGNN_CALL(g_e_large.reserve(size_t(batch) * n * 4));
+  LGNN_CALL(scratch().e_large.reserve(size_t(batch) * n * 4));
   const rocblas_status st = rocsolver_ssyevd_strided_batched(
       g_eig_handle, rocblas_evect_original, rocblas_fill_upper, rocblas_int(n), A, rocblas_int(n), rocblas_stride(n * n), W,
-      rocblas_stride(n), g_e_large.as<float>(), rocblas_stride(n), info, rocblas_int(batch));
+      rocblas_stride(n), scratch().e_large.as<float>(), rocblas_stride(n), info, rocblas_int(batch));
   if (st != rocblas_status_success) { set_error("rocsolver_ssyevd_strided_batched failed"); return 3; }
   return 0;
 }

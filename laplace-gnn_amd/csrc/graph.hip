@@ -322,90 +322,84 @@ int graph_update(lgnn_ctx* h, const int64_t* fi, const int64_t* fj, const uint8_
   LGNN_REQUIRE(fi && fj && st, "null flip list");
   const bool same = h->A.rowptr == h->AT.rowptr;
   DevBuf kA, kT, fk, tk, fks, tks, sts, tsts, addA, addT, remA, remT, pre, nk, tmp, cnt, flag;
-  DevBuf* all[] = {&kA, &kT, &fk, &tk, &fks, &tks, &sts, &tsts, &addA, &addT, &remA, &remT, &pre, &nk, &tmp, &cnt, &flag};
-  auto cleanup = [&]() { for (DevBuf* b : all) b->release(); };
-  int rc = [&]() -> int {
-    const size_t kb = size_t(std::max<int64_t>(nnz, 1)) * 8;
-    LGNN_CALL(kA.reserve(kb));
-    LGNN_CALL(kT.reserve(kb));
-    for (DevBuf* b : {&fk, &tk, &fks, &tks}) LGNN_CALL(b->reserve(size_t(K) * 8));
-    for (DevBuf* b : {&sts, &tsts}) LGNN_CALL(b->reserve(size_t(K)));
-    for (DevBuf* b : {&addA, &addT}) LGNN_CALL(b->reserve(size_t(K + 1) * 4));
-    for (DevBuf* b : {&remA, &remT}) LGNN_CALL(b->reserve(size_t(nnz + 1) * 4));
-    LGNN_CALL(flag.reserve(64));
-    LGNN_HIP_CHECK(hipMemsetAsync(flag.p, 0, 64, s));
-    int* d_flag = flag.as<int>();  // [0] bad id, [1] duplicate, [2] asymmetric, [4..5] counters of A, [6..7] of A^T
-    const dim3 rg(cdiv(N * 64, 256)), kg(cdiv(K, 256));
-    hipLaunchKernelGGL(expand_keys_kernel, rg, dim3(256), 0, s, h->A.rowptr, h->A.col, N, kA.as<uint64_t>());
-    hipLaunchKernelGGL(expand_keys_kernel, rg, dim3(256), 0, s, h->AT.rowptr, h->AT.col, N, kT.as<uint64_t>());
-    hipLaunchKernelGGL(flip_keys_kernel, kg, dim3(256), 0, s, fi, fj, K, N, fk.as<uint64_t>(), tk.as<uint64_t>(), d_flag);
-    auto sort_pairs = [&](uint64_t* kin, uint64_t* kout, uint8_t* vout) -> int {
-      size_t bytes = 0;
-      LGNN_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, st, vout, size_t(K), 0, 64, s));
-      LGNN_CALL(tmp.reserve(bytes));
-      LGNN_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, bytes, kin, kout, st, vout, size_t(K), 0, 64, s));
-      return 0;
-    };
-    LGNN_CALL(sort_pairs(fk.as<uint64_t>(), fks.as<uint64_t>(), sts.as<uint8_t>()));
-    LGNN_CALL(sort_pairs(tk.as<uint64_t>(), tks.as<uint64_t>(), tsts.as<uint8_t>()));
-    hipLaunchKernelGGL(flip_symmetry_kernel, kg, dim3(256), 0, s, fks.as<uint64_t>(), sts.as<uint8_t>(), K, N, d_flag + 2);
-    LGNN_HIP_CHECK(hipMemsetAsync(remA.p, 0, size_t(nnz + 1) * 4, s));
-    LGNN_HIP_CHECK(hipMemsetAsync(remT.p, 0, size_t(nnz + 1) * 4, s));
-    hipLaunchKernelGGL(flip_classify_kernel, kg, dim3(256), 0, s, kA.as<uint64_t>(), nnz, fks.as<uint64_t>(), sts.as<uint8_t>(),
-                       K, addA.as<int32_t>(), remA.as<int32_t>(), d_flag + 4, d_flag + 1);
-    hipLaunchKernelGGL(flip_classify_kernel, kg, dim3(256), 0, s, kT.as<uint64_t>(), nnz, tks.as<uint64_t>(), tsts.as<uint8_t>(),
-                       K, addT.as<int32_t>(), remT.as<int32_t>(), d_flag + 6, d_flag + 1);
-    int hf[8] = {};
-    LGNN_HIP_CHECK(hipMemcpyAsync(hf, flag.p, 32, hipMemcpyDeviceToHost, s));
-    LGNN_HIP_CHECK(hipStreamSynchronize(s));  // documented: the new entry count has to reach the host
-    LGNN_REQUIRE(hf[0] == 0, "flip entry out of [0, num_nodes)");
-    LGNN_REQUIRE(hf[1] == 0, "a pair is listed twice in the flips");
-    const bool new_same = same && hf[2] == 0;
-    const int64_t nnz2 = nnz - hf[5] + hf[4];
-    LGNN_REQUIRE(hf[4] - hf[5] == hf[6] - hf[7], "internal: adjacency and transpose disagree");
-    LGNN_REQUIRE(nnz2 < (int64_t(1) << 31) - 64, "nnz must fit int32");
-    LGNN_CALL(nk.reserve(size_t(std::max<int64_t>(nnz2, 1)) * 8));
-    LGNN_CALL(pre.reserve(size_t(nnz + K + 2) * 4));
-    auto merged_csr = [&](DevBuf& old, DevBuf& fkeys, DevBuf& add, DevBuf& rem, DevBuf& rowptr, DevBuf& col) -> int {
-      // exclusive prefix sums (n + 1 entries each; the extra entry of the inputs is zero) -> positions
-      int32_t* rem_prefix = pre.as<int32_t>();
-      int32_t* add_prefix = pre.as<int32_t>() + (nnz + 1);
-      LGNN_HIP_CHECK(hipMemsetAsync(add.as<int32_t>() + K, 0, 4, s));
-      LGNN_CALL(exclusive_scan_i32(rem.as<int32_t>(), rem_prefix, nnz + 1, tmp, s));
-      LGNN_CALL(exclusive_scan_i32(add.as<int32_t>(), add_prefix, K + 1, tmp, s));
-      if (nnz > 0)
-        hipLaunchKernelGGL(merge_kept_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, old.as<uint64_t>(), nnz, rem.as<int32_t>(),
-                           rem_prefix, fkeys.as<uint64_t>(), add_prefix, K, nk.as<uint64_t>());
-      hipLaunchKernelGGL(merge_added_kernel, kg, dim3(256), 0, s, fkeys.as<uint64_t>(), add.as<int32_t>(), add_prefix, K,
-                         old.as<uint64_t>(), nnz, rem_prefix, nk.as<uint64_t>());
-      LGNN_CALL(keys_to_csr(nk.as<uint64_t>(), nnz2, N, rowptr, col, tmp, cnt, s));
-      return 0;
-    };
-    LGNN_CALL(merged_csr(kA, fks, addA, remA, h->A_rowptr, h->A_col));
-    h->A.rowptr = h->A_rowptr.as<int32_t>();
-    h->A.col = h->A_col.as<int32_t>();
-    if (new_same) {
-      h->AT = h->A;
-    } else {
-      LGNN_CALL(merged_csr(kT, tks, addT, remT, h->AT_rowptr, h->AT_col));
-      h->AT.rowptr = h->AT_rowptr.as<int32_t>();
-      h->AT.col = h->AT_col.as<int32_t>();
-    }
-    h->nnz = nnz2;
-    h->sym = new_same;
-    LGNN_CALL(graph_values(h, new_same, s));
-    // everything cached from the graph
-    h->fc.valid = false; h->fc.aux_valid = false; h->fc.px_valid = false;
-    h->tr.tape_valid = false; h->tr.input_valid = false;
-    for (int l = 0; l < kMaxLayers; ++l) h->fc.gram_valid[l] = (l == 0 && h->kind == LGNN_KIND_GCN) ? h->fc.gram_valid[0] : false;
-    h->n_long = -1; h->n_long_fwd = -1; h->n_top_multi = 0; h->n_top_slices = 0; h->n_long_tasks = 0; h->two_hop = -1.0; h->two_hop_max = -1.0;
-    batch_cache_clear(h);  // the batches' active rows and path lists are functions of this graph
-    h->ws.planes_a_zero_ptr = nullptr;
-    LGNN_HIP_CHECK(hipStreamSynchronize(s));  // temporaries are released below
+  const size_t kb = size_t(std::max<int64_t>(nnz, 1)) * 8;
+  LGNN_CALL(kA.reserve(kb));
+  LGNN_CALL(kT.reserve(kb));
+  for (DevBuf* b : {&fk, &tk, &fks, &tks}) LGNN_CALL(b->reserve(size_t(K) * 8));
+  for (DevBuf* b : {&sts, &tsts}) LGNN_CALL(b->reserve(size_t(K)));
+  for (DevBuf* b : {&addA, &addT}) LGNN_CALL(b->reserve(size_t(K + 1) * 4));
+  for (DevBuf* b : {&remA, &remT}) LGNN_CALL(b->reserve(size_t(nnz + 1) * 4));
+  LGNN_CALL(flag.reserve(64));
+  LGNN_HIP_CHECK(hipMemsetAsync(flag.p, 0, 64, s));
+  int* d_flag = flag.as<int>();  // [0] bad id, [1] duplicate, [2] asymmetric, [4..5] counters of A, [6..7] of A^T
+  const dim3 rg(cdiv(N * 64, 256)), kg(cdiv(K, 256));
+  hipLaunchKernelGGL(expand_keys_kernel, rg, dim3(256), 0, s, h->A.rowptr, h->A.col, N, kA.as<uint64_t>());
+  hipLaunchKernelGGL(expand_keys_kernel, rg, dim3(256), 0, s, h->AT.rowptr, h->AT.col, N, kT.as<uint64_t>());
+  hipLaunchKernelGGL(flip_keys_kernel, kg, dim3(256), 0, s, fi, fj, K, N, fk.as<uint64_t>(), tk.as<uint64_t>(), d_flag);
+  auto sort_pairs = [&](uint64_t* kin, uint64_t* kout, uint8_t* vout) -> int {
+    size_t bytes = 0;
+    LGNN_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, st, vout, size_t(K), 0, 64, s));
+    LGNN_CALL(tmp.reserve(bytes));
+    LGNN_HIP_CHECK(rocprim::radix_sort_pairs(tmp.p, bytes, kin, kout, st, vout, size_t(K), 0, 64, s));
     return 0;
-  }();
-  cleanup();
-  return rc;
+  };
+  LGNN_CALL(sort_pairs(fk.as<uint64_t>(), fks.as<uint64_t>(), sts.as<uint8_t>()));
+  LGNN_CALL(sort_pairs(tk.as<uint64_t>(), tks.as<uint64_t>(), tsts.as<uint8_t>()));
+  hipLaunchKernelGGL(flip_symmetry_kernel, kg, dim3(256), 0, s, fks.as<uint64_t>(), sts.as<uint8_t>(), K, N, d_flag + 2);
+  LGNN_HIP_CHECK(hipMemsetAsync(remA.p, 0, size_t(nnz + 1) * 4, s));
+  LGNN_HIP_CHECK(hipMemsetAsync(remT.p, 0, size_t(nnz + 1) * 4, s));
+  hipLaunchKernelGGL(flip_classify_kernel, kg, dim3(256), 0, s, kA.as<uint64_t>(), nnz, fks.as<uint64_t>(), sts.as<uint8_t>(),
+                     K, addA.as<int32_t>(), remA.as<int32_t>(), d_flag + 4, d_flag + 1);
+  hipLaunchKernelGGL(flip_classify_kernel, kg, dim3(256), 0, s, kT.as<uint64_t>(), nnz, tks.as<uint64_t>(), tsts.as<uint8_t>(),
+                     K, addT.as<int32_t>(), remT.as<int32_t>(), d_flag + 6, d_flag + 1);
+  int hf[8] = {};
+  LGNN_HIP_CHECK(hipMemcpyAsync(hf, flag.p, 32, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));  // documented: the new entry count has to reach the host
+  LGNN_REQUIRE(hf[0] == 0, "flip entry out of [0, num_nodes)");
+  LGNN_REQUIRE(hf[1] == 0, "a pair is listed twice in the flips");
+  const bool new_same = same && hf[2] == 0;
+  const int64_t nnz2 = nnz - hf[5] + hf[4];
+  LGNN_REQUIRE(hf[4] - hf[5] == hf[6] - hf[7], "internal: adjacency and transpose disagree");
+  LGNN_REQUIRE(nnz2 < (int64_t(1) << 31) - 64, "nnz must fit int32");
+  LGNN_CALL(nk.reserve(size_t(std::max<int64_t>(nnz2, 1)) * 8));
+  LGNN_CALL(pre.reserve(size_t(nnz + K + 2) * 4));
+  auto merged_csr = [&](DevBuf& old, DevBuf& fkeys, DevBuf& add, DevBuf& rem, DevBuf& rowptr, DevBuf& col) -> int {
+    // exclusive prefix sums (n + 1 entries each; the extra entry of the inputs is zero) -> positions
+    int32_t* rem_prefix = pre.as<int32_t>();
+    int32_t* add_prefix = pre.as<int32_t>() + (nnz + 1);
+    LGNN_HIP_CHECK(hipMemsetAsync(add.as<int32_t>() + K, 0, 4, s));
+    LGNN_CALL(exclusive_scan_i32(rem.as<int32_t>(), rem_prefix, nnz + 1, tmp, s));
+    LGNN_CALL(exclusive_scan_i32(add.as<int32_t>(), add_prefix, K + 1, tmp, s));
+    if (nnz > 0)
+      hipLaunchKernelGGL(merge_kept_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, old.as<uint64_t>(), nnz, rem.as<int32_t>(),
+                         rem_prefix, fkeys.as<uint64_t>(), add_prefix, K, nk.as<uint64_t>());
+    hipLaunchKernelGGL(merge_added_kernel, kg, dim3(256), 0, s, fkeys.as<uint64_t>(), add.as<int32_t>(), add_prefix, K,
+                       old.as<uint64_t>(), nnz, rem_prefix, nk.as<uint64_t>());
+    LGNN_CALL(keys_to_csr(nk.as<uint64_t>(), nnz2, N, rowptr, col, tmp, cnt, s));
+    return 0;
+  };
+  LGNN_CALL(merged_csr(kA, fks, addA, remA, h->A_rowptr, h->A_col));
+  h->A.rowptr = h->A_rowptr.as<int32_t>();
+  h->A.col = h->A_col.as<int32_t>();
+  if (new_same) {
+    h->AT = h->A;
+  } else {
+    LGNN_CALL(merged_csr(kT, tks, addT, remT, h->AT_rowptr, h->AT_col));
+    h->AT.rowptr = h->AT_rowptr.as<int32_t>();
+    h->AT.col = h->AT_col.as<int32_t>();
+  }
+  h->nnz = nnz2;
+  h->sym = new_same;
+  LGNN_CALL(graph_values(h, new_same, s));
+  // everything cached from the graph
+  h->fc.valid = false; h->fc.aux_valid = false; h->fc.px_valid = false;
+  h->tr.tape_valid = false; h->tr.input_valid = false;
+  for (int l = 0; l < kMaxLayers; ++l) h->fc.gram_valid[l] = (l == 0 && h->kind == LGNN_KIND_GCN) ? h->fc.gram_valid[0] : false;
+  h->n_long = -1; h->n_long_fwd = -1; h->n_top_multi = 0; h->n_top_slices = 0; h->n_long_tasks = 0; h->two_hop = -1.0; h->two_hop_max = -1.0;
+  batch_cache_clear(h);  // the batches' active rows and path lists are functions of this graph
+  h->ws.planes_a_zero_ptr = nullptr;
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));  // temporaries are released below
+  return 0;
 }
 
 int graph_build(lgnn_ctx* h, const int64_t* ei, int64_t E, hipStream_t s) {
@@ -418,89 +412,77 @@ int graph_build(lgnn_ctx* h, const int64_t* ei, int64_t E, hipStream_t s) {
   LGNN_REQUIRE(total < (int64_t(1) << 31) - 64, "nnz must fit int32");
 
   DevBuf keys_a, keys_b, tmp, cnt, flag;
-  auto cleanup = [&]() {
-    keys_a.release(); keys_b.release(); tmp.release(); cnt.release(); flag.release();
-  };
-  int rc = [&]() -> int {
-    LGNN_CALL(keys_a.reserve(size_t(std::max<int64_t>(total, 1)) * 8));
-    LGNN_CALL(keys_b.reserve(size_t(std::max<int64_t>(total, 1)) * 8 + 8));
-    LGNN_CALL(flag.reserve(64));
-    LGNN_HIP_CHECK(hipMemsetAsync(flag.p, 0, 64, s));
-    int* d_bad = flag.as<int>();
-    int* d_differ = flag.as<int>() + 1;
-    size_t* d_count = reinterpret_cast<size_t*>(flag.as<char>() + 16);
+  LGNN_CALL(keys_a.reserve(size_t(std::max<int64_t>(total, 1)) * 8));
+  LGNN_CALL(keys_b.reserve(size_t(std::max<int64_t>(total, 1)) * 8 + 8));
+  LGNN_CALL(flag.reserve(64));
+  LGNN_HIP_CHECK(hipMemsetAsync(flag.p, 0, 64, s));
+  int* d_bad = flag.as<int>();
+  int* d_differ = flag.as<int>() + 1;
+  size_t* d_count = reinterpret_cast<size_t*>(flag.as<char>() + 16);
 
-    int64_t nnz = 0;
-    if (total > 0) {
-      hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(total)), dim3(256), 0, s, ei, E, N, sym, loops,
-                         keys_a.as<uint64_t>(), d_bad);
-      LGNN_CALL(sort_keys(keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 64, tmp, s));
-      // adjacent-unique == the clamp `adj[adj > 1] = 1`
-      size_t bytes = 0;
-      LGNN_HIP_CHECK(rocprim::unique(nullptr, bytes, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), d_count,
-                                     size_t(total), rocprim::equal_to<uint64_t>(), s));
-      LGNN_CALL(tmp.reserve(bytes));
-      LGNN_HIP_CHECK(rocprim::unique(tmp.p, bytes, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), d_count,
-                                     size_t(total), rocprim::equal_to<uint64_t>(), s));
-      size_t h_count = 0;
-      int h_flags[2] = {0, 0};
-      uint64_t last = 0;
-      LGNN_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(size_t), hipMemcpyDeviceToHost, s));
-      LGNN_HIP_CHECK(hipMemcpyAsync(h_flags, flag.p, 8, hipMemcpyDeviceToHost, s));
-      LGNN_HIP_CHECK(hipStreamSynchronize(s));  // documented: nnz has to reach the host
-      LGNN_REQUIRE(h_flags[0] == 0, "edge_index entry out of [0, num_nodes)");
-      nnz = int64_t(h_count);
-      if (nnz > 0) {
-        LGNN_HIP_CHECK(hipMemcpyAsync(&last, keys_a.as<uint64_t>() + (nnz - 1), 8, hipMemcpyDeviceToHost, s));
-        LGNN_HIP_CHECK(hipStreamSynchronize(s));
-        if (last == kSentinel) --nnz;  // dropped (diagonal / invalid) entries sort last
-      }
-    }
-    h->nnz = nnz;
-    // keys_a[0:nnz) = sorted unique keys of A
-    LGNN_CALL(keys_to_csr(keys_a.as<uint64_t>(), nnz, N, h->A_rowptr, h->A_col, tmp, cnt, s));
-    h->A.rowptr = h->A_rowptr.as<int32_t>();
-    h->A.col = h->A_col.as<int32_t>();
-
-    // transpose
-    bool same = true;
+  int64_t nnz = 0;
+  if (total > 0) {
+    hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(total)), dim3(256), 0, s, ei, E, N, sym, loops,
+                       keys_a.as<uint64_t>(), d_bad);
+    LGNN_CALL(sort_keys(keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 64, tmp, s));
+    // adjacent-unique == the clamp `adj[adj > 1] = 1`
+    size_t bytes = 0;
+    LGNN_HIP_CHECK(rocprim::unique(nullptr, bytes, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), d_count,
+                                   size_t(total), rocprim::equal_to<uint64_t>(), s));
+    LGNN_CALL(tmp.reserve(bytes));
+    LGNN_HIP_CHECK(rocprim::unique(tmp.p, bytes, keys_b.as<uint64_t>(), keys_a.as<uint64_t>(), d_count,
+                                   size_t(total), rocprim::equal_to<uint64_t>(), s));
+    size_t h_count = 0;
+    int h_flags[2] = {0, 0};
+    uint64_t last = 0;
+    LGNN_HIP_CHECK(hipMemcpyAsync(&h_count, d_count, sizeof(size_t), hipMemcpyDeviceToHost, s));
+    LGNN_HIP_CHECK(hipMemcpyAsync(h_flags, flag.p, 8, hipMemcpyDeviceToHost, s));
+    LGNN_HIP_CHECK(hipStreamSynchronize(s));  // documented: nnz has to reach the host
+    LGNN_REQUIRE(h_flags[0] == 0, "edge_index entry out of [0, num_nodes)");
+    nnz = int64_t(h_count);
     if (nnz > 0) {
-      hipLaunchKernelGGL(transpose_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, keys_a.as<uint64_t>(), nnz, N,
-                         keys_b.as<uint64_t>());
-      DevBuf keys_c;
-      int rc2 = [&]() -> int {
-        LGNN_CALL(keys_c.reserve(size_t(nnz) * 8));
-        LGNN_CALL(sort_keys(keys_b.as<uint64_t>(), keys_c.as<uint64_t>(), nnz, 64, tmp, s));
-        hipLaunchKernelGGL(compare_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, keys_a.as<uint64_t>(),
-                           keys_c.as<uint64_t>(), nnz, d_differ);
-        int differ = 0;
-        LGNN_HIP_CHECK(hipMemcpyAsync(&differ, d_differ, 4, hipMemcpyDeviceToHost, s));
-        LGNN_HIP_CHECK(hipStreamSynchronize(s));
-        same = differ == 0;
-        if (!same) {
-          LGNN_CALL(keys_to_csr(keys_c.as<uint64_t>(), nnz, N, h->AT_rowptr, h->AT_col, tmp, cnt, s));
-          LGNN_HIP_CHECK(hipStreamSynchronize(s));
-        }
-        return 0;
-      }();
-      keys_c.release();
-      if (rc2) return rc2;
+      LGNN_HIP_CHECK(hipMemcpyAsync(&last, keys_a.as<uint64_t>() + (nnz - 1), 8, hipMemcpyDeviceToHost, s));
+      LGNN_HIP_CHECK(hipStreamSynchronize(s));
+      if (last == kSentinel) --nnz;  // dropped (diagonal / invalid) entries sort last
     }
-    h->sym = same;
-    if (same) {
-      h->AT = h->A;
-    } else {
-      h->AT.rowptr = h->AT_rowptr.as<int32_t>();
-      h->AT.col = h->AT_col.as<int32_t>();
-    }
+  }
+  h->nnz = nnz;
+  // keys_a[0:nnz) = sorted unique keys of A
+  LGNN_CALL(keys_to_csr(keys_a.as<uint64_t>(), nnz, N, h->A_rowptr, h->A_col, tmp, cnt, s));
+  h->A.rowptr = h->A_rowptr.as<int32_t>();
+  h->A.col = h->A_col.as<int32_t>();
 
-    LGNN_CALL(graph_values(h, same, s));
-    LGNN_HIP_CHECK(hipStreamSynchronize(s));  // temporaries are released below
-    LGNN_HIP_CHECK(hipGetLastError());
-    return 0;
-  }();
-  cleanup();
-  return rc;
+  // transpose
+  bool same = true;
+  if (nnz > 0) {
+    hipLaunchKernelGGL(transpose_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, keys_a.as<uint64_t>(), nnz, N,
+                       keys_b.as<uint64_t>());
+    DevBuf keys_c;  // (freed at the end of this block, behind a stream synchronisation)
+    LGNN_CALL(keys_c.reserve(size_t(nnz) * 8));
+    LGNN_CALL(sort_keys(keys_b.as<uint64_t>(), keys_c.as<uint64_t>(), nnz, 64, tmp, s));
+    hipLaunchKernelGGL(compare_keys_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, keys_a.as<uint64_t>(),
+                       keys_c.as<uint64_t>(), nnz, d_differ);
+    int differ = 0;
+    LGNN_HIP_CHECK(hipMemcpyAsync(&differ, d_differ, 4, hipMemcpyDeviceToHost, s));
+    LGNN_HIP_CHECK(hipStreamSynchronize(s));
+    same = differ == 0;
+    if (!same) {
+      LGNN_CALL(keys_to_csr(keys_c.as<uint64_t>(), nnz, N, h->AT_rowptr, h->AT_col, tmp, cnt, s));
+      LGNN_HIP_CHECK(hipStreamSynchronize(s));
+    }
+  }
+  h->sym = same;
+  if (same) {
+    h->AT = h->A;
+  } else {
+    h->AT.rowptr = h->AT_rowptr.as<int32_t>();
+    h->AT.col = h->AT_col.as<int32_t>();
+  }
+
+  LGNN_CALL(graph_values(h, same, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));  // temporaries are released below
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 }  // namespace lgnn
@@ -537,24 +519,20 @@ extern "C" int lgnn_adj_to_edge_index(const lgnn_ctx* h, int64_t* out, int64_t* 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t N = h->N;
   DevBuf cnt, off, tmp;
-  int rc = [&]() -> int {
-    LGNN_CALL(cnt.reserve(size_t(N + 1) * 4));
-    LGNN_CALL(off.reserve(size_t(N + 1) * 4));
-    LGNN_HIP_CHECK(hipMemsetAsync(cnt.p, 0, size_t(N + 1) * 4, s));
-    hipLaunchKernelGGL(offdiag_count_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, h->A.rowptr, h->A.col, N,
-                       cnt.as<int32_t>());
-    LGNN_CALL(exclusive_scan_i32(cnt.as<int32_t>(), off.as<int32_t>(), N + 1, tmp, s));
-    int32_t total = 0;
-    LGNN_HIP_CHECK(hipMemcpyAsync(&total, off.as<int32_t>() + N, 4, hipMemcpyDeviceToHost, s));
-    LGNN_HIP_CHECK(hipStreamSynchronize(s));
-    *num_out = total;
-    if (out && total > 0) {
-      hipLaunchKernelGGL(offdiag_write_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, h->A.rowptr, h->A.col, N,
-                         off.as<int32_t>(), int64_t(total), out);
-      LGNN_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return 0;
-  }();
-  cnt.release(); off.release(); tmp.release();
-  return rc;
+  LGNN_CALL(cnt.reserve(size_t(N + 1) * 4));
+  LGNN_CALL(off.reserve(size_t(N + 1) * 4));
+  LGNN_HIP_CHECK(hipMemsetAsync(cnt.p, 0, size_t(N + 1) * 4, s));
+  hipLaunchKernelGGL(offdiag_count_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, h->A.rowptr, h->A.col, N,
+                     cnt.as<int32_t>());
+  LGNN_CALL(exclusive_scan_i32(cnt.as<int32_t>(), off.as<int32_t>(), N + 1, tmp, s));
+  int32_t total = 0;
+  LGNN_HIP_CHECK(hipMemcpyAsync(&total, off.as<int32_t>() + N, 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
+  *num_out = total;
+  if (out && total > 0) {
+    hipLaunchKernelGGL(offdiag_write_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, h->A.rowptr, h->A.col, N,
+                       off.as<int32_t>(), int64_t(total), out);
+    LGNN_HIP_CHECK(hipStreamSynchronize(s));  // (`off` goes out of scope below)
+  }
+  return 0;
 }

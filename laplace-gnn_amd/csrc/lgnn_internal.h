@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/laplace_gnn_hip.h"
@@ -38,16 +39,27 @@ void set_error(const std::string& msg);
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// grow-only device buffer (no allocation in steady state)
+// Grow-only device buffer (no allocation in steady state).  It owns its memory: the destructor frees it, so a member of a
+// context struct needs no entry in a release list, and a function's temporary may be left through LGNN_CALL / LGNN_HIP_CHECK /
+// LGNN_REQUIRE.  Move only.  hipFree waits for the device, so an error return never frees under a running kernel; success
+// paths synchronise their stream before a temporary goes out of scope.  What a struct owns is listed once, by the each_buf
+// visitor under its members (lgnn_device_bytes sums over it).
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
   bool host = false;  // reserve_host: pinned host memory the device reads and writes in place (same address on both sides)
+  DevBuf() = default;
+  ~DevBuf();
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept;
+  DevBuf& operator=(DevBuf&& o) noexcept;
   int reserve(size_t want);
   int reserve_host(size_t want);
   void release();
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+static_assert(!std::is_copy_constructible_v<DevBuf>);
 
 // CSR with int32 indices (N, nnz < 2^31), fp32 values aligned with `col`
 struct Csr {
@@ -87,6 +99,12 @@ struct ForwardCache {
   DevBuf rstd[kMaxLayers];           // LayerNorm: [N] 1/sqrt(var + eps) per row; BatchNorm (eval): [dims[l+1]] per channel
   DevBuf res_out;                    // [N, max width] res_l(h_l) of the layer being computed (GCN)
   DevBuf pre_norm;                   // [N, max width] s_l = res_l(h_l) + conv_l(h_l) before the norm
+  template <class F> void each_buf(F&& f) const {
+    for (int l = 0; l < kMaxLayers; ++l) {
+      f(lin_in[l]); f(act_out[l]); f(gram_raw[l]); f(prop_in[l]); f(mask_bits[l]); f(xhat[l]); f(rstd[l]);
+    }
+    f(Xpad); f(out); f(tmp); f(rowsum); f(dact0); f(res_out); f(pre_norm);
+  }
 };
 
 struct Workspace {
@@ -129,42 +147,56 @@ struct Workspace {
   DevBuf lora_rows, lora_cols, lora_state, lora_count, lora_part;
   DevBuf dense_stored;  // fp32 [nnz]: scratch accumulator of the stored-entry terms on the dense route
   DevBuf dense_rows;    // int32 [2 M + 1]: output / operand rows of the seed term on the dense route
+  template <class F> void each_buf(F&& f) const {
+    for (int l = 0; l < kMaxLayers; ++l) { f(gram_scratch[l]); f(gram_scratch_res[l]); }
+    f(pos); f(seeds); f(probs); f(mult); f(planes_a); f(planes_b); f(misc); f(jac); f(top); f(active); f(val_act);
+    f(act_list); f(act_count); f(select_tmp); f(flags); f(out_flags); f(out_list); f(out_count); f(val_act2);
+    f(path_coef); f(path_up); f(path_bg); f(path_cnt); f(path_rptr); f(path_rm); f(path_rw); f(path_zeros); f(path_alpha);
+    f(path_pcnt); f(path_pptr); f(path_pm); f(path_pv); f(path_pw); f(path_flags); f(path_nodes); f(path_nnodes);
+    f(planes_c); f(adj_z0); f(adj_dir); f(lora_rows); f(lora_cols); f(lora_state); f(lora_count); f(lora_part);
+    f(dense_stored); f(dense_rows);
+  }
 };
 
 // ---- batch-structure cache (batchcache.hip) ---------------------------------------------------------------------------
 // What a KFAC accumulate derives from the graph and a batch's node ids alone -- not from the weights: the active-row list
 // of the GCN top layer and the two-hop path list of the path route.  The caller names a batch by a 64-bit tag
 // (lgnn_kfac_batch_tag); a tag seen a second time gets an entry, every later accumulate of that batch launches none of the
-// kernels that build these lists.  Entries own their memory (exact sizes, plain hipMalloc: Workspace buffers move when
+// kernels that build these lists.  Entries own their memory (exact sizes, allocated once: Workspace buffers move when
 // they grow) and are dropped when the graph changes, never by lgnn_invalidate.
+template <class T>
+struct DevArray {  // typed array of an entry: filled once at its exact size (batchcache.hip), null until then
+  DevBuf buf;
+  operator T*() const { return buf.as<T>(); }
+};
 struct BatchEntry {
   uint64_t tag = 0;
   int64_t M = 0;
   uint64_t last_use = 0;
   size_t bytes = 0, path_bytes = 0;  // device bytes of the whole entry / of its path part
   bool refused = false;         // over the budget (or out of memory): the tag stays known, nothing is kept or built again
-  int64_t* ids = nullptr;      // [M] the node ids the entry was built from (compared on every hit by mark_batch_kernel)
+  DevArray<int64_t> ids;       // [M] the node ids the entry was built from (compared on every hit by mark_batch_kernel)
   // active rows: flags [N], sorted list [act_n], count (device int32)
   bool has_act = false;
-  uint8_t* active = nullptr;
-  int32_t* act_list = nullptr;
-  int32_t* act_count = nullptr;
+  DevArray<uint8_t> active;
+  DevArray<int32_t> act_list;
+  DevArray<int32_t> act_count;
   // two-hop paths per destination node (CSR over all N nodes); pm / pv / pw stay null when the list overflowed `cap`
   bool has_paths = false;
   int64_t cap = 0;              // the list capacity the build ran with (LGNN_PATH_LIST_CAP): another capacity is a rebuild
-  int32_t* pptr = nullptr;      // [N + 1]
-  int32_t* pm = nullptr;
-  int32_t* pv = nullptr;
-  float* pw = nullptr;
+  DevArray<int32_t> pptr;       // [N + 1]
+  DevArray<int32_t> pm;
+  DevArray<int32_t> pv;
+  DevArray<float> pw;
   // nodes of [0, N) with a path (short batches only): list, count (device int32)
   bool has_nodes = false;
-  int32_t* nodes = nullptr;
-  int32_t* nnodes = nullptr;
+  DevArray<int32_t> nodes;
+  DevArray<int32_t> nnodes;
   // R = P^T[:, batch], kept only where the overflow route can be reached
   bool has_r = false;
-  int32_t* rptr = nullptr;      // [N + 1]
-  int32_t* r_m = nullptr;
-  float* r_w = nullptr;
+  DevArray<int32_t> rptr;       // [N + 1]
+  DevArray<int32_t> r_m;
+  DevArray<float> r_w;
 };
 struct BatchCache {
   std::vector<BatchEntry*> entries;
@@ -177,7 +209,7 @@ struct BatchCache {
 
 // ---- training-mode forward / backward (train.hip) ---------------------------------------------------------------------
 // The tape of one lgnn_train_forward call and the scratch of its backward.  Nothing here is read by the eval-mode calls:
-// dropped activations never reach ForwardCache.  Every buffer is counted by lgnn_device_bytes (train_bytes).
+// dropped activations never reach ForwardCache.  Every buffer is counted by lgnn_device_bytes (each_buf).
 struct TrainState {
   bool tape_valid = false;   // a forward ran, neither parameters nor graph changed since, no backward consumed it yet
   bool input_valid = false;  // GraphSAGE: in[0] = [X | P X] matches the graph and X
@@ -194,9 +226,12 @@ struct TrainState {
   DevBuf part;               // split-K partials of the weight gradient [slabs][rows][cols + 1]
   DevBuf wstack;             // GCN with res: [W_l ; Wr_l] [2 dims[l+1], dims[l]]
   DevBuf norm_part;          // per-workgroup partials of d gamma / d beta [blocks][2][width]
+  template <class F> void each_buf(F&& f) const {
+    for (int l = 0; l < kMaxLayers; ++l) { f(in[l]); f(xhat[l]); f(rstd[l]); }
+    f(out); f(z); f(res); f(ga); f(gb); f(keys); f(keys_sorted); f(ord); f(ord_sorted); f(sort_tmp);
+    f(part); f(wstack); f(norm_part);
+  }
 };
-size_t train_bytes(const TrainState& t);
-void train_release(TrainState& t);
 
 }  // namespace lgnn
 
@@ -264,6 +299,15 @@ struct lgnn_ctx {
   int64_t ev_planes = 0;
   lgnn::BatchCache bcache;
   lgnn::TrainState tr;
+  // every DevBuf the context owns (the batch cache reports its own bytes: lgnn_batch_cache_stats)
+  template <class F> void each_buf(F&& f) const {
+    for (int l = 0; l < lgnn::kMaxLayers; ++l) { f(Wt[l]); f(Wrt[l]); f(Wcomb[l]); f(bcomb[l]); }
+    f(A_rowptr); f(A_col); f(AT_rowptr); f(AT_col); f(val_fwd); f(val_bwd); f(deg_scale);
+    f(long_rows); f(long_slot); f(long_tasks); f(hub); f(long_rows_fwd);
+    f(top_multi); f(top_tasks); f(top_task_count); f(top_cnt); f(top_offs); f(top_hub_tiles);
+    fc.each_buf(f); ws.each_buf(f); tr.each_buf(f);
+  }
+  ~lgnn_ctx();  // the timing events and the batch cache; the buffers free themselves
 };
 
 namespace lgnn {

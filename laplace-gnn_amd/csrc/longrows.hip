@@ -81,47 +81,37 @@ int long_rows_ensure(lgnn_ctx* h, hipStream_t s) {
   h->n_long = 0;
   h->n_long_tasks = 0;
   if (h->nnz <= 0) return 0;
-  DevBuf flags, cnt, bounds, tmp;
-  auto done = [&](int rc) { flags.release(); cnt.release(); bounds.release(); tmp.release(); return rc; };
-  if (flags.reserve(size_t(N)) || cnt.reserve(64)) return done(1);
+  DevBuf flags, cnt, bounds, tmp;  // (every return below follows a stream synchronisation or an error)
+  LGNN_CALL(flags.reserve(size_t(N)));
+  LGNN_CALL(cnt.reserve(64));
   hipLaunchKernelGGL(flag_long_rows_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, h->PT.rowptr, N, flags.as<uint8_t>());
-  if (h->long_rows.reserve(size_t(N) * 4)) return done(1);
-  if (compact_flags(flags.as<uint8_t>(), N, h->long_rows.as<int32_t>(), cnt.as<int32_t>(), tmp, s)) return done(1);
+  LGNN_CALL(h->long_rows.reserve(size_t(N) * 4));
+  LGNN_CALL(compact_flags(flags.as<uint8_t>(), N, h->long_rows.as<int32_t>(), cnt.as<int32_t>(), tmp, s));
   int32_t n = 0;
-  if (hipMemcpyAsync(&n, cnt.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-    set_error("long rows: count copy failed");
-    return done(1);
-  }
-  if (n == 0) return done(0);
-  if (h->long_slot.reserve(size_t(N) * 4) || bounds.reserve(size_t(n) * 8)) return done(1);
-  if (launch_fill_i32(h->long_slot.as<int32_t>(), N, -1, s)) return done(1);
+  LGNN_HIP_CHECK(hipMemcpyAsync(&n, cnt.p, 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
+  if (n == 0) return 0;
+  LGNN_CALL(h->long_slot.reserve(size_t(N) * 4));
+  LGNN_CALL(bounds.reserve(size_t(n) * 8));
+  LGNN_CALL(launch_fill_i32(h->long_slot.as<int32_t>(), N, -1, s));
   hipLaunchKernelGGL(long_slots_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, s, h->long_rows.as<int32_t>(), int64_t(n),
                      h->PT.rowptr, h->long_slot.as<int32_t>(), bounds.as<int32_t>());
   std::vector<int32_t> hb(size_t(n) * 2), tasks;
-  if (hipMemcpyAsync(hb.data(), bounds.p, size_t(n) * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_error("long rows: bounds copy failed");
-    return done(1);
-  }
+  LGNN_HIP_CHECK(hipMemcpyAsync(hb.data(), bounds.p, size_t(n) * 8, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
   for (int32_t i = 0; i < n; ++i)
     for (int32_t b = hb[2 * i]; b < hb[2 * i + 1]; b += kTask) {
       tasks.push_back(i);
       tasks.push_back(b);
       tasks.push_back(std::min<int32_t>(b + kTask, hb[2 * i + 1]));
     }
-  if (h->long_tasks.reserve(tasks.size() * 4)) return done(1);
-  if (hipMemcpyAsync(h->long_tasks.p, tasks.data(), tasks.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_error("long rows: task upload failed");
-    return done(1);
-  }
+  LGNN_CALL(h->long_tasks.reserve(tasks.size() * 4));
+  LGNN_HIP_CHECK(hipMemcpyAsync(h->long_tasks.p, tasks.data(), tasks.size() * 4, hipMemcpyHostToDevice, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
   // hubs the top-layer kernel cuts into slices of kTopSlice entries (kfac.hip)
   std::vector<int32_t> ids(static_cast<size_t>(n)), multi;
-  if (hipMemcpyAsync(ids.data(), h->long_rows.p, size_t(n) * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess) {
-    set_error("long rows: id copy failed");
-    return done(1);
-  }
+  LGNN_HIP_CHECK(hipMemcpyAsync(ids.data(), h->long_rows.p, size_t(n) * 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
   int64_t slices = 0;
   for (int32_t i = 0; i < n; ++i) {
     const int32_t deg = hb[2 * i + 1] - hb[2 * i];
@@ -130,18 +120,15 @@ int long_rows_ensure(lgnn_ctx* h, hipStream_t s) {
   const int64_t n_multi = int64_t(multi.size());
   if (!multi.empty()) {
     multi.push_back(int32_t(n_multi));  // the list's length behind it: the finishing launch reads its task count there
-    if (h->top_multi.reserve(multi.size() * 4)) return done(1);
-    if (hipMemcpyAsync(h->top_multi.p, multi.data(), multi.size() * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      set_error("long rows: hub list upload failed");
-      return done(1);
-    }
+    LGNN_CALL(h->top_multi.reserve(multi.size() * 4));
+    LGNN_HIP_CHECK(hipMemcpyAsync(h->top_multi.p, multi.data(), multi.size() * 4, hipMemcpyHostToDevice, s));
+    LGNN_HIP_CHECK(hipStreamSynchronize(s));
   }
   h->n_top_multi = n_multi;
   h->n_top_slices = slices;
   h->n_long = n;
   h->n_long_tasks = int64_t(tasks.size() / 3);
-  return done(0);
+  return 0;
 }
 
 int long_rows_fwd_ensure(lgnn_ctx* h, hipStream_t s) {
@@ -155,18 +142,16 @@ int long_rows_fwd_ensure(lgnn_ctx* h, hipStream_t s) {
   }
   const int64_t N = h->N;
   DevBuf flags, cnt, tmp;
-  auto done = [&](int rc) { flags.release(); cnt.release(); tmp.release(); return rc; };
-  if (flags.reserve(size_t(N)) || cnt.reserve(64)) return done(1);
+  LGNN_CALL(flags.reserve(size_t(N)));
+  LGNN_CALL(cnt.reserve(64));
   hipLaunchKernelGGL(flag_long_rows_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, h->P.rowptr, N, flags.as<uint8_t>());
-  if (h->long_rows_fwd.reserve(size_t(N) * 4)) return done(1);
-  if (compact_flags(flags.as<uint8_t>(), N, h->long_rows_fwd.as<int32_t>(), cnt.as<int32_t>(), tmp, s)) return done(1);
+  LGNN_CALL(h->long_rows_fwd.reserve(size_t(N) * 4));
+  LGNN_CALL(compact_flags(flags.as<uint8_t>(), N, h->long_rows_fwd.as<int32_t>(), cnt.as<int32_t>(), tmp, s));
   int32_t n = 0;
-  if (hipMemcpyAsync(&n, cnt.p, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-    set_error("long rows: count copy failed");
-    return done(1);
-  }
+  LGNN_HIP_CHECK(hipMemcpyAsync(&n, cnt.p, 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));  // (the temporaries go out of scope behind it)
   h->n_long_fwd = n;
-  return done(0);
+  return 0;
 }
 
 int launch_long_rows_spmm(lgnn_ctx* h, const float* val, const float* in, int64_t in_ld, int64_t in_plane_stride,

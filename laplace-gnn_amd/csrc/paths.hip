@@ -1329,17 +1329,13 @@ int two_hop_ensure(lgnn_ctx* h, hipStream_t s) {
   DevBuf acc;
   LGNN_CALL(acc.reserve(64));
   unsigned long long host[2] = {0, 0};
-  int rc = 0;
-  if (hipMemsetAsync(acc.p, 0, 16, s) != hipSuccess) rc = 1;
-  if (!rc) {
-    hipLaunchKernelGGL(two_hop_count_kernel, dim3(unsigned(std::min<int64_t>(cdiv(h->N, 256), 1024))), dim3(256), 0, s,
-                       h->P.rowptr, h->PT.rowptr, h->N, acc.as<unsigned long long>());
-    hipLaunchKernelGGL(two_hop_max_kernel, dim3(unsigned(std::min<int64_t>(cdiv(h->N, 256), 1024))), dim3(256), 0, s,
-                       h->P.rowptr, h->P.col, h->N, acc.as<unsigned long long>() + 1);
-    if (hipMemcpyAsync(host, acc.p, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) rc = 1;
-  }
-  acc.release();
-  if (rc) { set_error("two-hop path count failed"); return 1; }
+  LGNN_HIP_CHECK(hipMemsetAsync(acc.p, 0, 16, s));
+  hipLaunchKernelGGL(two_hop_count_kernel, dim3(unsigned(std::min<int64_t>(cdiv(h->N, 256), 1024))), dim3(256), 0, s,
+                     h->P.rowptr, h->PT.rowptr, h->N, acc.as<unsigned long long>());
+  hipLaunchKernelGGL(two_hop_max_kernel, dim3(unsigned(std::min<int64_t>(cdiv(h->N, 256), 1024))), dim3(256), 0, s,
+                     h->P.rowptr, h->P.col, h->N, acc.as<unsigned long long>() + 1);
+  LGNN_HIP_CHECK(hipMemcpyAsync(host, acc.p, 16, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
   h->two_hop = double(host[0]);
   h->two_hop_max = double(host[1]);
   return 0;

@@ -26,25 +26,6 @@ namespace lgnn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// every DevBuf of TrainState, for lgnn_device_bytes and lgnn_destroy (a buffer added to the struct is added here)
-template <class T, class F>
-static void for_each_train_buf(T& t, F f) {
-  for (int l = 0; l < kMaxLayers; ++l) { f(t.in[l]); f(t.xhat[l]); f(t.rstd[l]); }
-  f(t.out); f(t.z); f(t.res); f(t.ga); f(t.gb);
-  f(t.keys); f(t.keys_sorted); f(t.ord); f(t.ord_sorted); f(t.sort_tmp);
-  f(t.part); f(t.wstack); f(t.norm_part);
-}
-size_t train_bytes(const TrainState& t) {
-  size_t tot = 0;
-  for_each_train_buf(t, [&](const DevBuf& b) { tot += b.bytes; });
-  return tot;
-}
-void train_release(TrainState& t) {
-  for_each_train_buf(t, [](DevBuf& b) { b.release(); });
-  t.tape_valid = false;
-  t.input_valid = false;
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

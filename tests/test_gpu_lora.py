@@ -51,7 +51,11 @@ def test_dense_gradient_equals_the_sparse_route_on_the_fixtures(path, structure)
 
 @pytest.mark.parametrize("structure,sym", [("kron", True), ("kron", False), ("diag", True), ("diag", False)])
 def test_dense_gradient_midsize_vs_oracle(structure, sym):
-    """N = 1000, two batches, repeated node ids: the device's dense gradient against the oracle's ``dense=True`` (<= 1e-4)."""
+    """N = 1000, two batches, repeated node ids: the device's dense gradient against the oracle's ``dense=True`` (<= 1e-4).
+    ``device_bytes()`` counts the dense route's scratch accumulator of the stored entries (fp32 [nnz]), which the engine owns:
+    before every buffer was enumerated from its struct, ``lgnn_device_bytes`` left it out (and ``close()`` leaked it).  (The
+    route's other buffers grow in the same call -- 3.3 MB at this shape -- so this bound alone held before as well; measured once
+    for kron / symmetric: 3 350 276 B against 3 313 256 B with the old lists, the difference nnz * 4 + (2 M + 1) * 4 = 37 020.)"""
     import laplace_gnn_amd as lg
 
     N, F, H, C, E, M = 1000, 40, 64, 6, 4000, 300
@@ -66,7 +70,11 @@ def test_dense_gradient_midsize_vs_oracle(structure, sym):
     cls = lg.KronLaplace if structure == "kron" else lg.DiagLaplace
     la = cls(model, "classification", prior_precision=0.7)
     la.fit(loader)
+    before = model.engine.device_bytes()
     val, G = la.neg_marglik_adj_grad(loader, dense=True)
+    grown = model.engine.device_bytes() - before
+    print(f"dense adjacency gradient: device_bytes grew by {grown} B, nnz * 4 = {model.engine.nnz * 4} B")
+    assert grown >= model.engine.nnz * 4
     Ws = [c.lin.weight.detach().cpu().numpy() for c in model.convs]
     bs = [c.lin.bias.detach().cpu().numpy() for c in model.convs]
     om = oracle_from_arrays("gcn", N, ei.numpy(), X.numpy(), Ws, bs, sym)
@@ -129,6 +137,9 @@ def test_lora_threshold_at_the_cora_shape(r, alpha, sym):
 
 @pytest.mark.parametrize("N,r", [(300, 1), (1000, 16), (777, 33), (2708, 64)])
 def test_lora_grad_against_fp64(N, r):
+    """lgnn_lora_grad against fp64 torch, bit-identical on a second call.  Its per-row-tile partials of grad_A belong to the
+    engine, so ``device_bytes()`` grows by at least one tile [r, N] fp32 on the first call -- an assertion that fails before
+    every buffer was enumerated from its struct: ``lgnn_device_bytes`` left the LoRA scratch out (and ``close()`` leaked it)."""
     import laplace_gnn_amd as lg
 
     gen = torch.Generator().manual_seed(N + r)
@@ -139,7 +150,11 @@ def test_lora_grad_against_fp64(N, r):
     A = torch.randn(r, N, generator=gen)
     B = torch.randn(N, r, generator=gen)
     s = 0.37
+    before = eng.device_bytes()
     gA, gB = eng.lora_grad(G.cuda(), A.cuda(), B.cuda(), s)
+    grown = eng.device_bytes() - before
+    print(f"lora_grad: device_bytes grew by {grown} B, r * N * 4 = {r * N * 4} B")
+    assert grown >= r * N * 4
     rA = s * (B.double().T @ G.double())
     rB = s * (G.double() @ A.double().T)
     assert rel(gA.cpu().numpy(), rA.numpy()) < 1e-5

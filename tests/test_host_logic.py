@@ -106,6 +106,25 @@ def test_product_package_never_imports_the_oracle():
             assert "gnn_laplace_oracle" not in src and "oracle/" not in src, path
 
 
+def test_every_device_buffer_of_a_context_struct_is_enumerated():
+    """``lgnn_device_bytes`` is a sum over the ``each_buf`` visitors of ``lgnn_internal.h``: every ``DevBuf`` member of the four
+    structs that make up a context is visited by the visitor under its declaration, and nothing else is."""
+    import re
+
+    src = open(os.path.join(ROOT, "laplace-gnn_amd", "csrc", "lgnn_internal.h")).read()
+    for name in ("ForwardCache", "Workspace", "TrainState", "lgnn_ctx"):
+        body = re.search(r"struct %s \{(.*?)\n\};" % name, src, re.S).group(1)
+        members, visitor = body.split("template <class F> void each_buf")
+        declared = set()
+        for line in members.split("\n"):
+            m = re.match(r"\s*(?:lgnn::)?DevBuf ([^;]+);", line.split("//")[0])
+            if m:
+                declared |= {re.sub(r"\[.*", "", d.strip()) for d in m.group(1).split(",")}
+        visited = re.findall(r"\bf\((\w+)(?:\[l\])?\)", visitor.split("\n  }")[0])
+        assert len(declared) >= 14, name
+        assert sorted(visited) == sorted(declared), (name, declared ^ set(visited))
+
+
 # ---- Kron container (laplace tests/test_matrix.py patterns) ------------------------------------------
 def _rand_kron(seed=0):
     g = torch.Generator().manual_seed(seed)
