@@ -495,26 +495,63 @@ __device__ __forceinline__ int lds_min4(const int* c) {
   asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(uint32_t(reinterpret_cast<uintptr_t>(c))) : "memory");
   return __builtin_amdgcn_readfirstlane(min(min(v.x, v.y), min(v.z, v.w)));
 }
-// publish a counter after this wave's earlier LDS traffic has completed
+// publish a counter: one ds_write_b32 on the 32-bit LDS address (a store through the generic pointer is a system-scope
+// flat_store into the LDS aperture followed by vmcnt(0): a memory round trip per node on the product wave's chain).  A wave's
+// LDS operations execute in order, so the counter lands after the wave's earlier tile stores / tile reads; the lgkmcnt(0)
+// behind it keeps hipcc's own lgkmcnt(N) counts right (it does not see this operation).
 __device__ __forceinline__ void lds_publish(int* c, int value, int lane) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (lane == 0) *reinterpret_cast<volatile int*>(c) = value;
+  if (lane == 0)
+    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(uint32_t(reinterpret_cast<uintptr_t>(c))), "v"(value) : "memory");
 }
 
-// path range [p0, p1) of the i-th node of this workgroup (entry blockIdx.x + i * gridDim.x of the list of nodes with paths,
-// or of the whole range).  Wave uniform.  `pptr` / `list` are kernel parameters of their own (__restrict__): read through the
-// argument struct hipcc cannot prove them read-only and loads them with VECTOR loads followed by vmcnt(0) -- a drain of
-// every load in flight once per node; as restrict parameters they are scalar loads.
-template <bool LIST>
-__device__ __forceinline__ void node_range(const int32_t* __restrict__ pptr, const int32_t* __restrict__ list, int64_t n0,
-                                           int64_t cnt, int64_t i, int32_t& p0, int32_t& p1) {
-  p0 = p1 = 0;
-  if (i < cnt) {
-    const int64_t k = blockIdx.x + i * int64_t(gridDim.x);
-    const int64_t n = n0 + (LIST ? int64_t(list[k]) : k);
-    p0 = pptr[n]; p1 = pptr[n + 1];
-  }
+// Path ranges [p0, p1) of this workgroup's nodes (node i = entry blockIdx.x + i * gridDim.x of the list of nodes with paths,
+// or of the whole range), 32 nodes at a time in ONE register (the product role has none to spare): lanes l and 32 + l hold
+// the range of node base + l, a node's range is two v_readlane with a wave-uniform index.  Every 32 nodes the wave loads the
+// next window through buffer descriptors (the list entry first, then pptr[n] / pptr[n + 1]: one buffer_load_dword) and waits
+// for it right there with vmcnt(0): one memory round trip per 32 nodes.  (A scalar load per node -- the index is strided, so
+// every node is a new line -- put a scalar-cache miss on the wave's chain once per node: the values rotate into loop-carried
+// registers, so hipcc waits lgkmcnt(0) where the load is issued.)  Inline assembly as below: the product role counts its
+// vector loads by hand, and this block leaves none outstanding.  A lane past `cnt` reads outside the descriptor: zeros, the
+// empty range.  Nodes are asked for in ascending order.
+// Kept for what it does to the ISA (no scalar load, no lgkmcnt(0) behind one in the node loop), NOT for speed: measured
+// alone, neither this window nor the LDS-store publish above moves the launch time beyond the run-to-run spread (DESIGN
+// 12.15), and the kernel spills 12 / 24 more SGPRs to VGPR lanes with them.
+using i32x4 = int __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ i32x4 make_rsrc(const void* p, uint64_t bytes) {
+  const uint64_t u = reinterpret_cast<uint64_t>(p);
+  return i32x4{int(uint32_t(u)), int(uint32_t(u >> 32) & 0xffffu), int(uint32_t(bytes > 0xffffffffull ? 0xffffffffull : bytes)),
+               0x00020000};
 }
+template <bool LIST>
+struct NodeRanges {
+  i32x4 prs, lrs;    // pptr (N + 1 entries), the node list (nn entries)
+  uint32_t r;        // lane l < 32: pptr[n] of node base + l, lane 32 + l: its pptr[n + 1]
+  int64_t base, cnt;
+  uint32_t n0;
+  __device__ __forceinline__ void init(const int32_t* __restrict__ pptr, const int32_t* __restrict__ list, int64_t n0_, int64_t N,
+                                       int64_t nn, int64_t cnt_) {
+    prs = make_rsrc(pptr, uint64_t(N + 1) * 4);
+    lrs = make_rsrc(LIST ? list : pptr, uint64_t(LIST ? nn : 0) * 4);
+    n0 = uint32_t(n0_); cnt = cnt_;
+    fill(0);
+  }
+  __device__ __forceinline__ void fill(int64_t b) {
+    base = b;
+    const uint32_t ii = uint32_t(b) + (threadIdx.x & 31u);
+    const bool in = int64_t(ii) < cnt;
+    const uint32_t k = blockIdx.x + ii * gridDim.x;
+    uint32_t node = k;
+    if constexpr (LIST)
+      asm volatile("buffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(node) : "v"(in ? k * 4u : 0xfffffff0u), "s"(lrs) : "memory");
+    const uint32_t off = in ? (n0 + node) * 4u + ((threadIdx.x >> 3) & 4u) : 0xfffffff0u;
+    asm volatile("buffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(off), "s"(prs) : "memory");
+  }
+  __device__ __forceinline__ void get(int64_t i, int32_t& p0, int32_t& p1) {
+    if (i - base >= 32) fill(i);
+    const int l = int(i - base);
+    p0 = __builtin_amdgcn_readlane(int(r), l); p1 = __builtin_amdgcn_readlane(int(r), l + 32);
+  }
+};
 
 // ---- loads of the product waves: inline assembly with hand-placed wait counts.  hipcc's own counts are exact only along one
 // path; at the loop headers of this kernel it merges the paths pessimistically (measured: the wait for a step's operands also
@@ -527,12 +564,6 @@ __device__ __forceinline__ void node_range(const int32_t* __restrict__ pptr, con
 // ALUs, so every VALU instruction of either wave of a SIMD is matrix-pipe time lost, not work hidden behind the MFMAs
 // (measured: the product wave's MFMA time and the time of its other instructions add up, with or without the Gram wave) --
 // 64-bit address arithmetic per load was a quarter of this wave's instructions.  An offset past the table's end reads zeros.
-using i32x4 = int __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, uint64_t bytes) {
-  const uint64_t u = reinterpret_cast<uint64_t>(p);
-  return i32x4{int(uint32_t(u)), int(uint32_t(u >> 32) & 0xffffu), int(uint32_t(bytes > 0xffffffffull ? 0xffffffffull : bytes)),
-               0x00020000};
-}
 template <int OFF>
 __device__ __forceinline__ void bload4(f32x4v& d, uint32_t voff, const i32x4& rsrc) {
   asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(d) : "v"(voff), "s"(rsrc), "n"(OFF) : "memory");
@@ -677,23 +708,42 @@ __device__ __forceinline__ void p_mfma(const PCur& c, f32x4v (&t1)[3][4], f32x4v
       for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
   }
 }
+// A node's FIRST step: the alpha and beta products take the inline constant 0 as C and so START the node's accumulators
+// (the gamma product accumulates into the beta one): nothing clears the 96 accumulator registers between nodes.
+template <bool NOBG>
+__device__ __forceinline__ void p_mfma_first(const PCur& c, f32x4v (&t1)[3][4], f32x4v (&y2)[3][4]) {
+  const f32x4v zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) t1[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a0[t], c.mf[ct], zero, 0, 0, 0);
+  if constexpr (!NOBG) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], zero, 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
+  }
+}
 
 // The product wave's work as a stream of CHUNKS: at most 64 paths of one node (one register of triples); a node is one chunk
 // (a hub: several), a node without paths one empty chunk.  Wave-uniform scalar state; the range of the node after the one
-// being cut is fetched a node ahead.
+// being cut is read a node ahead (NodeRanges).
 template <bool LIST>
 struct ChunkGen {
   int64_t gi;            // node being cut into chunks (index into this workgroup's nodes; nodes >= cnt are empty)
   int32_t gp, gend;      // its remaining paths
   int32_t pa0, pa1;      // the path range of node gi + 1
-  const int32_t* __restrict__ pptr;
-  const int32_t* __restrict__ list;
-  int64_t n0;
-  __device__ __forceinline__ void init(const int32_t* __restrict__ pptr_, const int32_t* __restrict__ list_, int64_t n0_, int64_t cnt) {
-    pptr = pptr_; list = list_; n0 = n0_;
+  NodeRanges<LIST> nr;
+  __device__ __forceinline__ void init(const int32_t* __restrict__ pptr, const int32_t* __restrict__ list, int64_t n0, int64_t N,
+                                       int64_t nn, int64_t cnt) {
+    nr.init(pptr, list, n0, N, nn, cnt);
     gi = 0;
-    node_range<LIST>(pptr, list, n0, cnt, 0, gp, gend);
-    node_range<LIST>(pptr, list, n0, cnt, 1, pa0, pa1);
+    nr.get(0, gp, gend);
+    nr.get(1, pa0, pa1);
   }
   // the next chunk [q0, q1) and whether it is its node's last
   __device__ __forceinline__ void next(int64_t cnt, int32_t& q0, int32_t& q1, bool& last) {
@@ -702,7 +752,7 @@ struct ChunkGen {
     if (last) {
       ++gi;
       gp = pa0; gend = pa1;
-      node_range<LIST>(pptr, list, n0, cnt, gi + 1, pa0, pa1);
+      nr.get(gi + 1, pa0, pa1);
     } else {
       gp = q1;
     }
@@ -714,13 +764,45 @@ struct ChunkGen {
 // right after its values were turned into MFMA operands, so two steps' loads (12 instructions) are in flight behind the 36
 // MFMAs being issued.  The loads are unconditional and in one fixed order, the hand-counted waits rely on it; A / B are written
 // nowhere else inside the loop.  Hence the chunk stream: hubs and empty nodes take the same path as everything else; a step past
-// the chunk's last path multiplies zero weights (meta_finish), an empty chunk is one such pair.  The loop body is straight-line
-// code on purpose: skipping the MFMAs of a pair's empty second step with a branch gave wrong tiles now and then (the MFMA ->
-// VALU wait states hipcc inserts are counted along straight-line code; the tile write behind the loop read accumulators an
-// MFMA inside the branch had not finished writing).
+// the chunk's last path multiplies zero weights (meta_finish), an empty chunk is one such step.
+// A pair is ONE body with two wave-uniform flags, and the flags only choose among MFMAs and the operand transform: every load,
+// wait, p_keep pin and refill is outside the branches, in the same order and number whatever the flags are, so every counted
+// vmcnt holds whichever pairs follow each other.
+//   first  the first pair of a node: its first step's alpha and beta MFMAs take C = 0 (p_mfma_first), which is what clears
+//          the accumulators -- nothing else does;
+//   half   the last pair of a chunk whose second step has no path (4 (2 j + 1) >= paths of the chunk): p_wait(B) and B's refill
+//          stay, p_xform(B) and B's MFMAs are left out -- B's landed operands are overwritten by the refill unread.
+// (Four complete straight-line bodies, one per flag combination, is what was tried first: hipcc then gives the accumulators
+// and the in-flight operand registers new values per body, moves them between registers at the joins and spills 130 - 500
+// registers; with the branches around the MFMAs alone the accumulators stay where they are.)
+// An earlier branch around the second step's MFMAs "gave wrong tiles now and then".  Its code is gone, so the cause cannot be
+// read off it; the two suspects are the MFMA -> VALU wait states between a branch's last MFMA and the tile write's first
+// accumulator read, and a load inside the branch that broke the counts.  In the ISA of the straight-line loop twelve buffer
+// loads, the poll of `done` (an LDS read and its wait) and a vmcnt(0) lie between the two, far more than the 12 wait states of
+// the 8-pass 16x16x4 -- but nothing there is a guarantee, and hipcc places no s_nop of its own.  Both are excluded by
+// construction now: no branch holds a load, and `s_nop 11` (12 wait states) sits in front of the tile write's first
+// accumulator read on every path.
+template <bool NOBG, bool HI>
+__device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, int sx, const PLane& pl, POps& A, POps& B, PCur& cA,
+                                          PCur& cB, f32x4v (&t1)[3][4], f32x4v (&y2)[3][4], bool first, bool half) {
+  constexpr int NL = kStepLoads<NOBG>;
+  // A's loads: the NL youngest outstanding may be B's (the first pair of a chunk: B's and the three path loads -- there
+  // the count also waits for B's first half, issued a whole pair earlier)
+  p_wait<NOBG, NL>(A);
+  p_xform<NOBG, HI>(A, pl, cA);
+  p_keep<NOBG>(cB);  // (cB's MFMAs may still be queued: cA must not be prepared into their operand registers)
+  p_load<NOBG>(tb, mx, sx, pl, A);
+  if (first) p_mfma_first<NOBG>(cA, t1, y2);
+  else p_mfma<NOBG>(cA, t1, y2);
+  p_wait<NOBG, NL>(B);  // (younger: A's refill)
+  if (!half) p_xform<NOBG, HI>(B, pl, cB);
+  p_keep<NOBG>(cA);  // (likewise)
+  p_load<NOBG>(tb, mx, sx + 1, pl, B);
+  if (!half) p_mfma<NOBG>(cB, t1, y2);
+}
 template <bool LIST, bool NOBG, bool HI>
 __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
-                                             FusedShared& sh, int64_t cnt, int cg) {
+                                             FusedShared& sh, int64_t nn, int64_t cnt, int cg) {
   const int lane = threadIdx.x & 63;
   const int H = a.H;
   const bool path_wave = 64 * cg < H;  // (H <= 192: the last product wave has no columns)
@@ -751,7 +833,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   const int pc_lo = 8 * (col >> 2) + 4 * piece_swap(col >> 2), pc_hi = pc_lo ^ 4;
   constexpr int NL = kStepLoads<NOBG>;
   ChunkGen<LIST> gen;
-  gen.init(pptr, list, a.n0, cnt);
+  gen.init(pptr, list, a.n0, a.N, nn, cnt);
   int32_t q0c, q1c, q0n, q1n;
   bool lastc, lastn;
   gen.next(cnt, q0c, q1c, lastc);
@@ -764,6 +846,8 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   POps A, B;
   p_load<NOBG>(tb, mc, 0, pl, A);
   p_load<NOBG>(tb, mc, 1, pl, B);
+  // the node's accumulators: started by the first step of the node's first pair (pair_body, `first`), never cleared.  (The
+  // zeros here are y2's value under NOBG, where no MFMA writes it.)
   f32x4v t1[3][4], y2[3][4];
 #pragma unroll
   for (int t = 0; t < 3; ++t)
@@ -773,6 +857,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   // while the MFMAs of the previous one may still be reading theirs.
   PCur cA = {}, cB = {};
   bool node_has = false;  // the node being built has a path so far
+  bool firstc = true;     // the chunk being run is its node's first
   for (int64_t i = 0; i < cnt;) {  // node i's tile is built while the Gram waves contract node i - 1's (or i - 2's)
     // the chunk after the next: its range now, its paths a whole chunk before they are used.  In flight from here
     // (oldest first): A, B (issued by the previous chunk's last pair), these three loads
@@ -789,18 +874,8 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       PMeta mx;
       mx.oc = more ? mc.oc : mn.oc; mx.ob = more ? mc.ob : mn.ob; mx.om = more ? mc.om : mn.om; mx.w = more ? mc.w : mn.w;
       const int sx = more ? 2 * (j + 1) : 0;
-      // A's loads: the NL youngest outstanding may be B's (the first pair of a chunk: B's and the three path loads -- there
-      // the count also waits for B's first half, issued a whole pair earlier)
-      p_wait<NOBG, NL>(A);
-      p_xform<NOBG, HI>(A, pl, cA);
-      p_keep<NOBG>(cB);  // (cB's MFMAs may still be queued: cA must not be prepared into their operand registers)
-      p_load<NOBG>(tb, mx, sx, pl, A);
-      p_mfma<NOBG>(cA, t1, y2);
-      p_wait<NOBG, NL>(B);  // (younger: A's refill)
-      p_xform<NOBG, HI>(B, pl, cB);
-      p_keep<NOBG>(cA);  // (likewise)
-      p_load<NOBG>(tb, mx, sx + 1, pl, B);
-      p_mfma<NOBG>(cB, t1, y2);  // (unconditional: see the role's header)
+      const bool first = firstc && j == 0, half = !more && 4 * (2 * j + 1) >= kch;  // (wave uniform)
+      pair_body<NOBG, HI>(tb, mx, sx, pl, A, B, cA, cB, t1, y2, first, half);
     }
     if (lastc) {
       // W_1's 48 x 4 values of the lane: twelve 16-byte loads, the YOUNGEST vector-memory operations of the wave from here to
@@ -814,9 +889,13 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       // tile i & 1 was last read by the Gram of node i - 2: every Gram wave must have counted i - 1 nodes
       if (i >= 2)
         while (lds_min4(sh.done) < int(i) - 1) __builtin_amdgcn_s_sleep(2);
+      // (s_nop 11 behind the wait: the MFMA -> VALU wait states of the pair loop's last MFMAs, whichever body issued them;
+      // see the header)
 #pragma unroll
       for (int t = 0; t < 3; ++t)
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(w1[t][0]), "+v"(w1[t][1]), "+v"(w1[t][2]), "+v"(w1[t][3]) :: "memory");
+      asm volatile("s_nop 11" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);  // (no accumulator read moves above the pad)
       if (node_has && col_ok) {
         // Y[n] = W_1 (.) T1 + Y2.  Rows past the launch's classes come out as the zeros they already are (their coefficients
         // and their rows of W_1 are zero): one branch around unconditional 16-byte stores.
@@ -862,14 +941,19 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       }
       ++i;
       lds_publish(&sh.ready[cg], int(i), lane);
+      // The accumulators' values end here: the next pair is a node's first and starts them.  hipcc cannot know that (the
+      // flag is data), and would keep all 96 registers live through the tile write above -- where the 48 values of W_1 and
+      // the pieces need them: an empty statement that defines them anew, no instruction.
 #pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) { t1[t][ct] = f32x4v{0.f, 0.f, 0.f, 0.f}; y2[t][ct] = f32x4v{0.f, 0.f, 0.f, 0.f}; }
+      for (int t = 0; t < 3; ++t) {
+        asm volatile("" : "=v"(t1[t][0]), "=v"(t1[t][1]), "=v"(t1[t][2]), "=v"(t1[t][3]));
+        if constexpr (!NOBG) asm volatile("" : "=v"(y2[t][0]), "=v"(y2[t][1]), "=v"(y2[t][2]), "=v"(y2[t][3]));
+      }
       node_has = false;
     }
     // rotate the chunk stream (the paths issued at the top are older than the 2 NL loads of the last pair's refills)
     meta_finish<2 * NL>(q0f, q1f, lane, row_bytes, mask_bytes, mf2);
+    firstc = lastc;
     q0c = q0n; q1c = q1n; lastc = lastn; mc = mn;
     q0n = q0f; q1n = q1f; lastn = lastf; mn = mf2;
   }
@@ -907,7 +991,7 @@ __device__ __forceinline__ void gram16_mfma(const float (&x)[8][2], f32x4v (&acc
 }
 template <int W, bool LIST>
 __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
-                                          FusedShared& sh, int64_t cnt, float* __restrict__ scratch) {
+                                          FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
   const int lane = threadIdx.x & 63;
   f32x4v acc[9][2][2];
 #pragma unroll
@@ -915,11 +999,13 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[s][q >> 1][q & 1] = f32x4v{0.f, 0.f, 0.f, 0.f};
   const int nk = (a.R + 3) >> 2;  // tile rows four at a time (rows past R are zero)
+  NodeRanges<LIST> nr;
+  nr.init(pptr, list, a.n0, a.N, nn, cnt);
   int32_t p0, p1;
-  node_range<LIST>(pptr, list, a.n0, cnt, 0, p0, p1);
+  nr.get(0, p0, p1);
   for (int64_t i = 0; i < cnt; ++i) {
     int32_t q0, q1;
-    node_range<LIST>(pptr, list, a.n0, cnt, i + 1, q0, q1);
+    nr.get(i + 1, q0, q1);
     // node i's tile: every product wave must have published i + 1 nodes
     while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
     if (p1 > p0) {
@@ -1006,7 +1092,7 @@ __device__ __forceinline__ void piece_mfma(const PieceBlk (&x)[8], f32x16 (&acc)
 }
 template <int W, bool LIST>
 __device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
-                                                FusedShared& sh, int64_t cnt, float* __restrict__ scratch) {
+                                                FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
   const int lane = threadIdx.x & 63;
   f32x16 acc[9];
 #pragma unroll
@@ -1014,11 +1100,13 @@ __device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* _
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
   const int nch = (a.R + 7) >> 3;  // chunks of 8 tile rows (rows past R are zero; 8 nch <= kYRows)
+  NodeRanges<LIST> nr;
+  nr.init(pptr, list, a.n0, a.N, nn, cnt);
   int32_t p0, p1;
-  node_range<LIST>(pptr, list, a.n0, cnt, 0, p0, p1);
+  nr.get(0, p0, p1);
   for (int64_t i = 0; i < cnt; ++i) {
     int32_t q0, q1;
-    node_range<LIST>(pptr, list, a.n0, cnt, i + 1, q0, q1);
+    nr.get(i + 1, q0, q1);
     while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
     if (p1 > p0) {
       // chunk ck, lane half h: group 2 ck + h
@@ -1076,17 +1164,17 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   // (hardware waves g and g + 4 share a SIMD: one product wave and one Gram wave on each, see the kernel's header)
   switch (hw) {
     // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
-    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, cnt, scratch); break;
-    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<1, LIST>(a, pptr, list, sh, cnt, scratch); break;
-    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<2, LIST>(a, pptr, list, sh, cnt, scratch); break;
-    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, cnt, scratch); else gram_split_role<3, LIST>(a, pptr, list, sh, cnt, scratch); break;
+    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
     default:
       if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
-        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, cnt, hw);
-        else product_role<LIST, false, true>(a, pptr, list, sh, cnt, hw);
+        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, nn, cnt, hw);
+        else product_role<LIST, false, true>(a, pptr, list, sh, nn, cnt, hw);
       } else {
-        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, cnt, hw);
-        else product_role<LIST, false, false>(a, pptr, list, sh, cnt, hw);
+        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, nn, cnt, hw);
+        else product_role<LIST, false, false>(a, pptr, list, sh, nn, cnt, hw);
       }
       break;
   }
