@@ -19,7 +19,7 @@
  *       lgnn_check_async_errors                 by design (reports the sticky error flags);
  *       the FIRST KFAC / adjacency-gradient call on a graph, once per graph: the list of rows with
  *         more than 64 stored entries (hubs) and the graph's number of 2-hop paths;
- *       lgnn_glm_variance(_mapped), once per call: the size of the rotated-row table;
+ *       lgnn_glm_variance(_mapped), lgnn_glm_variance_ext, once per call: the size of the per-class row table;
  *       lgnn_update_adjacency: the new number of stored entries.
  *     Everything else -- KFAC of GCN / GraphSAGE models of any depth, diagonal and last-layer GGN, forward,
  *     Jacobians -- enqueue only; workspaces grow on first use of a shape and are reused after;
@@ -467,6 +467,27 @@ LGNN_API int lgnn_glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const
 LGNN_API int lgnn_glm_variance_mapped(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, int64_t Cm,
                              const float* QA0, const float* QB0, const float* S0, const float* QA1, const float* S1,
                              const float* QB1sq, const float* kappa, float* f_mu, float* var_mapped, void* stream);
+
+/* The same predictive for 2-layer GCN / GraphSAGE models built with res=True and / or norm="layer"|"batch" -- the reference's
+ * shipped GCN configurations for Cornell / Texas / Wisconsin (gnn/configs/original/gcn_config.yaml:36-58), evaluated by the
+ * driver with exactly this call (gnn/marglik_training.py:332-353) -- and, through the same route, for plain ones.  Replaces
+ * the same reference lines as lgnn_glm_variance (laplace/baselaplace.py:1123-1158 + laplace/utils/matrix.py:396-451 resp.
+ * baselaplace.py:1901-1903), whose autograd walks res[0] and norms[0] (gnn/models/base_gnn.py:136-161) once per class and
+ * evaluation node: here the norm's transposed Jacobian is applied in closed form to d_u * w_c, one wave per (node, class) row.
+ * The res.0 block (nn.Linear on X, gnn/models/base_gnn.py:100-113) adds one more first-layer term of the same shape.
+ *   W1m [Cm, in_dim_1] / Cm: as lgnn_glm_variance_mapped, or NULL / 0 for the model's own classes (S1 / QB1sq / kappa are the
+ *     mapped operands under a map);
+ *   QA0 .. kappa: as lgnn_glm_variance;
+ *   res.0, Kronecker posterior: QAr [F, F], QBr [H, H] = eigenvectors (columns) of A_r = X^T X's factor and B_r;
+ *     Sr [H, F + 1]: 1 / (f lBr_i lAr_j + delta_Wr), column F: 1 / (f lBr_i + delta_br)  (F = the feature width for both
+ *     families: res.0 reads X itself);  diagonal posterior: QAr = QBr = NULL, Sr = 1 / precision of (W_r | b_r);
+ *     all three NULL for a model without res.
+ * ReLU, hidden width <= 256.  The norm's own parameters are not Laplace parameters (laplace/curvature/curvature.py:74-79).
+ * An id out of range: sticky flag (lgnn_check_async_errors), variance row 0.                                           */
+LGNN_API int lgnn_glm_variance_ext(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, int64_t Cm,
+                          const float* QA0, const float* QB0, const float* S0, const float* QA1, const float* S1,
+                          const float* QB1sq, const float* kappa, const float* QAr, const float* QBr, const float* Sr,
+                          float* f_mu, float* f_var, void* stream);
 
 /* ---- decomposition of the fitted factors ("next" row: KronLaplace.fit -> Kron.decompose) ----------
  * Replaces the per-factor torch.linalg.eigh calls of laplace/utils/matrix.py:118-145 (symeig,

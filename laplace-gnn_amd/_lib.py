@@ -75,6 +75,8 @@ SIGNATURES = {
     "lgnn_lora_grad": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_float, _vp, _vp, _vp]),
     "lgnn_glm_variance": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lgnn_glm_variance_mapped": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_glm_variance_ext": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp]),
     "lgnn_symeig_batched": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "lgnn_jacobians": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
 }

@@ -77,6 +77,58 @@ __device__ __forceinline__ float wave_sum_p(float v) {
   return v;
 }
 
+// Models with res / norm: the signal of class c that arrives at the pre-norm row s_u, q_{u,c} = norm_u^T (d_u * w_c)
+// (resnorm.hip's backward of one row, with w_c as the incoming gradient):
+//   LayerNorm:  g = gamma * d_u * w_c,  q = rstd_u (g - mean(g) - xhat_u mean(g * xhat_u))     (means over the H channels)
+//   BatchNorm (eval): q = gamma * rstd_channel * d_u * w_c;      no norm: q = d_u * w_c
+// One wave per (node, class) row, H <= 256: four channels per lane in registers, two wave reductions for the LayerNorm.
+// Row r = (k, c): node = list[k0 + k] (the needed nodes) or idx[k0 + k] (the evaluation nodes themselves, GraphSAGE's self
+// entry; an id out of range gives a zero row).  A [(k, c), H].
+__global__ __launch_bounds__(256) void pred_q_kernel(const int32_t* __restrict__ list, const int64_t* __restrict__ idx,
+                                                     int64_t k0, int64_t kn, int64_t N, const float* __restrict__ dact,
+                                                     int64_t H, const float* __restrict__ W1, int64_t ldw, int64_t C,
+                                                     int norm, const float* __restrict__ gamma,
+                                                     const float* __restrict__ xhat, const float* __restrict__ rstd,
+                                                     float* __restrict__ A) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rows = kn * C, stride = int64_t(gridDim.x) * 4;
+  const float invH = 1.0f / float(H);
+  for (int64_t r = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); r < rows; r += stride) {
+    const int64_t k = r / C, c = r - k * C;
+    const int64_t node = list ? int64_t(list[k0 + k]) : idx[k0 + k];
+    float* __restrict__ out = A + r * H;
+    if (node < 0 || node >= N) {
+      for (int64_t j = lane; j < H; j += 64) out[j] = 0.f;
+      continue;
+    }
+    const float* __restrict__ dn = dact + node * H;
+    const float* __restrict__ w = W1 + c * ldw;
+    const float* __restrict__ xh = xhat + node * H;  // (read under a LayerNorm only)
+    float g[4], x[4], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int64_t j = lane + 64 * t;
+      g[t] = 0.f; x[t] = 0.f;
+      if (j < H) {
+        g[t] = w[j] * dn[j];
+        if (norm != LGNN_NORM_NONE) g[t] *= gamma[j];
+        if (norm == LGNN_NORM_LAYER) { x[t] = xh[j]; s1 += g[t]; s2 += g[t] * x[t]; }
+        else if (norm == LGNN_NORM_BATCH) g[t] *= rstd[j];
+      }
+    }
+    if (norm == LGNN_NORM_LAYER) {
+      const float m1 = wave_sum_p(s1) * invH, m2 = wave_sum_p(s2) * invH, rs = rstd[node];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) g[t] = rs * (g[t] - m1 - x[t] * m2);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int64_t j = lane + 64 * t;
+      if (j < H) out[j] = g[t];
+    }
+  }
+}
+
 // KRON = 1: R (rotated, per class) and the S tables; KRON = 0: diagonal posterior (class independent tile T_a).
 //   Zt  [N, ldz]   : ztilde (KRON) / [xhat | rowsum] (diag), F1 = F + 1 columns used
 //   R   [slots, C, H] (KRON) ; dact [N, H] (diag)
@@ -86,7 +138,12 @@ __device__ __forceinline__ float wave_sum_p(float v) {
 //   the caller passes as W1 (lgnn_glm_variance_mapped) -- and Ce = the model's classes (the eigen-directions of B_1)
 //   SAGE = 1: one more staged entry per node (the node itself, weight 1; rows R_self[m] resp. the self half of W_1),
 //   bias column 1 (rowsum == nullptr), last-layer width D1 = 2 H; W1 has row stride ldw, its neighbour half starts at wn_off
-template <int KRON, int SAGE>
+// TAB >= 1 (models with res / norm, lgnn_glm_variance_ext): the first-layer rows of every family and posterior come from the
+//   per-class table R [slots, C, H] / Rs [M, C, H] = q_{u,c} (pred_q_kernel; KRON: rotated), the tile loops over the classes
+//   and the diagonal posterior keeps its own last-layer tail.  TAB = 2: the pass of the res.0 block -- first layer only,
+//   Zt = X (KRON: X Q_Ar), bias column 1, S0 = Sr; its sum is ADDED to what the conv pass (launched before it on the same
+//   stream) wrote to var_out: one workgroup per row, plain loads and stores.
+template <int KRON, int SAGE, int TAB = 0>
 __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict__ idx, int64_t M, int64_t N,
                                                       const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                       const float* __restrict__ val, const int32_t* __restrict__ slot,
@@ -114,7 +171,8 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
   const int nsg = max(int(H), max(int(C), int(Ce)));
   int32_t* __restrict__ su = reinterpret_cast<int32_t*>(sg + nsg);  // [PUC] slot / node of the staged neighbours
   if (a < 0 || a >= N) {  // flagged by the marking kernel
-    for (int c = tid; c < C; c += 512) var_out[m * C + c] = 0.f;
+    if (TAB != 2)
+      for (int c = tid; c < C; c += 512) var_out[m * C + c] = 0.f;
     return;
   }
   for (int c = tid; c < nsg; c += 512) { if (c < C) svar[c] = 0.f; sg[c] = 0.f; }
@@ -136,7 +194,7 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
       if (j == 0) {
         // staged id: kron -> slot of the neighbour's rotated rows, -1 for the self entry; otherwise the node id, the self
         // entry as -1 - node
-        su[u] = KRON ? (self ? -1 : slot[node]) : (self ? int32_t(-1 - node) : int32_t(node));
+        su[u] = (KRON || TAB) ? (self ? -1 : slot[node]) : (self ? int32_t(-1 - node) : int32_t(node));
         syb[u] = pv * (rowsum ? rowsum[node] : 1.f);
       }
     }
@@ -155,7 +213,7 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
     const float Sb = (with_bias && row_ok) ? S0[int64_t(i) * F1 + F] : 0.f;
     int un = 0;
     if (nub == 1) { un = stage(0, jc0); __syncthreads(); }
-    const int ncls = (KRON || SAGE) ? int(C) : 1;
+    const int ncls = (KRON || SAGE || TAB) ? int(C) : 1;
     for (int c = 0; c < ncls; ++c) {
       float Mt[PJT], Mb = 0.f;
 #pragma unroll
@@ -169,7 +227,7 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
             r[q] = 0.f;
             if (u0 + q < un && row_ok) {
               const int32_t id = su[u0 + q];
-              if (KRON) r[q] = id >= 0 ? R[(int64_t(id) * C + c) * H + i] : Rs[(m * C + c) * H + i];
+              if (KRON || TAB) r[q] = id >= 0 ? R[(int64_t(id) * C + c) * H + i] : Rs[(m * C + c) * H + i];
               else if (SAGE) r[q] = id >= 0 ? dact[int64_t(id) * H + i] * W1[c * ldw + wn_off + i]
                                             : dact[int64_t(-1 - id) * H + i] * W1[c * ldw + i];
               else r[q] = dact[int64_t(id) * H + i];
@@ -193,7 +251,7 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
       float part = Mb * Mb * Sb;
 #pragma unroll
       for (int j = 0; j < PJT; ++j) part = fmaf(Mt[j] * Mt[j], Sreg[j], part);
-      if (KRON || SAGE) {
+      if (KRON || SAGE || TAB) {
         part = wave_sum_p(part);
         if (lane == 0) atomicAdd(&svar[c], part);
       } else if (row_ok) {
@@ -202,13 +260,17 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
     }
     __syncthreads();
   }
+  if (TAB == 2) {  // the res.0 pass ends here (svar is complete: the column loop ends with a barrier)
+    for (int c = tid; c < C; c += 512) var_out[m * C + c] += svar[c];
+    return;
+  }
   // ---- the class mixing of the diagonal posterior and the last layer
   const float sa = rowsum ? rowsum[a] : 1.f;
   const float* __restrict__ ph = Pt + m * D1;
   if (!KRON) {
     for (int c = tid; c < C; c += 512) {
-      float v = SAGE ? svar[c] : 0.f;
-      if (!SAGE)
+      float v = (SAGE || TAB) ? svar[c] : 0.f;
+      if (!SAGE && !TAB)
         for (int64_t h = 0; h < H; ++h) { const float w = W1[c * ldw + h]; v = fmaf(w * w, sg[h], v); }
       for (int64_t j = 0; j < D1; ++j) v = fmaf(ph[j] * ph[j], S1[c * D1 + j], v);
       var_out[m * C + c] = v + sa * sa * kappa[c];
@@ -359,6 +421,137 @@ int glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, i
   return 0;
 }
 
+// Models with res / norm (and, through the same table route, plain ones).  First-layer Jacobian blocks with a = idx[n]:
+//   d f_c / d W_0 = sum_u P[a,u] q_{u,c} (x) e_u,   d f_c / d b_0 = sum_u P[a,u] rho_u q_{u,c}     (e, rho: as above)
+//   d f_c / d W_r = sum_u P[a,u] q_{u,c} (x) x_u,   d f_c / d b_r = sum_u P[a,u] q_{u,c}           (res.0 reads X itself)
+// with q_{u,c} of pred_q_kernel in place of d_u * w_c (GraphSAGE: the node itself joins with weight 1 and the self half of
+// W_1's row).  The variance is glm_variance's expression per block, the res.0 block one more tile term of the same shape.
+// Two passes over ONE table [needed nodes][C][H] and ONE Zt buffer: conv pass (+ last layer), then -- models with res --
+// the res.0 pass.  Kronecker: the table is rebuilt for the second rotation (q rows are cheap, the table is the workspace);
+// diagonal posterior: both passes read the same unrotated table, Zt is E resp. X in place.
+// QAr [F_x, F_x], QBr [H, H] (kron), Sr [H, F_x + 1] for (W_r | b_r), F_x = dims[0]; null without res.
+int glm_variance_ext(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, int64_t Cm, const float* QA0, const float* QB0,
+                     const float* S0, const float* QA1, const float* S1, const float* QB1sq, const float* kappa,
+                     const float* QAr, const float* QBr, const float* Sr, float* f_mu, float* f_var, hipStream_t s) {
+  LGNN_REQUIRE(h->L == 2, "matrix-free GLM predictive: 2-layer models");
+  LGNN_REQUIRE(h->act == LGNN_ACT_RELU, "matrix-free GLM predictive with res / norm: ReLU models");
+  LGNN_REQUIRE(M > 0 && idx && S0 && S1 && kappa && f_var, "empty batch or null pointers");
+  const bool kron = QA0 != nullptr;
+  const bool sage = h->kind == LGNN_KIND_SAGE;
+  const bool res = h->has_res;
+  LGNN_REQUIRE(!kron || (QB0 && QA1 && QB1sq), "kron posterior needs all eigenvector matrices");
+  LGNN_REQUIRE((Sr != nullptr) == res, "Sr comes with a res model, and only with one");
+  LGNN_REQUIRE(res && kron ? (QAr && QBr) : (!QAr && !QBr), "QAr / QBr: kron posterior of a res model only");
+  LGNN_CALL(forward_ensure_aux(h, s));
+  const int64_t N = h->N, F = h->in_dim[0], Fx = h->dims[0], H = h->dims[1], Ce = h->dims[2], D1 = h->in_dim[1];
+  LGNN_REQUIRE(H <= 256, "matrix-free GLM predictive: hidden width <= 256");
+  LGNN_REQUIRE(W1m == nullptr || (Cm > 0 && Cm <= 4096), "mapped GLM predictive: 1 <= rows of the map <= 4096");
+  const int64_t C = W1m ? Cm : Ce;
+  const float* W1 = W1m ? W1m : h->W[1];
+  const int Hp = H <= 64 ? 64 : (H <= 128 ? 128 : 256);
+  int* bad = h->ws.flags.as<int>();
+  if (f_mu) LGNN_CALL(launch_gather_rows(h->fc.out.as<float>(), Ce, N, idx, M, Ce, f_mu, bad + 2, s));
+
+  // e_u = (P X)[u] / cat_0[u] and x_u (GraphSAGE: the first half of cat_0[u]) where the forward left them
+  const float* xhat = sage ? h->fc.lin_in_p[0] : h->fc.prop_in[0].as<float>();
+  const int64_t ldx = sage ? h->fc.lin_in_ld[0] : h->fc.prop_ld[0];
+  const float* xin = h->fc.lin_in_p[0];
+  const int64_t ldxin = h->fc.lin_in_ld[0];
+  const int64_t ldz = cdiv(F, 4) * 4;  // row stride of the rotated inputs (F >= F_x)
+  LGNN_CALL(h->ws.planes_a.reserve((kron ? size_t(N) * ldz * 4 : 0) + size_t(M) * D1 * 4 * 2));
+  h->ws.planes_a_zero_ptr = nullptr;
+  float* Ztw = h->ws.planes_a.as<float>();
+  float* PhiB = Ztw + (kron ? N * ldz : 0);
+  float* PhiT = PhiB + M * D1;
+  if (sage) LGNN_CALL(launch_gather_rows(h->fc.lin_in_p[1], h->fc.lin_in_ld[1], N, idx, M, D1, PhiB, bad + 2, s));
+  else LGNN_CALL(launch_gather_rows(h->fc.prop_in[1].as<float>(), h->fc.prop_ld[1], N, idx, M, D1, PhiB, bad + 2, s));
+  const float* Pt = PhiB;
+  if (kron) { LGNN_CALL(sgemm_rm_p(s, M, D1, D1, PhiB, D1, QA1, D1, PhiT, D1)); Pt = PhiT; }
+
+  // slots of the nodes whose rows are needed (both posteriors: the table is per node and class)
+  const int64_t ldw = h->in_dim[1], wn_off = sage ? H : 0;
+  LGNN_CALL(h->ws.active.reserve(size_t(N)));
+  LGNN_HIP_CHECK(hipMemsetAsync(h->ws.active.p, 0, size_t(N), s));
+  hipLaunchKernelGGL(pred_mark_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col,
+                     h->ws.active.as<uint8_t>(), bad);
+  LGNN_CALL(h->ws.act_list.reserve(size_t(N) * 4));
+  LGNN_CALL(h->ws.act_count.reserve(64));
+  LGNN_CALL(compact_flags(h->ws.active.as<uint8_t>(), N, h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(),
+                          h->ws.select_tmp, s));
+  int32_t nneed = 0;
+  LGNN_HIP_CHECK(hipMemcpyAsync(&nneed, h->ws.act_count.p, 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));  // the size of the table has to reach the host
+  LGNN_CALL(h->ws.misc.reserve(size_t(N) * 4));
+  int32_t* slot = h->ws.misc.as<int32_t>();
+  hipLaunchKernelGGL(pred_slots_kernel, dim3(unsigned(cdiv(std::max<int64_t>(nneed, 1), 256))), dim3(256), 0, s,
+                     h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(), slot);
+  const int64_t rows_r = std::max<int64_t>(nneed, 1), rows_s = sage ? M : 0;
+  LGNN_CALL(h->ws.top.reserve(size_t(rows_r + rows_s) * C * H * 4));
+  float* Rw = h->ws.top.as<float>();
+  float* Rsw = Rw + rows_r * C * H;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(nneed, rows_s), (int64_t(1) << 28) / (C * H)));
+  if (kron) LGNN_CALL(h->ws.planes_b.reserve(size_t(chunk) * C * H * 4));
+  const float* gamma = h->norm != LGNN_NORM_NONE ? h->norm_w[0] : nullptr;
+  const float* nxh = h->norm != LGNN_NORM_NONE ? h->fc.xhat[0].as<float>() : nullptr;
+  const float* nrs = h->norm != LGNN_NORM_NONE ? h->fc.rstd[0].as<float>() : nullptr;
+  // table[slot, c, :] = q_{u,c} (neighbour half of W_1) and, GraphSAGE, table_self[m, c, :] = q_{a,c} (self half); kron:
+  // rotated by QB through planes_b, in chunks of nodes (<= 1 GiB operand)
+  auto build_table = [&](const float* QB) -> int {
+    for (int pass = 0; pass < 2; ++pass) {
+      const int64_t total = pass == 0 ? nneed : rows_s;
+      float* dst = pass == 0 ? Rw : Rsw;
+      for (int64_t k0 = 0; k0 < total; k0 += chunk) {
+        const int64_t kn = std::min<int64_t>(chunk, total - k0);
+        float* qrows = QB ? h->ws.planes_b.as<float>() : dst + k0 * C * H;
+        hipLaunchKernelGGL(pred_q_kernel, dim3(unsigned(std::min<int64_t>(cdiv(kn * C, 4), 65536))), dim3(256), 0, s,
+                           pass == 0 ? h->ws.act_list.as<int32_t>() : static_cast<const int32_t*>(nullptr), idx, k0, kn, N,
+                           h->fc.dact0.as<float>(), H, pass == 0 ? W1 + wn_off : W1, ldw, C, h->norm, gamma, nxh, nrs, qrows);
+        if (QB) LGNN_CALL(sgemm_rm_p(s, kn * C, H, H, qrows, H, QB, H, dst + k0 * C * H, H));
+      }
+    }
+    LGNN_HIP_CHECK(hipGetLastError());
+    return 0;
+  };
+  const int NG = 512 / Hp, CW = NG * PJT;
+  const size_t smem = (size_t(PUC) * CW + PUC + size_t(C) + size_t(std::max<int64_t>(H, std::max(C, Ce))) + PUC) * 4;
+  LGNN_REQUIRE(smem <= 150 * 1024, "matrix-free GLM predictive: tile does not fit LDS");
+  // (the attribute is set on every call: it belongs to the current device's copy of the kernel)
+#define LGNN_GLM_VAR_TAB(K, S, T, ZT, LDZ, FF1, SS0, RS)                                                                     \
+  do {                                                                                                                       \
+    LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glm_var_kernel<K, S, T>),                              \
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));                            \
+    hipLaunchKernelGGL((glm_var_kernel<K, S, T>), dim3(unsigned(M)), dim3(512), smem, s, idx, M, N, h->P.rowptr, h->P.col,   \
+                       h->P.val, slot, ZT, LDZ, FF1, Rw, Rsw, h->fc.dact0.as<float>(), W1, ldw, wn_off, H, C, Ce, Hp, SS0,   \
+                       Pt, D1, S1, QB1sq, kappa, RS, f_var);                                                                 \
+  } while (0)
+#define LGNN_GLM_VAR_PASS(T, ZT, LDZ, FF1, SS0, RS)                                                                          \
+  do {                                                                                                                       \
+    if (kron && sage) LGNN_GLM_VAR_TAB(1, 1, T, ZT, LDZ, FF1, SS0, RS);                                                      \
+    else if (kron) LGNN_GLM_VAR_TAB(1, 0, T, ZT, LDZ, FF1, SS0, RS);                                                         \
+    else if (sage) LGNN_GLM_VAR_TAB(0, 1, T, ZT, LDZ, FF1, SS0, RS);                                                         \
+    else LGNN_GLM_VAR_TAB(0, 0, T, ZT, LDZ, FF1, SS0, RS);                                                                   \
+    LGNN_HIP_CHECK(hipGetLastError());                                                                                       \
+  } while (0)
+  // ---- conv pass: convs.0 (W_0 | b_0) and the last layer
+  LGNN_CALL(build_table(kron ? QB0 : nullptr));
+  const float* Zt = xhat;
+  int64_t ldzt = ldx;
+  if (kron) { LGNN_CALL(sgemm_rm_p(s, N, F, F, xhat, ldx, QA0, F, Ztw, ldz)); Zt = Ztw; ldzt = ldz; }
+  const float* rowsum = sage ? nullptr : h->fc.rowsum.as<float>();
+  LGNN_GLM_VAR_PASS(1, Zt, ldzt, F + 1, S0, rowsum);
+  // ---- res pass: res.0 (W_r | b_r), added to the conv pass's result
+  if (res) {
+    if (kron) LGNN_CALL(build_table(QBr));
+    Zt = xin;
+    ldzt = ldxin;
+    if (kron) { LGNN_CALL(sgemm_rm_p(s, N, Fx, Fx, xin, ldxin, QAr, Fx, Ztw, ldz)); Zt = Ztw; ldzt = ldz; }
+    LGNN_GLM_VAR_PASS(2, Zt, ldzt, Fx + 1, Sr, static_cast<const float*>(nullptr));
+  }
+#undef LGNN_GLM_VAR_PASS
+#undef LGNN_GLM_VAR_TAB
+  return 0;
+}
+
 }  // namespace lgnn
 
 extern "C" int lgnn_glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* QA0, const float* QB0, const float* S0,
@@ -376,4 +569,14 @@ extern "C" int lgnn_glm_variance_mapped(lgnn_ctx* h, const int64_t* idx, int64_t
   if (!W1m) { lgnn::set_error("lgnn_glm_variance_mapped: null head of the map"); return 2; }
   return lgnn::glm_variance(h, idx, M, W1m, Cm, QA0, QB0, S0, QA1, S1, QB1sq, kappa, f_mu, var_mapped,
                             static_cast<hipStream_t>(stream));
+}
+
+extern "C" int lgnn_glm_variance_ext(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, int64_t Cm, const float* QA0,
+                                     const float* QB0, const float* S0, const float* QA1, const float* S1, const float* QB1sq,
+                                     const float* kappa, const float* QAr, const float* QBr, const float* Sr, float* f_mu,
+                                     float* f_var, void* stream) {
+  if (!h) { lgnn::set_error("null context"); return 2; }
+  if (!W1m && Cm != 0) { lgnn::set_error("lgnn_glm_variance_ext: rows of a map without its head"); return 2; }
+  return lgnn::glm_variance_ext(h, idx, M, W1m, Cm, QA0, QB0, S0, QA1, S1, QB1sq, kappa, QAr, QBr, Sr, f_mu, f_var,
+                                static_cast<hipStream_t>(stream));
 }

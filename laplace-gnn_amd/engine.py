@@ -816,6 +816,31 @@ class GraphEngine:
         _lib.check(rc, "lgnn_glm_variance_mapped")
         return f_mu, f_var
 
+    def glm_variance_ext(self, idx: torch.Tensor, S0, S1, kappa, QA0=None, QB0=None, QA1=None, QB1sq=None, Sr=None, QAr=None,
+                         QBr=None, out_map=None):
+        """``glm_variance`` for 2-layer models built with res / norm (and, through the same route, plain ones): one entry
+        with or without ``out_map`` (lgnn_glm_variance_ext).  ``Sr`` [H, F + 1] (and ``QAr`` / ``QBr`` under a Kronecker
+        posterior) are the operands of the res.0 block; None for a model without res."""
+        self._sync_versions()
+        idx = idx.contiguous()
+        M, C = idx.shape[0], self.dims[-1]
+        Cm, W1m = 0, None
+        if out_map is not None:
+            if out_map.ndim != 2 or out_map.shape[1] != C:
+                raise ValueError(f"out_map must be [rows, {C}]")
+            Cm = int(out_map.shape[0])
+            W1m = (out_map.to(device=self.device, dtype=torch.float32) @ self._bound[1][-1].detach().to(torch.float32)).contiguous()
+        f_mu = torch.empty(M, C, dtype=torch.float32, device=self.device)
+        f_var = torch.empty(M, Cm or C, dtype=torch.float32, device=self.device)
+        keep = [t.contiguous().to(torch.float32) if t is not None else None
+                for t in (QA0, QB0, S0, QA1, S1, QB1sq, kappa, QAr, QBr, Sr)]
+        ptr = [None if t is None else _dev_ptr(t, torch.float32, "posterior operand") for t in keep]
+        rc = self.lib.lgnn_glm_variance_ext(self._h, _dev_ptr(idx, torch.int64, "idx"), M,
+                                            None if W1m is None else W1m.data_ptr(), Cm, *ptr, f_mu.data_ptr(),
+                                            f_var.data_ptr(), _stream(self.device))
+        _lib.check(rc, "lgnn_glm_variance_ext")
+        return f_mu, f_var
+
     def check_async_errors(self):
         """Synchronise and raise if any batch since the last check contained an invalid node id or label."""
         _lib.check(self.lib.lgnn_check_async_errors(self._h, _stream(self.device)), "lgnn_check_async_errors")

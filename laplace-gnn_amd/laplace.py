@@ -343,16 +343,22 @@ class ParametricLaplace(BaseLaplace):
     def _glm_variance_matrix_free(self, x, out_map=None):
         """(f_mu [M, C], diag f_var [M, C]) without Jacobians (csrc/predictive.hip), or None: 2-layer GCN / GraphSAGE models
         with a ReLU, hidden width <= 256, classification, Kronecker or diagonal posterior over all weights.  ``out_map`` =
-        E [Cm, C]: the variances of E f instead ([M, Cm])."""
+        E [Cm, C]: the variances of E f instead ([M, Cm]).  Models built with res / norm take the per-class table route
+        (``GraphEngine.glm_variance_ext``), plain ones the entry they always had."""
         eng = getattr(self.backend, "engine", None)
+        extras = bool(getattr(eng, "has_extras", False))
         if (eng is None or not hasattr(eng, "glm_variance") or getattr(eng, "kind", None) not in ("gcn", "sage") or len(eng.dims) != 3
-                or getattr(eng, "has_extras", False)
+                or (extras and not hasattr(eng, "glm_variance_ext"))
                 or eng.dims[1] > 256 or getattr(eng, "_bind_opts", ("relu",))[0] != "relu" or self.likelihood != "classification"):
             return None
         ops = self._matrix_free_operands(out_map)
         if ops is None:
             return None
+        if ("Sr" in ops) != bool(getattr(eng, "has_res", False)):  # the res.0 block comes with a res model, and only with one
+            return None
         eng.set_likelihood("classification")
+        if extras:
+            return eng.glm_variance_ext(x, out_map=out_map, **ops)
         return eng.glm_variance(x, **ops) if out_map is None else eng.glm_variance(x, out_map=out_map, **ops)
 
     def _bridge_moments_matrix_free(self, x):
@@ -970,7 +976,8 @@ class KronLaplace(ParametricLaplace):
 
     def _matrix_free_operands(self, out_map=None):
         H = self._refined_decomposition()
-        if not isinstance(H, KronDecomposed) or H.damping or len(H.eigenvalues) != 4:
+        nb = len(H.eigenvalues) if isinstance(H, KronDecomposed) else 0
+        if nb not in (4, 6) or H.damping:  # convs.0.{W,b}, convs.1.{W,b} and, models with res, res.0.{W,b}
             return None
         (lB0, lA0), (QB0, QA0) = H.eigenvalues[0], H.eigenvectors[0]
         (lB0b,), (QB0b,) = H.eigenvalues[1], H.eigenvectors[1]
@@ -979,7 +986,9 @@ class KronLaplace(ParametricLaplace):
         if not (QB0b is QB0 or torch.equal(QB0b, QB0)):  # the bias block must share its weight block's eigenbasis of B_0
             return None
         pp = torch.as_tensor(self.prior_precision, dtype=torch.float32, device=self._device).reshape(-1)
-        d = pp.expand(4) if pp.numel() == 1 else pp
+        if pp.numel() not in (1, nb):
+            return None
+        d = pp.expand(nb) if pp.numel() == 1 else pp
         f = self._H_factor
         S0 = torch.cat([1.0 / (f * torch.outer(lB0, lA0) + d[0]), (1.0 / (f * lB0b + d[1])).unsqueeze(1)], dim=1)
         S1 = 1.0 / (f * torch.outer(lB1, lA1) + d[2])
@@ -987,7 +996,15 @@ class KronLaplace(ParametricLaplace):
             E = out_map.to(QB1)
             QB1, QB1b = E @ QB1, E @ QB1b
         kappa = (QB1b * QB1b) @ (1.0 / (f * lB1b + d[3]))
-        return dict(S0=S0, S1=S1, kappa=kappa, QA0=QA0, QB0=QB0, QA1=QA1, QB1sq=QB1 * QB1)
+        ops = dict(S0=S0, S1=S1, kappa=kappa, QA0=QA0, QB0=QB0, QA1=QA1, QB1sq=QB1 * QB1)
+        if nb == 6:
+            (lBr, lAr), (QBr, QAr) = H.eigenvalues[4], H.eigenvectors[4]
+            (lBrb,), (QBrb,) = H.eigenvalues[5], H.eigenvectors[5]
+            if not (QBrb is QBr or torch.equal(QBrb, QBr)):
+                return None
+            ops.update(Sr=torch.cat([1.0 / (f * torch.outer(lBr, lAr) + d[4]), (1.0 / (f * lBrb + d[5])).unsqueeze(1)], dim=1),
+                       QAr=QAr, QBr=QBr)
+        return ops
 
     def _scale_samples(self, eps):  # laplace/baselaplace.py:1646-1655
         return self.posterior_precision_refined.bmm(eps, exponent=-0.5).reshape(eps.shape[0], self.n_params)
@@ -1128,19 +1145,26 @@ class DiagLaplace(ParametricLaplace):
 
     def _matrix_free_operands(self, out_map=None):
         shapes = [tuple(p.shape) for p in self.params]
-        if len(shapes) != 4:
+        if len(shapes) not in (4, 6) or [len(sh) for sh in shapes] != [2, 1] * (len(shapes) // 2):
             return None
-        (Hd, F), _, (C, D1), _ = shapes  # (GraphSAGE: F and D1 are the widths of the concatenations)
+        (Hd, F), _, (C, D1), _ = shapes[:4]  # (GraphSAGE: F and D1 are the widths of the concatenations)
         inv = 1.0 / self.posterior_precision
         o = 0
         w0 = inv[o:o + Hd * F].view(Hd, F); o += Hd * F
         b0 = inv[o:o + Hd].view(Hd, 1); o += Hd
         w1 = inv[o:o + C * D1].view(C, D1); o += C * D1
-        b1 = inv[o:o + C]
+        b1 = inv[o:o + C]; o += C
+        Sr = None
+        if len(shapes) == 6:  # res.0.{weight, bias} behind the convs (parameter order)
+            Hr, Fr = shapes[4]
+            Sr = torch.cat([inv[o:o + Hr * Fr].view(Hr, Fr), inv[o + Hr * Fr:o + Hr * Fr + Hr].view(Hr, 1)], dim=1)
         if out_map is not None:  # independent parameters: the variance of a combination weighs each class by E^2
             E2 = out_map.to(w1).square()
             w1, b1 = E2 @ w1, E2 @ b1
-        return dict(S0=torch.cat([w0, b0], dim=1), S1=w1, kappa=b1)
+        ops = dict(S0=torch.cat([w0, b0], dim=1), S1=w1, kappa=b1)
+        if Sr is not None:
+            ops["Sr"] = Sr
+        return ops
 
     def neg_marglik_adj_grad(self, train_loader, prior_precision=None, process_group=None, candidates=None, dense=False):
         """``-log_marginal_likelihood()`` of this fit and its gradient w.r.t. the adjacency -- what ``neg_marglik.backward()``
