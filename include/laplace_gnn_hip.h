@@ -387,7 +387,8 @@ LGNN_API int lgnn_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float*
  *                loss_scale * CE and of the softmax inside the GGN;  h1_bar [N, H] += d/dH_1 and e_bar [N, F + 1] +=
  *                d/d[P X | rowsum(P)] of the closed-form diagonal;  candidates as above;
  *   once      :  lgnn_diag_adjgrad_finish propagates out_bar, h1_bar and e_bar through the forward pass into grad_P and writes
- *                grad_adj [nnz] / grad_cand_adj exactly like lgnn_adjgrad_finish.
+ *                grad_adj [nnz] / grad_cand_adj exactly like lgnn_adjgrad_finish.  It serves the diagonal and the full posterior
+ *                (lgnn_full_adjgrad_batch below fills the same accumulators).
  * Workspace: [chunk][H][F + 1 rounded up to 4] floats for the first-layer tiles of a chunk of samples (0.5 GB for a Cora-shaped
  * batch), under the workspace limit (lgnn_set_workspace_limit); no synchronisation, nothing allocated after the first call.
  * Models bound with res / norm (GCN; the shipped WebKB / Circle configurations are exactly diag + res + LayerNorm): no closed
@@ -404,6 +405,28 @@ LGNN_API int lgnn_diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void
 LGNN_API int lgnn_diag_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float* h1_bar, const float* e_bar, float* grad_P,
                              float* grad_adj, const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand,
                              float* grad_cand, float* grad_cand_adj, void* stream);
+
+/* The same gradient under the FULL posterior -- the third choice of the structure-learning loop's --hessian_structure
+ * (gnn/utils.py:57-59; gnn/marglik_training.py:197-216 with FullLaplace, laplace/baselaplace.py:1377-1505; the full GGN it
+ * differentiates: laplace/curvature/curvature.py:374-410 over the fork's attached Jacobians, :89-130).  The identity of the
+ * diagonal posterior's (sample, class) chains does not need a diagonal weighting: with
+ *   Gamma [P, P] fp32, symmetric = d(1/2 logdet(f H + Delta))/dH = (f / 2) (f H + Delta)^-1, f = H_factor,
+ *   K_n = J_n Gamma J_n^T [C, C],  R_n = 2 Lambda_n J_n Gamma [C, P]   (one fp32-MFMA pass over J Gamma, csrc/fulladj.hip;
+ *   K_n's partial sums over the column blocks meet in float atomics),
+ * d<Gamma, H> = sum_n <K_n, d Lambda_n> + sum_{n,c} <R_n[c, :], d J_n[c, :]>, and the tangent / reverse chains are the diagonal
+ * posterior's.  lgnn_full_adjgrad_batch has the buffer contract of lgnn_diag_adjgrad_batch: it accumulates into grad_P, out_bar
+ * (incl. loss_scale * CE's adjoint), h1_bar, e_bar and grad_cand, runs chunks of samples under the workspace limit, takes
+ * repeated node ids, does not synchronise, and is finished by lgnn_diag_adjgrad_finish.  2-layer GCN, plain or with res / norm
+ * (the planes chain; e_bar stays untouched; workspace per sample of a chunk 2 C P floats + C N (3 H + C) floats of planes), and
+ * plain 2-layer GraphSAGE (the local chain; 2 C P floats per sample); ReLU, classification, C <= 127.  Gamma is read as
+ * stored; parameter order W_0, b_0, W_1, b_1[, Wr_0, br_0].
+ * lgnn_full_directions is the product alone: K_out [M, C, C] and R_out [M, C, P] of the samples idx (Lambda_n from the softmax
+ * of the model's logits), e.g. K_n = J_n Sigma J_n^T for Gamma = Sigma; same chunks, only the Jacobian rows in the workspace. */
+LGNN_API int lgnn_full_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* Gamma,
+                            float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar,
+                            const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand, float* grad_cand, void* stream);
+LGNN_API int lgnn_full_directions(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* Gamma, float* K_out, float* R_out,
+                         void* stream);
 
 /* ---- the adjacency gradient on ALL N x N pairs (LoRASTEGCN, gnn/models/models.py:186-235) --------------------------------
  * LoRA parameterises the whole adjacency, adj0 + scaling * (adj_lora_B @ adj_lora_A) (models.py:226-232), so the gradient

@@ -67,6 +67,8 @@ SIGNATURES = {
     "lgnn_adjgrad_finish": (_i32, [_vp, _vp, _pp, C.c_float, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_diag_adjgrad_batch": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "lgnn_diag_adjgrad_finish": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_full_adjgrad_batch": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "lgnn_full_directions": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "lgnn_kfac_adjgrad_batch_dense": (_i32, [_vp, _vp, _vp, _i64, _u32, _pp, C.c_float, _vp, _vp, _vp]),
     "lgnn_adjgrad_finish_dense": (_i32, [_vp, _vp, _pp, C.c_float, _vp, _vp]),
     "lgnn_diag_adjgrad_batch_dense": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),

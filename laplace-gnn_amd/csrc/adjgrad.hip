@@ -1157,6 +1157,27 @@ int sgemm_rm_nt_shared(hipStream_t s, int64_t R, int64_t Nout, int64_t K, const 
   return 0;
 }
 
+// K_n, probs and R of a chunk of samples, the three inputs of the tangent / reverse chains below, under either posterior:
+// gamma [P] (diagonal: K_n = J_n diag(gamma) J_n^T, R_n = 2 Lambda_n J_n diag(gamma)) or Gamma [P, P] (full: fulladj.hip's
+// product kernel, K_n = J_n Gamma J_n^T, R_n = 2 Lambda_n J_n Gamma).  Also adds the batch's part of out_bar.
+int chunk_directions(lgnn_ctx* h, const int64_t* idx, const int64_t* y, int64_t mc, const float* J, const float* gamma,
+                     const float* Gamma, float loss_scale, float* probs, float* Kn, float* R, float* out_bar, hipStream_t s) {
+  const int64_t N = h->N, C = h->dims[2], P = h->n_params;
+  if (Gamma) {
+    LGNN_CALL(launch_full_directions(J, Gamma, idx, h->fc.out.as<float>(), N, mc, C, P, R, Kn, s));
+    hipLaunchKernelGGL(diag_ext_sample_kernel, dim3(unsigned(mc)), dim3(64), size_t(C * C + C) * 4, s, idx, y, N, C, Kn,
+                       h->fc.out.as<float>(), loss_scale, probs, out_bar);
+  } else {
+    hipLaunchKernelGGL(diag_ext_gram_kernel, dim3(unsigned(mc), unsigned(C * (C + 1) / 2)), dim3(256), 0, s, C, P, J, gamma, Kn);
+    hipLaunchKernelGGL(diag_ext_sample_kernel, dim3(unsigned(mc)), dim3(64), size_t(C * C + C) * 4, s, idx, y, N, C, Kn,
+                       h->fc.out.as<float>(), loss_scale, probs, out_bar);
+    hipLaunchKernelGGL(diag_ext_direction_kernel, dim3(unsigned(std::min<int64_t>(cdiv(mc * P, 256), 8192))), dim3(256), 0, s, J,
+                       gamma, probs, mc, C, P, R);
+  }
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int check_model_ext(const lgnn_ctx* h) {
   LGNN_REQUIRE(h->L == 2, "adjacency gradient: 2-layer models (SURVEY.md 8(f)-4)");
   LGNN_REQUIRE(h->kind == LGNN_KIND_GCN, "adjacency gradient with res / norm: GCN models (the reference's STEGCN configurations)");
@@ -1282,11 +1303,15 @@ int kfac_adjgrad_batch_ext(lgnn_ctx* h, const int64_t* idx, const void* y, int64
 // (laplace/curvature/curvature.py:412-432 with the fork's attached Jacobians, :89-130).  <R, d grad_theta f_{n,c}> = the
 // derivative of the directional derivative of f_{n,c} along the parameter direction R: per (sample, class) plane one tangent
 // forward pass with the weights replaced by R's blocks, then its reverse pass.  Chunks of samples under the workspace cap.
-int diag_adjgrad_batch_ext(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, float loss_scale,
-                           float* grad_P, float* out_bar, float* h1_bar, const int32_t* cand_a, const int32_t* cand_b,
-                           int64_t K, float* grad_cand, hipStream_t s) {
+// The identity does not care that the weighting is diagonal: with Gamma [P, P] in place of gamma [P] (exactly one of them is
+// given) this is the full posterior's gradient, plain 2-layer GCNs included (chunk_directions).
+int diag_adjgrad_batch_ext(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, const float* Gamma,
+                           float loss_scale, float* grad_P, float* out_bar, float* h1_bar, const int32_t* cand_a,
+                           const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s) {
   LGNN_CALL(check_model_ext(h));
-  LGNN_REQUIRE(M > 0 && idx && y && gamma && grad_P && out_bar && h1_bar, "empty batch or null pointers");
+  // "diag" in the name is history: gamma [P] (diagonal posterior) or Gamma [P, P] (full posterior), exactly one of them
+  LGNN_REQUIRE(M > 0 && idx && y && (gamma != nullptr) != (Gamma != nullptr) && grad_P && out_bar && h1_bar,
+               "empty batch or null pointers");
   LGNN_REQUIRE(K == 0 || (cand_a && cand_b && grad_cand), "candidate pairs without their buffers");
   LGNN_CALL(forward_ensure(h, s));
   LGNN_CALL(ensure_wt(h, s));
@@ -1303,7 +1328,7 @@ int diag_adjgrad_batch_ext(lgnn_ctx* h, const int64_t* idx, const void* y, int64
   // per sample: J and R rows, three [C][N][H] plane sets + [C][N][C], and the Jacobian pass's own two plane sets
   const int64_t per_sample = C * (2 * P + N * (3 * H + C) + 2 * N * std::max(H, C)) * 4;
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(M, h->ws_limit / std::max<int64_t>(per_sample, 1)));
-  LGNN_REQUIRE(chunk * C < (int64_t(1) << 31), "diag adjacency gradient: chunk too large");
+  LGNN_REQUIRE(chunk * C < (int64_t(1) << 31), "adjacency gradient, diagonal / full posterior: chunk too large");
   LGNN_CALL(h->ws.jac.reserve(size_t(chunk) * C * P * 4));
   LGNN_CALL(h->ws.adj_dir.reserve(size_t(chunk) * C * P * 4));
   LGNN_CALL(h->ws.probs.reserve(size_t(chunk) * (C + C * C) * 4));
@@ -1317,12 +1342,7 @@ int diag_adjgrad_batch_ext(lgnn_ctx* h, const int64_t* idx, const void* y, int64
     const int64_t mc = std::min(chunk, M - m0);
     const int64_t Q = mc * C;
     LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
-    hipLaunchKernelGGL(diag_ext_gram_kernel, dim3(unsigned(mc), unsigned(C * (C + 1) / 2)), dim3(256), 0, s, C, P, J, gamma, Kn);
-    hipLaunchKernelGGL(diag_ext_sample_kernel, dim3(unsigned(mc)), dim3(64), size_t(C * C + C) * 4, s, idx + m0, yy + m0, N, C,
-                       Kn, h->fc.out.as<float>(), loss_scale, probs, out_bar);
-    hipLaunchKernelGGL(diag_ext_direction_kernel, dim3(unsigned(std::min<int64_t>(cdiv(mc * P, 256), 8192))), dim3(256), 0, s, J,
-                       gamma, probs, mc, C, P, R);
-    LGNN_HIP_CHECK(hipGetLastError());
+    LGNN_CALL(chunk_directions(h, idx + m0, yy + m0, mc, J, gamma, Gamma, loss_scale, probs, Kn, R, out_bar, s));
     float* Z0d = h->ws.planes_c.as<float>();  // [Q][N][H] tangent of Z0
     float* Sd = Z0d + Q * N * H;              // tangent of s; later the adjoint of s through the norm's statistics
     float* Hd = Sd + Q * N * H;               // tangent of H1; later nbar, then the adjoint of sdot
@@ -1495,12 +1515,15 @@ __global__ void add_strided_kernel(float* __restrict__ x, int64_t ldx, const flo
   }
 }
 
-int diag_adjgrad_batch_sage(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, float loss_scale,
-                            float* grad_P, float* out_bar, float* h1_bar, float* e_bar, const int32_t* cand_a,
+// (gamma [P]: diagonal posterior; Gamma [P, P]: full posterior; exactly one of them, see chunk_directions)
+int diag_adjgrad_batch_sage(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, const float* Gamma,
+                            float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar, const int32_t* cand_a,
                             const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s) {
-  LGNN_REQUIRE(h->L == 2 && !h->extras(), "adjacency gradient, diagonal posterior, GraphSAGE: plain 2-layer models");
+  LGNN_REQUIRE(h->L == 2 && !h->extras(), "adjacency gradient, diagonal / full posterior, GraphSAGE: plain 2-layer models");
   LGNN_REQUIRE(h->act == LGNN_ACT_RELU && h->lik == LGNN_LIK_CLASSIFICATION, "adjacency gradient: ReLU, classification");
-  LGNN_REQUIRE(M > 0 && idx && y && gamma && grad_P && out_bar && h1_bar && e_bar, "empty batch or null pointers");
+  // "diag" in the name is history: gamma [P] (diagonal posterior) or Gamma [P, P] (full posterior), exactly one of them
+  LGNN_REQUIRE(M > 0 && idx && y && (gamma != nullptr) != (Gamma != nullptr) && grad_P && out_bar && h1_bar && e_bar,
+               "empty batch or null pointers");
   LGNN_CALL(forward_ensure_aux(h, s));
   const int64_t N = h->N, C = h->dims[2], H = h->dims[1], F = h->dims[0], P = h->n_params;
   LGNN_REQUIRE(P == H * 2 * F + H + C * 2 * H + C, "internal: parameter count");
@@ -1519,11 +1542,7 @@ int diag_adjgrad_batch_sage(lgnn_ctx* h, const int64_t* idx, const void* y, int6
   for (int64_t m0 = 0; m0 < M; m0 += chunk) {
     const int64_t mc = std::min(chunk, M - m0);
     LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
-    hipLaunchKernelGGL(diag_ext_gram_kernel, dim3(unsigned(mc), unsigned(C * (C + 1) / 2)), dim3(256), 0, s, C, P, J, gamma, Kn);
-    hipLaunchKernelGGL(diag_ext_sample_kernel, dim3(unsigned(mc)), dim3(64), size_t(C * C + C) * 4, s, idx + m0, yy + m0, N, C,
-                       Kn, h->fc.out.as<float>(), loss_scale, probs, out_bar);
-    hipLaunchKernelGGL(diag_ext_direction_kernel, dim3(unsigned(std::min<int64_t>(cdiv(mc * P, 256), 8192))), dim3(256), 0, s, J,
-                       gamma, probs, mc, C, P, R);
+    LGNN_CALL(chunk_directions(h, idx + m0, yy + m0, mc, J, gamma, Gamma, loss_scale, probs, Kn, R, out_bar, s));
     hipLaunchKernelGGL(sage_diag_pair_kernel, dim3(unsigned(mc * C)), dim3(256), size_t(6 * H + 4) * 4, s, idx + m0, N, C, H, F, P,
                        h->P.rowptr, h->P.col, h->P.val, h->fc.lin_in_p[0], h->fc.lin_in_p[1], h->fc.dact0.as<float>(), h->W[1], R,
                        cand_a, cand_b, K, grad_P, grad_cand, h1_bar, e_bar, F + 1);
@@ -2067,10 +2086,11 @@ int diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
                        int64_t K, float* grad_cand, hipStream_t s, float* dense = nullptr) {
   LGNN_REQUIRE(K == 0 || (cand_a && cand_b && grad_cand), "candidate pairs without their buffers");
   if (h->kind == LGNN_KIND_SAGE)  // (e_bar [N, F + 1] carries the adjoint of P X in its first F columns)
-    return diag_adjgrad_batch_sage(h, idx, y, M, gamma, loss_scale, grad_P, out_bar, h1_bar, e_bar, cand_a, cand_b, K, grad_cand,
-                                   s);
+    return diag_adjgrad_batch_sage(h, idx, y, M, gamma, nullptr, loss_scale, grad_P, out_bar, h1_bar, e_bar, cand_a, cand_b, K,
+                                   grad_cand, s);
   if (h->extras())  // res / norm: no closed form, (sample, class) planes (e_bar stays untouched)
-    return diag_adjgrad_batch_ext(h, idx, y, M, gamma, loss_scale, grad_P, out_bar, h1_bar, cand_a, cand_b, K, grad_cand, s);
+    return diag_adjgrad_batch_ext(h, idx, y, M, gamma, nullptr, loss_scale, grad_P, out_bar, h1_bar, cand_a, cand_b, K, grad_cand,
+                                  s);
   LGNN_CALL(check_model(h));
   LGNN_REQUIRE(h->kind == LGNN_KIND_GCN, "adjacency gradient, diagonal posterior: GCN models");
   LGNN_REQUIRE(M > 0 && idx && y && gamma && grad_P && out_bar && h1_bar && e_bar, "empty batch or null pointers");
@@ -2115,6 +2135,56 @@ int diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M
                                        F, h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, dense, s));
   }
   LGNN_CALL(batch_epilogue(h, idx, M, s));
+  return 0;
+}
+
+// The full posterior's product kernel holds whole samples in a 128-row tile (fulladj.hip): refused here, up front, so that the
+// refusal costs no Jacobian pass (check_model_ext alone admits up to 256 classes)
+static int check_full_classes(const lgnn_ctx* h) {
+  LGNN_REQUIRE(h->L >= 1 && h->dims[h->L] <= 127, "adjacency gradient, full posterior: at most 127 classes");
+  return 0;
+}
+
+// Full posterior (FullLaplace): the (sample, class) chains of the diagonal posterior with the dense Gamma [P, P] as weighting.
+// 2-layer GCN, plain or with res / norm: the planes chain (e_bar stays untouched); plain 2-layer GraphSAGE: the local chain.
+int full_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* Gamma, float loss_scale,
+                       float* grad_P, float* out_bar, float* h1_bar, float* e_bar, const int32_t* cand_a, const int32_t* cand_b,
+                       int64_t K, float* grad_cand, hipStream_t s) {
+  LGNN_REQUIRE(K == 0 || (cand_a && cand_b && grad_cand), "candidate pairs without their buffers");
+  LGNN_REQUIRE(Gamma && e_bar, "empty batch or null pointers");
+  LGNN_CALL(check_full_classes(h));  // before any launch or workspace reservation
+  if (h->kind == LGNN_KIND_SAGE)
+    return diag_adjgrad_batch_sage(h, idx, y, M, nullptr, Gamma, loss_scale, grad_P, out_bar, h1_bar, e_bar, cand_a, cand_b, K,
+                                   grad_cand, s);
+  return diag_adjgrad_batch_ext(h, idx, y, M, nullptr, Gamma, loss_scale, grad_P, out_bar, h1_bar, cand_a, cand_b, K, grad_cand,
+                                s);
+}
+
+// The product alone: K_out [M, C, C] = J_m Gamma J_m^T and R_out [M, C, P] = 2 Lambda_m J_m Gamma, in the chunks of the batch
+// call (only the Jacobian rows of a chunk live in the workspace)
+int full_directions(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* Gamma, float* K_out, float* R_out, hipStream_t s) {
+  LGNN_REQUIRE(M > 0 && idx && Gamma && K_out && R_out, "empty batch or null pointers");
+  LGNN_CALL(check_full_classes(h));
+  const bool sage = h->kind == LGNN_KIND_SAGE;
+  if (sage) {
+    LGNN_REQUIRE(h->L == 2 && !h->extras(), "adjacency gradient, diagonal / full posterior, GraphSAGE: plain 2-layer models");
+    LGNN_REQUIRE(h->act == LGNN_ACT_RELU && h->lik == LGNN_LIK_CLASSIFICATION, "adjacency gradient: ReLU, classification");
+  } else {
+    LGNN_CALL(check_model_ext(h));
+  }
+  LGNN_CALL(forward_ensure(h, s));
+  const int64_t N = h->N, C = h->dims[2], H = h->dims[1], P = h->n_params;
+  const int64_t per_sample = sage ? C * 2 * P * 4 : C * (2 * P + N * (3 * H + C) + 2 * N * std::max(H, C)) * 4;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(M, h->ws_limit / std::max<int64_t>(per_sample, 1)));
+  LGNN_REQUIRE(chunk * C < (int64_t(1) << 31), "full posterior directions: chunk too large");
+  LGNN_CALL(h->ws.jac.reserve(size_t(chunk) * C * P * 4));
+  float* J = h->ws.jac.as<float>();
+  for (int64_t m0 = 0; m0 < M; m0 += chunk) {
+    const int64_t mc = std::min(chunk, M - m0);
+    LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
+    LGNN_CALL(launch_full_directions(J, Gamma, idx + m0, h->fc.out.as<float>(), N, mc, C, P, R_out + m0 * C * P,
+                                     K_out + m0 * C * C, s));
+  }
   return 0;
 }
 
@@ -2247,6 +2317,21 @@ extern "C" int lgnn_diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const vo
   if (!h) { lgnn::set_error("null context"); return 2; }
   return lgnn::diag_adjgrad_batch(h, idx, y, M, gamma, loss_scale, grad_P, out_bar, h1_bar, e_bar, cand_a, cand_b, num_cand,
                                   grad_cand, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int lgnn_full_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* Gamma,
+                                       float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar,
+                                       const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand, float* grad_cand,
+                                       void* stream) {
+  if (!h) { lgnn::set_error("null context"); return 2; }
+  return lgnn::full_adjgrad_batch(h, idx, y, M, Gamma, loss_scale, grad_P, out_bar, h1_bar, e_bar, cand_a, cand_b, num_cand,
+                                  grad_cand, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int lgnn_full_directions(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* Gamma, float* K_out, float* R_out,
+                                    void* stream) {
+  if (!h) { lgnn::set_error("null context"); return 2; }
+  return lgnn::full_directions(h, idx, M, Gamma, K_out, R_out, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int lgnn_diag_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float* h1_bar, const float* e_bar,

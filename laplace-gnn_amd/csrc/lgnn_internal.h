@@ -566,5 +566,10 @@ int ef_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y_seed, const voi
                   float scale, float* diag_out, float* full_out, float* grads_out, float* loss_out, hipStream_t s);
 // ---- jacobian.hip -----------------------------------------------------------------------
 int jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out, hipStream_t s);
+// ---- fulladj.hip ------------------------------------------------------------------------
+// full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
+// chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127
+int launch_full_directions(const float* J, const float* Gamma, const int64_t* idx, const float* logits, int64_t N,
+                           int64_t mc, int64_t C, int64_t P, float* R, float* Kn, hipStream_t s);
 
 }  // namespace lgnn

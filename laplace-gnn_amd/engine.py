@@ -713,6 +713,41 @@ class GraphEngine:
         _lib.check(rc, "lgnn_diag_adjgrad_finish")
         return out if cand is None else (out, cout)
 
+    def full_adjgrad_batch(self, idx, y, Gamma: torch.Tensor, grad_P: torch.Tensor, out_bar: torch.Tensor, h1_bar: torch.Tensor,
+                           e_bar: torch.Tensor, loss_scale: float = 1.0, cand=None):
+        """Full posterior (2-layer GCN, also with res / norm; plain 2-layer GraphSAGE): as ``diag_adjgrad_batch`` with the dense
+        symmetric ``Gamma`` [n_params, n_params] = d(-marglik)/dH as weighting (lgnn_full_adjgrad_batch); finished by
+        ``diag_adjgrad_finish``."""
+        self._sync_versions()
+        idx, y = idx.contiguous(), y.contiguous()
+        self._check_gamma(Gamma)
+        self._keep = Gamma
+        ca, cb, K, cacc = self._cand_ptrs(cand)
+        rc = self.lib.lgnn_full_adjgrad_batch(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
+            _dev_ptr(Gamma, torch.float32, "Gamma"), float(loss_scale), _dev_ptr(grad_P, torch.float32, "grad_P"),
+            _dev_ptr(out_bar, torch.float32, "out_bar"), _dev_ptr(h1_bar, torch.float32, "h1_bar"),
+            _dev_ptr(e_bar, torch.float32, "e_bar"), ca, cb, K, cacc, _stream(self.device))
+        _lib.check(rc, "lgnn_full_adjgrad_batch")
+
+    def full_directions(self, idx: torch.Tensor, Gamma: torch.Tensor):
+        """(K [M, C, C], R [M, C, P]): ``K_m = J_m Gamma J_m^T`` and ``R_m = 2 Lambda_m J_m Gamma`` of the samples ``idx`` for a
+        symmetric ``Gamma`` [n_params, n_params], ``Lambda_m`` the softmax Hessian of the model's logits (lgnn_full_directions)."""
+        self._sync_versions()
+        idx = idx.contiguous()
+        self._check_gamma(Gamma)
+        M, C = idx.shape[0], self.dims[-1]
+        Kn = torch.empty(M, C, C, dtype=torch.float32, device=self.device)
+        R = torch.empty(M, C, self.n_params, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_full_directions(self._h, _dev_ptr(idx, torch.int64, "idx"), M,
+                                                 _dev_ptr(Gamma, torch.float32, "Gamma"), Kn.data_ptr(), R.data_ptr(),
+                                                 _stream(self.device)), "lgnn_full_directions")
+        return Kn, R
+
+    def _check_gamma(self, Gamma: torch.Tensor):
+        if tuple(Gamma.shape) != (self.n_params, self.n_params) or not Gamma.is_contiguous():
+            raise ValueError(f"Gamma: a contiguous [{self.n_params}, {self.n_params}] matrix, got {tuple(Gamma.shape)}")
+
     # -- the same gradient on all N x N pairs (LoRASTEGCN: lgnn_*_dense, csrc/lora.hip) ---------------------------------
     def adjgrad_batch_dense(self, idx, y, gammas_B, out_bar: torch.Tensor, grad_dense: torch.Tensor, fork_exact: bool = True,
                             loss_scale: float = 1.0):

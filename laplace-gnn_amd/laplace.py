@@ -1351,6 +1351,77 @@ class FullLaplace(ParametricLaplace):
     def _scale_samples(self, eps):  # :1497-1508: samples @ posterior_scale
         return eps @ self.posterior_scale
 
+    def _adj_gamma(self) -> torch.Tensor:
+        """``Gamma = d(1/2 logdet(f H + Delta))/dH = (f / 2) (f H + Delta)^-1`` [P, P]: fp64 Cholesky and inverse, symmetrised,
+        contiguous fp32.  The inverse is ``cholesky_inverse`` while the fp64 matrix stays below 2 GiB; above that the solver's
+        one-call inverse fails on the device (seen at P = 23 063), so the identity is solved in column blocks of at most 1 GiB."""
+        chol = torch.linalg.cholesky(self.posterior_precision.double())
+        n = chol.shape[0]
+        if n * n * 8 < 2 ** 31:
+            Gamma = torch.cholesky_inverse(chol)
+        else:
+            Gamma = torch.empty_like(chol)
+            step = max(1, 2 ** 30 // (8 * n))
+            for c0 in range(0, n, step):
+                c1 = min(n, c0 + step)
+                E = torch.zeros(n, c1 - c0, dtype=chol.dtype, device=chol.device)
+                E[c0:c1].fill_diagonal_(1.0)
+                Gamma[:, c0:c1] = torch.cholesky_solve(E, chol)
+        del chol
+        Gamma.mul_(0.5 * float(self._H_factor))
+        Gamma.add_(Gamma.T.clone()).mul_(0.5)
+        return Gamma.to(torch.float32).contiguous()
+
+    def neg_marglik_adj_grad(self, train_loader, prior_precision=None, process_group=None, candidates=None, dense=False):
+        """``-log_marginal_likelihood()`` of this fit and its gradient w.r.t. the adjacency -- what ``neg_marglik.backward()``
+        leaves in ``model.adj.grad`` when the structure-learning loop runs with ``hessian_structure="full"``
+        (gnn/utils.py:57-59; gnn/marglik_training.py:197-216; laplace/baselaplace.py:1377-1505 over the fork's attached
+        Jacobians, laplace/curvature/curvature.py:374-410, :89-130).  Same return values and candidate pairs as
+        ``DiagLaplace.neg_marglik_adj_grad``.  2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE,
+        classification.  ``d(1/2 logdet(f H + Delta))/dH = Gamma = (f / 2) (f H + Delta)^-1`` is held fixed; it is built once per
+        call in fp64 (as ``posterior_scale``) and handed to the device in fp32.  The GGN is a sum over samples, so the ranks of a
+        job split every batch by samples.  ``dense=True`` (LoRA) stays on the Kronecker and diagonal posteriors."""
+        if self.H is None or not self.n_data:
+            raise AttributeError("Laplace not fitted. Run fit() first.")
+        if prior_precision is not None:
+            self.prior_precision = prior_precision
+        if self.likelihood != "classification":
+            raise NotImplementedError("adjacency gradient: classification likelihood")
+        if dense:
+            raise NotImplementedError("adjacency gradient under the full posterior: stored entries and candidates only "
+                                      "(dense=True is offered by KronLaplace and DiagLaplace)")
+        eng = getattr(self.backend, "engine", None)
+        if eng is None or not hasattr(eng, "full_adjgrad_batch") or eng.kind not in ("gcn", "sage") or len(eng.dims) != 3:
+            raise NotImplementedError("adjacency gradient under the full posterior: 2-layer GCN / GraphSAGE on the HIP backend")
+        value = -self.log_marginal_likelihood()
+        f = self._H_factor
+        Gamma = self._adj_gamma()
+        N, Hd, F, C = eng.num_nodes, eng.dims[1], eng.dims[0], eng.dims[-1]
+        grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
+        out_bar = torch.zeros(N, C, dtype=torch.float32, device=eng.device)
+        h1_bar = torch.zeros(N, Hd, dtype=torch.float32, device=eng.device)
+        e_bar = torch.zeros(N, F + 1, dtype=torch.float32, device=eng.device)
+        rank, world = _dist_info(process_group)
+        sym = bool(getattr(self.model, "symmetric", False))
+        cand = _adjacency_candidates(eng, candidates, sym)
+        eng.set_likelihood("classification")
+        for X, y in train_loader:
+            M = X.shape[0]
+            lo, hi = M * rank // world, M * (rank + 1) // world
+            if hi > lo:
+                eng.full_adjgrad_batch(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), Gamma, grad_P, out_bar, h1_bar, e_bar,
+                                       loss_scale=f, cand=cand)
+        if world > 1:
+            all_reduce_flat_([grad_P, out_bar, h1_bar, e_bar] + ([cand[2]] if cand is not None else []), process_group)
+        rows, cols = eng.export_adj()
+        if cand is None:
+            return value, torch.stack([rows, cols]), eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P)
+        grad, gc = eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P, cand=cand)
+        if sym:
+            K = candidates.shape[1]
+            gc = 0.5 * (gc[:K] + gc[K:])
+        return value, torch.stack([rows, cols]), grad, gc
+
 
 def _all_subclasses(cls) -> set:
     return set(cls.__subclasses__()).union([s for c in cls.__subclasses__() for s in _all_subclasses(c)])
