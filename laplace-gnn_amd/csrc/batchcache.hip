@@ -162,15 +162,15 @@ int batch_cache_store_active(lgnn_ctx* h, BatchEntry* e, hipStream_t s) {
   return 0;
 }
 
-// The same for the two-hop path list (and R where the overflow route can be reached, and the node list of a short batch when
-// the caller built one over all N nodes).  Synchronises the stream once.
-int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r, bool have_nodes, hipStream_t s) {
+// The same for the two-hop path list, R (the top-layer tiles read it on every accumulate, the overflow route where it can be
+// reached) and the node list of a short batch when the caller built one over all N nodes.  Synchronises the stream once.
+int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool have_nodes, hipStream_t s) {
   if (e->has_paths || e->refused) return 0;
   const int64_t N = h->N;
   Workspace& ws = h->ws;
   int32_t cnt[3] = {0, 0, 0};  // paths, entries of R, nodes with a path
   LGNN_HIP_CHECK(hipMemcpyAsync(&cnt[0], ws.path_pptr.as<int32_t>() + N, 4, hipMemcpyDeviceToHost, s));
-  if (keep_r) LGNN_HIP_CHECK(hipMemcpyAsync(&cnt[1], ws.path_rptr.as<int32_t>() + N, 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipMemcpyAsync(&cnt[1], ws.path_rptr.as<int32_t>() + N, 4, hipMemcpyDeviceToHost, s));
   if (have_nodes) LGNN_HIP_CHECK(hipMemcpyAsync(&cnt[2], ws.path_nnodes.p, 4, hipMemcpyDeviceToHost, s));
   LGNN_HIP_CHECK(hipStreamSynchronize(s));
   // (a list longer than its capacity was counted, not filled: the fused kernel returns at once and the overflow route runs)
@@ -179,12 +179,12 @@ int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r
                "internal: path structure counts out of range");
   const size_t nr = size_t(cnt[1]), nn = size_t(cnt[2]);
   size_t add = size_t(N + 1) * 4 + std::max<size_t>(np, 1) * 12;
-  if (keep_r) add += size_t(N + 1) * 4 + std::max<size_t>(nr, 1) * 8;
+  add += size_t(N + 1) * 4 + std::max<size_t>(nr, 1) * 8;
   if (have_nodes) add += std::max<size_t>(nn, 1) * 4 + 4;
   bool ok = make_room(h, e, add, batch_cache_budget());
   ok = ok && alloc_copy(e->pptr, ws.path_pptr.p, size_t(N + 1), s) == 0 && alloc_copy(e->pm, ws.path_pm.p, np, s) == 0 &&
        alloc_copy(e->pv, ws.path_pv.p, np, s) == 0 && alloc_copy(e->pw, ws.path_pw.p, np, s) == 0;
-  if (ok && keep_r)
+  if (ok)
     ok = alloc_copy(e->rptr, ws.path_rptr.p, size_t(N + 1), s) == 0 && alloc_copy(e->r_m, ws.path_rm.p, nr, s) == 0 &&
          alloc_copy(e->r_w, ws.path_rw.p, nr, s) == 0;
   if (ok && have_nodes)
@@ -194,17 +194,16 @@ int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r
   h->bcache.bytes += add;
   e->path_bytes = add;
   e->cap = cap;
-  e->has_r = keep_r;
   e->has_nodes = have_nodes;
   e->has_paths = true;
   return 0;
 }
 
-// another list capacity (LGNN_PATH_LIST_CAP) or an R that is needed now and was not kept: the path part is built again
+// another list capacity (LGNN_PATH_LIST_CAP): the path part is built again
 void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e) {
   if (!e->has_paths) return;
   e->pptr = {}; e->pm = {}; e->pv = {}; e->pw = {}; e->nodes = {}; e->nnodes = {}; e->rptr = {}; e->r_m = {}; e->r_w = {};
-  e->has_paths = e->has_r = e->has_nodes = false;
+  e->has_paths = e->has_nodes = false;
   h->bcache.bytes -= e->path_bytes;
   e->bytes -= e->path_bytes;
   e->path_bytes = 0;

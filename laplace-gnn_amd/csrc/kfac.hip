@@ -848,6 +848,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   }
   LGNN_CALL(h->ws.active.reserve(size_t(N)));
   bool have_act_list = false;
+  bool top_tiles = false;  // GCN path route: B_{L-1} comes from top_tiles_kernel instead of seed_spmm_gram_kernel
   // the GCN's active rows as the steps below read them: the workspace's, or the cache entry's on a hit
   const uint8_t* active_p = nullptr;
   const int32_t* act_list_p = nullptr;
@@ -886,7 +887,13 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
         // the unfused lower path reads every row of the planes: the rows this kernel skips must be zero
         LGNN_HIP_CHECK(hipMemsetAsync(gtop + cb * N * C, 0, size_t(N) * nq * 4, s));
       float* sc = h->ws.gram_scratch[L - 1].as<float>();
-      if (top_here) switch (int(cdiv(C, 16))) {
+      // path route, no planes wanted, no sliced hubs: the top layer runs on the matrix pipes from the path route's tables and
+      // R (toptiles.hip), launched by kfac_paths_first_layer below once both are in place
+      if (top_here && paths_route && !gplanes && C <= kCoefStride && nb < ne) {
+        LGNN_CALL(long_rows_ensure(h, s));
+        top_tiles = h->n_top_multi <= 0;
+      }
+      if (top_here && !top_tiles) switch (int(cdiv(C, 16))) {
         case 1: LGNN_CALL(seed_spmm_gram_launch<1>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
         case 2: LGNN_CALL(seed_spmm_gram_launch<2>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
         case 3: LGNN_CALL(seed_spmm_gram_launch<3>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
@@ -917,10 +924,13 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   // ---- 2-layer GCN: B_0 from the batch's 2-hop paths -- no class planes (paths.hip) -------------------------
   const bool paths_route = plan.paths && !fisher && (h->kind == LGNN_KIND_GCN ? seeds_on_the_fly : true);
   h->last_route_paths = paths_route;
+  h->last_top_tiles = top_tiles;
   if (paths_route) {
     const int mode = h->lik == LGNN_LIK_REGRESSION ? 2 : (fork_exact ? 1 : 0);
+    const TopTilesReq top{act_list_p, act_count_p, h->ws.gram_scratch[L - 1].as<float>()};
     if (h->kind == LGNN_KIND_GCN)
-      LGNN_CALL(kfac_paths_first_layer(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne, be, &be_built));
+      LGNN_CALL(kfac_paths_first_layer(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne, be, &be_built,
+                                       top_tiles ? &top : nullptr));
     else LGNN_CALL(kfac_paths_first_layer_sage(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne));
   }
 

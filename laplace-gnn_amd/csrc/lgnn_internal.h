@@ -192,8 +192,7 @@ struct BatchEntry {
   bool has_nodes = false;
   DevArray<int32_t> nodes;
   DevArray<int32_t> nnodes;
-  // R = P^T[:, batch], kept only where the overflow route can be reached
-  bool has_r = false;
+  // R = P^T[:, batch] (part of the path structure: the overflow route and the top-layer tiles, toptiles.hip, read it)
   DevArray<int32_t> rptr;       // [N + 1]
   DevArray<int32_t> r_m;
   DevArray<float> r_w;
@@ -280,6 +279,7 @@ struct lgnn_ctx {
   int64_t ws_limit = int64_t(32) << 30;  // backward planes (ping + pong) per class chunk: 288 GB of HBM, keep chunks large
   // rows of P^T with more than kLongRow stored entries (hubs), built once on first use (longrows.hip)
   bool last_route_paths = false;   // the last KFAC accumulate took the two-hop path route
+  bool last_top_tiles = false;     // ... and its top layer ran on top_tiles_kernel (toptiles.hip), not seed_spmm_gram_kernel
   double two_hop_max = -1.0;       // largest number of 2-hop paths starting at one node (same count pass)
   double two_hop = -1.0;           // number of 2-hop paths n <- v <- m of the graph (-1: not counted yet; paths.hip)
   int64_t n_long = -1;             // -1: not looked at yet
@@ -525,17 +525,27 @@ size_t batch_cache_budget();                 // LGNN_BATCH_CACHE_MB in bytes, re
 void batch_cache_clear(lgnn_ctx* h);         // the graph changed / the context goes: every entry and every remembered tag
 int batch_cache_lookup(lgnn_ctx* h, uint64_t tag, const int64_t* idx, int64_t M, BatchEntry** out, hipStream_t s);
 int batch_cache_store_active(lgnn_ctx* h, BatchEntry* e, hipStream_t s);   // from ws.active / act_list / act_count
-int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool keep_r, bool have_nodes, hipStream_t s);
+int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool have_nodes, hipStream_t s);  // path list, R, node list
 void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e);
 // ---- paths.hip ----------------------------------------------------------------------------
 bool paths_supported(int kind, int L, const int64_t* dims, int act, int64_t nnz);
 int two_hop_ensure(lgnn_ctx* h, hipStream_t s);   // h->two_hop = 2-hop paths of the graph, counted once (one synchronisation)
 bool paths_pay(const lgnn_ctx* h, int64_t M);     // expected paths per destination node of a batch of M small enough
+constexpr int kCoefStride = 64;  // classes per coefficient kind (zero padded): the class window [cb, cb + 64) of a call
+constexpr int kCoefRow = 256;    // floats per sample in the coefficient table: (alpha | -beta | -gamma | pad) = 1 KiB, one LDS-DMA piece
+struct PathR { const int32_t* rptr; const int32_t* r_m; const float* r_w; };  // R = P^T[:, batch] as CSR over the nodes
+// The GCN top layer of the path route on the matrix pipes (toptiles.hip): scratch [C, C] += B_1 of the classes [cb, ce) from R
+// and the tables path_tables_kernel has written for the same (cb, ce) (ws.path_coef, ws.path_up).
+int launch_top_tiles(lgnn_ctx* h, const PathR& r, int64_t M, int64_t cb, int64_t ce, const int32_t* act_list,
+                     const int32_t* act_count, float* scratch, hipStream_t s);
+struct TopTilesReq { const int32_t* act_list; const int32_t* act_count; float* scratch; };  // the batch's active rows, B_1 scratch
 // scratch [H, H] += B_0 of this batch's class columns [cb, ce) (seed_mode: 0 upstream, 1 fork exact, 2 regression)
+// (top: also run the top layer from the tables and R built here -- launch_top_tiles -- once both are in place)
 // (nb, ne: the destination nodes whose Y_n^T Y_n this call adds -- B_0 is a sum over nodes: the multi-GPU cut of these routes)
 // (entry: the batch's cache entry or null; its path part is used if present and built into it otherwise; *built is set then)
 int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce, float* scratch,
-                           hipStream_t s, int64_t nb = 0, int64_t ne = -1, BatchEntry* entry = nullptr, bool* built = nullptr);
+                           hipStream_t s, int64_t nb = 0, int64_t ne = -1, BatchEntry* entry = nullptr, bool* built = nullptr,
+                           const TopTilesReq* top = nullptr);
 int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce,
                                 float* scratch, hipStream_t s, int64_t nb = 0, int64_t ne = -1);  // GraphSAGE: one-hop paths through the same fused kernel
 // scratch [width, width] (upper 32 x 32 sub-tiles) += Y^T Y for rows of `width` floats (row stride ld), 128 < width <= 256:

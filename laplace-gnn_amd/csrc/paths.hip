@@ -22,8 +22,8 @@
 // buy the removal of the planes' gather.
 //
 // Kernels (per mini-batch):
-//   path_tables_kernel   per-sample coefficient rows (alpha, -beta, -gamma) and the rows (u, p) whose product with W_1 (one
-//                        small GEMM, kernels.hip) gives b_m, g_m
+//   path_tables_kernel   per-sample coefficient rows (alpha, -beta, -gamma), the rows (u, p) and their products with W_1:
+//                        b_m, g_m
 //   path_count / fill    R = P^T[:, batch] as CSR over v (counting sort: count, rocPRIM scan, fill): the batch neighbours of v
 //   path_list_kernel     the batch's 2-hop paths per destination node as CSR over n (count, rocPRIM scan, fill; one wave per node)
 //   ybuild_pipe_kernel   one persistent workgroup per CU, one wave per (32 classes x 64 columns): per node, windows of 16 paths
@@ -45,13 +45,14 @@ namespace lgnn {
 
 namespace {
 
-constexpr int kCoefStride = 64;  // classes per coefficient row (zero padded): two 32-row MFMA tiles
-constexpr int kCoefRow = 256;    // floats per sample in the coefficient table: (alpha | -beta | -gamma | pad) = 1 KiB, one LDS-DMA piece
+// (kCoefStride = 64 classes per coefficient kind -- two 32-row MFMA tiles -- and kCoefRow: lgnn_internal.h)
 constexpr int kPathWindow = 128; // paths staged in LDS per accumulation window
 // Where class c of a call's class range [cb, cb + 64) sits inside the 64 slots of one coefficient kind: the four 16-class MFMA
 // tiles of a slot i side by side, so that a product-wave lane fetches its A operands of all tiles with one 16-byte load.
 __device__ __forceinline__ int coef_slot(int rel) { return ((rel & 15) << 2) | (rel >> 4); }
 __device__ __forceinline__ int slot_class(int slot) { return ((slot & 3) << 4) | (slot >> 2); }
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
@@ -65,7 +66,8 @@ __device__ __forceinline__ float wsum(float v) {
 __global__ __launch_bounds__(256) void path_tables_kernel(const float* __restrict__ probs, const float* __restrict__ logits,
                                                           const int64_t* __restrict__ idx, const int32_t* __restrict__ pos,
                                                           int64_t M, int64_t N, int C, int cb, int ce, int mode,
-                                                          float* __restrict__ coef, float* __restrict__ up) {
+                                                          float* __restrict__ coef, float* __restrict__ up,
+                                                          const float* __restrict__ W1, int H, float* __restrict__ bg) {
   const int lane = threadIdx.x & 63;
   const int64_t m = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -95,6 +97,25 @@ __global__ __launch_bounds__(256) void path_tables_kernel(const float* __restric
   cm[2 * kCoefStride + lane] = have ? -sga : 0.f;
   cm[3 * kCoefStride + lane] = 0.f;
   if (lane < C) { um[lane] = u; pm[lane] = own ? pk : 0.f; }
+  // b_m = u_m^T W_1 and g_m = p_m^T W_1 (rows m and M + m of bg [2 M, H]; null: not wanted): u and p sit in the wave's lanes,
+  // the C rows of W_1 (L2 resident) are read 16 bytes per lane -- four columns of both products per lane
+  if (bg == nullptr) return;
+  const bool colv = 4 * lane < H;  // (H <= 256: every column has a lane; the lanes past H read column 0 and store nothing)
+  f32x4 b4 = {0.f, 0.f, 0.f, 0.f}, g4 = {0.f, 0.f, 0.f, 0.f};
+  if (own) {  // (wave uniform: the v_readlane below run with every lane active)
+    const float* __restrict__ w = W1 + (colv ? 4 * lane : 0);
+    for (int c = 0; c < C; ++c) {
+      const float uc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), c));
+      const float pc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pk), c));
+      const f32x4 wc = *reinterpret_cast<const f32x4*>(w + int64_t(c) * H);
+      b4 += uc * wc;
+      g4 += pc * wc;
+    }
+  }
+  if (colv) {
+    *reinterpret_cast<f32x4*>(bg + m * H + 4 * lane) = b4;
+    *reinterpret_cast<f32x4*>(bg + (M + m) * H + 4 * lane) = g4;
+  }
 }
 
 // R = P^T[:, batch]: for every distinct batch node u (its first position m) and every entry (v, val) of row u of P.
@@ -1491,7 +1512,7 @@ constexpr int64_t kFusedWorkgroups = 256;
 // B_0 scratch += sum over the class columns [cb, ce) of this batch (see the file header).  Needs batch_prologue's
 // probabilities / multiplicities / positions and the cached forward (logits, mask bits).
 int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce, float* scratch,
-                           hipStream_t s, int64_t nb, int64_t ne, BatchEntry* entry, bool* built) {
+                           hipStream_t s, int64_t nb, int64_t ne, BatchEntry* entry, bool* built, const TopTilesReq* top) {
   const int64_t N = h->N, C = h->dims[2], H = h->dims[1];
   if (ne < 0) ne = N;
   LGNN_REQUIRE(nb >= 0 && nb <= ne && ne <= N, "internal: node range");
@@ -1502,12 +1523,16 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
   LGNN_CALL(ws.path_coef.reserve(size_t(M) * kCoefRow * 4));
   LGNN_CALL(ws.path_up.reserve(size_t(2 * M) * C * 4));
   LGNN_CALL(ws.path_bg.reserve(size_t(2 * M) * H * 4));
+  // the wave that owns a sample also forms its rows b_m, g_m of the [2 M, H] table (16-byte loads of W_1's rows: a weight tensor
+  // that is not 16-byte aligned takes the small GEMM instead)
+  const bool no_bg = seed_mode == 2;
+  const bool bg_in_tables = !no_bg && (reinterpret_cast<uintptr_t>(h->W[1]) & 15) == 0;
   hipLaunchKernelGGL(path_tables_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, ws.probs.as<float>(),
                      h->fc.out.as<float>(), idx, ws.pos.as<int32_t>(), M, N, int(C), int(cb), int(ce), seed_mode,
-                     ws.path_coef.as<float>(), ws.path_up.as<float>());
+                     ws.path_coef.as<float>(), ws.path_up.as<float>(), h->W[1], int(H),
+                     bg_in_tables ? ws.path_bg.as<float>() : static_cast<float*>(nullptr));
   LGNN_HIP_CHECK(hipGetLastError());
-  const bool no_bg = seed_mode == 2;
-  if (!no_bg) {
+  if (!no_bg && !bg_in_tables) {
     GemmEpilogue none;
     LGNN_CALL(launch_gemm(ws.path_up.as<float>(), C, h->W[1], H, ws.path_bg.as<float>(), H, 2 * M, C, H, none, s));
   }
@@ -1516,7 +1541,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
   if (const char* e = getenv("LGNN_PATH_LIST_CAP")) cap = std::max<int64_t>(1, std::min<int64_t>(cap, atoll(e)));
   // the overflow route below is gated on the device (the host cannot know a batch's path count without a synchronisation).
   // What the host does know is a bound: M times the largest number of paths that start at one node (counted once per graph
-  // beside the graph's total).  If that fits the list, no batch can overflow and R is scratch of the list's build.
+  // beside the graph's total).  If that fits the list, no batch can overflow and the launches behind the fused kernel go.
   const bool can_overflow = !(h->two_hop_max >= 0 && double(M) * h->two_hop_max <= double(cap));
   // the list of nodes with paths pays when a good share of the nodes has none: with p expected paths per node that share is
   // about exp(-p) (a full arxiv-shaped batch: p = 13.7, every node has paths -- the list would be pure overhead, measured
@@ -1532,7 +1557,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     ws.path_zeros_set = true;
   }
   if (entry && entry->refused) entry = nullptr;
-  if (entry && entry->has_paths && (entry->cap != cap || (can_overflow && !entry->has_r))) batch_cache_drop_paths(h, entry);
+  if (entry && entry->has_paths && entry->cap != cap) batch_cache_drop_paths(h, entry);
   const bool cached = entry && entry->has_paths;
   PathLists pl{};
   if (cached) {
@@ -1585,9 +1610,12 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     }
   }
   if (entry && !cached) {  // (this call goes on with the workspace's copy: the entry may be refused for its size)
-    LGNN_CALL(batch_cache_store_paths(h, entry, cap, can_overflow, use_list && whole, s));
+    LGNN_CALL(batch_cache_store_paths(h, entry, cap, use_list && whole, s));
     if (built) *built = true;
   }
+  // ---- the top layer from the tables and R (toptiles.hip): B_1 scratch += sum_n G_n^T G_n
+  if (top)
+    LGNN_CALL(launch_top_tiles(h, PathR{pl.rptr, pl.r_m, pl.r_w}, M, cb, ce, top->act_list, top->act_count, top->scratch, s));
   // ---- class chunks of <= kYRows: everything of a node on one CU (paths_fused_kernel).  Only if the path list overflowed its
   // buffer do the two launches behind it run: the enumerating Y builder (planes in HBM, under the workspace cap) and the
   // streaming Gram over them; otherwise they return at once and no plane is ever allocated.

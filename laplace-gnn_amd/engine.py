@@ -199,6 +199,12 @@ class GraphEngine:
         """Whether the last KFAC accumulate took the two-hop path route (csrc/paths.hip) rather than class planes."""
         return bool(self.lib.lgnn_kfac_last_route(self._h))
 
+    @property
+    def last_kfac_top_on_tiles(self) -> bool:
+        """Whether the last KFAC accumulate's top layer ran on the path route's matrix-pipe kernel (csrc/toptiles.hip)
+        rather than on ``seed_spmm_gram_kernel``."""
+        return bool(self.lib.lgnn_kfac_last_top(self._h))
+
     def export_adj(self):
         nnz = self.nnz
         rows = torch.empty(nnz, dtype=torch.int64, device=self.device)
