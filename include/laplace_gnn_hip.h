@@ -69,7 +69,7 @@ extern "C" {
                                         modified by the fork) instead of upstream's detached S[:,c]          */
 #define LGNN_FLAG_NO_FUSE 2u         /* debugging: run SpMM^T and the Gram contraction as separate kernels    */
 #define LGNN_FLAG_NO_PATHS 4u        /* 2-layer GCN: keep the class-plane route (backward GEMM + fused SpMM^T -> Gram) instead
-                                        of the two-hop path route (csrc/paths.hip); same results up to fp32 reassociation */
+                                        of the two-hop path route (csrc/paths*.hip); same results up to fp32 reassociation */
 #define LGNN_FLAG_FORCE_PATHS 8u     /* take the path route wherever the model's shape allows it, also on hub-heavy graphs where
                                         the library would choose the planes (its default weighs the batch's expected number of
                                         2-hop paths per node); the first eligible call counts the graph's 2-hop paths once and
@@ -98,7 +98,7 @@ LGNN_API int64_t lgnn_num_nodes(const lgnn_ctx* h);
 /* Rows of the backward propagation matrix with more than 64 stored entries (hubs): the 256-wide fused kernel receives
  * them finished from a side kernel instead of gathering them in one wave.  -1 until the first KFAC call built the list. */
 LGNN_API int64_t lgnn_num_long_rows(const lgnn_ctx* h);
-/* 1 if the last lgnn_kfac_accumulate* call on this context took the two-hop path route (csrc/paths.hip), 0 if it built class
+/* 1 if the last lgnn_kfac_accumulate* call on this context took the two-hop path route (csrc/paths*.hip), 0 if it built class
  * planes: which of the two implementations of curvlinops/kfac.py:653-661, 777-817 ran (measurement labels; host value). */
 LGNN_API int lgnn_kfac_last_route(const lgnn_ctx* h);
 /* 1 if the top layer of that call ran on the matrix-pipe kernel of the path route (csrc/toptiles.hip: GCN, no sliced hub rows),

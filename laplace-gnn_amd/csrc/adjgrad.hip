@@ -354,12 +354,6 @@ __global__ __launch_bounds__(256) void seed_adjoint_gather_kernel(const int32_t*
   vbar[m * C * C + (c0 + c) * C + k] = acc;
 }
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // fbar_m = d/df sum_{k,c} Vbar[k,c] V[k,c](f) + softmax(f) - onehot(y); outbar[idx[m]] += fbar_m.  One wave per sample.
 // V[k,c] = alpha_c d_kc - beta_c u_k - gamma_c p_k (alpha = s (1 + t/2), beta = s, gamma = s t / 2, s = sqrt(p),
 // t = f - mbar, u = p (1 + t)).  With dp_k/df_m = p_k (d_km - p_m), dmbar/df_m = u_m, ds_c/df_m = s_c (d_cm - p_m) / 2:
@@ -385,7 +379,7 @@ __global__ __launch_bounds__(256) void seed_adjoint_kernel(const float* __restri
   float* __restrict__ sig_s = rho_s + C;
   float mb = 0.f;
   for (int64_t k = lane; k < C; k += 64) mb += probs[m * C + k] * logits[n * C + k];
-  mb = wsum(mb);
+  mb = wave_sum(mb);
   for (int64_t k = lane; k < C; k += 64) {
     const float p = probs[m * C + k], t = logits[n * C + k] - mb, s = sqrtf(p);
     p_s[k] = p; u_s[k] = p * (1.f + t); s_s[k] = s; al_s[k] = s * (1.f + 0.5f * t); ga_s[k] = 0.5f * s * t;
@@ -408,7 +402,7 @@ __global__ __launch_bounds__(256) void seed_adjoint_kernel(const float* __restri
       rho_s[k] = rho; sig_s[k] = sig;
       sru += rho * u_s[k]; srp += rho * p_s[k]; ssp += sig * p_s[k];
     }
-    sru = wsum(sru); srp = wsum(srp); ssp = wsum(ssp);
+    sru = wave_sum(sru); srp = wave_sum(srp); ssp = wave_sum(ssp);
   }
   // e1_c, e2_c (lane = c): r_c = sum_k Psi_kc u_k, q_c = sum_k Psi_kc p_k
   float e1_l[4], e2_l[4];  // C <= 256
@@ -429,7 +423,7 @@ __global__ __launch_bounds__(256) void seed_adjoint_kernel(const float* __restri
     e1_l[nl] = e1; e2_l[nl] = e2;
     se1 += e1; se2 += e2;
   }
-  se1 = wsum(se1); se2 = wsum(se2);
+  se1 = wave_sum(se1); se2 = wave_sum(se2);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

@@ -14,4 +14,11 @@ __device__ __forceinline__ float act_deriv_from_out(float h, int act) {
   return act == LGNN_ACT_RELU ? (h > 0.f ? 1.f : 0.f) : (1.f - h * h);
 }
 
+// sum over the wave's 64 lanes, in every lane (xor butterfly: the same summation order wherever it is used)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
 }  // namespace lgnn

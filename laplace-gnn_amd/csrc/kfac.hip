@@ -921,7 +921,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
     }
   }
 
-  // ---- 2-layer GCN: B_0 from the batch's 2-hop paths -- no class planes (paths.hip) -------------------------
+  // ---- 2-layer GCN: B_0 from the batch's 2-hop paths -- no class planes (paths.hip, paths_fused.hip) -------
   const bool paths_route = plan.paths && !fisher && (h->kind == LGNN_KIND_GCN ? seeds_on_the_fly : true);
   h->last_route_paths = paths_route;
   h->last_top_tiles = top_tiles;

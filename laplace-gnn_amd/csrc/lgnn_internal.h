@@ -495,7 +495,7 @@ struct KfacPlan {
   bool seeds_on_the_fly;       // GCN top layer rebuilds the seed blocks from probabilities + logits
   bool sage_compact;           // GraphSAGE top level over the batch nodes only (compacted backward GEMM + fused MODE 1)
   bool need_pong;              // the second plane buffer is written by some step
-  bool paths;                  // 2-layer GCN, ReLU, 128 < H <= 256, C <= 64: B_0 from the batch's 2-hop paths (paths.hip),
+  bool paths;                  // 2-layer GCN, ReLU, 128 < H <= 256, C <= 64: B_0 from the batch's 2-hop paths (paths.hip, paths_fused.hip),
                                // no class planes, no backward GEMM, no gather of planes
   bool fuse[kMaxLayers];       // step l (l = L-1 .. 1): fused SpMM^T -> Gram kernel (else SpMM + Gram through HBM)
   bool backgemm[kMaxLayers];   // step l: compacted producer / consumer backward GEMM (else the generic GEMM)
@@ -527,7 +527,12 @@ int batch_cache_lookup(lgnn_ctx* h, uint64_t tag, const int64_t* idx, int64_t M,
 int batch_cache_store_active(lgnn_ctx* h, BatchEntry* e, hipStream_t s);   // from ws.active / act_list / act_count
 int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool have_nodes, hipStream_t s);  // path list, R, node list
 void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e);
-// ---- paths.hip ----------------------------------------------------------------------------
+// ---- gram_stream.hip ----------------------------------------------------------------------
+// scratch [width, width] (upper 32 x 32 sub-tiles) += Y^T Y for rows of `width` floats (row stride ld), 128 < width <= 256:
+// all eight waves of a persistent workgroup per CU on the matrix pipes, row blocks by LDS-DMA
+int launch_gram256_stream(const float* Y, int64_t ld, int64_t rows, int64_t width, float* scratch, hipStream_t s,
+                          const int32_t* gate = nullptr, int64_t gate_cap = 0);
+// ---- paths.hip (its kernels: paths_fused.hip, paths_overflow.hip; what those three share: paths.h) ----------
 bool paths_supported(int kind, int L, const int64_t* dims, int act, int64_t nnz);
 int two_hop_ensure(lgnn_ctx* h, hipStream_t s);   // h->two_hop = 2-hop paths of the graph, counted once (one synchronisation)
 bool paths_pay(const lgnn_ctx* h, int64_t M);     // expected paths per destination node of a batch of M small enough
@@ -548,10 +553,6 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
                            const TopTilesReq* top = nullptr);
 int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce,
                                 float* scratch, hipStream_t s, int64_t nb = 0, int64_t ne = -1);  // GraphSAGE: one-hop paths through the same fused kernel
-// scratch [width, width] (upper 32 x 32 sub-tiles) += Y^T Y for rows of `width` floats (row stride ld), 128 < width <= 256:
-// all eight waves of a persistent workgroup per CU on the matrix pipes, row blocks by LDS-DMA (paths.hip)
-int launch_gram256_stream(const float* Y, int64_t ld, int64_t rows, int64_t width, float* scratch, hipStream_t s,
-                          const int32_t* gate = nullptr, int64_t gate_cap = 0);
 // ---- forward.hip ------------------------------------------------------------------------
 int forward_ensure(lgnn_ctx* h, hipStream_t s);
 int forward_ensure_grams(lgnn_ctx* h, hipStream_t s);

@@ -1,0 +1,770 @@
+// paths_fused_kernel and its launcher: B_0 of a 2-layer GCN / GraphSAGE from a batch's path list (paths.hip builds the list and
+// states the algebra).
+// The route (round 4): everything of a node on one CU, ONE persistent 512-thread workgroup per CU whose eight waves
+// have two ROLES.  The hardware deals a workgroup's waves round-robin to the CU's four SIMDs, so hardware waves g and g + 4
+// share a SIMD -- and its one matrix pipe:
+//   waves 0 .. 3, the PRODUCT waves (one per SIMD): wave cg owns the columns [64 cg, 64 cg + 64) of Y[n] for all <= 48
+//       classes of the launch.  Per step of FOUR paths: three 16-byte loads of the paths' coefficient rows (A operands: lane
+//       (i, k) = class slot i of path k, the four class tiles of a slot side by side in the table row), two 16-byte loads of
+//       the table rows b_m, g_m (B operands: lane (i, k) = columns 64 cg + 4 i .. + 3 of path k -- the four 16-column MFMA
+//       tiles of the wave interleave the columns, so one load feeds all four), one mask word; 36 v_mfma_f32_16x16x4_f32
+//       (3 class tiles x 4 column tiles x (alpha, beta, gamma)).  No LDS staging, no window, no restaging of hubs: the
+//       operands of step s + 1 are in flight while the MFMAs of step s issue, across node boundaries (a node's triples
+//       (m, v, w) arrive with ONE coalesced load a node ahead and are handed to the lanes with ds_bpermute).
+//       Y[n] = W_1 (.) T1 + Y2 (W_1's rows straight from L2) is split into three bf16 pieces HERE, once per value, and the
+//       pieces go to one of TWO LDS tiles (FusedShared; 18 16-byte stores per node) -- under LGNN_GRAM_F32 the fp32 values.
+//   waves 4 .. 7, the GRAM waves: S += Y[n - 1]^T Y[n - 1] from the other tile into register-resident upper-triangular
+//       accumulators (the 36 sub-tiles of gram256.h, 9 per wave, 144 accumulator registers), nothing else: their loop is LDS
+//       reads and MFMAs.
+// ONE hand-off per node (LDS counters).  The product wave of a SIMD needs the matrix pipe for about a third of a node's cycles
+// and sleeps on memory part of the rest; the Gram wave is a dense MFMA stream that takes every slot the product wave leaves: the
+// two phases that round 3 ran back to back in every wave (7.7 ms per arxiv batch, matrix pipes 57 % busy) now overlap.
+#include "gram256.h"
+#include "paths.h"
+
+namespace lgnn {
+namespace {
+
+constexpr int kYStride = 272;  // floats per row of the fp32 tile: 256 + 16, so that the four rows of a Gram operand read (lanes
+                               // 16 k .. 16 k + 15 read row k0 + k) fall on disjoint banks
+// The tile as bf16 PIECES (the default Gram role): a tile value y is y0 + y1 + y2, y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y -
+// y0 - y1) (see gram_split_role).  A dword holds the same piece of two tile rows (row r in the low half, r + 1 in the high
+// half); the tile rows come in GROUPS of four, g = row / 4, i.e. (chunk of 8 rows, lane half of the Gram's MFMA operand), and a
+// group is three PLANES (y2, y0, y1) of 256 columns x 2 dwords (rows 4 g, 4 g + 1 | rows 4 g + 2, 4 g + 3): 2 KiB each.  A Gram
+// lane reads the 8 bytes of its column from each plane (ds_read_b64; 32 lanes: 256 contiguous bytes); a product lane writes
+// the 32 bytes of its four columns to each plane (two ds_write_b128).  The 8 lanes one ds_write_b128 cycle serves are 32 bytes
+// apart, which would put them on 16 of the 32 banks twice: the two 16-byte halves of a lane's 32 bytes swap places in the lanes
+// piece_swap() names, and the 8 lanes cover the 32 banks once.  The reads stay permutations of one 256-byte bank row.
+constexpr int kPlaneDwords = 512;             // one plane: 256 columns x 2 dwords
+constexpr int kGroupDwords = 3 * kPlaneDwords;
+constexpr int kYGroups = kYRows / 4;
+// whether the four-column group q (columns 4 q .. 4 q + 3) stores its column pairs in swapped order
+__device__ __forceinline__ int piece_swap(int q) { return (q ^ (q >> 2)) & 1; }
+// dword offset inside a plane of column c's two dwords
+__device__ __forceinline__ int piece_col(int c) { return 8 * (c >> 2) + 4 * (((c >> 1) & 1) ^ piece_swap(c >> 2)) + 2 * (c & 1); }
+
+struct alignas(16) FusedShared {
+  union {  // the node tiles (double buffered), in the form the launch's Gram role reads
+    uint32_t pc[2][kYGroups][3][kPlaneDwords];  // bf16 pieces: 2 x 72 KiB
+    float y[2][kYRows][kYStride];               // fp32 (LGNN_GRAM_F32)
+  };
+  // hand-off counters (one writer each): ready[p] = nodes whose tile columns product wave p has published, done[g] = nodes
+  // Gram wave g has contracted
+  int ready[4], done[4];
+};
+static_assert(sizeof(FusedShared) <= 160 * 1024, "the CU's LDS");
+
+// min over the four counters of a hand-off array (one 16-byte LDS read; wave uniform)
+__device__ __forceinline__ int lds_min4(const int* c) {
+  int4 v;
+  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(uint32_t(reinterpret_cast<uintptr_t>(c))) : "memory");
+  return __builtin_amdgcn_readfirstlane(min(min(v.x, v.y), min(v.z, v.w)));
+}
+// publish a counter: one ds_write_b32 on the 32-bit LDS address (a store through the generic pointer is a system-scope
+// flat_store into the LDS aperture followed by vmcnt(0): a memory round trip per node on the product wave's chain).  A wave's
+// LDS operations execute in order, so the counter lands after the wave's earlier tile stores / tile reads; the lgkmcnt(0)
+// behind it keeps hipcc's own lgkmcnt(N) counts right (it does not see this operation).
+__device__ __forceinline__ void lds_publish(int* c, int value, int lane) {
+  if (lane == 0)
+    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" :: "v"(uint32_t(reinterpret_cast<uintptr_t>(c))), "v"(value) : "memory");
+}
+
+// Path ranges [p0, p1) of this workgroup's nodes (node i = entry blockIdx.x + i * gridDim.x of the list of nodes with paths,
+// or of the whole range), 32 nodes at a time in ONE register (the product role has none to spare): lanes l and 32 + l hold
+// the range of node base + l, a node's range is two v_readlane with a wave-uniform index.  Every 32 nodes the wave loads the
+// next window through buffer descriptors (the list entry first, then pptr[n] / pptr[n + 1]: one buffer_load_dword) and waits
+// for it right there with vmcnt(0): one memory round trip per 32 nodes.  (A scalar load per node -- the index is strided, so
+// every node is a new line -- put a scalar-cache miss on the wave's chain once per node: the values rotate into loop-carried
+// registers, so hipcc waits lgkmcnt(0) where the load is issued.)  Inline assembly as below: the product role counts its
+// vector loads by hand, and this block leaves none outstanding.  A lane past `cnt` reads outside the descriptor: zeros, the
+// empty range.  Nodes are asked for in ascending order.
+// Kept for what it does to the ISA (no scalar load, no lgkmcnt(0) behind one in the node loop), NOT for speed: measured
+// alone, neither this window nor the LDS-store publish above moves the launch time beyond the run-to-run spread (DESIGN
+// 12.15), and the kernel spills 12 / 24 more SGPRs to VGPR lanes with them.
+using i32x4 = int __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ i32x4 make_rsrc(const void* p, uint64_t bytes) {
+  const uint64_t u = reinterpret_cast<uint64_t>(p);
+  return i32x4{int(uint32_t(u)), int(uint32_t(u >> 32) & 0xffffu), int(uint32_t(bytes > 0xffffffffull ? 0xffffffffull : bytes)),
+               0x00020000};
+}
+template <bool LIST>
+struct NodeRanges {
+  i32x4 prs, lrs;    // pptr (N + 1 entries), the node list (nn entries)
+  uint32_t r;        // lane l < 32: pptr[n] of node base + l, lane 32 + l: its pptr[n + 1]
+  int64_t base, cnt;
+  uint32_t n0;
+  __device__ __forceinline__ void init(const int32_t* __restrict__ pptr, const int32_t* __restrict__ list, int64_t n0_, int64_t N,
+                                       int64_t nn, int64_t cnt_) {
+    prs = make_rsrc(pptr, uint64_t(N + 1) * 4);
+    lrs = make_rsrc(LIST ? list : pptr, uint64_t(LIST ? nn : 0) * 4);
+    n0 = uint32_t(n0_); cnt = cnt_;
+    fill(0);
+  }
+  __device__ __forceinline__ void fill(int64_t b) {
+    base = b;
+    const uint32_t ii = uint32_t(b) + (threadIdx.x & 31u);
+    const bool in = int64_t(ii) < cnt;
+    const uint32_t k = blockIdx.x + ii * gridDim.x;
+    uint32_t node = k;
+    if constexpr (LIST)
+      asm volatile("buffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(node) : "v"(in ? k * 4u : 0xfffffff0u), "s"(lrs) : "memory");
+    const uint32_t off = in ? (n0 + node) * 4u + ((threadIdx.x >> 3) & 4u) : 0xfffffff0u;
+    asm volatile("buffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(off), "s"(prs) : "memory");
+  }
+  __device__ __forceinline__ void get(int64_t i, int32_t& p0, int32_t& p1) {
+    if (i - base >= 32) fill(i);
+    const int l = int(i - base);
+    p0 = __builtin_amdgcn_readlane(int(r), l); p1 = __builtin_amdgcn_readlane(int(r), l + 32);
+  }
+};
+
+// ---- loads of the product waves: inline assembly with hand-placed wait counts.  hipcc's own counts are exact only along one
+// path; at the loop headers of this kernel it merges the paths pessimistically (measured: the wait for a step's operands also
+// waited for half of the NEXT step's, i.e. one step of prefetch distance instead of two), and any load it tracks itself would
+// make it wait for vmcnt(0) -- it does not see the assembly loads queued behind.  So every vector load of the role's loop is
+// issued here and waited for with a counted s_waitcnt whose "+v" operands tie the loaded registers to the wait (uses cannot
+// move above it).  vmcnt counts in order: waiting until at most n operations are outstanding retires everything older than
+// the n youngest.
+// BUFFER loads (descriptor in SGPRs + one 32-bit byte offset per lane): on this chip the fp32 MFMAs run on the SIMD's vector
+// ALUs, so every VALU instruction of either wave of a SIMD is matrix-pipe time lost, not work hidden behind the MFMAs
+// (measured: the product wave's MFMA time and the time of its other instructions add up, with or without the Gram wave) --
+// 64-bit address arithmetic per load was a quarter of this wave's instructions.  An offset past the table's end reads zeros.
+template <int OFF>
+__device__ __forceinline__ void bload4(f32x4& d, uint32_t voff, const i32x4& rsrc) {
+  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(d) : "v"(voff), "s"(rsrc), "n"(OFF) : "memory");
+}
+__device__ __forceinline__ void bload1(uint32_t& d, uint32_t voff, const i32x4& rsrc) {
+  asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rsrc) : "memory");
+}
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
+using u32x2v = __attribute__((ext_vector_type(2))) uint32_t;
+
+__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest, NaN stays NaN)
+  using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+  const bf16x2 v = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
+  return __builtin_bit_cast(uint32_t, v);
+}
+// The three bf16 pieces of two tile values (ya in the low halves, yb in the high halves), each rounded to nearest:
+// q0 = bf16(y), q1 = bf16(y - q0), q2 = bf16(y - q0 - q1) = y - q0 - q1 (see gram_split_role).  11 vector instructions.
+__device__ __forceinline__ void split_pair(float ya, float yb, uint32_t& q0, uint32_t& q1, uint32_t& q2) {
+  q0 = pk_bf16(ya, yb);
+  asm("" : "+v"(q0));  // (keeps the two values in one cvt: hipcc otherwise converts and widens each on its own)
+  const float r1a = ya - __uint_as_float(q0 << 16), r1b = yb - __uint_as_float(q0 & 0xffff0000u);
+  q1 = pk_bf16(r1a, r1b);
+  asm("" : "+v"(q1));
+  q2 = pk_bf16(r1a - __uint_as_float(q1 << 16), r1b - __uint_as_float(q1 & 0xffff0000u));
+}
+
+struct PTables {  // descriptors of what the role reads
+  i32x4 coef, b, g, mask, pm, pv, pw;
+};
+
+// The paths of a chunk (up to 64): lane l holds path p0 + l as the BYTE OFFSETS of its sample's rows in the coefficient table
+// (oc) and the b / g tables (ob), of its middle node's mask words (om), and its weight.  Unconditional loads from a clamped
+// index; lanes past the range get offsets 0 and weight 0 in meta_finish: every load formed from them is valid, every product
+// with them is zero.
+struct PMeta { uint32_t oc, ob, om, w; };  // (w: the bits of a float)
+__device__ __forceinline__ void meta_issue(const PTables& tb, int32_t p0, int32_t p1, int lane, PMeta& t) {
+  const uint32_t q = uint32_t(max(min(p0 + lane, p1 - 1), 0)) * 4u;
+  bload1(t.oc, q, tb.pm);  // (sample m, node v: turned into offsets in meta_finish)
+  bload1(t.om, q, tb.pv);
+  bload1(t.w, q, tb.pw);
+}
+template <int YOUNGER>  // vector-memory operations issued after the triples' loads that may still be in flight
+__device__ __forceinline__ void meta_finish(int32_t p0, int32_t p1, int lane, uint32_t row_bytes, uint32_t mask_bytes, PMeta& t) {
+  asm volatile("s_waitcnt vmcnt(%3)" : "+v"(t.oc), "+v"(t.om), "+v"(t.w) : "n"(YOUNGER) : "memory");
+  const bool in = p0 + lane < p1;
+  const uint32_t m = in ? t.oc : 0u, v = in ? t.om : 0u;
+  t.oc = m * uint32_t(kCoefRow * 4); t.ob = m * row_bytes; t.om = v * mask_bytes;
+  t.w = in ? t.w : 0u;
+}
+
+struct PLane {        // what a product-wave lane is: class slot / column slot i, path k of a step
+  int kq;
+  uint32_t oc, ob, om;  // the lane's byte offsets inside a coefficient row (16 i), a table row (4 (64 cg + 4 i)) and a node's
+                        // mask words; past H: the row's start resp. an offset outside the mask (reads zero: no bit set)
+  int mshift;           // bit of the lane's first column inside its mask word
+};
+
+struct POps {        // the loaded operands of one step (22 registers)
+  f32x4 ca[3];      // coefficient rows (alpha | -beta | -gamma), class slots (i, t = 0 .. 3)
+  f32x4 b4, g4;     // rows b_m, g_m at the lane's four columns
+  uint32_t mw;       // mask word of the path's middle node
+  float w;           // path weight (0 past the chunk's last path)
+};
+
+// Issue the loads of step s (paths 4 s .. 4 s + 3 of the chunk `mt`): kStepLoads<NOBG> instructions, nothing conditional.
+template <bool NOBG> constexpr int kStepLoads = NOBG ? 2 : 6;
+template <bool NOBG>
+__device__ __forceinline__ void p_load(const PTables& tb, const PMeta& mt, int s, const PLane& pl, POps& o) {
+  const int src = 4 * s + pl.kq;  // the lane that holds this lane's path (s < 16)
+  const uint32_t oc = uint32_t(__shfl(int(mt.oc), src)) + pl.oc;
+  const uint32_t om = uint32_t(__shfl(int(mt.om), src)) + pl.om;
+  o.w = __uint_as_float(uint32_t(__shfl(int(mt.w), src)));
+  bload4<0>(o.ca[0], oc, tb.coef);
+  if constexpr (!NOBG) {
+    const uint32_t ob = uint32_t(__shfl(int(mt.ob), src)) + pl.ob;
+    bload4<kCoefStride * 4>(o.ca[1], oc, tb.coef);
+    bload4<2 * kCoefStride * 4>(o.ca[2], oc, tb.coef);
+    bload4<0>(o.b4, ob, tb.b);
+    bload4<0>(o.g4, ob, tb.g);
+  }
+  bload1(o.mw, om, tb.mask);
+}
+// the step's loads have landed once at most YOUNGER younger vector-memory operations are outstanding
+template <bool NOBG, int YOUNGER>
+__device__ __forceinline__ void p_wait(POps& o) {
+  if constexpr (NOBG)
+    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(o.ca[0]), "+v"(o.mw) : "n"(YOUNGER) : "memory");
+  else
+    asm volatile("s_waitcnt vmcnt(%6)" : "+v"(o.ca[0]), "+v"(o.ca[1]), "+v"(o.ca[2]), "+v"(o.b4), "+v"(o.g4), "+v"(o.mw)
+                 : "n"(YOUNGER) : "memory");
+}
+
+// A step's MFMA operands: lane (i, k): A[row i][k] = weighted coefficient of class 16 t + i, B[k][col i] = mask bit / masked
+// table value of the lane's column ct.  HI (a second launch of a call with more than 48 classes): the launch's only class
+// tile is the fourth of the slot.  26 vector instructions (each costs the SIMD's matrix pipe its issue cycles, see above):
+// bit ct of the mask word as 0 / -1 with one v_bfe_i32, ANDed with 1.0f.
+struct PCur { float a0[3], a1[3], a2[3], mf[4], bb[4], gg[4]; };
+template <bool NOBG, bool HI>
+__device__ __forceinline__ void p_xform(const POps& o, const PLane& pl, PCur& c) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const int tt = HI ? 3 : t;
+    c.a0[t] = (HI && t > 0) ? 0.f : o.w * o.ca[0][tt];
+    if constexpr (!NOBG) {
+      c.a1[t] = (HI && t > 0) ? 0.f : o.w * o.ca[1][tt];
+      c.a2[t] = (HI && t > 0) ? 0.f : o.w * o.ca[2][tt];
+    }
+  }
+  const int bits = int(o.mw >> pl.mshift);
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    const int on = __builtin_amdgcn_sbfe(bits, ct, 1);  // 0 or -1
+    c.mf[ct] = __int_as_float(on & 0x3f800000);
+    if constexpr (!NOBG) { c.bb[ct] = c.mf[ct] * o.b4[ct]; c.gg[ct] = c.mf[ct] * o.g4[ct]; }
+  }
+}
+// an empty statement that reads every register of `c`: keeps the set alive (and out of the other set's registers) up to here
+template <bool NOBG>
+__device__ __forceinline__ void p_keep(const PCur& c) {
+  asm volatile("" :: "v"(c.a0[0]), "v"(c.a0[1]), "v"(c.a0[2]), "v"(c.mf[0]), "v"(c.mf[1]), "v"(c.mf[2]), "v"(c.mf[3]));
+  if constexpr (!NOBG) {
+    asm volatile("" :: "v"(c.a1[0]), "v"(c.a1[1]), "v"(c.a1[2]), "v"(c.a2[0]), "v"(c.a2[1]), "v"(c.a2[2]));
+    asm volatile("" :: "v"(c.bb[0]), "v"(c.bb[1]), "v"(c.bb[2]), "v"(c.bb[3]), "v"(c.gg[0]), "v"(c.gg[1]), "v"(c.gg[2]), "v"(c.gg[3]));
+  }
+}
+// the 36 (NOBG: 12) MFMAs of one step;  D: col = i, row = 4 k + r
+template <bool NOBG>
+__device__ __forceinline__ void p_mfma(const PCur& c, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4]) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) t1[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a0[t], c.mf[ct], t1[t][ct], 0, 0, 0);
+  if constexpr (!NOBG) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], y2[t][ct], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
+  }
+}
+// A node's FIRST step: the alpha and beta products take the inline constant 0 as C and so START the node's accumulators
+// (the gamma product accumulates into the beta one): nothing clears the 96 accumulator registers between nodes.
+template <bool NOBG>
+__device__ __forceinline__ void p_mfma_first(const PCur& c, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) t1[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a0[t], c.mf[ct], zero, 0, 0, 0);
+  if constexpr (!NOBG) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], zero, 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
+  }
+}
+
+// The product wave's work as a stream of CHUNKS: at most 64 paths of one node (one register of triples); a node is one chunk
+// (a hub: several), a node without paths one empty chunk.  Wave-uniform scalar state; the range of the node after the one
+// being cut is read a node ahead (NodeRanges).
+template <bool LIST>
+struct ChunkGen {
+  int64_t gi;            // node being cut into chunks (index into this workgroup's nodes; nodes >= cnt are empty)
+  int32_t gp, gend;      // its remaining paths
+  int32_t pa0, pa1;      // the path range of node gi + 1
+  NodeRanges<LIST> nr;
+  __device__ __forceinline__ void init(const int32_t* __restrict__ pptr, const int32_t* __restrict__ list, int64_t n0, int64_t N,
+                                       int64_t nn, int64_t cnt) {
+    nr.init(pptr, list, n0, N, nn, cnt);
+    gi = 0;
+    nr.get(0, gp, gend);
+    nr.get(1, pa0, pa1);
+  }
+  // the next chunk [q0, q1) and whether it is its node's last
+  __device__ __forceinline__ void next(int64_t cnt, int32_t& q0, int32_t& q1, bool& last) {
+    q0 = gp; q1 = min(gp + 64, gend);
+    last = q1 >= gend;
+    if (last) {
+      ++gi;
+      gp = pa0; gend = pa1;
+      nr.get(gi + 1, pa0, pa1);
+    } else {
+      gp = q1;
+    }
+  }
+};
+
+// The product wave of SIMD cg.  Steps come in PAIRS (8 paths): buffer A holds the loaded operands of the pair's first step, B
+// of its second; each is refilled for the NEXT pair -- this chunk's, or the next chunk's first (usually the next node's) --
+// right after its values were turned into MFMA operands, so two steps' loads (12 instructions) are in flight behind the 36
+// MFMAs being issued.  The loads are unconditional and in one fixed order, the hand-counted waits rely on it; A / B are written
+// nowhere else inside the loop.  Hence the chunk stream: hubs and empty nodes take the same path as everything else; a step past
+// the chunk's last path multiplies zero weights (meta_finish), an empty chunk is one such step.
+// A pair is ONE body with two wave-uniform flags, and the flags only choose among MFMAs and the operand transform: every load,
+// wait, p_keep pin and refill is outside the branches, in the same order and number whatever the flags are, so every counted
+// vmcnt holds whichever pairs follow each other.
+//   first  the first pair of a node: its first step's alpha and beta MFMAs take C = 0 (p_mfma_first), which is what clears
+//          the accumulators -- nothing else does;
+//   half   the last pair of a chunk whose second step has no path (4 (2 j + 1) >= paths of the chunk): p_wait(B) and B's refill
+//          stay, p_xform(B) and B's MFMAs are left out -- B's landed operands are overwritten by the refill unread.
+// (Four complete straight-line bodies, one per flag combination, is what was tried first: hipcc then gives the accumulators
+// and the in-flight operand registers new values per body, moves them between registers at the joins and spills 130 - 500
+// registers; with the branches around the MFMAs alone the accumulators stay where they are.)
+// An earlier branch around the second step's MFMAs "gave wrong tiles now and then".  Its code is gone, so the cause cannot be
+// read off it; the two suspects are the MFMA -> VALU wait states between a branch's last MFMA and the tile write's first
+// accumulator read, and a load inside the branch that broke the counts.  In the ISA of the straight-line loop twelve buffer
+// loads, the poll of `done` (an LDS read and its wait) and a vmcnt(0) lie between the two, far more than the 12 wait states of
+// the 8-pass 16x16x4 -- but nothing there is a guarantee, and hipcc places no s_nop of its own.  Both are excluded by
+// construction now: no branch holds a load, and `s_nop 11` (12 wait states) sits in front of the tile write's first
+// accumulator read on every path.
+template <bool NOBG, bool HI>
+__device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, int sx, const PLane& pl, POps& A, POps& B, PCur& cA,
+                                          PCur& cB, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4], bool first, bool half) {
+  constexpr int NL = kStepLoads<NOBG>;
+  // A's loads: the NL youngest outstanding may be B's (the first pair of a chunk: B's and the three path loads -- there
+  // the count also waits for B's first half, issued a whole pair earlier)
+  p_wait<NOBG, NL>(A);
+  p_xform<NOBG, HI>(A, pl, cA);
+  p_keep<NOBG>(cB);  // (cB's MFMAs may still be queued: cA must not be prepared into their operand registers)
+  p_load<NOBG>(tb, mx, sx, pl, A);
+  if (first) p_mfma_first<NOBG>(cA, t1, y2);
+  else p_mfma<NOBG>(cA, t1, y2);
+  p_wait<NOBG, NL>(B);  // (younger: A's refill)
+  if (!half) p_xform<NOBG, HI>(B, pl, cB);
+  p_keep<NOBG>(cA);  // (likewise)
+  p_load<NOBG>(tb, mx, sx + 1, pl, B);
+  if (!half) p_mfma<NOBG>(cB, t1, y2);
+}
+template <bool LIST, bool NOBG, bool HI>
+__device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
+                                             FusedShared& sh, int64_t nn, int64_t cnt, int cg) {
+  const int lane = threadIdx.x & 63;
+  const int H = a.H;
+  const bool path_wave = 64 * cg < H;  // (H <= 192: the last product wave has no columns)
+  if (!path_wave) return;  // (its ready counter was set to "everything" at the kernel's top)
+  PLane pl;
+  const int li = lane & 15;
+  pl.kq = lane >> 4;
+  const int col = 64 * cg + 4 * li;
+  const bool col_ok = col < H;  // (H % 4 == 0: the lane's four columns are in or out together)
+  pl.oc = 16u * uint32_t(li);
+  pl.ob = col_ok ? 4u * uint32_t(col) : 0u;
+  pl.om = col_ok ? 4u * uint32_t(col >> 5) : 0x7ffffff0u;  // (past H: outside the mask, the load returns zero bits)
+  pl.mshift = col & 31;
+  const uint32_t row_bytes = uint32_t(H) * 4u, mask_bytes = uint32_t(a.mask_words) * 4u;
+  PTables tb;
+  tb.coef = make_rsrc(a.coef, uint64_t(a.n_coef) * kCoefRow * 4);
+  tb.b = make_rsrc(a.bg, uint64_t(a.M) * row_bytes);
+  tb.g = make_rsrc(a.bg + a.M * int64_t(H), uint64_t(a.M) * row_bytes);
+  tb.mask = make_rsrc(a.mask, uint64_t(a.N) * mask_bytes);
+  tb.pm = make_rsrc(a.pm, uint64_t(a.cap) * 4);
+  tb.pv = make_rsrc(a.pv, uint64_t(a.cap) * 4);
+  tb.pw = make_rsrc(a.pw, uint64_t(a.cap) * 4);
+  // W_1's rows of the launch, read at the tile write (48 KB that every workgroup reads: L2 resident)
+  const uint32_t w1_row_bytes = uint32_t(a.w1_ld) * 4u;
+  const i32x4 w1rs = make_rsrc(a.W1 + int64_t(a.c0) * a.w1_ld, uint64_t(a.R - 1) * w1_row_bytes + row_bytes);
+  const uint32_t w1_off = col_ok ? uint32_t(4 * pl.kq) * w1_row_bytes + 4u * uint32_t(col) : 0x7ff00000u;
+  // the lane's two 16-byte stores inside a piece plane (dword offsets: columns col, col + 1 and col + 2, col + 3)
+  const int pc_lo = 8 * (col >> 2) + 4 * piece_swap(col >> 2), pc_hi = pc_lo ^ 4;
+  constexpr int NL = kStepLoads<NOBG>;
+  ChunkGen<LIST> gen;
+  gen.init(pptr, list, a.n0, a.N, nn, cnt);
+  int32_t q0c, q1c, q0n, q1n;
+  bool lastc, lastn;
+  gen.next(cnt, q0c, q1c, lastc);
+  gen.next(cnt, q0n, q1n, lastn);
+  PMeta mc, mn;
+  meta_issue(tb, q0c, q1c, lane, mc);
+  meta_issue(tb, q0n, q1n, lane, mn);
+  meta_finish<0>(q0c, q1c, lane, row_bytes, mask_bytes, mc);
+  meta_finish<0>(q0n, q1n, lane, row_bytes, mask_bytes, mn);
+  POps A, B;
+  p_load<NOBG>(tb, mc, 0, pl, A);
+  p_load<NOBG>(tb, mc, 1, pl, B);
+  // the node's accumulators: started by the first step of the node's first pair (pair_body, `first`), never cleared.  (The
+  // zeros here are y2's value under NOBG, where no MFMA writes it.)
+  f32x4 t1[3][4], y2[3][4];
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) { t1[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f}; y2[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  // Two sets of prepared MFMA operands, alternating (p_keep pins them to registers of their own): the next step is prepared
+  // while the MFMAs of the previous one may still be reading theirs.
+  PCur cA = {}, cB = {};
+  bool node_has = false;  // the node being built has a path so far
+  bool firstc = true;     // the chunk being run is its node's first
+  for (int64_t i = 0; i < cnt;) {  // node i's tile is built while the Gram waves contract node i - 1's (or i - 2's)
+    // the chunk after the next: its range now, its paths a whole chunk before they are used.  In flight from here
+    // (oldest first): A, B (issued by the previous chunk's last pair), these three loads
+    int32_t q0f, q1f;
+    bool lastf;
+    gen.next(cnt, q0f, q1f, lastf);
+    PMeta mf2;
+    meta_issue(tb, q0f, q1f, lane, mf2);
+    const int kch = q1c - q0c, np = max((kch + 7) >> 3, 1);
+    node_has = node_has || kch > 0;
+    for (int j = 0; j < np; ++j) {
+      // the pair after this one: this chunk's, else the next chunk's first
+      const bool more = j + 1 < np;
+      PMeta mx;
+      mx.oc = more ? mc.oc : mn.oc; mx.ob = more ? mc.ob : mn.ob; mx.om = more ? mc.om : mn.om; mx.w = more ? mc.w : mn.w;
+      const int sx = more ? 2 * (j + 1) : 0;
+      const bool first = firstc && j == 0, half = !more && 4 * (2 * j + 1) >= kch;  // (wave uniform)
+      pair_body<NOBG, HI>(tb, mx, sx, pl, A, B, cA, cB, t1, y2, first, half);
+    }
+    if (lastc) {
+      // W_1's 48 x 4 values of the lane: twelve 16-byte loads, the YOUNGEST vector-memory operations of the wave from here to
+      // the vmcnt(0) below (older, in order: the three path loads of the loop's top, the refills of A and B).  A row past the
+      // launch's classes lies outside the descriptor and reads zeros; so does every row of a lane past H (w1_off).
+      f32x4 w1[3][4];
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bload4<0>(w1[t][r], w1_off + uint32_t(16 * t + r) * w1_row_bytes, w1rs);
+      // tile i & 1 was last read by the Gram of node i - 2: every Gram wave must have counted i - 1 nodes
+      if (i >= 2)
+        while (lds_min4(sh.done) < int(i) - 1) __builtin_amdgcn_s_sleep(2);
+      // (s_nop 11 behind the wait: the MFMA -> VALU wait states of the pair loop's last MFMAs, whichever body issued them;
+      // see the header)
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(w1[t][0]), "+v"(w1[t][1]), "+v"(w1[t][2]), "+v"(w1[t][3]) :: "memory");
+      asm volatile("s_nop 11" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);  // (no accumulator read moves above the pad)
+      if (node_has && col_ok) {
+        // Y[n] = W_1 (.) T1 + Y2.  Rows past the launch's classes come out as the zeros they already are (their coefficients
+        // and their rows of W_1 are zero): one branch around unconditional 16-byte stores.
+        if (a.gram_f32) {  // the fp32 tile: twelve stores
+          float (*ytile)[kYStride] = sh.y[i & 1];
+#pragma unroll
+          for (int t = 0; t < 3; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              f32x4 o;
+#pragma unroll
+              for (int ct = 0; ct < 4; ++ct) o[ct] = w1[t][r][ct] * t1[t][ct][r] + y2[t][ct][r];
+              *reinterpret_cast<f32x4*>(&ytile[16 * t + 4 * pl.kq + r][col]) = o;
+            }
+        } else {
+          // the pieces: the lane's rows 16 t + 4 kq + 0 .. 3 are group 4 t + kq, its columns two 16-byte stores per plane
+          uint32_t* __restrict__ grp = &sh.pc[i & 1][pl.kq][0][0];
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            u32x4v pz[3][2];  // [piece y0, y1, y2][column pair]: (rows 0 1 | rows 2 3) of the pair's two columns
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+              for (int rp = 0; rp < 2; ++rp) {
+                const float ya = w1[t][2 * rp][ct] * t1[t][ct][2 * rp] + y2[t][ct][2 * rp];
+                const float yb = w1[t][2 * rp + 1][ct] * t1[t][ct][2 * rp + 1] + y2[t][ct][2 * rp + 1];
+                uint32_t q0, q1, q2;
+                split_pair(ya, yb, q0, q1, q2);
+                pz[0][ct >> 1][2 * (ct & 1) + rp] = q0;
+                pz[1][ct >> 1][2 * (ct & 1) + rp] = q1;
+                pz[2][ct >> 1][2 * (ct & 1) + rp] = q2;
+              }
+            uint32_t* __restrict__ g = grp + 4 * t * kGroupDwords;
+            // planes in the order (y2, y0, y1)
+            *reinterpret_cast<u32x4v*>(g + pc_lo) = pz[2][0];
+            *reinterpret_cast<u32x4v*>(g + pc_hi) = pz[2][1];
+            *reinterpret_cast<u32x4v*>(g + kPlaneDwords + pc_lo) = pz[0][0];
+            *reinterpret_cast<u32x4v*>(g + kPlaneDwords + pc_hi) = pz[0][1];
+            *reinterpret_cast<u32x4v*>(g + 2 * kPlaneDwords + pc_lo) = pz[1][0];
+            *reinterpret_cast<u32x4v*>(g + 2 * kPlaneDwords + pc_hi) = pz[1][1];
+          }
+        }
+      }
+      ++i;
+      lds_publish(&sh.ready[cg], int(i), lane);
+      // The accumulators' values end here: the next pair is a node's first and starts them.  hipcc cannot know that (the
+      // flag is data), and would keep all 96 registers live through the tile write above -- where the 48 values of W_1 and
+      // the pieces need them: an empty statement that defines them anew, no instruction.
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        asm volatile("" : "=v"(t1[t][0]), "=v"(t1[t][1]), "=v"(t1[t][2]), "=v"(t1[t][3]));
+        if constexpr (!NOBG) asm volatile("" : "=v"(y2[t][0]), "=v"(y2[t][1]), "=v"(y2[t][2]), "=v"(y2[t][3]));
+      }
+      node_has = false;
+    }
+    // rotate the chunk stream (the paths issued at the top are older than the 2 NL loads of the last pair's refills)
+    meta_finish<2 * NL>(q0f, q1f, lane, row_bytes, mask_bytes, mf2);
+    firstc = lastc;
+    q0c = q0n; q1c = q1n; lastc = lastn; mc = mn;
+    q0n = q0f; q1n = q1f; lastn = lastf; mn = mf2;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the refills past the last chunk
+}
+
+// The Gram wave W: its 9 upper 32 x 32 sub-tiles of gram256.h, each as 2 x 2 tiles of v_mfma_f32_16x16x4_f32 (the lower tile
+// of a diagonal sub-tile is never read by the symmetrising pass and is skipped: 34 MFMAs per four tile rows).  The SAME
+// instruction shape as the product wave's on purpose: the two waves of a SIMD take turns on its matrix pipe instruction by
+// instruction, so with 64-cycle 32x32x2 instructions here every one of the product wave's 32-cycle instructions waited 64
+// cycles and that wave -- a third of the pipe's time for a third of the work plus its serial sections -- was the critical path
+// (measured: its node time = time alone + 155 x 64 cycles; Gram waves idle 30 %).
+// Operand of a k step (4 tile rows) for the 16 columns 32 b + 16 h: lane l holds Y[k0 + (l >> 4)][32 b + 16 h + (l & 15)] -- as
+// A operand (row l & 15, k = l >> 4) and as B operand (k = l >> 4, column l & 15) alike.
+template <int W>
+__device__ __forceinline__ void gram16_load(const float* __restrict__ p, float (&x)[8][2]) {
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    x[b][0] = tiles256_uses<W>(b) ? p[b * 32] : 0.f;
+    x[b][1] = tiles256_uses<W>(b) ? p[b * 32 + 16] : 0.f;
+  }
+}
+template <int W>
+__device__ __forceinline__ void gram16_mfma(const float (&x)[8][2], f32x4 (&acc)[9][2][2]) {
+#pragma unroll
+  for (int s = 0; s < 9; ++s)
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+      for (int hj = 0; hj < 2; ++hj) {
+        if (Tiles256<W>::si[s] == Tiles256<W>::sj[s] && hi > hj) continue;  // (below the diagonal)
+        acc[s][hi][hj] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[Tiles256<W>::si[s]][hi], x[Tiles256<W>::sj[s]][hj],
+                                                              acc[s][hi][hj], 0, 0, 0);
+      }
+}
+template <int W, bool LIST>
+__device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
+                                          FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
+  const int lane = threadIdx.x & 63;
+  f32x4 acc[9][2][2];
+#pragma unroll
+  for (int s = 0; s < 9; ++s)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[s][q >> 1][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nk = (a.R + 3) >> 2;  // tile rows four at a time (rows past R are zero)
+  NodeRanges<LIST> nr;
+  nr.init(pptr, list, a.n0, a.N, nn, cnt);
+  int32_t p0, p1;
+  nr.get(0, p0, p1);
+  for (int64_t i = 0; i < cnt; ++i) {
+    int32_t q0, q1;
+    nr.get(i + 1, q0, q1);
+    // node i's tile: every product wave must have published i + 1 nodes
+    while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
+    if (p1 > p0) {
+      const float* __restrict__ base = &sh.y[i & 1][0][0] + (lane >> 4) * kYStride + (lane & 15);
+      float xa[8][2], xb[8][2];
+      gram16_load<W>(base, xa);
+      for (int kk = 0; kk < nk; kk += 2) {
+        if (kk + 1 < nk) gram16_load<W>(base + (kk + 1) * 4 * kYStride, xb);
+        __builtin_amdgcn_sched_barrier(0);
+        gram16_mfma<W>(xa, acc);
+        __builtin_amdgcn_sched_barrier(0);
+        if (kk + 1 < nk) {
+          if (kk + 2 < nk) gram16_load<W>(base + (kk + 2) * 4 * kYStride, xa);
+          __builtin_amdgcn_sched_barrier(0);
+          gram16_mfma<W>(xb, acc);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
+    p0 = q0; p1 = q1;
+  }
+  // accumulator layout of 16x16x4: column l & 15, rows 4 (l >> 4) + r
+  const int64_t D = a.H;
+  const int li = lane & 15, lq = lane >> 4;
+#pragma unroll
+  for (int s = 0; s < 9; ++s)
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+      for (int hj = 0; hj < 2; ++hj) {
+        if (Tiles256<W>::si[s] == Tiles256<W>::sj[s] && hi > hj) continue;
+        const int64_t jj = Tiles256<W>::sj[s] * 32 + 16 * hj + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t ii = Tiles256<W>::si[s] * 32 + 16 * hi + 4 * lq + r;
+          if (ii < D && jj < D) atomicAdd(&scratch[ii * D + jj], acc[s][hi][hj][r]);
+        }
+      }
+}
+
+// The same Gram on v_mfma_f32_32x32x16_bf16 (the default; LGNN_GRAM_F32=1 runs gram_role above).  Every fp32 tile value y is
+// split into three bf16 pieces, each rounded to nearest:  y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y - y0 - y1) = y - y0 - y1
+// (both differences are exact; each piece carries 8 of the 24 significand bits).  A product y z keeps six of the nine piece
+// products, y0 z0 + y0 z1 + y1 z0 + y0 z2 + y1 z1 + y2 z0: the three dropped ones are at most 2^-23 |y z| together and of either
+// sign (fp32 rounding level).  The product waves form the pieces (split_pair) and store them in the layout of FusedShared: this
+// role only reads them.  The K slots of an MFMA are (piece, class): lane half h holds the classes 8 ck + 4 h + 0 .. 3 of chunk
+// ck, two classes of one piece per register, six registers per column block (y2a y2b y0a y0b y1a y1b; a = classes 0 1, b =
+// classes 2 3), in two operand forms that overlap:  T = (y2a y2b y0a y0b),  U = (y0a y0b y1a y1b).  Per chunk and sub-tile
+// (si, sj) three MFMAs:
+//     U[si] x U[sj] = y0 z0 + y1 z1,   T[si] x U[sj] = y2 z0 + y0 z1,   U[si] x T[sj] = y0 z2 + y1 z0
+// (A and B of one lane share the slot map, see the operand layout: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and
+// B[k = 8 (l >> 5) + j][col l & 31]).  hipcc keeps T and U in registers of their own: two moves per column block and chunk.
+// Rounding can take only a value above 3.39e38 to infinity (its square overflows in fp32 anyway); a NaN or an infinity turns
+// into NaN pieces (inf - inf): a non-finite input gives a non-finite factor, as the fp32 role does.
+// 27 MFMAs of 32 cycles per chunk of 8 tile rows against gram_role's 68 of 16x16x4 fp32 (32 cycles each): 0.4x the matrix cycles.
+struct PieceBlk { u32x2v y2, y0, y1; };  // a column block's pieces of the lane's 4 classes of a chunk: (rows 0 1 | rows 2 3)
+
+// the lane's pieces of its column in every column block the wave uses (`p`: the chunk's group of the lane half + piece_col)
+template <int W>
+__device__ __forceinline__ void piece_load(const uint32_t* __restrict__ p, PieceBlk (&x)[8]) {
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+    if (tiles256_uses<W>(b)) {
+      x[b].y2 = *reinterpret_cast<const u32x2v*>(p + b * 64);
+      x[b].y0 = *reinterpret_cast<const u32x2v*>(p + kPlaneDwords + b * 64);
+      x[b].y1 = *reinterpret_cast<const u32x2v*>(p + 2 * kPlaneDwords + b * 64);
+    }
+}
+__device__ __forceinline__ f32x16 mfma_bf16(u32x4v a, u32x4v b, f32x16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+template <int W>
+__device__ __forceinline__ void piece_mfma(const PieceBlk (&x)[8], f32x16 (&acc)[9]) {
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const PieceBlk &A = x[Tiles256<W>::si[s]], &B = x[Tiles256<W>::sj[s]];
+    const u32x4v ua = {A.y0[0], A.y0[1], A.y1[0], A.y1[1]}, ta = {A.y2[0], A.y2[1], A.y0[0], A.y0[1]};
+    const u32x4v ub = {B.y0[0], B.y0[1], B.y1[0], B.y1[1]}, tb = {B.y2[0], B.y2[1], B.y0[0], B.y0[1]};
+    acc[s] = mfma_bf16(ua, ub, acc[s]);
+    acc[s] = mfma_bf16(ta, ub, acc[s]);
+    acc[s] = mfma_bf16(ua, tb, acc[s]);
+  }
+}
+template <int W, bool LIST>
+__device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
+                                                FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
+  const int lane = threadIdx.x & 63;
+  f32x16 acc[9];
+#pragma unroll
+  for (int s = 0; s < 9; ++s)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+  const int nch = (a.R + 7) >> 3;  // chunks of 8 tile rows (rows past R are zero; 8 nch <= kYRows)
+  NodeRanges<LIST> nr;
+  nr.init(pptr, list, a.n0, a.N, nn, cnt);
+  int32_t p0, p1;
+  nr.get(0, p0, p1);
+  for (int64_t i = 0; i < cnt; ++i) {
+    int32_t q0, q1;
+    nr.get(i + 1, q0, q1);
+    while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
+    if (p1 > p0) {
+      // chunk ck, lane half h: group 2 ck + h
+      const uint32_t* __restrict__ base = &sh.pc[i & 1][lane >> 5][0][0] + piece_col(lane & 31);
+      PieceBlk xa[8], xb[8];
+      piece_load<W>(base, xa);
+      for (int ck = 0; ck < nch; ck += 2) {  // (wave-uniform trip count; the next chunk's pieces are read while this one's MFMAs run)
+        if (ck + 1 < nch) piece_load<W>(base + (ck + 1) * 2 * kGroupDwords, xb);
+        __builtin_amdgcn_sched_barrier(0);
+        piece_mfma<W>(xa, acc);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ck + 1 < nch) {
+          if (ck + 2 < nch) piece_load<W>(base + (ck + 2) * 2 * kGroupDwords, xa);
+          __builtin_amdgcn_sched_barrier(0);
+          piece_mfma<W>(xb, acc);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
+    p0 = q0; p1 = q1;
+  }
+  // accumulator layout of 32x32x16 (gram256.h's): column l & 31, rows (r & 3) + 8 (r >> 2) + 4 (l >> 5).  The part below the
+  // diagonal of a diagonal sub-tile is left out, as gram_role leaves it out (the symmetrising pass rewrites it)
+  const int64_t D = a.H;
+  const int l31 = lane & 31, lhi = lane >> 5;
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    const int64_t j = Tiles256<W>::sj[s] * 32 + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t ii = Tiles256<W>::si[s] * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+      if (ii < D && j < D && (Tiles256<W>::si[s] != Tiles256<W>::sj[s] || ii <= j)) atomicAdd(&scratch[ii * D + j], acc[s][r]);
+    }
+  }
+}
+
+// LIST: the node loop runs over a device-side list of the nodes that have a path
+template <bool LIST>
+__global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int32_t* __restrict__ pptr,
+                                                             const int32_t* __restrict__ list, float* __restrict__ scratch) {
+  __shared__ FusedShared sh;  // ONE LDS object
+  if (int64_t(pptr[a.N]) > a.cap) return;  // the path list overflowed its buffer: the enumerating route takes over
+  // the tiles are zero where nobody writes: columns >= H, the odd row out (zero bits are zero pieces)
+  for (int q = threadIdx.x; q < int(sizeof(sh.pc) / 16); q += 512) reinterpret_cast<u32x4v*>(&sh.pc[0][0][0][0])[q] = u32x4v{0u, 0u, 0u, 0u};
+  if (threadIdx.x < 4) {
+    sh.ready[threadIdx.x] = 64 * int(threadIdx.x) < a.H ? 0 : INT32_MAX;  // (H <= 192: the last product wave has no columns)
+    sh.done[threadIdx.x] = 0;
+  }
+  __syncthreads();
+  const int hw = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t stride = gridDim.x;
+  const int64_t nn = LIST ? int64_t(__builtin_amdgcn_readfirstlane(*a.n_list)) : a.n1 - a.n0;
+  const int64_t cnt = nn > int64_t(blockIdx.x) ? (nn - blockIdx.x + stride - 1) / stride : 0;
+  // (hardware waves g and g + 4 share a SIMD: one product wave and one Gram wave on each, see the kernel's header)
+  switch (hw) {
+    // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
+    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    default:
+      if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
+        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, nn, cnt, hw);
+        else product_role<LIST, false, true>(a, pptr, list, sh, nn, cnt, hw);
+      } else {
+        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, nn, cnt, hw);
+        else product_role<LIST, false, false>(a, pptr, list, sh, nn, cnt, hw);
+      }
+      break;
+  }
+}
+
+// persistent workgroups of paths_fused_kernel: one per CU (144 KB of LDS each).  Leaving CUs to the side stream's eigensolver
+// did not help (252 / 248 / 240 workgroups: 50.6 / 51.5 / 52.4 ms per GraphSAGE fit)
+constexpr int64_t kFusedWorkgroups = 256;
+
+}  // namespace
+
+int launch_paths_fused(lgnn_ctx* h, YArgs y, int64_t cb, int64_t ce, float* scratch, hipStream_t s) {
+  LGNN_REQUIRE(y.N < (int64_t(1) << 31), "too many nodes for one launch");
+  const dim3 grid{unsigned(std::min<int64_t>(y.n1 - y.n0, kFusedWorkgroups))};
+  const char* e = getenv("LGNN_GRAM_F32");  // =1: the Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
+  y.Y = nullptr; y.gram_f32 = e && atoi(e) != 0 ? 1 : 0;
+  for (int64_t c0 = cb; c0 < ce; c0 += kYRows) {
+    y.c0 = int(c0); y.R = int(std::min<int64_t>(kYRows, ce - c0));
+    if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the KFAC path (bench.py roofline)
+    if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    else hipLaunchKernelGGL(paths_fused_kernel<false>, grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    LGNN_HIP_CHECK(hipGetLastError());
+    if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += y.R; }
+  }
+  return 0;
+}
+
+}  // namespace lgnn

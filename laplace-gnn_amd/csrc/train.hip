@@ -26,12 +26,6 @@ namespace lgnn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---- forward epilogue ------------------------------------------------------------------------------------------------
 struct TrainEpArgs {
   float* S; int64_t ld;        // [N, W] in place: pre-norm sum in, layer output out

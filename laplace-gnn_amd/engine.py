@@ -196,7 +196,7 @@ class GraphEngine:
 
     @property
     def last_kfac_used_paths(self) -> bool:
-        """Whether the last KFAC accumulate took the two-hop path route (csrc/paths.hip) rather than class planes."""
+        """Whether the last KFAC accumulate took the two-hop path route (csrc/paths.hip, paths_fused.hip) rather than class planes."""
         return bool(self.lib.lgnn_kfac_last_route(self._h))
 
     @property
@@ -513,7 +513,7 @@ class GraphEngine:
         # what the library may keep for this batch across fits (lgnn_kfac_batch_tag; consumed by the accumulate call below)
         tag = self._batch_tags.tag(idx, copied=idx is not given)
         yp = self._labels(y, idx.shape[0])
-        # 2-layer GCN: two-hop path route (csrc/paths.hip).  paths=None: the library decides (shape and the batch's expected
+        # 2-layer GCN: two-hop path route (csrc/paths.hip, paths_fused.hip).  paths=None: the library decides (shape and the batch's expected
         # paths per node; LGNN_NO_PATHS=1 keeps the planes); True / False force one route where the shape allows
         no_paths = _no_paths_default() if paths is None else not paths
         flags = (_lib.FLAG_FORK_EXACT_SEED if fork_exact else 0) | (0 if fuse else _lib.FLAG_NO_FUSE) | \

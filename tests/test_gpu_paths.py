@@ -1,4 +1,4 @@
-"""The two-hop path route of the 2-layer GCN KFAC (csrc/paths.hip): B_0 without class planes, from the
+"""The two-hop path route of the 2-layer GCN KFAC (csrc/paths.hip, paths_fused.hip, paths_overflow.hip): B_0 without class planes, from the
 diagonal + rank-2 structure of the seed blocks, against the CPU oracle (pinned to the reference, incl. the identity itself:
 tests/test_oracle_golden.py::test_first_layer_B_from_two_hop_paths_...) and against the class-plane route of the same
 library.  fp32 <= 1e-4 relative Frobenius error per block (BASELINE.json north_star)."""

@@ -1,4 +1,4 @@
-"""The product wave's pair loop of paths_fused_kernel (csrc/paths.hip): a node's first step starts the
+"""The product wave's pair loop of paths_fused_kernel (csrc/paths_fused.hip): a node's first step starts the
 accumulators (C = 0, nothing clears them between nodes), a chunk's last pair leaves out an empty second step, the node
 ranges come from a register window refilled every 32 nodes, the hand-off counters are LDS stores.  Random graphs hit the step
 (4 paths), pair (8) and chunk (64) boundaries only by chance, so the graphs here are built to hit them: "spokes" -- a

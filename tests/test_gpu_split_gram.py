@@ -1,4 +1,4 @@
-"""The Gram role of paths_fused_kernel on bf16 MFMAs over a three-piece split of every fp32 tile value (csrc/paths.hip,
+"""The Gram role of paths_fused_kernel on bf16 MFMAs over a three-piece split of every fp32 tile value (csrc/paths_fused.hip,
 gram_split_role) against the fp32 role (LGNN_GRAM_F32=1, read per call), fp64 restatements and the CPU oracle: the headline
 shape, a sweep over classes per launch (R), widths, model families and both kernel instances (node list or not), inputs that
 span many binades, and non-finite inputs."""

@@ -1,4 +1,4 @@
-"""The node tile of paths_fused_kernel as bf16 pieces, split once by the product wave that forms a value (csrc/paths.hip,
+"""The node tile of paths_fused_kernel as bf16 pieces, split once by the product wave that forms a value (csrc/paths_fused.hip,
 DESIGN 12.11), against the fp32 Gram role (LGNN_GRAM_F32=1, read per call) on the shapes the piece layout can break: classes
 per launch R = 1, 7, 8, 9, 40, 41, 48 (a chunk of 8 tile rows partly filled, the row pair of a dword half filled, every row), a
 second launch for the classes past 48, widths 132 / 192 (the last product wave has no columns) / 256, GCN and GraphSAGE, a
