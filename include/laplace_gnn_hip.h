@@ -372,7 +372,13 @@ LGNN_API int lgnn_jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J
  * Texas / Wisconsin / Circle, gnn/configs/original/stegcn_config.yaml:54-105, 129-145): GCN only.  gamma_B then has one more
  * entry per hidden layer after the conv entries (the res.{l} blocks, named_parameters order; res=True only); the chain gains
  * the norm's row-local backward, the res block's B and the adjoint of the pre-norm rows through the LayerNorm statistics.
- * All N rows, unfused kernels: these configurations are graphs of a few hundred to a few thousand nodes.               */
+ * All N rows, unfused kernels: these configurations are graphs of a few hundred to a few thousand nodes.
+ * One-layer GCN models (the Banana block of gnn/configs/original/stegcn_config.yaml:108-127 and gcn_config.yaml: num_layers 1;
+ * out = P (X W^T + 1 b^T), gnn/models/base_gnn.py:136-161 with a single conv): gamma_B / gamma_A are host arrays of ONE
+ * pointer.  A_0 = X^T X a_scale does not depend on the adjacency (the Linear sees all N rows of X), so gamma_A is not read;
+ * B_0 is the top layer of the chain above: gbar = 2 g Gamma_B, the seed SDDMM on the batch rows' entries, the seed adjoint
+ * into out_bar; the finish adds <out_bar[a], Z[b]>, Z = X W^T + 1 b^T.  Any activation (there is none to apply).  One-layer
+ * GraphSAGE, deeper models and the dense variants below for one layer are refused.                                        */
 LGNN_API int lgnn_kfac_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags,
                             const float* const* gamma_B /* host array of L device ptrs */, float loss_scale,
                             float* grad_P, float* out_bar, const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand,
@@ -401,7 +407,14 @@ LGNN_API int lgnn_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float*
  * (Jacobian rows and directions) + C N (3 H + C) floats of planes -- sized for graphs of a few hundred to a few thousand nodes.
  * Plain 2-layer GraphSAGE models (STEGraphSAGE + DiagLaplace; the driver offers the pair, gnn/utils.py:55-59, 81): the same identity,
  * evaluated locally -- everything of a (sample, class) pair lives on the rows {n} + N(n), one workgroup per pair, no planes; e_bar
- * [N, F + 1] carries the adjoint of P X in its first F columns, h1_bar the direct adjoint of H_1; workspace 2 C P floats per sample. */
+ * [N, F + 1] carries the adjoint of P X in its first F columns, h1_bar the direct adjoint of H_1; workspace 2 C P floats per sample.
+ * One-layer GCN models (stegcn_config.yaml:108-127, Banana: diag, num_layers 1): gamma [C F + C] in the order W [C, F] row
+ * major, b [C]; h1_bar is ignored and may be NULL (both calls).  With psi_n = [P X | rowsum(P)][n] the diagonal GGN is
+ * H_{(c, j)} = sum_n p_c (1 - p_c) psi_n[j]^2 (laplace/curvature/curvature.py:412-432 on J_n[c, (c', j)] = delta_cc' psi_n[j]),
+ * so a batch only adds to out_bar and e_bar, one wave per sample: kappa_c = sum_j Gamma_c[j] psi_j^2, pbar_c = (1 - 2 p_c)
+ * kappa_c, out_bar[n] += p * (pbar - <p, pbar>) + loss_scale (p - onehot(y)), e_bar[n] += 2 psi * sum_c p_c (1 - p_c) Gamma_c;
+ * grad_P and the candidates take <out_bar[a], Z[b]> + <e_bar[a, :F], X[b]> + e_bar[a, F] in the finish.  No workspace beyond
+ * the batch prologue's.                                                                                                    */
 LGNN_API int lgnn_diag_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma,
                             float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar,
                             const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand, float* grad_cand, void* stream);
@@ -424,7 +437,11 @@ LGNN_API int lgnn_diag_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const f
  * plain 2-layer GraphSAGE (the local chain; 2 C P floats per sample); ReLU, classification, C <= 127.  Gamma is read as
  * stored; parameter order W_0, b_0, W_1, b_1[, Wr_0, br_0].
  * lgnn_full_directions is the product alone: K_out [M, C, C] and R_out [M, C, P] of the samples idx (Lambda_n from the softmax
- * of the model's logits), e.g. K_n = J_n Sigma J_n^T for Gamma = Sigma; same chunks, only the Jacobian rows in the workspace. */
+ * of the model's logits), e.g. K_n = J_n Sigma J_n^T for Gamma = Sigma; same chunks, only the Jacobian rows in the workspace.
+ * One-layer GCN models: Gamma in the order W [C, F] row major, b [C]; h1_bar is ignored and may be NULL.  K_n and R_n come from
+ * the closed-form Jacobian rows and the same product kernel (2 C P floats per sample of a chunk); no tangent pass, no planes:
+ * d J_n[c, :] = delta_cc' d psi_n, hence e_bar[n, j] += sum_c R_n[c, pos(c, j)], pos(c, j) = c F + j / C F + c for j = F.
+ * Both entry points take one-layer GCN models.                                                                             */
 LGNN_API int lgnn_full_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* Gamma,
                             float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar,
                             const int32_t* cand_a, const int32_t* cand_b, int64_t num_cand, float* grad_cand, void* stream);
@@ -468,7 +485,7 @@ LGNN_API int lgnn_lora_grad(lgnn_ctx* h, const float* grad_adj_dense, const floa
 
 /* ---- matrix-free GLM predictive ("next" row 8(f)-3 at scale) -------------------------------------------------------
  * Replaces the Jacobian route of the default la(x) (laplace/baselaplace.py:1123-1158 + laplace/utils/matrix.py:396-451 resp.
- * baselaplace.py:1901-1903) for 2-layer GCN and GraphSAGE models: f_mu [M, C] = logits and f_var_diag [M, C] = diag(J P^-1 J^T) per
+ * baselaplace.py:1901-1903) for 1- and 2-layer GCN and GraphSAGE models: f_mu [M, C] = logits and f_var_diag [M, C] = diag(J P^-1 J^T) per
  * evaluation node from the closed-form Jacobian, nothing of size M * C * P is formed.  The probit link (the default,
  * baselaplace.py:610-616) needs exactly this diagonal.
  *   Kronecker posterior: QA0 [F, F], QB0 [H, H], QA1 [H, H] = eigenvectors (columns) of A_0, B_0, A_1;
@@ -477,7 +494,12 @@ LGNN_API int lgnn_lora_grad(lgnn_ctx* h, const float* grad_adj_dense, const floa
  *   diagonal posterior: QA0 = QB0 = QA1 = QB1sq = NULL; S0 [H, F + 1] = 1 / precision of (W_0 | b_0), S1 [C, H] of W_1,
  *     kappa [C] of b_1.
  *   GraphSAGE: F and the H of QA1 / S1's second dimension read as the widths of what the two Linear layers multiply
- *     (2 F and 2 H: cat = [h | P h], gnn/models/layers.py:26-29).                                                */
+ *     (2 F and 2 H: cat = [h | P h], gnn/models/layers.py:26-29).
+ *   One-layer models (GCN and GraphSAGE; gnn/configs/original/gcn_config.yaml, Banana: num_layers 1): QA0 = QB0 = S0 = NULL and
+ *     QA1 [F', F'], S1 [C, F'], QB1sq, kappa describe the ONLY layer, F' = the width its Linear multiplies (F, GraphSAGE 2 F).
+ *     J_n[c, (c', j)] = delta_cc' xt_n[j] with xt_n = (P X)[n], bias entry rho_n = rowsum(P)[n] (GraphSAGE: xt_n = [x_n | (P X)_n],
+ *     rho_n = 1):  Kronecker  var_n[c] = sum_a Q_B[c, a]^2 sum_i S1[a, i] (Q_A^T xt_n)_i^2 + kappa[c] rho_n^2,
+ *     diagonal  var_n[c] = sum_i S1[c, i] xt_n[i]^2 + kappa[c] rho_n^2.  The mapped variant reads W1m's rows as Cm only.  */
 LGNN_API int lgnn_glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* QA0, const float* QB0, const float* S0,
                       const float* QA1, const float* S1, const float* QB1sq, const float* kappa, float* f_mu,
                       float* f_var_diag, void* stream);

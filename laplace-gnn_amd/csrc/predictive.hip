@@ -1,5 +1,5 @@
-// Matrix-free GLM predictive variance for 2-layer GCN and GraphSAGE models: diag(J P^-1 J^T) per evaluation node without ever
-// materialising the Jacobians.
+// Matrix-free GLM predictive variance for 1- and 2-layer GCN and GraphSAGE models: diag(J P^-1 J^T) per evaluation node
+// without ever materialising the Jacobians (one-layer models: glm_var_onelayer_kernel below).
 //
 // Reference: la(x) -> _glm_predictive_distribution (laplace/baselaplace.py:1123-1158): Js [M, C, P] from
 // torch.func.jacrev of the dense model (laplace/curvature/curvature.py:89-130), f_var = Js P^-1 Js^T through
@@ -292,6 +292,46 @@ __global__ __launch_bounds__(512) void glm_var_kernel(const int64_t* __restrict_
   }
 }
 
+// One-layer models (out = P (X W^T + b) resp. [x | P x] W^T + b): J_n[c, (c', j)] = delta_cc' xt_n[j], bias entry rho_n, with
+// xt_n = (P X)[n], rho_n = rowsum(P)[n] (GCN) or xt_n = cat_0[n], rho_n = 1 (GraphSAGE).  No tile, no neighbours:
+//   KRON: var_c = sum_a QBsq[c, a] t_a + kappa_c rho^2,  t_a = sum_i S1[a, i] (Q_A^T xt)_i^2   (Pt holds the rotated rows)
+//   diag: var_c = sum_i S1[c, i] xt_i^2 + kappa_c rho^2
+// C counts the output rows (a linear map's rows under lgnn_glm_variance_mapped), Ce the model's classes.  One workgroup per
+// evaluation node, one wave per row of S1.
+template <int KRON>
+__global__ __launch_bounds__(256) void glm_var_onelayer_kernel(const int64_t* __restrict__ idx, int64_t M, int64_t N,
+                                                               const float* __restrict__ Pt, int64_t D, int64_t C, int64_t Ce,
+                                                               const float* __restrict__ S1, const float* __restrict__ QBsq,
+                                                               const float* __restrict__ kappa,
+                                                               const float* __restrict__ rowsum, float* __restrict__ var_out) {
+  extern __shared__ float sm[];  // t [KRON ? Ce : C]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t m = blockIdx.x;
+  const int64_t a = idx[m];
+  if (a < 0 || a >= N) {  // flagged by the row gather
+    for (int64_t c = tid; c < C; c += 256) var_out[m * C + c] = 0.f;
+    return;
+  }
+  const float* __restrict__ ph = Pt + m * D;
+  const int64_t rows = KRON ? Ce : C;
+  for (int64_t r = wave; r < rows; r += 4) {
+    float t = 0.f;
+    for (int64_t i = lane; i < D; i += 64) t = fmaf(ph[i] * ph[i], S1[r * D + i], t);
+    t = wave_sum_p(t);
+    if (lane == 0) sm[r] = t;
+  }
+  __syncthreads();
+  const float rho = rowsum ? rowsum[a] : 1.f;
+  for (int64_t c = tid; c < C; c += 256) {
+    float v = 0.f;
+    if (KRON)
+      for (int64_t k = 0; k < Ce; ++k) v = fmaf(QBsq[c * Ce + k], sm[k], v);
+    else
+      v = sm[c];
+    var_out[m * C + c] = v + rho * rho * kappa[c];
+  }
+}
+
 int sgemm_rm_p(hipStream_t s, int64_t R, int64_t Nout, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                float* Cm, int64_t ldc) {
   rocblas_handle blas = static_cast<rocblas_handle>(blas_handle(s));
@@ -307,6 +347,42 @@ int sgemm_rm_p(hipStream_t s, int64_t R, int64_t Nout, int64_t K, const float* A
 
 }  // namespace
 
+// One-layer GCN / GraphSAGE: the only layer's operands arrive in the last layer's places (QA1 [F', F'], S1 [C, F'], QB1sq,
+// kappa; F' = in_dim[0]), the first layer's (QA0, QB0, S0) are null.  Cm > 0: the rows of a linear map of the logits.
+int glm_variance_onelayer(lgnn_ctx* h, const int64_t* idx, int64_t M, int64_t Cm, const float* QA1, const float* S1,
+                          const float* QB1sq, const float* kappa, float* f_mu, float* f_var, hipStream_t s) {
+  LGNN_REQUIRE(M > 0 && idx && S1 && kappa && f_var, "empty batch or null pointers");
+  LGNN_REQUIRE(h->lik == LGNN_LIK_CLASSIFICATION, "matrix-free GLM predictive: classification");
+  const bool kron = QA1 != nullptr;
+  const bool sage = h->kind == LGNN_KIND_SAGE;
+  LGNN_REQUIRE(!kron || QB1sq, "kron posterior needs all eigenvector matrices");
+  LGNN_REQUIRE(Cm >= 0 && Cm <= 4096, "mapped GLM predictive: 1 <= rows of the map <= 4096");
+  LGNN_CALL(forward_ensure_aux(h, s));
+  const int64_t N = h->N, D = h->in_dim[0], Ce = h->dims[1], C = Cm > 0 ? Cm : Ce;
+  int* bad = h->ws.flags.as<int>();
+  if (f_mu) LGNN_CALL(launch_gather_rows(h->fc.out.as<float>(), Ce, N, idx, M, Ce, f_mu, bad + 2, s));
+  const float* xt = sage ? h->fc.lin_in_p[0] : h->fc.prop_in[0].as<float>();
+  const int64_t ldx = sage ? h->fc.lin_in_ld[0] : h->fc.prop_ld[0];
+  LGNN_CALL(h->ws.planes_a.reserve(size_t(M) * D * 4 * 2));
+  h->ws.planes_a_zero_ptr = nullptr;
+  float* PhiB = h->ws.planes_a.as<float>();  // [M, D] the evaluation nodes' rows
+  float* PhiT = PhiB + M * D;                // [M, D] rotated
+  LGNN_CALL(launch_gather_rows(xt, ldx, N, idx, M, D, PhiB, bad + 2, s));
+  const float* Pt = PhiB;
+  if (kron) { LGNN_CALL(sgemm_rm_p(s, M, D, D, PhiB, D, QA1, D, PhiT, D)); Pt = PhiT; }
+  const float* rowsum = sage ? nullptr : h->fc.rowsum.as<float>();
+  const size_t smem = size_t(std::max(C, Ce)) * 4;
+  LGNN_REQUIRE(smem <= 48 * 1024, "matrix-free GLM predictive: too many output rows");
+  if (kron)
+    hipLaunchKernelGGL(glm_var_onelayer_kernel<1>, dim3(unsigned(M)), dim3(256), smem, s, idx, M, N, Pt, D, C, Ce, S1, QB1sq, kappa,
+                       rowsum, f_var);
+  else
+    hipLaunchKernelGGL(glm_var_onelayer_kernel<0>, dim3(unsigned(M)), dim3(256), smem, s, idx, M, N, Pt, D, C, Ce, S1, QB1sq, kappa,
+                       rowsum, f_var);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // kron: QA0 [F, F], QB0 [H, H], QA1 [H, H] rotate; diag posterior: the three are null.  S0 [H, F + 1], S1 [C, H],
 // QB1sq [C, C] (kron only), kappa [C].
 // W1m [Cm, in_dim_1] (row major, or null): the head E W_1 of a linear map E [Cm, C] of the logits; f_var is then [M, Cm] =
@@ -314,7 +390,11 @@ int sgemm_rm_p(hipStream_t s, int64_t R, int64_t Nout, int64_t K, const float* A
 int glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, int64_t Cm, const float* QA0, const float* QB0,
                  const float* S0, const float* QA1, const float* S1, const float* QB1sq, const float* kappa, float* f_mu,
                  float* f_var, hipStream_t s) {
-  LGNN_REQUIRE(h->L == 2, "matrix-free GLM predictive: 2-layer models");
+  if (h->L == 1) {  // (W1m: the head of the map only feeds the first layer's terms; a one-layer model has none)
+    LGNN_REQUIRE(!QA0 && !QB0 && !S0, "matrix-free GLM predictive, 1-layer models: the first-layer operands are null");
+    return glm_variance_onelayer(h, idx, M, W1m ? Cm : 0, QA1, S1, QB1sq, kappa, f_mu, f_var, s);
+  }
+  LGNN_REQUIRE(h->L == 2, "matrix-free GLM predictive: 1- and 2-layer models");
   LGNN_REQUIRE(!h->extras(), "matrix-free GLM predictive: models without res / norm (use the Jacobian route)");
   LGNN_REQUIRE(M > 0 && idx && S0 && S1 && kappa && f_var, "empty batch or null pointers");
   const bool kron = QA0 != nullptr;

@@ -659,6 +659,11 @@ class GraphEngine:
         return _dev_ptr(a, torch.int32, "cand_a"), _dev_ptr(b, torch.int32, "cand_b"), int(a.shape[0]), \
             _dev_ptr(acc, torch.float32, "grad_cand")
 
+    @staticmethod
+    def _opt_ptr(t, what: str):
+        """A buffer a 1-layer model does not have (``h1_bar``): None -> NULL."""
+        return None if t is None else _dev_ptr(t, torch.float32, what)
+
     def adjgrad_batch(self, idx, y, gammas_B, grad_P: torch.Tensor, out_bar: torch.Tensor, fork_exact: bool = True,
                       loss_scale: float = 1.0, cand=None):
         """Add one batch's terms to ``grad_P`` [nnz] (stored entries of the propagation matrix), ``out_bar`` [N, C] and,
@@ -692,8 +697,9 @@ class GraphEngine:
 
     def diag_adjgrad_batch(self, idx, y, gamma: torch.Tensor, grad_P: torch.Tensor, out_bar: torch.Tensor, h1_bar: torch.Tensor,
                            e_bar: torch.Tensor, loss_scale: float = 1.0, cand=None):
-        """Diagonal posterior (2-layer GCN): add one batch's terms to ``grad_P`` [nnz], ``out_bar`` [N, C], ``h1_bar`` [N, H],
-        ``e_bar`` [N, F + 1] and the candidates' accumulator; ``gamma`` [n_params] = d(-marglik)/dH (lgnn_diag_adjgrad_batch)."""
+        """Diagonal posterior (1- and 2-layer GCN): add one batch's terms to ``grad_P`` [nnz], ``out_bar`` [N, C], ``h1_bar`` [N, H]
+        (None for a 1-layer model), ``e_bar`` [N, F + 1] and the candidates' accumulator; ``gamma`` [n_params] = d(-marglik)/dH
+        (lgnn_diag_adjgrad_batch)."""
         self._sync_versions()
         idx, y = idx.contiguous(), y.contiguous()
         self._keep = gamma.contiguous()
@@ -701,7 +707,7 @@ class GraphEngine:
         rc = self.lib.lgnn_diag_adjgrad_batch(
             self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
             _dev_ptr(self._keep, torch.float32, "gamma"), float(loss_scale), _dev_ptr(grad_P, torch.float32, "grad_P"),
-            _dev_ptr(out_bar, torch.float32, "out_bar"), _dev_ptr(h1_bar, torch.float32, "h1_bar"),
+            _dev_ptr(out_bar, torch.float32, "out_bar"), self._opt_ptr(h1_bar, "h1_bar"),
             _dev_ptr(e_bar, torch.float32, "e_bar"), ca, cb, K, cacc, _stream(self.device))
         _lib.check(rc, "lgnn_diag_adjgrad_batch")
 
@@ -713,7 +719,7 @@ class GraphEngine:
         ca, cb, K, cacc = self._cand_ptrs(cand)
         cout = torch.zeros(K, dtype=torch.float32, device=self.device) if K else None
         rc = self.lib.lgnn_diag_adjgrad_finish(self._h, _dev_ptr(out_bar, torch.float32, "out_bar"),
-                                               _dev_ptr(h1_bar, torch.float32, "h1_bar"), _dev_ptr(e_bar, torch.float32, "e_bar"),
+                                               self._opt_ptr(h1_bar, "h1_bar"), _dev_ptr(e_bar, torch.float32, "e_bar"),
                                                _dev_ptr(grad_P, torch.float32, "grad_P"), out.data_ptr(), ca, cb, K, cacc,
                                                None if cout is None else cout.data_ptr(), _stream(self.device))
         _lib.check(rc, "lgnn_diag_adjgrad_finish")
@@ -721,8 +727,8 @@ class GraphEngine:
 
     def full_adjgrad_batch(self, idx, y, Gamma: torch.Tensor, grad_P: torch.Tensor, out_bar: torch.Tensor, h1_bar: torch.Tensor,
                            e_bar: torch.Tensor, loss_scale: float = 1.0, cand=None):
-        """Full posterior (2-layer GCN, also with res / norm; plain 2-layer GraphSAGE): as ``diag_adjgrad_batch`` with the dense
-        symmetric ``Gamma`` [n_params, n_params] = d(-marglik)/dH as weighting (lgnn_full_adjgrad_batch); finished by
+        """Full posterior (1-layer GCN; 2-layer GCN, also with res / norm; plain 2-layer GraphSAGE): as ``diag_adjgrad_batch`` with
+        the dense symmetric ``Gamma`` [n_params, n_params] = d(-marglik)/dH as weighting (lgnn_full_adjgrad_batch); finished by
         ``diag_adjgrad_finish``."""
         self._sync_versions()
         idx, y = idx.contiguous(), y.contiguous()
@@ -732,7 +738,7 @@ class GraphEngine:
         rc = self.lib.lgnn_full_adjgrad_batch(
             self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
             _dev_ptr(Gamma, torch.float32, "Gamma"), float(loss_scale), _dev_ptr(grad_P, torch.float32, "grad_P"),
-            _dev_ptr(out_bar, torch.float32, "out_bar"), _dev_ptr(h1_bar, torch.float32, "h1_bar"),
+            _dev_ptr(out_bar, torch.float32, "out_bar"), self._opt_ptr(h1_bar, "h1_bar"),
             _dev_ptr(e_bar, torch.float32, "e_bar"), ca, cb, K, cacc, _stream(self.device))
         _lib.check(rc, "lgnn_full_adjgrad_batch")
 

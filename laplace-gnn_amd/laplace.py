@@ -156,6 +156,15 @@ def _adjacency_candidates(eng, candidates, sym: bool):
             torch.zeros(ci.shape[0], dtype=torch.float32, device=eng.device))
 
 
+def _adjgrad_scope(eng, what: str, depth: bool = False):
+    """1-layer models: GCN only (the reference's Banana configurations).  ``depth``: also refuse models deeper than two layers
+    here (the Kronecker and diagonal fronts leave that to the device entry points)."""
+    if len(eng.dims) == 2 and eng.kind != "gcn":
+        raise NotImplementedError(f"{what}: 1-layer GraphSAGE is not covered (1-layer GCN, 2-layer GCN / GraphSAGE)")
+    if depth and len(eng.dims) not in (2, 3):
+        raise NotImplementedError(f"{what}: 1- and 2-layer GCN / 2-layer GraphSAGE on the HIP backend")
+
+
 def _dense_scope(eng, what: str):
     """``dense=True`` of ``neg_marglik_adj_grad``: the all-pairs gradient (LoRASTEGCN) covers plain 2-layer GCN models on the
     HIP backend, and N x N floats must fit the workspace limit and int32 indexing."""
@@ -342,14 +351,17 @@ class ParametricLaplace(BaseLaplace):
 
     def _glm_variance_matrix_free(self, x, out_map=None):
         """(f_mu [M, C], diag f_var [M, C]) without Jacobians (csrc/predictive.hip), or None: 2-layer GCN / GraphSAGE models
-        with a ReLU, hidden width <= 256, classification, Kronecker or diagonal posterior over all weights.  ``out_map`` =
+        with a ReLU and hidden width <= 256, and 1-layer ones, classification, Kronecker or diagonal posterior over all weights.  ``out_map`` =
         E [Cm, C]: the variances of E f instead ([M, Cm]).  Models built with res / norm take the per-class table route
         (``GraphEngine.glm_variance_ext``), plain ones the entry they always had."""
         eng = getattr(self.backend, "engine", None)
         extras = bool(getattr(eng, "has_extras", False))
-        if (eng is None or not hasattr(eng, "glm_variance") or getattr(eng, "kind", None) not in ("gcn", "sage") or len(eng.dims) != 3
-                or (extras and not hasattr(eng, "glm_variance_ext"))
-                or eng.dims[1] > 256 or getattr(eng, "_bind_opts", ("relu",))[0] != "relu" or self.likelihood != "classification"):
+        if (eng is None or not hasattr(eng, "glm_variance") or getattr(eng, "kind", None) not in ("gcn", "sage")
+                or len(eng.dims) not in (2, 3) or (extras and not hasattr(eng, "glm_variance_ext"))
+                or self.likelihood != "classification"):
+            return None
+        # (a 1-layer model has no hidden layer: no width limit, any activation)
+        if len(eng.dims) == 3 and (eng.dims[1] > 256 or getattr(eng, "_bind_opts", ("relu",))[0] != "relu"):
             return None
         ops = self._matrix_free_operands(out_map)
         if ops is None:
@@ -357,7 +369,7 @@ class ParametricLaplace(BaseLaplace):
         if ("Sr" in ops) != bool(getattr(eng, "has_res", False)):  # the res.0 block comes with a res model, and only with one
             return None
         eng.set_likelihood("classification")
-        if extras:
+        if extras and len(eng.dims) == 3:
             return eng.glm_variance_ext(x, out_map=out_map, **ops)
         return eng.glm_variance(x, **ops) if out_map is None else eng.glm_variance(x, out_map=out_map, **ops)
 
@@ -884,7 +896,7 @@ class KronLaplace(ParametricLaplace):
         what ``neg_marglik.backward()`` leaves in ``model.adj.grad`` in the reference's structure-learning loop
         (gnn/marglik_training.py:197-216), here on the stored sparsity pattern: returns ``(neg_marglik, edge_index [2, nnz],
         grad [nnz])`` over the stored entries of the 0/1 adjacency (``model.engine.export_adj()`` order; a GCN's self loops
-        carry gradient 0 like the reference's overwritten diagonal).  2-layer GCN (STEGCN) and GraphSAGE (STEGraphSAGE).  ``train_loader`` must be the loader of the fit
+        carry gradient 0 like the reference's overwritten diagonal).  1- and 2-layer GCN (STEGCN) and 2-layer GraphSAGE (STEGraphSAGE).  ``train_loader`` must be the loader of the fit
         (same batch boundaries: the B factors depend on them).  Inside a ``torch.distributed`` job whole batches are
         dealt round-robin and the accumulators are all-reduced once.
 
@@ -906,6 +918,7 @@ class KronLaplace(ParametricLaplace):
             if candidates is not None:
                 raise ValueError("dense=True covers every pair: no candidates")
             _dense_scope(eng, "KronLaplace.neg_marglik_adj_grad")
+        _adjgrad_scope(eng, "adjacency gradient under the Kronecker posterior")
         value = -self._log_marginal_likelihood64()
         gB, gA = self._logdet_factor_gradients()
         gB = [0.5 * g for g in gB]  # neg marglik = H_factor * loss + 1/2 (logdet P - logdet P_0 + scatter)
@@ -977,8 +990,21 @@ class KronLaplace(ParametricLaplace):
     def _matrix_free_operands(self, out_map=None):
         H = self._refined_decomposition()
         nb = len(H.eigenvalues) if isinstance(H, KronDecomposed) else 0
-        if nb not in (4, 6) or H.damping:  # convs.0.{W,b}, convs.1.{W,b} and, models with res, res.0.{W,b}
+        if nb not in (2, 4, 6) or H.damping:  # convs.0.{W,b}, convs.1.{W,b} and, models with res, res.0.{W,b}
             return None
+        if nb == 2:  # a 1-layer model: its only layer's operands go where the last layer's go, the first layer's stay None
+            (lB, lA), (QB, QA) = H.eigenvalues[0], H.eigenvectors[0]
+            (lBb,), (QBb,) = H.eigenvalues[1], H.eigenvectors[1]
+            pp = torch.as_tensor(self.prior_precision, dtype=torch.float32, device=self._device).reshape(-1)
+            if pp.numel() not in (1, nb):
+                return None
+            d = pp.expand(nb) if pp.numel() == 1 else pp
+            f = self._H_factor
+            if out_map is not None:
+                E = out_map.to(QB)
+                QB, QBb = E @ QB, E @ QBb
+            return dict(S0=None, S1=1.0 / (f * torch.outer(lB, lA) + d[0]), kappa=(QBb * QBb) @ (1.0 / (f * lBb + d[1])), QA1=QA,
+                        QB1sq=QB * QB)
         (lB0, lA0), (QB0, QA0) = H.eigenvalues[0], H.eigenvectors[0]
         (lB0b,), (QB0b,) = H.eigenvalues[1], H.eigenvectors[1]
         (lB1, lA1), (QB1, QA1) = H.eigenvalues[2], H.eigenvectors[2]
@@ -1145,8 +1171,16 @@ class DiagLaplace(ParametricLaplace):
 
     def _matrix_free_operands(self, out_map=None):
         shapes = [tuple(p.shape) for p in self.params]
-        if len(shapes) not in (4, 6) or [len(sh) for sh in shapes] != [2, 1] * (len(shapes) // 2):
+        if len(shapes) not in (2, 4, 6) or [len(sh) for sh in shapes] != [2, 1] * (len(shapes) // 2):
             return None
+        if len(shapes) == 2:  # a 1-layer model: S1 [C, F'] and kappa [C] describe its only layer
+            C, D = shapes[0]
+            inv = 1.0 / self.posterior_precision
+            w, b = inv[:C * D].view(C, D), inv[C * D:C * D + C]
+            if out_map is not None:
+                E2 = out_map.to(w).square()
+                w, b = E2 @ w, E2 @ b
+            return dict(S0=None, S1=w, kappa=b)
         (Hd, F), _, (C, D1), _ = shapes[:4]  # (GraphSAGE: F and D1 are the widths of the concatenations)
         inv = 1.0 / self.posterior_precision
         o = 0
@@ -1171,7 +1205,7 @@ class DiagLaplace(ParametricLaplace):
         leaves in ``model.adj.grad`` when the structure-learning loop runs with ``hessian_structure="diag"``, the shipped
         STE-GCN configuration (gnn/configs/original/stegcn_config.yaml:7; gnn/marglik_training.py:197-216; the fork's
         Jacobians keep the graph, laplace/curvature/curvature.py:89-130).  Same return values and candidate pairs as
-        ``KronLaplace.neg_marglik_adj_grad``.  2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE (STEGraphSAGE),
+        ``KronLaplace.neg_marglik_adj_grad``.  1-layer GCN, 2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE (STEGraphSAGE),
         classification; the diagonal GGN is a sum over samples, so
         the loader's batch boundaries do not matter and the ranks of a job split every batch by samples.  ``dense=True``: as
         ``KronLaplace.neg_marglik_adj_grad`` (plain 2-layer GCN, ``(neg_marglik, grad [N, N])``)."""
@@ -1188,13 +1222,15 @@ class DiagLaplace(ParametricLaplace):
             if candidates is not None:
                 raise ValueError("dense=True covers every pair: no candidates")
             _dense_scope(eng, "DiagLaplace.neg_marglik_adj_grad")
+        _adjgrad_scope(eng, "adjacency gradient under a diagonal posterior")
         value = -self.log_marginal_likelihood()
         f = self._H_factor
         gamma = (0.5 * f / self.posterior_precision).to(torch.float32).contiguous()  # d(1/2 logdet P) / dH_p
-        N, Hd, F, C = eng.num_nodes, eng.dims[1], eng.dims[0], eng.dims[-1]
+        N, F, C = eng.num_nodes, eng.dims[0], eng.dims[-1]
         grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
         out_bar = torch.zeros(N, C, dtype=torch.float32, device=eng.device)
-        h1_bar = torch.zeros(N, Hd, dtype=torch.float32, device=eng.device)
+        # (a 1-layer model has no hidden layer: the device calls take a null h1_bar)
+        h1_bar = torch.zeros(N, eng.dims[1], dtype=torch.float32, device=eng.device) if len(eng.dims) != 2 else None
         e_bar = torch.zeros(N, F + 1, dtype=torch.float32, device=eng.device)
         rank, world = _dist_info(process_group)
         sym = bool(getattr(self.model, "symmetric", False))
@@ -1220,7 +1256,8 @@ class DiagLaplace(ParametricLaplace):
                 eng.diag_adjgrad_batch(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), gamma, grad_P, out_bar, h1_bar, e_bar,
                                        loss_scale=f, cand=cand)
         if world > 1:
-            all_reduce_flat_([grad_P, out_bar, h1_bar, e_bar] + ([cand[2]] if cand is not None else []), process_group)
+            all_reduce_flat_([t for t in (grad_P, out_bar, h1_bar, e_bar) if t is not None]
+                             + ([cand[2]] if cand is not None else []), process_group)
         rows, cols = eng.export_adj()
         if cand is None:
             return value, torch.stack([rows, cols]), eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P)
@@ -1377,7 +1414,7 @@ class FullLaplace(ParametricLaplace):
         leaves in ``model.adj.grad`` when the structure-learning loop runs with ``hessian_structure="full"``
         (gnn/utils.py:57-59; gnn/marglik_training.py:197-216; laplace/baselaplace.py:1377-1505 over the fork's attached
         Jacobians, laplace/curvature/curvature.py:374-410, :89-130).  Same return values and candidate pairs as
-        ``DiagLaplace.neg_marglik_adj_grad``.  2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE,
+        ``DiagLaplace.neg_marglik_adj_grad``.  1-layer GCN, 2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE,
         classification.  ``d(1/2 logdet(f H + Delta))/dH = Gamma = (f / 2) (f H + Delta)^-1`` is held fixed; it is built once per
         call in fp64 (as ``posterior_scale``) and handed to the device in fp32.  The GGN is a sum over samples, so the ranks of a
         job split every batch by samples.  ``dense=True`` (LoRA) stays on the Kronecker and diagonal posteriors."""
@@ -1391,15 +1428,17 @@ class FullLaplace(ParametricLaplace):
             raise NotImplementedError("adjacency gradient under the full posterior: stored entries and candidates only "
                                       "(dense=True is offered by KronLaplace and DiagLaplace)")
         eng = getattr(self.backend, "engine", None)
-        if eng is None or not hasattr(eng, "full_adjgrad_batch") or eng.kind not in ("gcn", "sage") or len(eng.dims) != 3:
+        if eng is None or not hasattr(eng, "full_adjgrad_batch") or eng.kind not in ("gcn", "sage"):
             raise NotImplementedError("adjacency gradient under the full posterior: 2-layer GCN / GraphSAGE on the HIP backend")
+        _adjgrad_scope(eng, "adjacency gradient under the full posterior", depth=True)
         value = -self.log_marginal_likelihood()
         f = self._H_factor
         Gamma = self._adj_gamma()
-        N, Hd, F, C = eng.num_nodes, eng.dims[1], eng.dims[0], eng.dims[-1]
+        N, F, C = eng.num_nodes, eng.dims[0], eng.dims[-1]
         grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
         out_bar = torch.zeros(N, C, dtype=torch.float32, device=eng.device)
-        h1_bar = torch.zeros(N, Hd, dtype=torch.float32, device=eng.device)
+        # (a 1-layer model has no hidden layer: the device calls take a null h1_bar)
+        h1_bar = torch.zeros(N, eng.dims[1], dtype=torch.float32, device=eng.device) if len(eng.dims) != 2 else None
         e_bar = torch.zeros(N, F + 1, dtype=torch.float32, device=eng.device)
         rank, world = _dist_info(process_group)
         sym = bool(getattr(self.model, "symmetric", False))
@@ -1412,7 +1451,8 @@ class FullLaplace(ParametricLaplace):
                 eng.full_adjgrad_batch(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), Gamma, grad_P, out_bar, h1_bar, e_bar,
                                        loss_scale=f, cand=cand)
         if world > 1:
-            all_reduce_flat_([grad_P, out_bar, h1_bar, e_bar] + ([cand[2]] if cand is not None else []), process_group)
+            all_reduce_flat_([t for t in (grad_P, out_bar, h1_bar, e_bar) if t is not None]
+                             + ([cand[2]] if cand is not None else []), process_group)
         rows, cols = eng.export_adj()
         if cand is None:
             return value, torch.stack([rows, cols]), eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P)
