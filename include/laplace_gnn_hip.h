@@ -499,7 +499,10 @@ LGNN_API int lgnn_lora_grad(lgnn_ctx* h, const float* grad_adj_dense, const floa
  *     QA1 [F', F'], S1 [C, F'], QB1sq, kappa describe the ONLY layer, F' = the width its Linear multiplies (F, GraphSAGE 2 F).
  *     J_n[c, (c', j)] = delta_cc' xt_n[j] with xt_n = (P X)[n], bias entry rho_n = rowsum(P)[n] (GraphSAGE: xt_n = [x_n | (P X)_n],
  *     rho_n = 1):  Kronecker  var_n[c] = sum_a Q_B[c, a]^2 sum_i S1[a, i] (Q_A^T xt_n)_i^2 + kappa[c] rho_n^2,
- *     diagonal  var_n[c] = sum_i S1[c, i] xt_n[i]^2 + kappa[c] rho_n^2.  The mapped variant reads W1m's rows as Cm only.  */
+ *     diagonal  var_n[c] = sum_i S1[c, i] xt_n[i]^2 + kappa[c] rho_n^2.  The mapped variant reads W1m's rows as Cm only.
+ *   Activation: this entry and the mapped one read act' as a float per hidden unit and accept relu and tanh alike (checked
+ *     against the Jacobian route under tanh, tests/test_gpu_tanh.py); lgnn_glm_variance_ext and every adjacency-gradient
+ *     entry (lgnn_*_adjgrad_*, lgnn_full_directions) refuse a 2-layer tanh model with a message naming ReLU.                */
 LGNN_API int lgnn_glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* QA0, const float* QB0, const float* S0,
                       const float* QA1, const float* S1, const float* QB1sq, const float* kappa, float* f_mu,
                       float* f_var_diag, void* stream);
