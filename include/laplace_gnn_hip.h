@@ -550,6 +550,23 @@ LGNN_API int lgnn_glm_variance_ext(lgnn_ctx* h, const int64_t* idx, int64_t M, c
  * `stream`; no graph handle involved.    */
 LGNN_API int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W, int32_t* info, void* stream);
 
+/* ---- kNN initial graph (the reference's `--init_graph knng` configurations) ----------------------
+ * Replaces torch_geometric.nn.knn_graph(X, k, loop=False, cosine=False) inside get_knn_graph (gnn/utils.py:355-369, handed
+ * to the model at gnn/marglik_training.py:407-408): the exact k nearest neighbours of every row of X by squared Euclidean
+ * distance, self excluded, without forming N x N distances (csrc/knn.hip: a Gram-form filter on the fp32 matrix cores keeps
+ * 64 candidates per row, they are re-ranked in the difference form, a per-row certificate decides whether that was enough,
+ * the rows without one are recomputed by brute force -- the result is exact either way).
+ *   X: device fp32 [N, F], row stride ld >= F floats (64-bit row offsets);  1 <= k <= 32, k < N < 2^31, F >= 1;
+ *   nbr: device int32 [N, k], dist: device fp32 [N, k], ascending per row.
+ * Order: by (d, index) with d the fp32 difference form sum_f (x_f - y_f)^2 (one fixed summation order); equal d: the
+ * smaller index first.  Two calls on the same input agree bit for bit.  X is expected to be finite.
+ *   num_fallback: HOST int64, the number of rows that took the brute-force route.
+ * The call synchronises `stream` once (to read that count; a second time, after the brute force, if the count is not zero).
+ * No graph handle involved; the workspace (O(N * 64 * splits)) lives for the call.  Anything else: an error through
+ * lgnn_last_error.                                                                                                      */
+LGNN_API int lgnn_knn(const float* X, int64_t N, int64_t F, int64_t ld, int k, int32_t* nbr, float* dist,
+                      int64_t* num_fallback, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

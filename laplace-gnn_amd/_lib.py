@@ -82,6 +82,7 @@ SIGNATURES = {
                                      _vp]),
     "lgnn_symeig_batched": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "lgnn_jacobians": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_knn": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
 }
 
 _lib = None
