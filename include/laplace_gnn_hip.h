@@ -101,9 +101,12 @@ LGNN_API int64_t lgnn_num_long_rows(const lgnn_ctx* h);
 /* 1 if the last lgnn_kfac_accumulate* call on this context took the two-hop path route (csrc/paths*.hip), 0 if it built class
  * planes: which of the two implementations of curvlinops/kfac.py:653-661, 777-817 ran (measurement labels; host value). */
 LGNN_API int lgnn_kfac_last_route(const lgnn_ctx* h);
-/* 1 if the top layer of that call ran on the matrix-pipe kernel of the path route (csrc/toptiles.hip: GCN, no sliced hub rows),
- * 0 if seed_spmm_gram_kernel ran (host value). */
+/* 1 if the top layer of that call ran on a matrix-pipe kernel of the path route (csrc/toptiles.hip or csrc/toppairs.hip: GCN,
+ * no sliced hub rows), 0 if seed_spmm_gram_kernel ran (host value). */
 LGNN_API int lgnn_kfac_last_top(const lgnn_ctx* h);
+/* Which kernel that was: 0 seed_spmm_gram_kernel, 1 top_tiles_kernel (per-node tiles and Grams), 2 top_pairs_kernel (one MFMA
+ * K step per sample and per pair of samples that share a node; taken when a host-known bound of the pairs fits the list). */
+LGNN_API int lgnn_kfac_last_top_kernel(const lgnn_ctx* h);
 /* 1 if the stored adjacency equals its transpose (then forward and backward share one CSR) */
 LGNN_API int lgnn_is_symmetric(const lgnn_ctx* h);
 

@@ -199,9 +199,40 @@ int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool have_n
   return 0;
 }
 
+// The top layer's term lists (toppairs.hip), which the caller has just built in the workspace from the entry's R (or from
+// the workspace's R the entry's was copied from): part of the path structure.  Synchronises the stream once.  The caller may be
+// reading the entry's R and path list in this very call: lists that cannot be kept (over the budget, out of memory) leave the
+// rest of the entry as it is -- only the pair part stays out, for good (pairs_refused), and is built per call.
+int batch_cache_store_pairs(lgnn_ctx* h, BatchEntry* e, hipStream_t s) {
+  if (e->has_pairs || e->pairs_refused || e->refused || !e->has_paths) return 0;
+  const int64_t N = h->N;
+  Workspace& ws = h->ws;
+  int32_t np = 0;
+  LGNN_HIP_CHECK(hipMemcpyAsync(&np, ws.pair_ptr.as<int32_t>() + N, 4, hipMemcpyDeviceToHost, s));
+  LGNN_HIP_CHECK(hipStreamSynchronize(s));
+  LGNN_REQUIRE(np >= 0 && size_t(np) * 4 <= ws.pair_m.bytes, "internal: pair count out of range");
+  const size_t M = size_t(e->M), add = M * 4 + std::max<size_t>(size_t(np), 1) * 12 + 4;
+  const bool ok = make_room(h, e, add, batch_cache_budget()) && alloc_copy(e->pair_s, ws.pair_s.p, M, s) == 0 &&
+                  alloc_copy(e->pair_m, ws.pair_m.p, size_t(np), s) == 0 && alloc_copy(e->pair_m2, ws.pair_m2.p, size_t(np), s) == 0 &&
+                  alloc_copy(e->pair_w, ws.pair_w.p, size_t(np), s) == 0 &&
+                  alloc_copy(e->pair_n, ws.pair_ptr.as<int32_t>() + N, 1, s) == 0;
+  if (!ok) {
+    e->pair_s = {}; e->pair_m = {}; e->pair_m2 = {}; e->pair_w = {}; e->pair_n = {};
+    e->pairs_refused = true;
+    return 0;
+  }
+  e->bytes += add;
+  h->bcache.bytes += add;
+  e->path_bytes += add;
+  e->has_pairs = true;
+  return 0;
+}
+
 // another list capacity (LGNN_PATH_LIST_CAP): the path part is built again
 void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e) {
   if (!e->has_paths) return;
+  e->pair_s = {}; e->pair_m = {}; e->pair_m2 = {}; e->pair_w = {}; e->pair_n = {};
+  e->has_pairs = e->pairs_refused = false;
   e->pptr = {}; e->pm = {}; e->pv = {}; e->pw = {}; e->nodes = {}; e->nnodes = {}; e->rptr = {}; e->r_m = {}; e->r_w = {};
   e->has_paths = e->has_nodes = false;
   h->bcache.bytes -= e->path_bytes;

@@ -848,7 +848,8 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   }
   LGNN_CALL(h->ws.active.reserve(size_t(N)));
   bool have_act_list = false;
-  bool top_tiles = false;  // GCN path route: B_{L-1} comes from top_tiles_kernel instead of seed_spmm_gram_kernel
+  bool top_tiles = false;  // GCN path route: B_{L-1} comes from top_tiles_kernel / top_pairs_kernel instead of seed_spmm_gram_kernel
+  bool top_pairs = false;  // ... from top_pairs_kernel (toppairs.hip): the host knows that the batch's pairs fit their list
   // the GCN's active rows as the steps below read them: the workspace's, or the cache entry's on a hit
   const uint8_t* active_p = nullptr;
   const int32_t* act_list_p = nullptr;
@@ -892,6 +893,7 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
       if (top_here && paths_route && !gplanes && C <= kCoefStride && nb < ne) {
         LGNN_CALL(long_rows_ensure(h, s));
         top_tiles = h->n_top_multi <= 0;
+        top_pairs = top_tiles && top_pairs_fit(h, M);
       }
       if (top_here && !top_tiles) switch (int(cdiv(C, 16))) {
         case 1: LGNN_CALL(seed_spmm_gram_launch<1>(h, fork_exact, gplanes, cb, ce, sc, s, act_list_p, act_count_p, active_p)); break;
@@ -924,10 +926,10 @@ int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, i
   // ---- 2-layer GCN: B_0 from the batch's 2-hop paths -- no class planes (paths.hip, paths_fused.hip) -------
   const bool paths_route = plan.paths && !fisher && (h->kind == LGNN_KIND_GCN ? seeds_on_the_fly : true);
   h->last_route_paths = paths_route;
-  h->last_top_tiles = top_tiles;
+  h->last_top_kernel = top_pairs ? 2 : (top_tiles ? 1 : 0);
   if (paths_route) {
     const int mode = h->lik == LGNN_LIK_REGRESSION ? 2 : (fork_exact ? 1 : 0);
-    const TopTilesReq top{act_list_p, act_count_p, h->ws.gram_scratch[L - 1].as<float>()};
+    const TopTilesReq top{act_list_p, act_count_p, h->ws.gram_scratch[L - 1].as<float>(), top_pairs};
     if (h->kind == LGNN_KIND_GCN)
       LGNN_CALL(kfac_paths_first_layer(h, idx, M, mode, cb, ce, h->ws.gram_scratch[0].as<float>(), s, nb, ne, be, &be_built,
                                        top_tiles ? &top : nullptr));

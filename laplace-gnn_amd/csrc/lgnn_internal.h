@@ -136,6 +136,9 @@ struct Workspace {
   DevBuf path_alpha;  // GraphSAGE: the samples' alpha coefficients, class major [M][64] (weights of the one-hot paths)
   DevBuf path_pcnt, path_pptr, path_pm, path_pv, path_pw;  // the batch's paths per destination node (CSR over n)
   DevBuf path_flags, path_nodes, path_nnodes;              // nodes of the launch's range that have a path: flags, list, count
+  // the top layer's term lists (toppairs.hip): s_m [M]; per-node pair counts and their scan [N + 1]; the pairs (m, m', w w')
+  DevBuf pair_s, pair_cnt, pair_ptr, pair_m, pair_m2, pair_w;
+  DevBuf pair_part;  // top_pairs_kernel's partial sums, one row of upper tiles per workgroup
   // (the list's capacity is max(4 nnz, 4 M entries); a batch whose list is longer takes the enumerating route on the device)
   bool path_zeros_set = false;
   DevBuf gram_scratch_res[kMaxLayers];  // res / norm models: per-call partial B of res.{l} (GCN; GraphSAGE shares the conv's)
@@ -153,6 +156,7 @@ struct Workspace {
     f(act_list); f(act_count); f(select_tmp); f(flags); f(out_flags); f(out_list); f(out_count); f(val_act2);
     f(path_coef); f(path_up); f(path_bg); f(path_cnt); f(path_rptr); f(path_rm); f(path_rw); f(path_zeros); f(path_alpha);
     f(path_pcnt); f(path_pptr); f(path_pm); f(path_pv); f(path_pw); f(path_flags); f(path_nodes); f(path_nnodes);
+    f(pair_s); f(pair_cnt); f(pair_ptr); f(pair_m); f(pair_m2); f(pair_w); f(pair_part);
     f(planes_c); f(adj_z0); f(adj_dir); f(lora_rows); f(lora_cols); f(lora_state); f(lora_count); f(lora_part);
     f(dense_stored); f(dense_rows);
   }
@@ -196,6 +200,15 @@ struct BatchEntry {
   DevArray<int32_t> rptr;       // [N + 1]
   DevArray<int32_t> r_m;
   DevArray<float> r_w;
+  // the top layer's term lists (toppairs.hip), built from R the first time a call of this batch runs top_pairs_kernel: s_m [M],
+  // the pairs of samples that share a node (m, m', w w') and their number (device int32); counted in path_bytes
+  bool has_pairs = false;
+  bool pairs_refused = false;   // the lists did not fit the budget: the rest of the entry stays, they are built per call
+  DevArray<float> pair_s;
+  DevArray<int32_t> pair_m;
+  DevArray<int32_t> pair_m2;
+  DevArray<float> pair_w;
+  DevArray<int32_t> pair_n;
 };
 struct BatchCache {
   std::vector<BatchEntry*> entries;
@@ -279,8 +292,9 @@ struct lgnn_ctx {
   int64_t ws_limit = int64_t(32) << 30;  // backward planes (ping + pong) per class chunk: 288 GB of HBM, keep chunks large
   // rows of P^T with more than kLongRow stored entries (hubs), built once on first use (longrows.hip)
   bool last_route_paths = false;   // the last KFAC accumulate took the two-hop path route
-  bool last_top_tiles = false;     // ... and its top layer ran on top_tiles_kernel (toptiles.hip), not seed_spmm_gram_kernel
+  int last_top_kernel = 0;         // ... and its top layer ran on 0: seed_spmm_gram_kernel, 1: top_tiles_kernel, 2: top_pairs_kernel
   double two_hop_max = -1.0;       // largest number of 2-hop paths starting at one node (same count pass)
+  double pair_hop_max = -1.0;      // largest number of samples one sample can share a node with: P row, then P^T rows (same pass)
   double two_hop = -1.0;           // number of 2-hop paths n <- v <- m of the graph (-1: not counted yet; paths.hip)
   int64_t n_long = -1;             // -1: not looked at yet
   int64_t n_long_tasks = 0;
@@ -526,6 +540,7 @@ void batch_cache_clear(lgnn_ctx* h);         // the graph changed / the context 
 int batch_cache_lookup(lgnn_ctx* h, uint64_t tag, const int64_t* idx, int64_t M, BatchEntry** out, hipStream_t s);
 int batch_cache_store_active(lgnn_ctx* h, BatchEntry* e, hipStream_t s);   // from ws.active / act_list / act_count
 int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool have_nodes, hipStream_t s);  // path list, R, node list
+int batch_cache_store_pairs(lgnn_ctx* h, BatchEntry* e, hipStream_t s);   // from ws.pair_* (an entry that has its path part)
 void batch_cache_drop_paths(lgnn_ctx* h, BatchEntry* e);
 // ---- gram_stream.hip ----------------------------------------------------------------------
 // scratch [width, width] (upper 32 x 32 sub-tiles) += Y^T Y for rows of `width` floats (row stride ld), 128 < width <= 256:
@@ -543,9 +558,16 @@ struct PathR { const int32_t* rptr; const int32_t* r_m; const float* r_w; };  //
 // and the tables path_tables_kernel has written for the same (cb, ce) (ws.path_coef, ws.path_up).
 int launch_top_tiles(lgnn_ctx* h, const PathR& r, int64_t M, int64_t cb, int64_t ce, const int32_t* act_list,
                      const int32_t* act_count, float* scratch, hipStream_t s);
-struct TopTilesReq { const int32_t* act_list; const int32_t* act_count; float* scratch; };  // the batch's active rows, B_1 scratch
+// The same sum from sample pairs (toppairs.hip): s_m [M], the pairs (m, m', w w') of samples that share a node, their number
+struct TopPairs { const float* sq; const int32_t* pm; const int32_t* pm2; const float* pw; const int32_t* npairs; };
+int64_t top_pairs_bound(const lgnn_ctx* h, int64_t M);  // a host-known bound of a batch's pairs (-1: none)
+bool top_pairs_fit(const lgnn_ctx* h, int64_t M);       // ... fits the pair list (LGNN_PAIR_LIST_CAP, read per call)
+int build_top_pairs(lgnn_ctx* h, const int64_t* idx, int64_t M, const PathR& r, TopPairs& out, hipStream_t s);  // into ws.pair_*
+int launch_top_pairs(lgnn_ctx* h, const TopPairs& p, int64_t M, int64_t cb, int64_t ce, float* scratch, hipStream_t s);
+// the batch's active rows, B_1 scratch; pairs: top_pairs_kernel instead of top_tiles_kernel
+struct TopTilesReq { const int32_t* act_list; const int32_t* act_count; float* scratch; bool pairs; };
 // scratch [H, H] += B_0 of this batch's class columns [cb, ce) (seed_mode: 0 upstream, 1 fork exact, 2 regression)
-// (top: also run the top layer from the tables and R built here -- launch_top_tiles -- once both are in place)
+// (top: also run the top layer from the tables and R built here -- launch_top_tiles / launch_top_pairs -- once both are in place)
 // (nb, ne: the destination nodes whose Y_n^T Y_n this call adds -- B_0 is a sum over nodes: the multi-GPU cut of these routes)
 // (entry: the batch's cache entry or null; its path part is used if present and built into it otherwise; *built is set then)
 int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce, float* scratch,

@@ -268,14 +268,15 @@ __global__ void two_hop_count_kernel(const int32_t* __restrict__ rp, const int32
 }
 
 // max over m of the paths n <- k <- m that START at m: sum over the entries k of row m of P of the entries of row k of P.
-// M times this bounds a batch's path count from the host (duplicated batch nodes share their paths).
-__global__ void two_hop_max_kernel(const int32_t* __restrict__ rp, const int32_t* __restrict__ col, int64_t N,
-                                   unsigned long long* __restrict__ out) {
+// M times this bounds a batch's path count from the host (duplicated batch nodes share their paths).  With P^T's row pointers
+// as `rp2`: the samples m' that can share a node k with m -- M times that bounds twice the pairs of toppairs.hip.
+__global__ void two_hop_max_kernel(const int32_t* __restrict__ rp, const int32_t* __restrict__ col,
+                                   const int32_t* __restrict__ rp2, int64_t N, unsigned long long* __restrict__ out) {
   unsigned long long best = 0;
   const int64_t stride = int64_t(gridDim.x) * blockDim.x;
   for (int64_t m = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; m < N; m += stride) {
     unsigned long long acc = 0;
-    for (int32_t p = rp[m]; p < rp[m + 1]; ++p) { const int32_t k = col[p]; acc += (unsigned long long)(rp[k + 1] - rp[k]); }
+    for (int32_t p = rp[m]; p < rp[m + 1]; ++p) { const int32_t k = col[p]; acc += (unsigned long long)(rp2[k + 1] - rp2[k]); }
     best = acc > best ? acc : best;
   }
   for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(best, o); best = t > best ? t : best; }
@@ -293,17 +294,22 @@ int two_hop_ensure(lgnn_ctx* h, hipStream_t s) {
   if (h->nnz <= 0) return 0;
   DevBuf acc;
   LGNN_CALL(acc.reserve(64));
-  unsigned long long host[2] = {0, 0};
-  LGNN_HIP_CHECK(hipMemsetAsync(acc.p, 0, 16, s));
+  unsigned long long host[3] = {0, 0, 0};
+  LGNN_HIP_CHECK(hipMemsetAsync(acc.p, 0, 24, s));
   const dim3 grid{unsigned(std::min<int64_t>(cdiv(h->N, 256), 1024))};
   hipLaunchKernelGGL(two_hop_count_kernel, grid, dim3(256), 0, s, h->P.rowptr, h->PT.rowptr, h->N, acc.as<unsigned long long>());
   LGNN_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(two_hop_max_kernel, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->N, acc.as<unsigned long long>() + 1);
+  hipLaunchKernelGGL(two_hop_max_kernel, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.rowptr, h->N,
+                     acc.as<unsigned long long>() + 1);
   LGNN_HIP_CHECK(hipGetLastError());
-  LGNN_HIP_CHECK(hipMemcpyAsync(host, acc.p, 16, hipMemcpyDeviceToHost, s));
+  hipLaunchKernelGGL(two_hop_max_kernel, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->PT.rowptr, h->N,
+                     acc.as<unsigned long long>() + 2);
+  LGNN_HIP_CHECK(hipGetLastError());
+  LGNN_HIP_CHECK(hipMemcpyAsync(host, acc.p, 24, hipMemcpyDeviceToHost, s));
   LGNN_HIP_CHECK(hipStreamSynchronize(s));
   h->two_hop = double(host[0]);
   h->two_hop_max = double(host[1]);
+  h->pair_hop_max = double(host[2]);
   return 0;
 }
 // ... at most this many: arxiv's 13.7 take the path route, the power-law graph's 24x the node count keep the class planes
@@ -317,6 +323,23 @@ bool paths_supported(int kind, int L, const int64_t* dims, int act, int64_t nnz)
   const int64_t C = dims[L], H = L >= 2 ? dims[L - 1] : 0;
   return (kind == LGNN_KIND_GCN || kind == LGNN_KIND_SAGE) && L == 2 && act == LGNN_ACT_RELU && nnz > 0 && C <= kCoefStride &&
          H > 128 && H <= 256 && H % 4 == 0;
+}
+
+// Entries of a batch's path list buffer (arxiv shape: 2.2 M paths per batch of 10 000 against 10 M).  LGNN_PATH_LIST_CAP, read
+// per call: tests force the enumerating route
+static int64_t path_list_cap(const lgnn_ctx* h) {
+  int64_t cap = std::max<int64_t>(4 * h->nnz, int64_t(1) << 22);
+  if (const char* e = getenv("LGNN_PATH_LIST_CAP")) cap = std::max<int64_t>(1, std::min<int64_t>(cap, atoll(e)));
+  return cap;
+}
+// The top layer runs on top_pairs_kernel (toppairs.hip) when the host knows that the batch's pairs fit a list of the path
+// list's capacity (the same kind of bound as can_overflow below: no device-side gate, no synchronisation); otherwise on
+// top_tiles_kernel.  LGNN_PAIR_LIST_CAP, read per call: tests lower the capacity to keep that kernel covered
+bool top_pairs_fit(const lgnn_ctx* h, int64_t M) {
+  int64_t cap = path_list_cap(h);
+  if (const char* e = getenv("LGNN_PAIR_LIST_CAP")) cap = std::max<int64_t>(1, std::min<int64_t>(cap, atoll(e)));
+  const int64_t bound = top_pairs_bound(h, M);
+  return bound > 0 && bound <= cap;
 }
 
 // The nodes of [nb, ne) that have a path, as a device-side list (GraphSAGE: 65 % of the nodes at the arxiv shape; a short last
@@ -392,9 +415,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     GemmEpilogue none;
     LGNN_CALL(launch_gemm(ws.path_up.as<float>(), C, h->W[1], H, ws.path_bg.as<float>(), H, 2 * M, C, H, none, s));
   }
-  // (arxiv shape: 2.2 M paths per batch of 10 000.  LGNN_PATH_LIST_CAP, read per call: tests force the enumerating route)
-  int64_t cap = std::max<int64_t>(4 * h->nnz, int64_t(1) << 22);
-  if (const char* e = getenv("LGNN_PATH_LIST_CAP")) cap = std::max<int64_t>(1, std::min<int64_t>(cap, atoll(e)));
+  const int64_t cap = path_list_cap(h);
   // the overflow route below is gated on the device (the host cannot know a batch's path count without a synchronisation).
   // What the host does know is a bound: M times the largest number of paths that start at one node (counted once per graph
   // beside the graph's total).  If that fits the list, no batch can overflow: no planes, no launches behind the fused kernel
@@ -458,8 +479,20 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     LGNN_CALL(batch_cache_store_paths(h, entry, cap, use_list && whole, s));
     if (built) *built = true;
   }
-  // ---- the top layer from the tables and R (toptiles.hip): B_1 scratch += sum_n G_n^T G_n
-  if (top) LGNN_CALL(launch_top_tiles(h, PathR{pl.rptr, pl.r_m, pl.r_w}, M, cb, ce, top->act_list, top->act_count, top->scratch, s));
+  // ---- the top layer from the tables and R: B_1 scratch += sum_n G_n^T G_n, from sample pairs (toppairs.hip; the term lists
+  // are the entry's, or built from R into the workspace and copied into an entry that holds R) or per node (toptiles.hip)
+  if (top && top->pairs) {
+    TopPairs tp{};
+    if (entry && entry->has_pairs) {
+      tp = {entry->pair_s, entry->pair_m, entry->pair_m2, entry->pair_w, entry->pair_n};
+    } else {
+      LGNN_CALL(build_top_pairs(h, idx, M, PathR{pl.rptr, pl.r_m, pl.r_w}, tp, s));
+      if (entry && entry->has_paths) LGNN_CALL(batch_cache_store_pairs(h, entry, s));  // (this call goes on with the workspace's)
+    }
+    LGNN_CALL(launch_top_pairs(h, tp, M, cb, ce, top->scratch, s));
+  } else if (top) {
+    LGNN_CALL(launch_top_tiles(h, PathR{pl.rptr, pl.r_m, pl.r_w}, M, cb, ce, top->act_list, top->act_count, top->scratch, s));
+  }
   YArgs y = path_args(h, pl, cb, cap, nb, ne);
   y.W1 = h->W[1]; y.w1_ld = int(H); y.M = M; y.n_coef = M; y.no_bg = no_bg ? 1 : 0;
   LGNN_CALL(launch_paths_fused(h, y, cb, ce, scratch, s));

@@ -201,9 +201,15 @@ class GraphEngine:
 
     @property
     def last_kfac_top_on_tiles(self) -> bool:
-        """Whether the last KFAC accumulate's top layer ran on the path route's matrix-pipe kernel (csrc/toptiles.hip)
-        rather than on ``seed_spmm_gram_kernel``."""
+        """Whether the last KFAC accumulate's top layer ran on one of the path route's matrix-pipe kernels (csrc/toptiles.hip
+        or csrc/toppairs.hip; ``last_kfac_top_kernel`` says which) rather than on ``seed_spmm_gram_kernel``."""
         return bool(self.lib.lgnn_kfac_last_top(self._h))
+
+    @property
+    def last_kfac_top_kernel(self) -> int:
+        """Which kernel ran the last KFAC accumulate's top layer: 0 ``seed_spmm_gram_kernel``, 1 ``top_tiles_kernel``
+        (csrc/toptiles.hip), 2 ``top_pairs_kernel`` (csrc/toppairs.hip)."""
+        return int(self.lib.lgnn_kfac_last_top_kernel(self._h))
 
     def export_adj(self):
         nnz = self.nnz
