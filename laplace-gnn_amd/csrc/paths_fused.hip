@@ -14,8 +14,9 @@
 //       Y[n] = W_1 (.) T1 + Y2 (W_1's rows straight from L2) is split into three bf16 pieces HERE, once per value, and the
 //       pieces go to one of TWO LDS tiles (FusedShared; 18 16-byte stores per node) -- under LGNN_GRAM_F32 the fp32 values.
 //   waves 4 .. 7, the GRAM waves: S += Y[n - 1]^T Y[n - 1] from the other tile into register-resident upper-triangular
-//       accumulators (the 36 sub-tiles of gram256.h, 9 per wave, 144 accumulator registers), nothing else: their loop is LDS
-//       reads and MFMAs.
+//       accumulators (the 36 sub-tiles of gram256.h, 9 per wave, as 34 tiles of 16 x 16: 136 accumulator registers), nothing
+//       else: their loop is LDS reads and MFMAs -- v_mfma_f32_16x16x32_bf16 on the pieces, 16 cycles each, so that a product
+//       wave's MFMA waits 16 cycles for this wave's turn on the pipe, not 32 (gram_split16_role).
 // ONE hand-off per node (LDS counters).  The product wave of a SIMD needs the matrix pipe for about a third of a node's cycles
 // and sleeps on memory part of the rest; the Gram wave is a dense MFMA stream that takes every slot the product wave leaves: the
 // two phases that round 3 ran back to back in every wave (7.7 ms per arxiv batch, matrix pipes 57 % busy) now overlap.
@@ -28,13 +29,14 @@ namespace {
 constexpr int kYStride = 272;  // floats per row of the fp32 tile: 256 + 16, so that the four rows of a Gram operand read (lanes
                                // 16 k .. 16 k + 15 read row k0 + k) fall on disjoint banks
 // The tile as bf16 PIECES (the default Gram role): a tile value y is y0 + y1 + y2, y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y -
-// y0 - y1) (see gram_split_role).  A dword holds the same piece of two tile rows (row r in the low half, r + 1 in the high
-// half); the tile rows come in GROUPS of four, g = row / 4, i.e. (chunk of 8 rows, lane half of the Gram's MFMA operand), and a
+// y0 - y1) (see gram_split16_role).  A dword holds the same piece of two tile rows (row r in the low half, r + 1 in the high
+// half); the tile rows come in GROUPS of four, g = row / 4, i.e. (chunk of 16 rows, lane group of the Gram's MFMA operand), and a
 // group is three PLANES (y2, y0, y1) of 256 columns x 2 dwords (rows 4 g, 4 g + 1 | rows 4 g + 2, 4 g + 3): 2 KiB each.  A Gram
-// lane reads the 8 bytes of its column from each plane (ds_read_b64; 32 lanes: 256 contiguous bytes); a product lane writes
+// lane reads the 8 bytes of its column from each plane (ds_read_b64; 16 lanes: 128 contiguous bytes); a product lane writes
 // the 32 bytes of its four columns to each plane (two ds_write_b128).  The 8 lanes one ds_write_b128 cycle serves are 32 bytes
 // apart, which would put them on 16 of the 32 banks twice: the two 16-byte halves of a lane's 32 bytes swap places in the lanes
-// piece_swap() names, and the 8 lanes cover the 32 banks once.  The reads stay permutations of one 256-byte bank row.
+// piece_swap() names, and the 8 lanes cover the 32 banks once.  A lane group's reads stay a permutation of 128 contiguous bytes
+// (two lane groups share an LDS cycle and the same banks there: see gram_split16_role).
 constexpr int kPlaneDwords = 512;             // one plane: 256 columns x 2 dwords
 constexpr int kGroupDwords = 3 * kPlaneDwords;
 constexpr int kYGroups = kYRows / 4;
@@ -146,7 +148,7 @@ __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // one v_cvt_
   return __builtin_bit_cast(uint32_t, v);
 }
 // The three bf16 pieces of two tile values (ya in the low halves, yb in the high halves), each rounded to nearest:
-// q0 = bf16(y), q1 = bf16(y - q0), q2 = bf16(y - q0 - q1) = y - q0 - q1 (see gram_split_role).  11 vector instructions.
+// q0 = bf16(y), q1 = bf16(y - q0), q2 = bf16(y - q0 - q1) = y - q0 - q1 (see gram_split16_role).  11 vector instructions.
 __device__ __forceinline__ void split_pair(float ya, float yb, uint32_t& q0, uint32_t& q1, uint32_t& q2) {
   q0 = pk_bf16(ya, yb);
   asm("" : "+v"(q0));  // (keeps the two values in one cvt: hipcc otherwise converts and widens each on its own)
@@ -612,59 +614,159 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
       }
 }
 
-// The same Gram on v_mfma_f32_32x32x16_bf16 (the default; LGNN_GRAM_F32=1 runs gram_role above).  Every fp32 tile value y is
+// The same Gram on v_mfma_f32_16x16x32_bf16 (the default; LGNN_GRAM_F32=1 runs gram_role above).  Every fp32 tile value y is
 // split into three bf16 pieces, each rounded to nearest:  y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y - y0 - y1) = y - y0 - y1
 // (both differences are exact; each piece carries 8 of the 24 significand bits).  A product y z keeps six of the nine piece
 // products, y0 z0 + y0 z1 + y1 z0 + y0 z2 + y1 z1 + y2 z0: the three dropped ones are at most 2^-23 |y z| together and of either
 // sign (fp32 rounding level).  The product waves form the pieces (split_pair) and store them in the layout of FusedShared: this
-// role only reads them.  The K slots of an MFMA are (piece, class): lane half h holds the classes 8 ck + 4 h + 0 .. 3 of chunk
-// ck, two classes of one piece per register, six registers per column block (y2a y2b y0a y0b y1a y1b; a = classes 0 1, b =
-// classes 2 3), in two operand forms that overlap:  T = (y2a y2b y0a y0b),  U = (y0a y0b y1a y1b).  Per chunk and sub-tile
-// (si, sj) three MFMAs:
-//     U[si] x U[sj] = y0 z0 + y1 z1,   T[si] x U[sj] = y2 z0 + y0 z1,   U[si] x T[sj] = y0 z2 + y1 z0
-// (A and B of one lane share the slot map, see the operand layout: lane l holds A[row l & 31][k = 8 (l >> 5) + j] and
-// B[k = 8 (l >> 5) + j][col l & 31]).  hipcc keeps T and U in registers of their own: two moves per column block and chunk.
+// role only reads them.
+// WHY THIS SHAPE: the two waves of a SIMD take turns on its matrix pipe instruction by instruction (gram_role's header), so
+// every MFMA of the product wave waits one instruction of this wave.  The 32x32x16 form this role ran on before is 32 cycles
+// long, this one 16 for half the flops: the Gram's matrix cycles stay what they were, the product wave's wait halves.
+// Measured: a full arxiv batch 3.75 -> 3.62 ms, its short last batch 1.70 -> 1.60 ms -- a fifth of what strict
+// alternation would give: the product wave is paced by more than this wave's turns.
+// Tiles: gram_role's, acc[9][2][2] of 16 x 16 (34 per wave, 136 accumulator registers; lane l holds D[4 (l >> 4) + r][l & 15]).
+// Operands: a lane is (column l & 15 of a 16-column block, K group q = l >> 4); for the 16-row chunk cc lane group q reads the
+// row group 4 cc + q: per 16-column block the 8 bytes of its column from each plane, six registers (y2a y2b y0a y0b y1a y1b;
+// a = rows 0 1 of the group, b = rows 2 3), in two operand forms that overlap:  T = (y2a y2b y0a y0b),  U = (y0a y0b y1a y1b).
+// Per chunk and tile three MFMAs with K = 32 = 4 row groups x (2 pieces x 4 rows):
+//     U[i] x U[j] = y0 z0 + y1 z1,   T[i] x U[j] = y2 z0 + y0 z1,   U[i] x T[j] = y0 z2 + y1 z0.
+// Which K slot a (lane group, register half) is does not matter and is nowhere written down: the instruction's A and B layouts
+// mirror each other (lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15]), and A and B of one
+// lane are filled by the same reads, so slot k of A and slot k of B are the same (tile row, piece) whatever k is.
+// AN ODD NUMBER OF 8-ROW CHUNKS (R = 40: five): the last one is not run as a 16-row chunk of which half is zero rows.  Lane
+// groups 2, 3 read the same two row groups as lane groups 0, 1, and two MFMAs do the work of three:
+//     (U | T) x U = U x U + T x U   (A: U in lane groups 0 1, T in 2 3),      (U | 0) x T = U x T.
+// (Zeroing A alone is enough: a finite B times zero is zero, and a non-finite input gives a non-finite factor anyway.)
+// R = 40 is 3 + 3 + 2 = 8 MFMAs of 16 cycles per tile: 34 x 8 x 16 = 4 352 matrix cycles per node against 27 x 5 x 32 = 4 320 before.
+// ONE operand set (hipcc keeps U in registers of its own, two moves and eight registers per block: 96 beside 136 accumulators,
+// 255 in all -- a second set, or half of one, does not fit): a wave's sub-tiles run in the order GramOrder names, chosen so that
+// its column blocks are used up one after the other; the reads of the NEXT chunk's block go out right behind the last MFMA
+// that reads the block, a sub-tile and a half (300 cycles) or more before their first use.  Behind a node's last chunk those
+// reads fetch the same chunk again (values nobody uses): the body stays straight-line.
+// Inside a sub-tile the order is all U x U, all T x U, all U x T: an accumulator comes round every third or fourth MFMA.
+// Bank conflicts: the 16 lanes of a lane group read 128 contiguous bytes of a plane (permuted by piece_col), but groups and
+// planes are multiples of 256 bytes apart, so the two lane groups that share an LDS cycle (ds_read_b64 serves lanes 0 - 31,
+// then 32 - 63) meet on the same 32 banks: every read is 2-way, 4 LDS cycles instead of 2 -- 36 reads per chunk beside
+// 102 MFMAs of 16 cycles.  (Only a layout with the rows of a group pair side by side could avoid it.)
 // Rounding can take only a value above 3.39e38 to infinity (its square overflows in fp32 anyway); a NaN or an infinity turns
 // into NaN pieces (inf - inf): a non-finite input gives a non-finite factor, as the fp32 role does.
-// 27 MFMAs of 32 cycles per chunk of 8 tile rows against gram_role's 68 of 16x16x4 fp32 (32 cycles each): 0.4x the matrix cycles.
-struct PieceBlk { u32x2v y2, y0, y1; };  // a column block's pieces of the lane's 4 classes of a chunk: (rows 0 1 | rows 2 3)
+struct PieceBlk { u32x4v t; u32x2v y1; };  // a 16-column block's pieces of the lane's 4 rows of a chunk, (rows 0 1 | rows 2 3)
+                                            // each: t = (y2, y0) is the form T as it stands, U is its upper half beside y1
 
-// the lane's pieces of its column in every column block the wave uses (`p`: the chunk's group of the lane half + piece_col)
+// the order a wave runs its sub-tiles in (indices into Tiles256<W>).  Wave 0: (0,0) (0,2) (0,3) (0,4) (0,5) (0,1) (1,1) (1,2)
+// (1,3); waves 1, 2: the two with the far row block, the 2 x 2 between the pairs, the own pair's; wave 3: (6,6) (1,6) (2,6)
+// (3,6) (6,7) (1,7) (2,7) (3,7) (7,7)
+template <int W> struct GramOrder;
+template <> struct GramOrder<0> { static constexpr int o[9] = {0, 3, 4, 7, 8, 1, 2, 5, 6}; };
+template <> struct GramOrder<1> { static constexpr int o[9] = {7, 8, 3, 4, 5, 6, 0, 1, 2}; };
+template <> struct GramOrder<2> { static constexpr int o[9] = {7, 8, 3, 4, 5, 6, 0, 1, 2}; };
+template <> struct GramOrder<3> { static constexpr int o[9] = {0, 7, 3, 5, 1, 8, 4, 6, 2}; };
+// position in that order of the last sub-tile that reads the 32-column block b (-1: the wave does not use it)
+template <int W> __device__ __forceinline__ constexpr int gram_last_use(int b) {
+  int last = -1;
+  for (int p = 0; p < 9; ++p)
+    if (Tiles256<W>::si[GramOrder<W>::o[p]] == b || Tiles256<W>::sj[GramOrder<W>::o[p]] == b) last = p;
+  return last;
+}
+template <int W> __device__ __forceinline__ constexpr int gram_first_use(int b) {  // (likewise the first)
+  for (int p = 0; p < 9; ++p)
+    if (Tiles256<W>::si[GramOrder<W>::o[p]] == b || Tiles256<W>::sj[GramOrder<W>::o[p]] == b) return p;
+  return -1;
+}
+
+// the lane's pieces of its column in both 16-column halves of the 32-column block b: three ds_read_b64 each.  `off`: dword
+// offset in the tile of the chunk's row group of the lane group + piece_col of the lane's column li in an even 16-column block;
+// in the odd block beside it the swap of piece_col is the other one, piece_col(16 + li) = 32 + (piece_col(li) ^ 4), and
+// everything else in `off` is a multiple of 8
+__device__ __forceinline__ void piece_load(const uint32_t* __restrict__ tile, int off, int b, PieceBlk (&x)[8][2]) {
+  const uint32_t* __restrict__ pe = tile + off;
+  const uint32_t* __restrict__ po = tile + (off ^ 4) + 32;
+  const u32x2v e2 = *reinterpret_cast<const u32x2v*>(pe + b * 64), e0 = *reinterpret_cast<const u32x2v*>(pe + kPlaneDwords + b * 64);
+  const u32x2v o2 = *reinterpret_cast<const u32x2v*>(po + b * 64), o0 = *reinterpret_cast<const u32x2v*>(po + kPlaneDwords + b * 64);
+  x[b][0].t = u32x4v{e2[0], e2[1], e0[0], e0[1]};
+  x[b][0].y1 = *reinterpret_cast<const u32x2v*>(pe + 2 * kPlaneDwords + b * 64);
+  x[b][1].t = u32x4v{o2[0], o2[1], o0[0], o0[1]};
+  x[b][1].y1 = *reinterpret_cast<const u32x2v*>(po + 2 * kPlaneDwords + b * 64);
+}
+__device__ __forceinline__ f32x4 mfma_bf16(u32x4v a, u32x4v b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ u32x4v piece_u(const PieceBlk& p) { return u32x4v{p.t[2], p.t[3], p.y1[0], p.y1[1]}; }
+__device__ __forceinline__ u32x4v piece_t(const PieceBlk& p) { return p.t; }
+// A 16-row chunk: 34 x 3 MFMAs, and the next chunk's reads (at `off` of the tile) as the blocks are used up.
 template <int W>
-__device__ __forceinline__ void piece_load(const uint32_t* __restrict__ p, PieceBlk (&x)[8]) {
+__device__ __forceinline__ void piece_chunk16(PieceBlk (&x)[8][2], f32x4 (&acc)[9][2][2], const uint32_t* __restrict__ tile, int off) {
 #pragma unroll
-  for (int b = 0; b < 8; ++b)
-    if (tiles256_uses<W>(b)) {
-      x[b].y2 = *reinterpret_cast<const u32x2v*>(p + b * 64);
-      x[b].y0 = *reinterpret_cast<const u32x2v*>(p + kPlaneDwords + b * 64);
-      x[b].y1 = *reinterpret_cast<const u32x2v*>(p + 2 * kPlaneDwords + b * 64);
+  for (int p = 0; p < 9; ++p) {
+    const int s = GramOrder<W>::o[p], si = Tiles256<W>::si[s], sj = Tiles256<W>::sj[s];
+    // An empty statement that redefines a block's registers where the chunk first uses them: hipcc otherwise forms U (a copy
+    // of y0 beside y1) right behind the reads and waits for them there, with the latency in the open.
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+      if (gram_first_use<W>(b) == p)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(x[b][h].t), "+v"(x[b][h].y1));
+    const u32x4v ua[2] = {piece_u(x[si][0]), piece_u(x[si][1])}, ta[2] = {piece_t(x[si][0]), piece_t(x[si][1])};
+    const u32x4v ub[2] = {piece_u(x[sj][0]), piece_u(x[sj][1])}, tb[2] = {piece_t(x[sj][0]), piece_t(x[sj][1])};
+#pragma unroll
+    for (int f = 0; f < 3; ++f)
+#pragma unroll
+      for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+        for (int hj = 0; hj < 2; ++hj) {
+          if (si == sj && hi > hj) continue;  // (below the diagonal)
+          acc[s][hi][hj] = mfma_bf16(f == 1 ? ta[hi] : ua[hi], f == 2 ? tb[hj] : ub[hj], acc[s][hi][hj]);
+        }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+      if (gram_last_use<W>(b) == p) piece_load(tile, off, b, x);
+  }
+}
+// The odd last 8-row chunk: 34 x 2 MFMAs (`low`: the lane is of lane group 0 or 1).
+template <int W>
+__device__ __forceinline__ void piece_chunk8(const PieceBlk (&x)[8][2], f32x4 (&acc)[9][2][2], bool low) {
+#pragma unroll
+  for (int p = 0; p < 9; ++p) {
+    const int s = GramOrder<W>::o[p], si = Tiles256<W>::si[s], sj = Tiles256<W>::sj[s];
+    u32x4v a1[2], a2[2];
+#pragma unroll
+    for (int hi = 0; hi < 2; ++hi) {
+      const u32x4v u = piece_u(x[si][hi]), t = piece_t(x[si][hi]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { a1[hi][j] = low ? u[j] : t[j]; a2[hi][j] = low ? u[j] : 0u; }
     }
-}
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4v a, u32x4v b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-template <int W>
-__device__ __forceinline__ void piece_mfma(const PieceBlk (&x)[8], f32x16 (&acc)[9]) {
+    const u32x4v ub[2] = {piece_u(x[sj][0]), piece_u(x[sj][1])}, tb[2] = {piece_t(x[sj][0]), piece_t(x[sj][1])};
 #pragma unroll
-  for (int s = 0; s < 9; ++s) {
-    const PieceBlk &A = x[Tiles256<W>::si[s]], &B = x[Tiles256<W>::sj[s]];
-    const u32x4v ua = {A.y0[0], A.y0[1], A.y1[0], A.y1[1]}, ta = {A.y2[0], A.y2[1], A.y0[0], A.y0[1]};
-    const u32x4v ub = {B.y0[0], B.y0[1], B.y1[0], B.y1[1]}, tb = {B.y2[0], B.y2[1], B.y0[0], B.y0[1]};
-    acc[s] = mfma_bf16(ua, ub, acc[s]);
-    acc[s] = mfma_bf16(ta, ub, acc[s]);
-    acc[s] = mfma_bf16(ua, tb, acc[s]);
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+        for (int hj = 0; hj < 2; ++hj) {
+          if (si == sj && hi > hj) continue;
+          acc[s][hi][hj] = mfma_bf16(f == 0 ? a1[hi] : a2[hi], f == 0 ? ub[hj] : tb[hj], acc[s][hi][hj]);
+        }
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 template <int W, bool LIST>
-__device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
-                                                FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
+__device__ __forceinline__ void gram_split16_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
+                                                  FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
   const int lane = threadIdx.x & 63;
-  f32x16 acc[9];
+  f32x4 acc[9][2][2];
 #pragma unroll
   for (int s = 0; s < 9; ++s)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
-  const int nch = (a.R + 7) >> 3;  // chunks of 8 tile rows (rows past R are zero; 8 nch <= kYRows)
+    for (int q = 0; q < 4; ++q) acc[s][q >> 1][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // chunks of 8 tile rows (rows past R are zero; 8 n8 <= kYRows): n16 pairs of them and, if n8 is odd, the last one alone
+  const int n8 = (a.R + 7) >> 3, n16 = n8 >> 1;
+  const bool odd = n8 & 1;
+  // dword offsets inside a tile (piece_load): of the lane's reads of chunk 0 -- lane group q reads the row group q of a 16-row
+  // chunk, q & 1 of the odd 8-row one -- and the step from the last 16-row chunk to the odd chunk behind it
+  const int gq = lane >> 4;
+  const int start = (n16 > 0 ? gq : gq & 1) * kGroupDwords + piece_col(lane & 15);
+  const int to_odd = (4 - 2 * (gq >> 1)) * kGroupDwords;
   NodeRanges<LIST> nr;
   nr.init(pptr, list, a.n0, a.N, nn, cnt);
   int32_t p0, p1;
@@ -672,41 +774,44 @@ __device__ __forceinline__ void gram_split_role(const YArgs& a, const int32_t* _
   for (int64_t i = 0; i < cnt; ++i) {
     int32_t q0, q1;
     nr.get(i + 1, q0, q1);
+    // node i's tile: every product wave must have published i + 1 nodes
     while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
     if (p1 > p0) {
-      // chunk ck, lane half h: group 2 ck + h
-      const uint32_t* __restrict__ base = &sh.pc[i & 1][lane >> 5][0][0] + piece_col(lane & 31);
-      PieceBlk xa[8], xb[8];
-      piece_load<W>(base, xa);
-      for (int ck = 0; ck < nch; ck += 2) {  // (wave-uniform trip count; the next chunk's pieces are read while this one's MFMAs run)
-        if (ck + 1 < nch) piece_load<W>(base + (ck + 1) * 2 * kGroupDwords, xb);
-        __builtin_amdgcn_sched_barrier(0);
-        piece_mfma<W>(xa, acc);
-        __builtin_amdgcn_sched_barrier(0);
-        if (ck + 1 < nch) {
-          if (ck + 2 < nch) piece_load<W>(base + (ck + 2) * 2 * kGroupDwords, xa);
-          __builtin_amdgcn_sched_barrier(0);
-          piece_mfma<W>(xb, acc);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+      const uint32_t* __restrict__ tile = &sh.pc[i & 1][0][0][0];
+      int off = start;
+      PieceBlk x[8][2];
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+        if (tiles256_uses<W>(b)) piece_load(tile, off, b, x);
+      __builtin_amdgcn_sched_barrier(0);
+      for (int cc = 0; cc < n16; ++cc) {  // (wave-uniform trip count)
+        off += cc + 1 < n16 ? 4 * kGroupDwords : odd ? to_odd : 0;
+        piece_chunk16<W>(x, acc, tile, off);
       }
+      if (odd) piece_chunk8<W>(x, acc, gq < 2);
     }
-    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
+    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: LDS operations execute in order)
     p0 = q0; p1 = q1;
   }
-  // accumulator layout of 32x32x16 (gram256.h's): column l & 31, rows (r & 3) + 8 (r >> 2) + 4 (l >> 5).  The part below the
-  // diagonal of a diagonal sub-tile is left out, as gram_role leaves it out (the symmetrising pass rewrites it)
+  // gram_role's flush; of a diagonal sub-tile only the part on and above the diagonal (the symmetrising pass rewrites the rest).
+  // (The lane's place is worked out anew, from nothing that lives through the node loop: two registers less there.)
   const int64_t D = a.H;
-  const int l31 = lane & 31, lhi = lane >> 5;
+  const int fl = int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
+  const int li = fl & 15, lq = (fl >> 4) & 3;
 #pragma unroll
-  for (int s = 0; s < 9; ++s) {
-    const int64_t j = Tiles256<W>::sj[s] * 32 + l31;
+  for (int s = 0; s < 9; ++s)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int64_t ii = Tiles256<W>::si[s] * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-      if (ii < D && j < D && (Tiles256<W>::si[s] != Tiles256<W>::sj[s] || ii <= j)) atomicAdd(&scratch[ii * D + j], acc[s][r]);
-    }
-  }
+    for (int hi = 0; hi < 2; ++hi)
+#pragma unroll
+      for (int hj = 0; hj < 2; ++hj) {
+        if (Tiles256<W>::si[s] == Tiles256<W>::sj[s] && hi > hj) continue;
+        const int64_t jj = Tiles256<W>::sj[s] * 32 + 16 * hj + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t ii = Tiles256<W>::si[s] * 32 + 16 * hi + 4 * lq + r;
+          if (ii < D && jj < D && (Tiles256<W>::si[s] != Tiles256<W>::sj[s] || ii <= jj)) atomicAdd(&scratch[ii * D + jj], acc[s][hi][hj][r]);
+        }
+      }
 }
 
 // LIST: the node loop runs over a device-side list of the nodes that have a path
@@ -729,10 +834,10 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   // (hardware waves g and g + 4 share a SIMD: one product wave and one Gram wave on each, see the kernel's header)
   switch (hw) {
     // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
-    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
-    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
-    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
-    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
     default:
       if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
         if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, nn, cnt, hw);
