@@ -305,6 +305,23 @@ LGNN_API int lgnn_lastlayer_pairs_accumulate(lgnn_ctx* h, const int64_t* idx, co
                                     float* Sb_pairs, float* loss_out, void* stream);
 LGNN_API int lgnn_lastlayer_pairs_place(lgnn_ctx* h, const float* S_pairs, const float* Sb_pairs, float* H_out, void* stream);
 
+/* ---- last-layer Kronecker and diagonal GGN of one mini-batch --------------------------------------
+ * What KronLLLaplace / DiagLLLaplace (laplace/lllaplace.py:381-475, 477-...) ask of their backend on the final nn.Linear
+ * alone: CurvlinopsInterface.kron (laplace/curvature/curvlinops.py:77-108) resp. GGNInterface.diag with
+ * last_layer_jacobians (laplace/curvature/curvature.py:132-167, 412-432).  With f_n = W phi_n + s_n b per batch row
+ * (phi_n, s_n as lgnn_lastlayer_features) and the KFAC seeds V_n [C, C] of lgnn_kfac_accumulate (flags:
+ * LGNN_FLAG_FORK_EXACT_SEED or upstream's, for which V_n V_n^T = Lambda_n = diag(p_n) - p_n p_n^T):
+ *   A_out  [D, D] += Phi^T Phi / n_train            Bb_out [C, C] += sum_n s_n^2 V_n V_n^T  (bias block; = B for GraphSAGE)
+ *   B_out  [C, C] += sum_n V_n V_n^T                *loss_out     += sum_n CE(f_n, y_n)
+ *   diag_out [C D + C] += diag(sum_n J_n^T Lambda_n J_n): [c D + d] += Lambda_n[c, c] phi_n[d]^2, [C D + c] += Lambda_n[c, c] s_n^2
+ * All outputs are caller-owned fp32 device buffers that are ADDED to; the calls are asynchronous on `stream`.  Every batch
+ * row is one sample (a repeated node id counts twice).  Classification only; models of any depth.  Nothing of size M C C
+ * is written to memory: softmax and seeds live in registers / LDS, the sums are reduced per workgroup.                */
+LGNN_API int lgnn_lastlayer_kron_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, int64_t n_train,
+                                   uint32_t flags, float* A_out, float* B_out, float* Bb_out, float* loss_out, void* stream);
+LGNN_API int lgnn_lastlayer_diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* diag_out,
+                                   float* loss_out, void* stream);
+
 /* Invalid batch contents (node ids outside [0, N), labels outside [0, C)) are detected on the device: such
  * samples contribute nothing and a sticky flag is raised.  This call synchronises `stream`, reports the flag
  * (non-zero return + message) and clears it; call it once per fit, not per batch.                          */

@@ -10,12 +10,12 @@ from .curvature import HipCurvatureInterface, HipEF, HipGGN  # noqa: F401
 from .data import TensorBatchLoader, batches_of_rank, units_of_rank  # noqa: F401
 from .engine import GraphEngine  # noqa: F401
 from .knn import get_knn_graph, knn, knn_candidates, knn_graph  # noqa: F401
-from .laplace import (BaseLaplace, DiagLaplace, FullLaplace, FullLLLaplace, KronLaplace, Laplace,  # noqa: F401
-                      ParametricLaplace, all_reduce_flat_)
+from .laplace import (BaseLaplace, DiagLaplace, DiagLLLaplace, FullLaplace, FullLLLaplace, KronLaplace,  # noqa: F401
+                      KronLLLaplace, Laplace, ParametricLaplace, all_reduce_flat_)
 from .matrix import Kron, KronDecomposed, symeig  # noqa: F401
 from .models import GCN, STEGCN, GraphSAGE, LoRASTEGCN  # noqa: F401
 
 __all__ = ["GraphEngine", "HipGGN", "HipEF", "HipCurvatureInterface", "Laplace", "BaseLaplace", "ParametricLaplace",
-           "KronLaplace", "DiagLaplace", "FullLaplace", "FullLLLaplace", "Kron", "KronDecomposed", "symeig", "GCN", "STEGCN", "LoRASTEGCN", "GraphSAGE",
+           "KronLaplace", "DiagLaplace", "FullLaplace", "FullLLLaplace", "KronLLLaplace", "DiagLLLaplace", "Kron", "KronDecomposed", "symeig", "GCN", "STEGCN", "LoRASTEGCN", "GraphSAGE",
            "TensorBatchLoader", "batches_of_rank", "units_of_rank", "all_reduce_flat_", "knn", "knn_graph", "get_knn_graph",
            "knn_candidates"]

@@ -57,6 +57,8 @@ SIGNATURES = {
     "lgnn_lastlayer_features": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_lastlayer_pairs_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "lgnn_lastlayer_pairs_place": (_i32, [_vp, _vp, _vp, _vp, _vp]),
+    "lgnn_lastlayer_kron_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_lastlayer_diag_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_check_async_errors": (_i32, [_vp, _vp]),
     "lgnn_peek_async_errors": (_i32, [_vp]),
     "lgnn_kfac_batch_tag": (_i32, [_vp, C.c_uint64]),

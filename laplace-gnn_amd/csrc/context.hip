@@ -572,6 +572,19 @@ extern "C" int lgnn_lastlayer_pairs_place(lgnn_ctx* h, const float* S_pairs, con
   return lastlayer_pairs_place(h, S_pairs, Sb_pairs, H_out, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int lgnn_lastlayer_kron_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, int64_t n_train,
+                                              uint32_t flags, float* A_out, float* B_out, float* Bb_out, float* loss_out,
+                                              void* stream) {
+  if (!h) { set_error("null context"); return 2; }
+  return lastlayer_kron_accumulate(h, idx, y, M, n_train, flags, A_out, B_out, Bb_out, loss_out,
+                                   static_cast<hipStream_t>(stream));
+}
+extern "C" int lgnn_lastlayer_diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* diag_out,
+                                              float* loss_out, void* stream) {
+  if (!h) { set_error("null context"); return 2; }
+  return lastlayer_diag_accumulate(h, idx, y, M, diag_out, loss_out, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int lgnn_lastlayer_features(lgnn_ctx* h, const int64_t* idx, int64_t M, float* phi_out, float* f_out, void* stream) {
   if (!h) { set_error("null context"); return 2; }
   return lastlayer_features(h, idx, M, phi_out, f_out, static_cast<hipStream_t>(stream));

@@ -26,20 +26,6 @@ namespace lgnn {
 
 namespace {
 
-struct FeatView {  // E[v, i]: i < width -> base[v*ld + i]; i == width -> bias column
-  const float* base;
-  int64_t ld;
-  int64_t width;
-  const float* bias_col;  // per-node scale (rowsum) or nullptr for the constant 1
-  int64_t nrows;          // node ids outside [0, nrows) (flagged by the batch prologue) read as zero rows
-};
-
-__device__ __forceinline__ float feat(const FeatView& f, int64_t v, int64_t i) {
-  if (v < 0 || v >= f.nrows) return 0.f;
-  if (i < f.width) return f.base[v * f.ld + i];
-  return f.bias_col ? f.bias_col[v] : 1.f;
-}
-
 // q[m, j] = w_j^T Lambda_m u_j = sum_k p_k w_kj u_kj - (sum_k p_k w_kj)(sum_k p_k u_kj)
 // out[0] = (neigh,neigh), out[1] = (self,neigh), out[2] = (self,self); W1 is [C, ldw]
 __global__ void q_kernel(const float* __restrict__ probs, int64_t M, int64_t C, const float* __restrict__ W1,
@@ -908,6 +894,8 @@ __global__ __launch_bounds__(256) void sumsq_rows_kernel(const float* __restrict
   atomicAdd(&diag[p], scale * acc);
 }
 
+}  // namespace
+
 int feat_views(lgnn_ctx* h, int layer, FeatView& f) {
   f.nrows = h->N;
   // what Linear `layer` multiplies, seen from an output node: propagated input (GCN) or cat (GraphSAGE)
@@ -925,7 +913,12 @@ int feat_views(lgnn_ctx* h, int layer, FeatView& f) {
   return 0;
 }
 
-}  // namespace
+int launch_ll_build_phi(const int64_t* idx, int64_t M, const FeatView& Phi, int64_t ldp, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(ll_build_phi_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M * ldp, 256), 8192))), dim3(256), 0, s, idx, M,
+                     Phi, ldp, out);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 
 int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags, float* diag_out,
                     float* loss_out, hipStream_t s) {
@@ -1202,9 +1195,7 @@ int lastlayer_features(lgnn_ctx* h, const int64_t* idx, int64_t M, float* out, f
   FeatView Phi;
   feat_views(h, h->L - 1, Phi);
   const int64_t D1 = Phi.width + 1;
-  hipLaunchKernelGGL(ll_build_phi_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M * D1, 256), 8192))), dim3(256), 0, s, idx, M,
-                     Phi, D1, out);
-  LGNN_HIP_CHECK(hipGetLastError());
+  LGNN_CALL(launch_ll_build_phi(idx, M, Phi, D1, out, s));
   if (f_out)
     LGNN_CALL(launch_gather_rows(h->fc.out.as<float>(), h->dims[h->L], h->N, idx, M, h->dims[h->L], f_out,
                                  h->ws.flags.as<int>() + 2, s));
@@ -1237,9 +1228,7 @@ int lastlayer_pairs_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, i
   float* rs = PhiM + M * ldp;
   float* wsg = rs + qc_max * M;
   float* zsign = wsg + qc_max * M;
-  hipLaunchKernelGGL(ll_build_phi_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M * ldp, 256), 8192))), dim3(256), 0, s,
-                     idx, M, Phi, ldp, PhiM);
-  LGNN_HIP_CHECK(hipGetLastError());
+  LGNN_CALL(launch_ll_build_phi(idx, M, Phi, ldp, PhiM, s));
   for (int64_t q0 = 0; q0 < Q; q0 += qc_max) {
     const int64_t qc = std::min(qc_max, Q - q0);
     hipLaunchKernelGGL(ll_pair_weights_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M, 256), 64)), unsigned(qc)),

@@ -586,6 +586,22 @@ int ensure_wt(lgnn_ctx* h, hipStream_t s);           // transposed weights (forw
 bool gcn2_small_forward_supported(const lgnn_ctx* h);
 int gcn2_forward_through_px(lgnn_ctx* h, hipStream_t s);
 // ---- diag.hip ---------------------------------------------------------------------------
+// What a Linear multiplies, seen from an output node, plus its bias column: the rows the diagonal and last-layer kernels gather
+struct FeatView {  // E[v, i]: i < width -> base[v*ld + i]; i == width -> bias column
+  const float* base;
+  int64_t ld;
+  int64_t width;
+  const float* bias_col;  // per-node scale (rowsum) or nullptr for the constant 1
+  int64_t nrows;          // node ids outside [0, nrows) (flagged by the batch prologue) read as zero rows
+};
+__device__ __forceinline__ float feat(const FeatView& f, int64_t v, int64_t i) {
+  if (v < 0 || v >= f.nrows) return 0.f;
+  if (i < f.width) return f.base[v * f.ld + i];
+  return f.bias_col ? f.bias_col[v] : 1.f;
+}
+int feat_views(lgnn_ctx* h, int layer, FeatView& f);  // needs forward_ensure_aux
+// out [M, ldp] = [phi_n | s_n | 0 ...] of the batch rows (ll_build_phi_kernel)
+int launch_ll_build_phi(const int64_t* idx, int64_t M, const FeatView& Phi, int64_t ldp, float* out, hipStream_t s);
 int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags, float* diag_out,
                     float* loss_out, hipStream_t s);
 int lastlayer_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out,
@@ -597,6 +613,11 @@ int lastlayer_pairs_place(lgnn_ctx* h, const float* S, const float* Sb, float* H
 int full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out, float* loss_out, hipStream_t s);
 int ef_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y_seed, const void* y_loss, int64_t M, float resid_scale,
                   float scale, float* diag_out, float* full_out, float* grads_out, float* loss_out, hipStream_t s);
+// ---- lastlayer_kron.hip -----------------------------------------------------------------
+int lastlayer_kron_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, int64_t n_train, uint32_t flags,
+                              float* A_out, float* B_out, float* Bb_out, float* loss_out, hipStream_t s);
+int lastlayer_diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* diag_out, float* loss_out,
+                              hipStream_t s);
 // ---- jacobian.hip -----------------------------------------------------------------------
 int jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out, hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------

@@ -9,6 +9,8 @@ laplace/curvature/curvlinops.py:20-167 (CurvlinopsInterface / CurvlinopsGGN):
   A already rescaled by M/N, everything multiplied by ``factor`` the way ``Kron.__mul__`` does
   (curvlinops.py:55-75, 46-53, 104-108); fresh tensors on every call (callers mutate them);
 * ``diag(x, y, **kw) -> (loss, H[P])``  (curvature.py:412-432);
+* ``last_layer=True``: ``kron`` returns the two-block ``Kron([[B, A], [B_b]])`` of the final nn.Linear alone and ``diag`` the
+  ``[C D + C]`` diagonal of its GGN (what laplace/lllaplace.py:381-475, 477-... fit);
 * ``full(x, y, **kw) -> (loss, H[P, P])`` -- implemented for ``last_layer=True`` (curvature.py:374-410
   with last_layer_jacobians :132-167);
 * attributes ``lossfunc``, ``factor``, ``params``, ``params_dict``, ``buffers_dict``, ``model``,
@@ -90,7 +92,7 @@ class HipCurvatureInterface:
             raise TypeError("HipGGN needs a model that exposes a HIP `engine` (laplace_gnn_amd.models.GCN / "
                             "GraphSAGE); there is no generic autograd fallback")
         if likelihood == "regression" and last_layer:
-            raise NotImplementedError("last-layer full GGN: classification likelihood only")
+            raise NotImplementedError("last-layer GGN (full / kron / diag): classification likelihood only")
         if stochastic and last_layer:
             # the reference applies the MC functional Fisher to last_layer_jacobians here (laplace/curvature/curvature.py:
             # 343-364, 374-432); the last-layer kernels build the exact GGN only -- refuse rather than ignore the flag
@@ -166,6 +168,10 @@ class HipCurvatureInterface:
         device unless the caller brings them (reproducibility across devices)."""
         if kwargs:
             raise NotImplementedError(f"unsupported kron kwargs {sorted(kwargs)} (kfac_approx)")
+        if self.last_layer:  # (stochastic / regression / HipEF with last_layer were refused by the constructor)
+            _, A, B, Bb, loss = self.engine.new_lastlayer_kron_buffers()
+            self.lastlayer_kron_accumulate_(A, B, Bb, loss, x, y, N)
+            return self.factor * loss[0].clone(), self.pack_lastlayer_kron(A, B, Bb)
         if self._kron_fisher_type == "mc":
             draws = list(mc_labels) if mc_labels is not None else [self.draw_labels(x) for _ in range(int(mc_samples))]
             return self._fisher_kron(x, y, N, draws)
@@ -190,8 +196,40 @@ class HipCurvatureInterface:
                               full=H if full else None, loss=loss if s_ == 0 else None)
         return self.factor * loss[0], H
 
+    # ---- kron / diag of the final nn.Linear alone (last_layer=True) -------------------------------
+    def lastlayer_kron_accumulate_(self, A: torch.Tensor, B: torch.Tensor, Bb: torch.Tensor, loss_buf: torch.Tensor,
+                                   x: torch.Tensor, y: torch.Tensor, N: int):
+        """Add this batch's RAW last-layer factors (``A = Phi^T Phi / N``, ``B = sum V V^T``, ``B_b = sum s^2 V V^T``) and loss
+        into caller-owned buffers (``GraphEngine.new_lastlayer_kron_buffers``): CurvlinopsInterface.kron on the head
+        (laplace/curvature/curvlinops.py:77-108) as KronLLLaplace asks for it (laplace/lllaplace.py:381-475)."""
+        if not self.last_layer or self.likelihood != "classification":
+            raise NotImplementedError("last-layer Kronecker accumulation: last_layer=True, classification likelihood")
+        self.engine.set_likelihood("classification")
+        self.engine.lastlayer_kron_accumulate(x, y, N, A, B, Bb, loss_buf, fork_exact=self.fork_exact_seed)
+
+    def pack_lastlayer_kron(self, A: torch.Tensor, B: torch.Tensor, Bb: torch.Tensor) -> Kron:
+        """``Kron([[B, A], [B_b]])`` times ``factor`` distributed like ``pack_kron``; fresh tensors.  No tied-factor hint: a
+        GCN's bias block is ``sum s^2 V V^T``, not ``B``."""
+        f, f2 = self.factor, self.factor ** 0.5
+        return _kron_class()([[B * f2 if f != 1.0 else B.clone(), A * f2 if f != 1.0 else A.clone()],
+                              [Bb * f if f != 1.0 else Bb.clone()]])
+
+    def lastlayer_diag_accumulate_(self, H: torch.Tensor, loss_buf: torch.Tensor, x: torch.Tensor, y: torch.Tensor):
+        """Diagonal of the last-layer GGN of one batch added IN PLACE to the caller's ``H [C D + C]`` and the raw loss sum to
+        ``loss_buf``: GGNInterface.diag on last_layer_jacobians (laplace/curvature/curvature.py:132-167, 412-432)."""
+        if not self.last_layer or self.likelihood != "classification":
+            raise NotImplementedError("last-layer diagonal accumulation: last_layer=True, classification likelihood")
+        self.engine.set_likelihood("classification")
+        self.engine.lastlayer_diag_accumulate(x, y, H, loss_buf)
+
     # ---- diag ----------------------------------------------------------------------------------
     def diag(self, x: torch.Tensor, y: torch.Tensor, mc_labels=None, **kwargs: Any):
+        if self.last_layer:
+            eng = self.engine
+            H = torch.zeros(eng.in_dims[-1] * eng.dims[-1] + eng.dims[-1], dtype=torch.float32, device=eng.device)
+            loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
+            self.lastlayer_diag_accumulate_(H, loss, x, y)
+            return self.factor * loss[0], H
         if self.stochastic:
             return self._mc_functional_fisher(x, y, full=False, mc_labels=mc_labels)
         self.engine.set_likelihood(self.likelihood)  # regression: H = sum J^T J on the device (no factor on H)
@@ -283,6 +321,11 @@ class HipCurvatureInterface:
         Jw = torch.einsum("kp,ij->kijp", phi, eye).reshape(M, C, C * D)
         Jb = s.reshape(M, 1, 1) * eye.unsqueeze(0)
         return torch.cat([Jw, Jb], dim=2), f
+
+    def lastlayer_features(self, x: torch.Tensor):
+        """(phi [M, D], s [M], f [M, C]) with ``f_n = W phi_n + s_n b`` for the head ``model.convs[-1].lin``: what the
+        last-layer posteriors evaluate their predictive from."""
+        return self.engine.lastlayer_features(x)
 
     def gradients(self, x: torch.Tensor, y: torch.Tensor):
         """(Gs [M, P], loss): per-sample gradients of the summed loss, ``G_n = J_n^T d loss_n / d f_n``

@@ -643,6 +643,37 @@ class GraphEngine:
                                                  _dev_ptr(H, torch.float32, "H"), _stream(self.device))
         _lib.check(rc, "lgnn_lastlayer_pairs_place")
 
+    def new_lastlayer_kron_buffers(self):
+        """Zeroed accumulators of the last-layer Kronecker GGN as ONE flat buffer [A | B | B_b | loss] (one all-reduce) plus
+        views: A [D, D], B [C, C], B_b [C, C] (the bias block's factor), loss [1]."""
+        C, D = self.dims[-1], self.in_dims[-1]
+        flat = torch.zeros(D * D + 2 * C * C + 1, dtype=torch.float32, device=self.device)
+        A = flat[:D * D].view(D, D)
+        B = flat[D * D:D * D + C * C].view(C, C)
+        Bb = flat[D * D + C * C:D * D + 2 * C * C].view(C, C)
+        return flat, A, B, Bb, flat[-1:]
+
+    def lastlayer_kron_accumulate(self, idx, y, n_train: int, A: torch.Tensor, B: torch.Tensor, Bb: torch.Tensor,
+                                  loss: torch.Tensor, fork_exact: bool = True):
+        """A += Phi^T Phi / n_train, B += sum_n V_n V_n^T, B_b += sum_n s_n^2 V_n V_n^T, loss += CE sum of the batch over the
+        final Linear alone (``lgnn_lastlayer_kron_accumulate``); classification bindings only."""
+        self._sync_versions()
+        idx, y = idx.contiguous(), y.contiguous()
+        rc = self.lib.lgnn_lastlayer_kron_accumulate(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0], int(n_train),
+            _lib.FLAG_FORK_EXACT_SEED if fork_exact else 0, _dev_ptr(A, torch.float32, "A"), _dev_ptr(B, torch.float32, "B"),
+            _dev_ptr(Bb, torch.float32, "Bb"), loss.data_ptr(), _stream(self.device))
+        _lib.check(rc, "lgnn_lastlayer_kron_accumulate")
+
+    def lastlayer_diag_accumulate(self, idx, y, diag: torch.Tensor, loss: torch.Tensor):
+        """diag [C D + C] += diagonal of the last-layer GGN of the batch (weight row major, then bias), loss += CE sum."""
+        self._sync_versions()
+        idx, y = idx.contiguous(), y.contiguous()
+        rc = self.lib.lgnn_lastlayer_diag_accumulate(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
+            _dev_ptr(diag, torch.float32, "diag"), loss.data_ptr(), _stream(self.device))
+        _lib.check(rc, "lgnn_lastlayer_diag_accumulate")
+
     def jacobians(self, idx: torch.Tensor):
         """(J [M, C, P], f [M, C]): per-sample Jacobians of the logits w.r.t. all parameters, parameters in
         module order (weight row major, bias) -- laplace/curvature/curvature.py:89-130."""
