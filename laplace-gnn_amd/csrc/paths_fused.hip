@@ -7,8 +7,10 @@
 //       classes of the launch.  Per step of FOUR paths: three 16-byte loads of the paths' coefficient rows (A operands: lane
 //       (i, k) = class slot i of path k, the four class tiles of a slot side by side in the table row), two 16-byte loads of
 //       the table rows b_m, g_m (B operands: lane (i, k) = columns 64 cg + 4 i .. + 3 of path k -- the four 16-column MFMA
-//       tiles of the wave interleave the columns, so one load feeds all four), one mask word; 36 v_mfma_f32_16x16x4_f32
-//       (3 class tiles x 4 column tiles x (alpha, beta, gamma)).  No LDS staging, no window, no restaging of hubs: the
+//       tiles of the wave interleave the columns, so one load feeds all four), one mask word; 24 v_mfma_f32_16x16x4_f32
+//       (3 class tiles x 4 column tiles x (beta, gamma): 768 cycles) per step and, per PAIR of steps, 12
+//       v_mfma_f32_16x16x32_bf16 for the alpha product of both (192 cycles, exact: the mask is 0 / 1 and the weighted
+//       coefficient goes in as three bf16 pieces along K, see PAlpha).  No LDS staging, no window, no restaging of hubs: the
 //       operands of step s + 1 are in flight while the MFMAs of step s issue, across node boundaries (a node's triples
 //       (m, v, w) arrive with ONE coalesced load a node ahead and are handed to the lanes with ds_bpermute).
 //       Y[n] = W_1 (.) T1 + Y2 (W_1's rows straight from L2) is split into three bf16 pieces HERE, once per value, and the
@@ -224,76 +226,128 @@ __device__ __forceinline__ void p_wait(POps& o) {
                  : "n"(YOUNGER) : "memory");
 }
 
-// A step's MFMA operands: lane (i, k): A[row i][k] = weighted coefficient of class 16 t + i, B[k][col i] = mask bit / masked
-// table value of the lane's column ct.  HI (a second launch of a call with more than 48 classes): the launch's only class
-// tile is the fourth of the slot.  26 vector instructions (each costs the SIMD's matrix pipe its issue cycles, see above):
-// bit ct of the mask word as 0 / -1 with one v_bfe_i32, ANDed with 1.0f.
-struct PCur { float a0[3], a1[3], a2[3], mf[4], bb[4], gg[4]; };
-template <bool NOBG, bool HI>
-__device__ __forceinline__ void p_xform(const POps& o, const PLane& pl, PCur& c) {
+// A step's beta / gamma MFMA operands: lane (i, k): A[row i][k] = weighted coefficient of class 16 t + i, B[k][col i] = masked
+// table value of the lane's column ct.
+struct PCur { float a1[3], a2[3], bb[4], gg[4]; };
+// The alpha product T1 += (w alpha) Mk of a PAIR of steps as v_mfma_f32_16x16x32_bf16, exactly.  Mk is 0 or 1 and a bf16 as it
+// is; a = w alpha is cut into three bf16 pieces by TRUNCATION,
+//   r1 = a - (a & 0xffff0000), r2 = r1 - (r1 & 0xffff0000), pieces = the high halves of a, r1, r2:
+// a's high half keeps 8 significant bits, so r1 has at most 16 and r2 at most 8: both differences are exact, r2's low half
+// is zero, and the three pieces sum to a.  (Only a piece below fp32's normal range, |r2| < 1.2e-38, is not safe: the bf16 MFMA
+// may flush it, an error below 1e-38 per term.)  Every piece meets 0 or 1, so the products are exact and no cross term exists.
+// The instruction's lane (i, q) holds A[row i][k = 8 q + j] and B[k = 8 q + j][col i], j = 0 .. 7, in four registers: lane
+// group q is path q of the pair's step A and path q of its step B, and its eight K slots are its own registers,
+//   A operand of class tile t:   a a1 | a2 b | b1 b2 | 0 0     (pieces of step A's path, of step B's path, two empty slots)
+//   B operand of column tile ct: mA mA | mA mB | mB mB | 0 0   (bf16 1.0 where the step's path has the column's mask bit)
+// with D laid out as the fp32 16x16x4's (col i, rows 4 q + r).  Step A's transform writes its slots (and zero into the high
+// half of the shared register), step B's adds its own.  In a `half` pair step B's slots are written all the same, from B's
+// landed operands: its paths lie past the chunk's last one and have weight zero (meta_finish), so its slots of the A operand
+// are zero whatever its mask bits are.
+struct PAlpha { u32x4v a[3], m[4]; };
+constexpr uint32_t kHiHalves = 0x07060302u;  // v_perm_b32(x, y): y's high half below x's high half
+// One step's MFMA operands.  SB: the pair's second step.  HI (a second launch of a call with more than 48 classes): the
+// launch's only class tile is the fourth of the slot.  `bg`: also the beta / gamma operands (not in a `half` pair's second
+// step).  About 48 vector instructions (each costs the SIMD's matrix pipe its issue cycles, see above): 7 per class tile for
+// the alpha pieces (multiply, two ANDs, two subtractions, two to pack), 13 for the mask -- bit ct of the mask word as 0 / -1
+// with one v_bfe_i32, ANDed with the bf16 ones of its slots --, 6 + 8 for beta / gamma.
+template <bool NOBG, bool HI, bool SB>
+__device__ __forceinline__ void p_xform(const POps& o, const PLane& pl, PCur& c, PAlpha& al, bool bg) {
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
     const int tt = HI ? 3 : t;
-    c.a0[t] = (HI && t > 0) ? 0.f : o.w * o.ca[0][tt];
-    if constexpr (!NOBG) {
-      c.a1[t] = (HI && t > 0) ? 0.f : o.w * o.ca[1][tt];
-      c.a2[t] = (HI && t > 0) ? 0.f : o.w * o.ca[2][tt];
+    if (HI && t > 0) {
+      if constexpr (!SB) al.a[t][0] = 0u;
+      al.a[t][1] = 0u; al.a[t][2] = 0u;
+      continue;
+    }
+    // (the empty statement keeps hipcc from contracting the multiply into the subtraction: the pieces are those of the
+    // ROUNDED product, and r1 has 16 significant bits only as the difference of two fp32 numbers)
+    float av = o.w * o.ca[0][tt];
+    asm("" : "+v"(av));
+    const uint32_t h0 = __float_as_uint(av) & 0xffff0000u;
+    const float r1 = av - __uint_as_float(h0);
+    const float r2 = r1 - __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
+    if constexpr (!SB) {
+      al.a[t][0] = __builtin_amdgcn_perm(__float_as_uint(r1), __float_as_uint(av), kHiHalves);
+      al.a[t][1] = __float_as_uint(r2) >> 16;
+    } else {
+      al.a[t][1] |= h0;
+      al.a[t][2] = __builtin_amdgcn_perm(__float_as_uint(r2), __float_as_uint(r1), kHiHalves);
     }
   }
   const int bits = int(o.mw >> pl.mshift);
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
     const int on = __builtin_amdgcn_sbfe(bits, ct, 1);  // 0 or -1
-    c.mf[ct] = __int_as_float(on & 0x3f800000);
-    if constexpr (!NOBG) { c.bb[ct] = c.mf[ct] * o.b4[ct]; c.gg[ct] = c.mf[ct] * o.g4[ct]; }
+    if constexpr (!SB) {
+      al.m[ct][0] = uint32_t(on) & 0x3f803f80u;
+      al.m[ct][1] = uint32_t(on) & 0x00003f80u;
+    } else {
+      al.m[ct][1] |= uint32_t(on) & 0x3f800000u;
+      al.m[ct][2] = uint32_t(on) & 0x3f803f80u;
+    }
+  }
+  if constexpr (!NOBG) {
+    if (bg) {  // (wave uniform)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const int tt = HI ? 3 : t;
+        c.a1[t] = (HI && t > 0) ? 0.f : o.w * o.ca[1][tt];
+        c.a2[t] = (HI && t > 0) ? 0.f : o.w * o.ca[2][tt];
+      }
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const int on = __builtin_amdgcn_sbfe(bits, ct, 1);
+        c.bb[ct] = __uint_as_float(uint32_t(on) & __float_as_uint(o.b4[ct]));
+        c.gg[ct] = __uint_as_float(uint32_t(on) & __float_as_uint(o.g4[ct]));
+      }
+    }
   }
 }
 // an empty statement that reads every register of `c`: keeps the set alive (and out of the other set's registers) up to here
 template <bool NOBG>
 __device__ __forceinline__ void p_keep(const PCur& c) {
-  asm volatile("" :: "v"(c.a0[0]), "v"(c.a0[1]), "v"(c.a0[2]), "v"(c.mf[0]), "v"(c.mf[1]), "v"(c.mf[2]), "v"(c.mf[3]));
   if constexpr (!NOBG) {
     asm volatile("" :: "v"(c.a1[0]), "v"(c.a1[1]), "v"(c.a1[2]), "v"(c.a2[0]), "v"(c.a2[1]), "v"(c.a2[2]));
     asm volatile("" :: "v"(c.bb[0]), "v"(c.bb[1]), "v"(c.bb[2]), "v"(c.bb[3]), "v"(c.gg[0]), "v"(c.gg[1]), "v"(c.gg[2]), "v"(c.gg[3]));
   }
 }
-// the 36 (NOBG: 12) MFMAs of one step;  D: col = i, row = 4 k + r
-template <bool NOBG>
-__device__ __forceinline__ void p_mfma(const PCur& c, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4]) {
+__device__ __forceinline__ f32x4 mfma_bf16(u32x4v a, u32x4v b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// the 24 beta / gamma MFMAs of one step (v_mfma_f32_16x16x4_f32);  D: col = i, row = 4 k + r
+__device__ __forceinline__ void p_mfma(const PCur& c, f32x4 (&y2)[3][4]) {
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) t1[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a0[t], c.mf[ct], t1[t][ct], 0, 0, 0);
-  if constexpr (!NOBG) {
+    for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], y2[t][ct], 0, 0, 0);
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+  for (int t = 0; t < 3; ++t)
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], y2[t][ct], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
-  }
+    for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
 }
-// A node's FIRST step: the alpha and beta products take the inline constant 0 as C and so START the node's accumulators
-// (the gamma product accumulates into the beta one): nothing clears the 96 accumulator registers between nodes.
-template <bool NOBG>
-__device__ __forceinline__ void p_mfma_first(const PCur& c, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4]) {
+// A node's FIRST pair: its alpha product and its first step's beta product take the inline constant 0 as C and so START the
+// node's accumulators (the gamma product accumulates into the beta one): nothing clears the 96 accumulator registers between
+// nodes.
+__device__ __forceinline__ void p_mfma_first(const PCur& c, f32x4 (&y2)[3][4]) {
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) t1[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a0[t], c.mf[ct], zero, 0, 0, 0);
-  if constexpr (!NOBG) {
+    for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], zero, 0, 0, 0);
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+  for (int t = 0; t < 3; ++t)
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a1[t], c.bb[ct], zero, 0, 0, 0);
+    for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
+}
+// the 12 alpha MFMAs of a pair (v_mfma_f32_16x16x32_bf16)
+template <bool FIRST>
+__device__ __forceinline__ void p_mfma_alpha(const PAlpha& al, f32x4 (&t1)[3][4]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < 3; ++t)
+  for (int t = 0; t < 3; ++t)
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
-  }
+    for (int ct = 0; ct < 4; ++ct) t1[t][ct] = mfma_bf16(al.a[t], al.m[ct], FIRST ? zero : t1[t][ct]);
 }
 
 // The product wave's work as a stream of CHUNKS: at most 64 paths of one node (one register of triples); a node is one chunk
@@ -328,44 +382,53 @@ struct ChunkGen {
 
 // The product wave of SIMD cg.  Steps come in PAIRS (8 paths): buffer A holds the loaded operands of the pair's first step, B
 // of its second; each is refilled for the NEXT pair -- this chunk's, or the next chunk's first (usually the next node's) --
-// right after its values were turned into MFMA operands, so two steps' loads (12 instructions) are in flight behind the 36
-// MFMAs being issued.  The loads are unconditional and in one fixed order, the hand-counted waits rely on it; A / B are written
+// right after its values were turned into MFMA operands, so two steps' loads (12 instructions) are in flight behind the
+// MFMAs being issued.  A pair's order: wait A, transform A (its beta / gamma operands and its slots of the alpha operands),
+// refill A, A's 24 beta / gamma MFMAs, wait B, transform B, refill B, the pair's 12 alpha MFMAs, B's 24 beta / gamma MFMAs
+// (regression likelihood, NOBG: the 12 alpha MFMAs are the pair's only ones).  The loads are unconditional and in one fixed order, the hand-counted waits rely on it; A / B are written
 // nowhere else inside the loop.  Hence the chunk stream: hubs and empty nodes take the same path as everything else; a step past
 // the chunk's last path multiplies zero weights (meta_finish), an empty chunk is one such step.
 // A pair is ONE body with two wave-uniform flags, and the flags only choose among MFMAs and the operand transform: every load,
 // wait, p_keep pin and refill is outside the branches, in the same order and number whatever the flags are, so every counted
 // vmcnt holds whichever pairs follow each other.
-//   first  the first pair of a node: its first step's alpha and beta MFMAs take C = 0 (p_mfma_first), which is what clears
-//          the accumulators -- nothing else does;
+//   first  the first pair of a node: its alpha MFMAs and its first step's beta MFMAs take C = 0 (p_mfma_alpha<true>,
+//          p_mfma_first), which is what clears the accumulators -- nothing else does;
 //   half   the last pair of a chunk whose second step has no path (4 (2 j + 1) >= paths of the chunk): p_wait(B) and B's refill
-//          stay, p_xform(B) and B's MFMAs are left out -- B's landed operands are overwritten by the refill unread.
+//          stay, B's beta / gamma operands and MFMAs are left out; its slots of the alpha operands are written as ever (zero
+//          weights: see PAlpha) -- a branch around them makes hipcc keep the seven operand tuples twice and copy them.
 // (Four complete straight-line bodies, one per flag combination, is what was tried first: hipcc then gives the accumulators
 // and the in-flight operand registers new values per body, moves them between registers at the joins and spills 130 - 500
 // registers; with the branches around the MFMAs alone the accumulators stay where they are.)
 // An earlier branch around the second step's MFMAs "gave wrong tiles now and then".  Its code is gone, so the cause cannot be
 // read off it; the two suspects are the MFMA -> VALU wait states between a branch's last MFMA and the tile write's first
-// accumulator read, and a load inside the branch that broke the counts.  In the ISA of the straight-line loop twelve buffer
+// accumulator read (in a `half` pair that MFMA is a 16x16x32 bf16 one now: no more passes than the fp32 one), and a load inside
+// the branch that broke the counts.  In the ISA of the straight-line loop twelve buffer
 // loads, the poll of `done` (an LDS read and its wait) and a vmcnt(0) lie between the two, far more than the 12 wait states of
 // the 8-pass 16x16x4 -- but nothing there is a guarantee, and hipcc places no s_nop of its own.  Both are excluded by
 // construction now: no branch holds a load, and `s_nop 11` (12 wait states) sits in front of the tile write's first
 // accumulator read on every path.
 template <bool NOBG, bool HI>
 __device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, int sx, const PLane& pl, POps& A, POps& B, PCur& cA,
-                                          PCur& cB, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4], bool first, bool half) {
+                                          PCur& cB, PAlpha& al, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4], bool first, bool half) {
   constexpr int NL = kStepLoads<NOBG>;
   // A's loads: the NL youngest outstanding may be B's (the first pair of a chunk: B's and the three path loads -- there
   // the count also waits for B's first half, issued a whole pair earlier)
   p_wait<NOBG, NL>(A);
-  p_xform<NOBG, HI>(A, pl, cA);
+  p_xform<NOBG, HI, false>(A, pl, cA, al, true);
   p_keep<NOBG>(cB);  // (cB's MFMAs may still be queued: cA must not be prepared into their operand registers)
   p_load<NOBG>(tb, mx, sx, pl, A);
-  if (first) p_mfma_first<NOBG>(cA, t1, y2);
-  else p_mfma<NOBG>(cA, t1, y2);
+  if constexpr (!NOBG) {
+    if (first) p_mfma_first(cA, y2);
+    else p_mfma(cA, y2);
+  }
   p_wait<NOBG, NL>(B);  // (younger: A's refill)
-  if (!half) p_xform<NOBG, HI>(B, pl, cB);
+  p_xform<NOBG, HI, true>(B, pl, cB, al, !half);
   p_keep<NOBG>(cA);  // (likewise)
   p_load<NOBG>(tb, mx, sx + 1, pl, B);
-  if (!half) p_mfma<NOBG>(cB, t1, y2);
+  if (first) p_mfma_alpha<true>(al, t1);
+  else p_mfma_alpha<false>(al, t1);
+  if constexpr (!NOBG)
+    if (!half) p_mfma(cB, y2);
 }
 template <bool LIST, bool NOBG, bool HI>
 __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
@@ -395,9 +458,6 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   // W_1's rows of the launch, read at the tile write (48 KB that every workgroup reads: L2 resident)
   const uint32_t w1_row_bytes = uint32_t(a.w1_ld) * 4u;
   const i32x4 w1rs = make_rsrc(a.W1 + int64_t(a.c0) * a.w1_ld, uint64_t(a.R - 1) * w1_row_bytes + row_bytes);
-  const uint32_t w1_off = col_ok ? uint32_t(4 * pl.kq) * w1_row_bytes + 4u * uint32_t(col) : 0x7ff00000u;
-  // the lane's two 16-byte stores inside a piece plane (dword offsets: columns col, col + 1 and col + 2, col + 3)
-  const int pc_lo = 8 * (col >> 2) + 4 * piece_swap(col >> 2), pc_hi = pc_lo ^ 4;
   constexpr int NL = kStepLoads<NOBG>;
   ChunkGen<LIST> gen;
   gen.init(pptr, list, a.n0, a.N, nn, cnt);
@@ -423,6 +483,12 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   // Two sets of prepared MFMA operands, alternating (p_keep pins them to registers of their own): the next step is prepared
   // while the MFMAs of the previous one may still be reading theirs.
   PCur cA = {}, cB = {};
+  // the pair's alpha operands; the fourth register of each (the two empty K slots) stays zero
+  PAlpha al;
+#pragma unroll
+  for (int t = 0; t < 3; ++t) al.a[t] = u32x4v{0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) al.m[ct] = u32x4v{0u, 0u, 0u, 0u};
   bool node_has = false;  // the node being built has a path so far
   bool firstc = true;     // the chunk being run is its node's first
   for (int64_t i = 0; i < cnt;) {  // node i's tile is built while the Gram waves contract node i - 1's (or i - 2's)
@@ -435,6 +501,11 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
     meta_issue(tb, q0f, q1f, lane, mf2);
     const int kch = q1c - q0c, np = max((kch + 7) >> 3, 1);
     node_has = node_has || kch > 0;
+    // NOT peeled (unroll(disable) also keeps hipcc from peeling the first pair off for the sake of `first`): the peeled pair
+    // and the loop's body kept A's coefficient registers in different places, and the copy between them sat on the loop's exit
+    // -- in front of the wait, where the refill was still in flight: stale operands now and then.  Nothing but the counted
+    // waits orders a use behind these loads, so the kernel's ISA must not copy an operand register between a load and its wait.
+#pragma clang loop unroll(disable)
     for (int j = 0; j < np; ++j) {
       // the pair after this one: this chunk's, else the next chunk's first
       const bool more = j + 1 < np;
@@ -442,12 +513,22 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       mx.oc = more ? mc.oc : mn.oc; mx.ob = more ? mc.ob : mn.ob; mx.om = more ? mc.om : mn.om; mx.w = more ? mc.w : mn.w;
       const int sx = more ? 2 * (j + 1) : 0;
       const bool first = firstc && j == 0, half = !more && 4 * (2 * j + 1) >= kch;  // (wave uniform)
-      pair_body<NOBG, HI>(tb, mx, sx, pl, A, B, cA, cB, t1, y2, first, half);
+      pair_body<NOBG, HI>(tb, mx, sx, pl, A, B, cA, cB, al, t1, y2, first, half);
     }
     if (lastc) {
       // W_1's 48 x 4 values of the lane: twelve 16-byte loads, the YOUNGEST vector-memory operations of the wave from here to
       // the vmcnt(0) below (older, in order: the three path loads of the loop's top, the refills of A and B).  A row past the
       // launch's classes lies outside the descriptor and reads zeros; so does every row of a lane past H (w1_off).
+      // The lane's place in the tile is worked out HERE, per node, from an opaque copy of the lane number: as loop invariants
+      // the twelve load offsets and the store offsets would hold some twenty registers through the pair loop, which has
+      // none to spare (the alpha operands took them), for the sake of as many vector instructions per node.
+      int wl = lane;
+      asm volatile("" : "+v"(wl));
+      const int wkq = wl >> 4, wcol = 64 * cg + 4 * (wl & 15);
+      const bool wcol_ok = wcol < H;
+      const uint32_t w1_off = wcol_ok ? uint32_t(4 * wkq) * w1_row_bytes + 4u * uint32_t(wcol) : 0x7ff00000u;
+      // the lane's two 16-byte stores inside a piece plane (dword offsets: columns col, col + 1 and col + 2, col + 3)
+      const int pc_lo = 8 * (wcol >> 2) + 4 * piece_swap(wcol >> 2), pc_hi = pc_lo ^ 4;
       f32x4 w1[3][4];
 #pragma unroll
       for (int t = 0; t < 3; ++t)
@@ -463,7 +544,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(w1[t][0]), "+v"(w1[t][1]), "+v"(w1[t][2]), "+v"(w1[t][3]) :: "memory");
       asm volatile("s_nop 11" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);  // (no accumulator read moves above the pad)
-      if (node_has && col_ok) {
+      if (node_has && wcol_ok) {
         // Y[n] = W_1 (.) T1 + Y2.  Rows past the launch's classes come out as the zeros they already are (their coefficients
         // and their rows of W_1 are zero): one branch around unconditional 16-byte stores.
         if (a.gram_f32) {  // the fp32 tile: twelve stores
@@ -475,11 +556,11 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
               f32x4 o;
 #pragma unroll
               for (int ct = 0; ct < 4; ++ct) o[ct] = w1[t][r][ct] * t1[t][ct][r] + y2[t][ct][r];
-              *reinterpret_cast<f32x4*>(&ytile[16 * t + 4 * pl.kq + r][col]) = o;
+              *reinterpret_cast<f32x4*>(&ytile[16 * t + 4 * wkq + r][wcol]) = o;
             }
         } else {
           // the pieces: the lane's rows 16 t + 4 kq + 0 .. 3 are group 4 t + kq, its columns two 16-byte stores per plane
-          uint32_t* __restrict__ grp = &sh.pc[i & 1][pl.kq][0][0];
+          uint32_t* __restrict__ grp = &sh.pc[i & 1][wkq][0][0];
 #pragma unroll
           for (int t = 0; t < 3; ++t) {
             u32x4v pz[3][2];  // [piece y0, y1, y2][column pair]: (rows 0 1 | rows 2 3) of the pair's two columns
@@ -688,9 +769,6 @@ __device__ __forceinline__ void piece_load(const uint32_t* __restrict__ tile, in
   x[b][0].y1 = *reinterpret_cast<const u32x2v*>(pe + 2 * kPlaneDwords + b * 64);
   x[b][1].t = u32x4v{o2[0], o2[1], o0[0], o0[1]};
   x[b][1].y1 = *reinterpret_cast<const u32x2v*>(po + 2 * kPlaneDwords + b * 64);
-}
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4v a, u32x4v b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ u32x4v piece_u(const PieceBlk& p) { return u32x4v{p.t[2], p.t[3], p.y1[0], p.y1[1]}; }
 __device__ __forceinline__ u32x4v piece_t(const PieceBlk& p) { return p.t; }
