@@ -370,6 +370,24 @@ LGNN_API int lgnn_kernel_timing_launches(lgnn_ctx* h, double* ms_out, int64_t ca
  * reference; the samples are processed in chunks that fit the workspace cap.                              */
 LGNN_API int lgnn_jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out, void* stream);
 
+/* ---- subnetwork Laplace: Jacobians and full GGN over a subset of the parameters ---------------------------------
+ * What FullSubnetLaplace (laplace/subnetlaplace.py:175-199) asks of its backend: GGNInterface with subnetwork_indices
+ * slices the columns of the whole Jacobian (laplace/curvature/curvature.py:127-128) and contracts the slice
+ * (laplace/curvature/curvature.py:374-410).  `subnet` int64 [S] (device): DISTINCT indices in [0, P) into the parameter
+ * vector of lgnn_jacobians (named_parameters order, weight row major, then bias), in any order; every output is in the
+ * caller's order.
+ *   lgnn_jacobians_subset:        J [M, C, S] = columns subnet[0..S) of lgnn_jacobians' J; f_out [M, C] = logits[idx] or NULL
+ *   lgnn_subnet_full_accumulate:  H_out [S, S] += sum_n J_S,n^T Lambda_n J_S,n  (regression: sum_n J_S,n^T J_S,n, no factor);
+ *                                 *loss_out += loss(model(idx), y) without the interface factor, as lgnn_full_accumulate
+ * 1- and 2-layer GCN / GraphSAGE without res / norm: only the selected columns are built, from the closed form, with the
+ * Hessian square root applied on the way (M C S floats written, 2 M C S^2 flops contracted); every other model: chunks of
+ * lgnn_jacobians' rows and a column gather.  Chunks follow the workspace limit.  Invalid batch ids: zero rows and the sticky
+ * flag, as lgnn_jacobians; an index outside [0, P): a zero column and the sticky flag (lgnn_check_async_errors).          */
+LGNN_API int lgnn_jacobians_subset(lgnn_ctx* h, const int64_t* idx, int64_t M, const int64_t* subnet, int64_t S, float* J,
+                          float* f_out, void* stream);
+LGNN_API int lgnn_subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const int64_t* subnet,
+                                int64_t S, float* H_out, float* loss_out, void* stream);
+
 /* ---- gradient of the negative log marginal likelihood w.r.t. the adjacency ("next" row 8(f)-4) --------------
  * Replaces what autograd does for ``neg_marglik.backward()`` into ``model.adj`` (gnn/marglik_training.py:197-216):
  * back through KronDecomposed.logdet / log_marginal_likelihood (laplace/utils/matrix.py:371-394,

@@ -10,12 +10,18 @@ from .curvature import HipCurvatureInterface, HipEF, HipGGN  # noqa: F401
 from .data import TensorBatchLoader, batches_of_rank, units_of_rank  # noqa: F401
 from .engine import GraphEngine  # noqa: F401
 from .knn import get_knn_graph, knn, knn_candidates, knn_graph  # noqa: F401
-from .laplace import (BaseLaplace, DiagLaplace, DiagLLLaplace, FullLaplace, FullLLLaplace, KronLaplace,  # noqa: F401
-                      KronLLLaplace, Laplace, ParametricLaplace, all_reduce_flat_)
+from . import subnetmask  # noqa: F401
+from .laplace import (BaseLaplace, DiagLaplace, DiagLLLaplace, DiagSubnetLaplace, FullLaplace, FullLLLaplace,  # noqa: F401
+                      FullSubnetLaplace, KronLaplace, KronLLLaplace, Laplace, ParametricLaplace, SubnetLaplace,
+                      all_reduce_flat_)
 from .matrix import Kron, KronDecomposed, symeig  # noqa: F401
+from .subnetmask import (LargestMagnitudeSubnetMask, LargestVarianceDiagLaplaceSubnetMask,  # noqa: F401
+                         LastLayerSubnetMask, ModuleNameSubnetMask, ParamNameSubnetMask, RandomSubnetMask, SubnetMask)
 from .models import GCN, STEGCN, GraphSAGE, LoRASTEGCN  # noqa: F401
 
 __all__ = ["GraphEngine", "HipGGN", "HipEF", "HipCurvatureInterface", "Laplace", "BaseLaplace", "ParametricLaplace",
            "KronLaplace", "DiagLaplace", "FullLaplace", "FullLLLaplace", "KronLLLaplace", "DiagLLLaplace", "Kron", "KronDecomposed", "symeig", "GCN", "STEGCN", "LoRASTEGCN", "GraphSAGE",
            "TensorBatchLoader", "batches_of_rank", "units_of_rank", "all_reduce_flat_", "knn", "knn_graph", "get_knn_graph",
-           "knn_candidates"]
+           "knn_candidates", "SubnetLaplace", "FullSubnetLaplace", "DiagSubnetLaplace", "subnetmask", "SubnetMask",
+           "RandomSubnetMask", "LargestMagnitudeSubnetMask", "LargestVarianceDiagLaplaceSubnetMask", "ParamNameSubnetMask",
+           "ModuleNameSubnetMask", "LastLayerSubnetMask"]

@@ -85,6 +85,8 @@ SIGNATURES = {
                                      _vp]),
     "lgnn_symeig_batched": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "lgnn_jacobians": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_jacobians_subset": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_subnet_full_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_knn": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
 }
 

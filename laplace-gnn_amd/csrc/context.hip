@@ -448,13 +448,14 @@ extern "C" int lgnn_check_async_errors(lgnn_ctx* h, void* stream) {
   if (!h->ws.flags.p) return 0;
   // the flags live in pinned host memory the kernels store to directly: wait for the stream, read, clear
   LGNN_HIP_CHECK(hipStreamSynchronize(s));
-  int flags[4];
+  int flags[5];
   volatile int* dev = h->ws.flags.as<int>();
-  for (int i = 0; i < 4; ++i) { flags[i] = dev[i]; dev[i] = 0; }
+  for (int i = 0; i < 5; ++i) { flags[i] = dev[i]; dev[i] = 0; }
   LGNN_REQUIRE(flags[1] == 0 && flags[0] != 1 && flags[2] == 0, "a batch contained a node index outside [0, num_nodes)");
   LGNN_REQUIRE(flags[0] != 2, "a batch contained a label outside [0, num_classes)");
   LGNN_REQUIRE(flags[3] == 0, "a batch's node ids differ from the ids its cached structure was built from (the index tensor "
                               "was written without a version bump): drop the batch cache or pass a fresh tensor");
+  LGNN_REQUIRE(flags[4] == 0, "a subnetwork index lies outside [0, n_params)");
   return 0;
 }
 
@@ -463,14 +464,15 @@ extern "C" int lgnn_peek_async_errors(lgnn_ctx* h) {
   if (!h->ws.flags.p) return 0;
   // no synchronisation: whatever the kernels that have FINISHED stored into the pinned flags (sticky until a raising read)
   volatile int* dev = h->ws.flags.as<int>();
-  int flags[4];
-  for (int i = 0; i < 4; ++i) flags[i] = dev[i];
-  if (flags[0] == 0 && flags[1] == 0 && flags[2] == 0 && flags[3] == 0) return 0;
-  for (int i = 0; i < 4; ++i) dev[i] = 0;
+  int flags[5];
+  for (int i = 0; i < 5; ++i) flags[i] = dev[i];
+  if (flags[0] == 0 && flags[1] == 0 && flags[2] == 0 && flags[3] == 0 && flags[4] == 0) return 0;
+  for (int i = 0; i < 5; ++i) dev[i] = 0;
   LGNN_REQUIRE(flags[1] == 0 && flags[0] != 1 && flags[2] == 0, "a batch contained a node index outside [0, num_nodes)");
   LGNN_REQUIRE(flags[0] != 2, "a batch contained a label outside [0, num_classes)");
   LGNN_REQUIRE(flags[3] == 0, "a batch's node ids differ from the ids its cached structure was built from (the index tensor "
                               "was written without a version bump): drop the batch cache or pass a fresh tensor");
+  LGNN_REQUIRE(flags[4] == 0, "a subnetwork index lies outside [0, n_params)");
   return 0;
 }
 

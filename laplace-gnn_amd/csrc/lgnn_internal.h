@@ -150,6 +150,10 @@ struct Workspace {
   DevBuf lora_rows, lora_cols, lora_state, lora_count, lora_part;
   DevBuf dense_stored;  // fp32 [nnz]: scratch accumulator of the stored-entry terms on the dense route
   DevBuf dense_rows;    // int32 [2 M + 1]: output / operand rows of the seed term on the dense route
+  // subnetwork Laplace (subnet.hip): the caller's indices sorted (int64 [S]) with their positions in the caller's list
+  // (int32 [S]; subnet_iota: the unsorted positions), the sort's scratch, the decoded columns of the closed-form route
+  // and the chunk X [mc C, ld] the Gram kernel reads
+  DevBuf subnet_keys, subnet_ord, subnet_iota, subnet_tmp, subnet_plan, subnet_x;
   template <class F> void each_buf(F&& f) const {
     for (int l = 0; l < kMaxLayers; ++l) { f(gram_scratch[l]); f(gram_scratch_res[l]); }
     f(pos); f(seeds); f(probs); f(mult); f(planes_a); f(planes_b); f(misc); f(jac); f(top); f(active); f(val_act);
@@ -159,6 +163,7 @@ struct Workspace {
     f(pair_s); f(pair_cnt); f(pair_ptr); f(pair_m); f(pair_m2); f(pair_w); f(pair_part);
     f(planes_c); f(adj_z0); f(adj_dir); f(lora_rows); f(lora_cols); f(lora_state); f(lora_count); f(lora_part);
     f(dense_stored); f(dense_rows);
+    f(subnet_keys); f(subnet_ord); f(subnet_iota); f(subnet_tmp); f(subnet_plan); f(subnet_x);
   }
 };
 
@@ -620,6 +625,12 @@ int lastlayer_diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, in
                               hipStream_t s);
 // ---- jacobian.hip -----------------------------------------------------------------------
 int jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out, hipStream_t s);
+// ---- subnet.hip -------------------------------------------------------------------------
+// columns subnet[0..S) (device, caller's order) of the Jacobians: J [M, C, S]
+int jacobians_subset(lgnn_ctx* h, const int64_t* idx, int64_t M, const int64_t* subnet, int64_t S, float* J, float* f_out,
+                     hipStream_t s);
+int subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const int64_t* subnet, int64_t S,
+                           float* H_out, float* loss_out, hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------
 // full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127

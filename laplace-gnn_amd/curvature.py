@@ -13,6 +13,8 @@ laplace/curvature/curvlinops.py:20-167 (CurvlinopsInterface / CurvlinopsGGN):
   ``[C D + C]`` diagonal of its GGN (what laplace/lllaplace.py:381-475, 477-... fit);
 * ``full(x, y, **kw) -> (loss, H[P, P])`` -- implemented for ``last_layer=True`` (curvature.py:374-410
   with last_layer_jacobians :132-167);
+* ``subnetwork_indices`` (constructor argument or attribute set later, laplace/subnetlaplace.py:110): indices into the Laplace
+  parameter vector; ``jacobians`` -> ``[M, C, S]``, ``full`` -> ``[S, S]``, ``diag`` -> ``[S]`` (HipGGN, all weights, exact GGN);
 * attributes ``lossfunc``, ``factor``, ``params``, ``params_dict``, ``buffers_dict``, ``model``,
   ``_model``, ``likelihood``, ``last_layer``, ``stochastic``.
 
@@ -64,12 +66,10 @@ class HipCurvatureInterface:
                  dict_key_y: str = "labels", stochastic: bool = False, fork_exact_seed: bool = True,
                  num_samples: int = 1, generator: torch.Generator | None = None):
         assert likelihood in ["regression", "classification"]
-        if subnetwork_indices is not None:
-            raise NotImplementedError("subnetwork Laplace is out of scope for the HIP backend")
         self.likelihood = likelihood
         self.model = model
         self.last_layer = last_layer
-        self.subnetwork_indices = None
+        self._subnetwork_indices = None
         self.dict_key_x, self.dict_key_y = dict_key_x, dict_key_y
         # stochastic=True: Monte-Carlo Fisher instead of the GGN (CurvlinopsGGN, laplace/curvature/curvlinops.py:143-167;
         # GGNInterface, laplace/curvature/curvature.py:327-364 with ``num_samples`` draws for diag / full)
@@ -97,6 +97,32 @@ class HipCurvatureInterface:
             # the reference applies the MC functional Fisher to last_layer_jacobians here (laplace/curvature/curvature.py:
             # 343-364, 374-432); the last-layer kernels build the exact GGN only -- refuse rather than ignore the flag
             raise NotImplementedError("stochastic=True together with last_layer=True is not implemented")
+        self.subnetwork_indices = subnetwork_indices  # (last: the setter looks at the flags above)
+
+    # Subnetwork Laplace (laplace/subnetlaplace.py:108-111 sets the attribute AFTER construction; the constructor argument
+    # does the same).  The indices address the Laplace parameter vector -- ``self.params`` flattened row major and
+    # concatenated, the columns of ``jacobians`` and the rows of ``full`` -- not ``model.parameters()``: a structure-learning
+    # model's ``adj`` is a parameter of the module and no part of that vector.  With indices set, ``jacobians`` returns
+    # [M, C, S], ``full`` [S, S] and ``diag`` [S], all in the order of the indices (laplace/curvature/curvature.py:127-128).
+    @property
+    def subnetwork_indices(self):
+        return self._subnetwork_indices
+
+    @subnetwork_indices.setter
+    def subnetwork_indices(self, indices):
+        if indices is not None:
+            self._refuse_subnetwork()
+            indices = torch.as_tensor(indices)
+            if indices.dtype != torch.int64 or indices.dim() != 1 or indices.numel() == 0:
+                raise ValueError("Subnetwork indices must be non-empty 1-dimensional torch.LongTensor.")
+            indices = indices.detach().to(self.engine.device).contiguous()
+        self._subnetwork_indices = indices
+
+    def _refuse_subnetwork(self):
+        if self.last_layer:
+            raise NotImplementedError("subnetwork_indices together with last_layer=True is not implemented")
+        if self.stochastic:
+            raise NotImplementedError("subnetwork_indices together with stochastic=True is not implemented")
 
     @property
     def _model(self) -> nn.Module:
@@ -237,13 +263,15 @@ class HipCurvatureInterface:
         H = torch.zeros(eng.n_params, dtype=torch.float32, device=eng.device)
         loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
         eng.diag_accumulate(x, y, H, loss)
+        if self._subnetwork_indices is not None:  # the diagonal kernels are closed form already: P floats, then the subset
+            H = H[self._subnetwork_indices]
         return self.factor * loss[0], H
 
     def diag_accumulate_(self, H: torch.Tensor, loss_buf: torch.Tensor, x: torch.Tensor, y: torch.Tensor):
         """Diagonal GGN of one batch added IN PLACE to the caller's ``H`` and the raw loss sum to ``loss_buf`` (the caller
         applies ``factor``): no temporaries, no torch kernels per batch (laplace/curvature/curvature.py:412-432)."""
-        if self.stochastic:
-            raise NotImplementedError("in-place accumulation exists for the GGN diagonal")
+        if self.stochastic or self._subnetwork_indices is not None:
+            raise NotImplementedError("in-place accumulation exists for the GGN diagonal over all weights")
         self.engine.set_likelihood(self.likelihood)
         self.engine.diag_accumulate(x, y, H, loss_buf)
 
@@ -283,10 +311,17 @@ class HipCurvatureInterface:
         (``lgnn_full_accumulate``).  Regression: ``sum J^T J`` (H_lik = None, :406-407), no factor on H."""
         eng = self.engine
         eng.set_likelihood(self.likelihood)
-        P = eng.n_params
-        H = torch.zeros(P, P, dtype=torch.float32, device=eng.device)
         loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
-        eng.full_accumulate(x, y, H, loss)
+        if self._subnetwork_indices is not None:
+            # the sub-block [S][:, S] of that matrix (laplace/curvature/curvature.py:127-128 slices J, :374-410 contracts
+            # the slice): only the selected columns are built (``lgnn_subnet_full_accumulate``, csrc/subnet.hip)
+            S = self._subnetwork_indices.shape[0]
+            H = torch.zeros(S, S, dtype=torch.float32, device=eng.device)
+            eng.subnet_full_accumulate(x, y, self._subnetwork_indices, H, loss)
+        else:
+            P = eng.n_params
+            H = torch.zeros(P, P, dtype=torch.float32, device=eng.device)
+            eng.full_accumulate(x, y, H, loss)
         if self.likelihood == "regression":
             return self.factor * loss[0], H
         return self.factor * loss[0], self.factor * H
@@ -304,6 +339,8 @@ class HipCurvatureInterface:
             raise NotImplementedError("the HIP Jacobians carry no autograd graph (enable_backprop=False only)")
         if self.last_layer:
             return self.last_layer_jacobians(x)
+        if self._subnetwork_indices is not None:  # [M, C, S]: the selected columns only (``lgnn_jacobians_subset``)
+            return self.engine.jacobians_subset(x, self._subnetwork_indices)
         return self.engine.jacobians(x)
 
     functorch_jacobians = jacobians
@@ -353,6 +390,9 @@ class HipEF(HipCurvatureInterface):
         if last_layer:
             raise NotImplementedError("empirical Fisher: all-weights Laplace only")
         super().__init__(model, likelihood, last_layer, subnetwork_indices, dict_key_x, dict_key_y, stochastic=False, **kwargs)
+
+    def _refuse_subnetwork(self):
+        raise NotImplementedError("subnetwork_indices with the empirical Fisher (HipEF) is not implemented: HipGGN only")
 
     @property
     def _kron_fisher_type(self) -> str:

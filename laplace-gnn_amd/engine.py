@@ -686,6 +686,41 @@ class GraphEngine:
                                            _stream(self.device)), "lgnn_jacobians")
         return J, f
 
+    # -- subnetwork Laplace (csrc/subnet.hip) ---------------------------------------------------------------------
+    def _subnet(self, subnet: torch.Tensor) -> torch.Tensor:
+        """int64 [S] on the device.  The indices address the Laplace parameter vector (the columns of ``jacobians``); the
+        front validates them once on the host (``SubnetLaplace._check_subnetwork_indices``), the device only flags."""
+        if subnet.dim() != 1 or subnet.numel() == 0:
+            raise ValueError("subnetwork indices must be a non-empty 1-dimensional tensor")
+        if subnet.dtype != torch.int64:
+            raise TypeError(f"subnetwork indices must be torch.int64, got {subnet.dtype}")
+        return subnet.to(self.device).contiguous()
+
+    def jacobians_subset(self, idx: torch.Tensor, subnet: torch.Tensor):
+        """(J [M, C, S], f [M, C]): the columns ``subnet`` (distinct indices into the Laplace parameter vector, any order)
+        of ``jacobians(idx)`` in the caller's order -- laplace/curvature/curvature.py:127-128 without the M C P slab."""
+        self._sync_versions()
+        idx, subnet = idx.contiguous(), self._subnet(subnet)
+        M, C, S = idx.shape[0], self.dims[-1], subnet.shape[0]
+        J = torch.empty(M, C, S, dtype=torch.float32, device=self.device)
+        f = torch.empty(M, C, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_jacobians_subset(self._h, _dev_ptr(idx, torch.int64, "idx"), M, subnet.data_ptr(), S,
+                                                  J.data_ptr(), f.data_ptr(), _stream(self.device)), "lgnn_jacobians_subset")
+        return J, f
+
+    def subnet_full_accumulate(self, idx, y, subnet: torch.Tensor, H: torch.Tensor, loss: torch.Tensor):
+        """H [S, S] += the sub-block ``[subnet][:, subnet]`` of the batch's full GGN (regression binding: sum J_S^T J_S),
+        loss += raw loss sum."""
+        self._sync_versions()
+        idx, subnet = idx.contiguous(), self._subnet(subnet)
+        S = subnet.shape[0]
+        if tuple(H.shape) != (S, S):
+            raise ValueError(f"H must be [{S}, {S}], got {tuple(H.shape)}")
+        rc = self.lib.lgnn_subnet_full_accumulate(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), self._labels(y, idx.shape[0]), idx.shape[0], subnet.data_ptr(), S,
+            _dev_ptr(H, torch.float32, "H"), loss.data_ptr(), _stream(self.device))
+        _lib.check(rc, "lgnn_subnet_full_accumulate")
+
     # -- marginal-likelihood gradient w.r.t. the adjacency ("next" row 8(f)-4) ---------------------------------
     @staticmethod
     def _cand_ptrs(cand):

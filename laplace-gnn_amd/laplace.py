@@ -114,6 +114,11 @@ class BaseLaplace:
         return 1 / self.sigma_noise ** 2 / self.temperature
 
     @property
+    def _n_params_posterior(self) -> int:
+        """Width of the posterior: the columns of the Jacobians the predictive asks its backend for (SubnetLaplace: S)."""
+        return self.n_params
+
+    @property
     def prior_precision_diag(self) -> torch.Tensor:
         pp = torch.as_tensor(self.prior_precision, dtype=torch.float32, device=self._device).reshape(-1)
         if pp.numel() == 1:
@@ -436,12 +441,12 @@ class ParametricLaplace(BaseLaplace):
         # Jacobian route (models with res / norm, deeper models, full posteriors): the reference forms Js [M, C, P] for all
         # evaluation nodes at once (laplace/baselaplace.py:1123-1158), which cannot exist at scale; here the nodes go in chunks
         # whose Jacobians stay under _JACOBIAN_BYTES_MAX -- the same numbers, any M
-        per_node = max(1, self.n_outputs * self.n_params * 4)
+        per_node = max(1, self.n_outputs * self._n_params_posterior * 4)
         chunk = max(1, min(int(x.shape[0]), self._JACOBIAN_BYTES_MAX // per_node))
         mus, fvars = [], []
         for s0 in range(0, max(int(x.shape[0]), 1), chunk):
             Js, f_mu = self.backend.jacobians(x[s0:s0 + chunk], enable_backprop=False)
-            if Js.shape[1:] != (self.n_outputs, self.n_params):
+            if Js.shape[1:] != (self.n_outputs, self._n_params_posterior):
                 raise ValueError("Invalid Jacobians shape for Laplace posterior approx.")
             f_var = self.functional_variance(Js)
             if diagonal_output:
@@ -463,7 +468,7 @@ class ParametricLaplace(BaseLaplace):
             if diagonal_output:  # samples of N(f_mu, diag f_var): the diagonal is all that is read (:667-709)
                 f_mu, f_var_diag = self._glm_predictive_distribution(x, diagonal_output=True)
                 return self._glm_predictive_samples(f_mu, f_var_diag, n_samples, False, generator, eps).mean(dim=0)
-            big = x.shape[0] * self.n_outputs * self.n_params * 4 > self._JACOBIAN_BYTES_MAX
+            big = x.shape[0] * self.n_outputs * self._n_params_posterior * 4 > self._JACOBIAN_BYTES_MAX
             full = self._glm_covariance_matrix_free(x) if big else None
             if full is not None:
                 f_mu, f_var = full
@@ -583,7 +588,7 @@ class ParametricLaplace(BaseLaplace):
             pp = init_prior_prec if torch.is_tensor(init_prior_prec) else torch.tensor(float(init_prior_prec))
             pp = pp.detach().to(self._device, torch.float32).reshape(-1)
             if pp.numel() == 1 and prior_structure != "scalar":
-                n = {"layerwise": self.n_layers, "diag": self.n_params}.get(prior_structure)
+                n = {"layerwise": self.n_layers, "diag": self._n_params_posterior}.get(prior_structure)
                 if n is None:
                     raise ValueError(f"Invalid prior structure {prior_structure}.")
                 pp = torch.full((n,), float(pp), device=self._device)
@@ -1268,7 +1273,7 @@ class DiagLaplace(ParametricLaplace):
         return value, torch.stack([rows, cols]), grad, gc
 
     def _scale_samples(self, eps):  # laplace/baselaplace.py:1912-1919: samples * posterior_scale
-        return eps * (1.0 / self.posterior_precision.sqrt()).reshape(1, self.n_params)
+        return eps * (1.0 / self.posterior_precision.sqrt()).reshape(1, -1)
 
     def functional_variance(self, Js):  # laplace/baselaplace.py:1901-1903
         return torch.einsum("ncp,p,nkp->nck", Js, 1.0 / self.posterior_precision, Js)
@@ -1644,6 +1649,131 @@ class FullLaplace(ParametricLaplace):
             K = candidates.shape[1]
             gc = 0.5 * (gc[:K] + gc[K:])
         return value, torch.stack([rows, cols]), grad, gc
+
+
+class SubnetLaplace(ParametricLaplace):
+    """Subnetwork Laplace (Daxberger et al. 2021; laplace/subnetlaplace.py:15-172): the posterior covers the ``S`` weights
+    named by ``subnetwork_indices``, everything else stays at the MAP.  Full or diagonal Hessian structure only.
+
+    ``subnetwork_indices`` index the LAPLACE PARAMETER VECTOR ``la.mean``: the parameters in ``named_parameters()`` order
+    without names containing ``adj`` or ``norms`` (the fork's filter, laplace/baselaplace.py:118-122), each flattened row
+    major -- the vector ``lgnn_jacobians`` and ``FullLaplace.H`` use.  (The reference documents
+    ``parameters_to_vector(model.parameters())``; for its GNNs that vector contains the dense ``adj`` and is not the one its
+    own ``SubnetLaplace`` checks the indices against.)  Non-empty 1-D int64, in ``[0, n_params)``, no duplicates, any device,
+    any order: ``H``, ``prior_precision_diag``, ``mean_subnet`` and the Jacobians follow the order of the indices.
+    ``laplace_gnn_amd.subnetmask`` builds such index sets.
+
+    ``n_params`` stays the size of the whole vector (``mean``, ``sample()``), ``n_params_subnet = S`` is the size of ``H``.
+    The prior is scalar or a length-``S`` diagonal.  Marginal likelihood, prior-precision tuning, the GLM predictive with
+    every link, ``state_dict`` and the ``process_group`` reduction are the inherited code on the ``S``-sized objects;
+    ``sample()`` returns full ``[n, P]`` vectors, so ``pred_type="nn"`` works unchanged."""
+
+    def __init__(self, model, likelihood, subnetwork_indices, *args, asdl_fisher_kwargs=None, **kwargs):
+        if asdl_fisher_kwargs is not None:
+            raise ValueError("Subnetwork Laplace does not support asdl_fisher_kwargs.")
+        self.H = None
+        super().__init__(model, likelihood, *args, **kwargs)
+        self._check_subnetwork_indices(subnetwork_indices)
+        self.subnetwork_indices = subnetwork_indices.detach().to(self._device).contiguous()
+        # laplace/subnetlaplace.py:108-112: the backend learns the indices after its construction (a backend that cannot
+        # serve a subnetwork -- HipEF, last_layer / stochastic flags -- refuses here, by name)
+        self.backend.subnetwork_indices = self.subnetwork_indices
+        self.n_params_subnet = int(subnetwork_indices.numel())
+        self._init_H()
+
+    def _check_subnetwork_indices(self, subnetwork_indices) -> None:
+        """laplace/subnetlaplace.py:114-138, against the Laplace parameter vector; one host round trip per construction."""
+        if subnetwork_indices is None:
+            raise ValueError("Subnetwork indices cannot be None.")
+        if not (torch.is_tensor(subnetwork_indices) and subnetwork_indices.dtype == torch.int64
+                and subnetwork_indices.dim() == 1 and subnetwork_indices.numel() > 0):
+            raise ValueError("Subnetwork indices must be non-empty 1-dimensional torch.LongTensor.")
+        if bool(((subnetwork_indices < 0) | (subnetwork_indices >= self.n_params)).any()):
+            raise ValueError(f"Subnetwork indices must lie between 0 and n_params={self.n_params}.")
+        if subnetwork_indices.unique().numel() != subnetwork_indices.numel():
+            raise ValueError("Subnetwork indices must not contain duplicate entries.")
+
+    @property
+    def _n_params_posterior(self) -> int:
+        return self.n_params_subnet
+
+    @property
+    def prior_precision_diag(self) -> torch.Tensor:
+        """Scalar or length-S diagonal prior (laplace/subnetlaplace.py:140-158)."""
+        pp = torch.as_tensor(self.prior_precision, dtype=torch.float32, device=self._device).reshape(-1)
+        if pp.numel() == 1:
+            return pp.expand(self.n_params_subnet).clone()
+        if pp.numel() == self.n_params_subnet:
+            return pp
+        raise ValueError("Mismatch of prior and model. Diagonal or scalar prior.")
+
+    @property
+    def mean_subnet(self) -> torch.Tensor:
+        return self.mean[self.subnetwork_indices.to(self.mean.device)]
+
+    @property
+    def scatter(self) -> torch.Tensor:
+        delta = self.mean_subnet - torch.as_tensor(self.prior_mean, device=self.mean.device, dtype=self.mean.dtype)
+        return (delta * self.prior_precision_diag) @ delta
+
+    def assemble_full_samples(self, subnet_samples: torch.Tensor) -> torch.Tensor:
+        """[n, S] samples of the subnetwork -> [n, P] parameter vectors, the MAP everywhere else
+        (laplace/subnetlaplace.py:169-172)."""
+        full_samples = self.mean.repeat(subnet_samples.shape[0], 1)
+        full_samples[:, self.subnetwork_indices.to(self.mean.device)] = subnet_samples.to(full_samples.dtype)
+        return full_samples
+
+    def sample(self, n_samples: int = 100, generator: torch.Generator | None = None, eps: torch.Tensor | None = None):
+        """Full parameter vectors [n, P] (laplace/subnetlaplace.py:191-198, 224-233); ``eps``: [n, S] standard normal draws."""
+        if eps is None:
+            eps = torch.randn(n_samples, self.n_params_subnet, device=self._device, generator=generator)
+        return self.assemble_full_samples(self.mean_subnet.reshape(1, -1) + self._scale_samples(eps.to(self._device)))
+
+    def _matrix_free_operands(self, out_map=None):
+        return None  # the matrix-free predictive covers posteriors over all weights; here: Jacobian columns [M, C, S]
+
+    def state_dict(self) -> dict:
+        state = super().state_dict()
+        state["subnetwork_indices"] = self.subnetwork_indices
+        return state
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        if tuple(state_dict["H"].shape) != tuple(self.H.shape):
+            raise ValueError(f"Attempting to load a subnetwork Laplace with H of shape {tuple(state_dict['H'].shape)} into "
+                             f"one with {tuple(self.H.shape)}.")
+        saved = state_dict.get("subnetwork_indices")
+        if saved is not None and not torch.equal(saved.to(self.subnetwork_indices.device), self.subnetwork_indices):
+            raise ValueError("Attempting to load a subnetwork Laplace fitted on different subnetwork indices.")
+        super().load_state_dict(state_dict)
+
+    def neg_marglik_adj_grad(self, *args, **kwargs):
+        raise NotImplementedError("adjacency gradient under a subnetwork posterior is not implemented "
+                                  "(KronLaplace, DiagLaplace and FullLaplace over all weights offer it)")
+
+
+class FullSubnetLaplace(SubnetLaplace, FullLaplace):
+    """Dense ``S x S`` posterior precision over the subnetwork (laplace/subnetlaplace.py:175-199).  With the HIP backend only
+    the selected Jacobian columns are built (``lgnn_subnet_full_accumulate``): M C S floats and 2 M C S^2 flops per batch
+    where ``FullLaplace`` needs M C P and 2 M C P^2."""
+    _key = ("subnetwork", "full")
+
+    def _init_H(self):
+        self.H = torch.zeros(self.n_params_subnet, self.n_params_subnet, device=self._device)
+        self._posterior_scale = None
+
+
+class DiagSubnetLaplace(SubnetLaplace, DiagLaplace):
+    """Diagonal posterior precision over the subnetwork (laplace/subnetlaplace.py:201-233): the existing closed-form diagonal
+    indexed by the subnetwork.  Plain per-batch path (no in-place buffer, no captured-graph fit)."""
+    _key = ("subnetwork", "diag")
+    fit_graph = False
+
+    def _init_H(self):
+        self._hl = None
+        self.H = torch.zeros(self.n_params_subnet, device=self._device)
+
+    def fit(self, train_loader, override: bool = True, progress_bar: bool = False, process_group=None) -> None:
+        self._fit_plain(train_loader, override=override, progress_bar=progress_bar, process_group=process_group)
 
 
 def _all_subclasses(cls) -> set:
