@@ -388,6 +388,30 @@ LGNN_API int lgnn_jacobians_subset(lgnn_ctx* h, const int64_t* idx, int64_t M, c
 LGNN_API int lgnn_subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const int64_t* subnet,
                                 int64_t S, float* H_out, float* loss_out, void* stream);
 
+/* ---- functional (GP) Laplace: the kernel J J^T without the Jacobians ------------------------------------------------
+ * What FunctionalLaplace (laplace/baselaplace.py:1922-2960) contracts from two batches' Jacobians (_kernel_batch :2684-2715,
+ * _kernel_star :2717-2747, _kernel_batch_star :2749-2776, _mean_scatter_term_batch :2787-2812), with J as lgnn_jacobians
+ * defines it.  idx_a [Ma], idx_b [Mb] int64 on the device; C = number of outputs.
+ *   lgnn_gp_kernel writes (never accumulates) K = J(idx_a) J(idx_b)^T:
+ *     flags == 0                  K[(n C + c) ldk + (m C + e)]: the [Ma C, Mb C] block, ldk >= Mb C
+ *     LGNN_GP_INDEPENDENT         C planes K[c][n][m] = <J[n, c, :], J[m, c, :]>, row stride ldk >= Mb, plane stride Ma ldk
+ *     LGNN_GP_MATCHED             Ma == Mb: K[n][c][e] = <J_a[n, c, :], J_b[n, e, :]> (dense [Ma, C, C]; ldk unused);
+ *                                 with LGNN_GP_INDEPENDENT K[n][c] (dense [Ma, C])
+ *     LGNN_GP_FROM_JACOBIANS      take the general route on any model (cross-check, timing baseline)
+ *   lgnn_gp_jvp: out [M, C] = sum_p J[m, c, p] v[p] for v [P] on the device.
+ * 1- and 2-layer GCN / GraphSAGE without res / norm: from per-sample tables of the first layer and the last layer's feature
+ * rows, a batched NT GEMM on the fp32 matrix cores and a class contraction -- no Jacobian is written.  Every other model:
+ * chunks of lgnn_jacobians' rows through the same NT GEMM.  Chunks follow the workspace limit.  No float atomics: two calls
+ * on the same input return the same bits; with idx_a == idx_b (the same pointer) the result is exactly symmetric.  Invalid
+ * ids: zero rows / columns and the sticky flag, as lgnn_jacobians (lgnn_check_async_errors).  With kernel timing enabled
+ * the structured route records four event pairs per chunk pair: tables, NT GEMM, class contraction, placement.          */
+#define LGNN_GP_INDEPENDENT 1
+#define LGNN_GP_MATCHED 2
+#define LGNN_GP_FROM_JACOBIANS 4
+LGNN_API int lgnn_gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int flags,
+                            float* K, int64_t ldk, void* stream);
+LGNN_API int lgnn_gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, void* stream);
+
 /* ---- gradient of the negative log marginal likelihood w.r.t. the adjacency ("next" row 8(f)-4) --------------
  * Replaces what autograd does for ``neg_marglik.backward()`` into ``model.adj`` (gnn/marglik_training.py:197-216):
  * back through KronDecomposed.logdet / log_marginal_likelihood (laplace/utils/matrix.py:371-394,

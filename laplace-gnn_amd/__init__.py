@@ -14,6 +14,7 @@ from . import subnetmask  # noqa: F401
 from .laplace import (BaseLaplace, DiagLaplace, DiagLLLaplace, DiagSubnetLaplace, FullLaplace, FullLLLaplace,  # noqa: F401
                       FullSubnetLaplace, KronLaplace, KronLLLaplace, Laplace, ParametricLaplace, SubnetLaplace,
                       all_reduce_flat_)
+from .gp import FunctionalLaplace  # noqa: F401
 from .matrix import Kron, KronDecomposed, symeig  # noqa: F401
 from .subnetmask import (LargestMagnitudeSubnetMask, LargestVarianceDiagLaplaceSubnetMask,  # noqa: F401
                          LastLayerSubnetMask, ModuleNameSubnetMask, ParamNameSubnetMask, RandomSubnetMask, SubnetMask)
@@ -24,4 +25,4 @@ __all__ = ["GraphEngine", "HipGGN", "HipEF", "HipCurvatureInterface", "Laplace",
            "TensorBatchLoader", "batches_of_rank", "units_of_rank", "all_reduce_flat_", "knn", "knn_graph", "get_knn_graph",
            "knn_candidates", "SubnetLaplace", "FullSubnetLaplace", "DiagSubnetLaplace", "subnetmask", "SubnetMask",
            "RandomSubnetMask", "LargestMagnitudeSubnetMask", "LargestVarianceDiagLaplaceSubnetMask", "ParamNameSubnetMask",
-           "ModuleNameSubnetMask", "LastLayerSubnetMask"]
+           "ModuleNameSubnetMask", "LastLayerSubnetMask", "FunctionalLaplace"]

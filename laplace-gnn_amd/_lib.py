@@ -16,6 +16,7 @@ ACT_RELU, ACT_TANH = 0, 1
 LIK_CLASSIFICATION, LIK_REGRESSION = 0, 1
 NORM_NONE, NORM_LAYER, NORM_BATCH = 0, 1, 2
 FLAG_FORK_EXACT_SEED, FLAG_NO_FUSE, FLAG_NO_PATHS, FLAG_FORCE_PATHS = 1, 2, 4, 8
+GP_INDEPENDENT, GP_MATCHED, GP_FROM_JACOBIANS = 1, 2, 4
 
 # name -> (restype, argtypes); mirrors include/laplace_gnn_hip.h one to one
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
@@ -87,6 +88,8 @@ SIGNATURES = {
     "lgnn_jacobians": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_jacobians_subset": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_subnet_full_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_gp_kernel": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "lgnn_gp_jvp": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_knn": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
 }
 

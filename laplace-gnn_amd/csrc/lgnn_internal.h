@@ -154,6 +154,10 @@ struct Workspace {
   // (int32 [S]; subnet_iota: the unsorted positions), the sort's scratch, the decoded columns of the closed-form route
   // and the chunk X [mc C, ld] the Gram kernel reads
   DevBuf subnet_keys, subnet_ord, subnet_iota, subnet_tmp, subnet_plan, subnet_x;
+  // functional Laplace (gpkernel.hip): tables [z][mc][ld] and [phi | s] rows of the two chunks, G [z'][ma mb], the class
+  // contraction's output Kt [(c, e)][ma mb], Phi Phi^T [ma][mb], W_pair [(c, e)][z'], split-K partials, and the two chunks of
+  // Jacobian rows of the general route
+  DevBuf gp_tab_a, gp_tab_b, gp_phi_a, gp_phi_b, gp_g, gp_kt, gp_s, gp_wpair, gp_part, gp_jac_a, gp_jac_b;
   template <class F> void each_buf(F&& f) const {
     for (int l = 0; l < kMaxLayers; ++l) { f(gram_scratch[l]); f(gram_scratch_res[l]); }
     f(pos); f(seeds); f(probs); f(mult); f(planes_a); f(planes_b); f(misc); f(jac); f(top); f(active); f(val_act);
@@ -164,6 +168,8 @@ struct Workspace {
     f(planes_c); f(adj_z0); f(adj_dir); f(lora_rows); f(lora_cols); f(lora_state); f(lora_count); f(lora_part);
     f(dense_stored); f(dense_rows);
     f(subnet_keys); f(subnet_ord); f(subnet_iota); f(subnet_tmp); f(subnet_plan); f(subnet_x);
+    f(gp_tab_a); f(gp_tab_b); f(gp_phi_a); f(gp_phi_b); f(gp_g); f(gp_kt); f(gp_s); f(gp_wpair); f(gp_part); f(gp_jac_a);
+    f(gp_jac_b);
   }
 };
 
@@ -631,6 +637,11 @@ int jacobians_subset(lgnn_ctx* h, const int64_t* idx, int64_t M, const int64_t* 
                      hipStream_t s);
 int subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const int64_t* subnet, int64_t S,
                            float* H_out, float* loss_out, hipStream_t s);
+// ---- gpkernel.hip -----------------------------------------------------------------------
+// K = J(idx_a) J(idx_b)^T in the layout `flags` names (LGNN_GP_*); out [M, C] = J(idx) v
+int gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int flags, float* K, int64_t ldk,
+              hipStream_t s);
+int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------
 // full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127

@@ -379,6 +379,28 @@ class HipGGN(HipCurvatureInterface):
     """GGN backend on MI355X; the counterpart of ``CurvlinopsGGN`` (curvlinops.py:143-167); ``stochastic=True`` switches
     to the Monte-Carlo Fisher like the reference's flag."""
 
+    def _refuse_gp(self, what: str):
+        if self._subnetwork_indices is not None:
+            raise NotImplementedError(f"{what} together with subnetwork_indices is not implemented")
+        if self.last_layer:
+            raise NotImplementedError(f"{what} together with last_layer=True is not implemented")
+        if self.stochastic:
+            raise NotImplementedError(f"{what} together with stochastic=True is not implemented")
+
+    def gp_kernel(self, xa: torch.Tensor, xb: torch.Tensor, independent: bool = False, matched: bool = False,
+                  from_jacobians: bool = False) -> torch.Tensor:
+        """The kernel of the functional posterior, ``J(xa) J(xb)^T`` (FunctionalLaplace._kernel_batch / _kernel_star /
+        _kernel_batch_star, laplace/baselaplace.py:2684-2776), as a fresh tensor: [Ma C, Mb C]; ``independent``: [C, Ma, Mb];
+        ``matched``: [M, C, C] (with ``independent`` [M, C]).  See ``GraphEngine.gp_kernel``."""
+        self._refuse_gp("gp_kernel")
+        return self.engine.gp_kernel(xa, xb, independent=independent, matched=matched, from_jacobians=from_jacobians)
+
+    def gp_jvp(self, x: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """``einsum("bcp,p->bc", J(x), v)`` (the mean of the scatter term, laplace/baselaplace.py:2787-2812) as a fresh
+        [M, C] tensor."""
+        self._refuse_gp("gp_jvp")
+        return self.engine.gp_jvp(x, v)
+
 
 class HipEF(HipCurvatureInterface):
     """Empirical Fisher backend; the counterpart of ``CurvlinopsEF`` / ``EFInterface`` (laplace/curvature/curvlinops.py:

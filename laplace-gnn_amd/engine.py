@@ -686,6 +686,46 @@ class GraphEngine:
                                            _stream(self.device)), "lgnn_jacobians")
         return J, f
 
+    # -- functional Laplace (csrc/gpkernel.hip) --------------------------------------------------------------------
+    def gp_kernel(self, idx_a: torch.Tensor, idx_b: torch.Tensor, independent: bool = False, matched: bool = False,
+                  from_jacobians: bool = False) -> torch.Tensor:
+        """``J(idx_a) J(idx_b)^T`` without the Jacobians where the model has a closed form (``lgnn_gp_kernel``): [Ma C, Mb C];
+        ``independent``: [C, Ma, Mb]; ``matched`` (Ma == Mb): [Ma, C, C], with ``independent`` [Ma, C].  Passing the same
+        tensor twice gives an exactly symmetric result.  ``from_jacobians`` forces the route over ``lgnn_jacobians`` rows."""
+        self._sync_versions()
+        same = idx_a is idx_b
+        idx_a = idx_a.contiguous()
+        idx_b = idx_a if same else idx_b.contiguous()
+        Ma, Mb, C = idx_a.shape[0], idx_b.shape[0], self.dims[-1]
+        flags = ((_lib.GP_INDEPENDENT if independent else 0) | (_lib.GP_MATCHED if matched else 0)
+                 | (_lib.GP_FROM_JACOBIANS if from_jacobians else 0))
+        if matched:
+            if Ma != Mb:
+                raise ValueError(f"matched=True needs as many samples on both sides, got {Ma} and {Mb}")
+            shape, ldk = ((Ma, C) if independent else (Ma, C, C)), C
+        elif independent:
+            shape, ldk = (C, Ma, Mb), Mb
+        else:
+            shape, ldk = (Ma * C, Mb * C), Mb * C
+        K = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_gp_kernel(self._h, _dev_ptr(idx_a, torch.int64, "idx_a"), Ma,
+                                           _dev_ptr(idx_b, torch.int64, "idx_b"), Mb, flags, K.data_ptr(), ldk,
+                                           _stream(self.device)), "lgnn_gp_kernel")
+        return K
+
+    def gp_jvp(self, idx: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+        """``out[m, c] = sum_p J[m, c, p] v[p]`` for ``v`` [n_params] (``lgnn_gp_jvp``); no Jacobian is written where the
+        model has a closed form."""
+        self._sync_versions()
+        idx = idx.contiguous()
+        v = v.detach().to(self.device, torch.float32).contiguous()
+        if v.dim() != 1 or v.shape[0] != self.n_params:
+            raise ValueError(f"v must be [{self.n_params}], got {tuple(v.shape)}")
+        out = torch.empty(idx.shape[0], self.dims[-1], dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_gp_jvp(self._h, _dev_ptr(idx, torch.int64, "idx"), idx.shape[0], v.data_ptr(),
+                                        out.data_ptr(), _stream(self.device)), "lgnn_gp_jvp")
+        return out
+
     # -- subnetwork Laplace (csrc/subnet.hip) ---------------------------------------------------------------------
     def _subnet(self, subnet: torch.Tensor) -> torch.Tensor:
         """int64 [S] on the device.  The indices address the Laplace parameter vector (the columns of ``jacobians``); the

@@ -129,6 +129,15 @@ class BaseLaplace:
             return torch.cat([d.expand(p.numel()) for d, p in zip(pp, self.params)])
         raise ValueError("Mismatch of prior and model. Diagonal, scalar, or per-layer prior.")
 
+    @property
+    def log_likelihood(self) -> torch.Tensor:
+        """laplace/baselaplace.py:895-922: -H_factor * loss for classification."""
+        factor = -self._H_factor
+        if self.likelihood == "regression":
+            c = self.n_data * self.n_outputs * log(self.sigma_noise * (2 * pi) ** 0.5)
+            return factor * self.loss - c
+        return factor * self.loss
+
 
 def _is_zero_number(v) -> bool:
     return isinstance(v, (int, float)) and v == 0
@@ -182,7 +191,69 @@ def _dense_scope(eng, what: str):
                                   f"({limit} bytes) or int32 indexing")
 
 
-class ParametricLaplace(BaseLaplace):
+class _GLMLinkMixin:
+    """The link code of the classification predictive, shared by the parametric posteriors and ``FunctionalLaplace``: both hand
+    it ``_glm_predictive_distribution(x, diagonal_output)`` (and, where they have one, the matrix-free shortcuts
+    ``_bridge_moments_matrix_free`` / ``_glm_covariance_matrix_free``; ``None`` from either means the Jacobian route)."""
+
+    def _glm_forward_call(self, x, link_approx, n_samples, diagonal_output, generator, eps):
+        """laplace/baselaplace.py:570-665 (classification branches)."""
+        if link_approx == "probit":  # reads the diagonal of f_var only (laplace/baselaplace.py:610-616)
+            f_mu, f_var_diag = self._glm_predictive_distribution(x, diagonal_output=True)
+            kappa = 1 / torch.sqrt(1.0 + pi / 8 * f_var_diag)
+            return torch.softmax(kappa * f_mu, dim=-1)
+        if link_approx == "mc":
+            if diagonal_output:  # samples of N(f_mu, diag f_var): the diagonal is all that is read (:667-709)
+                f_mu, f_var_diag = self._glm_predictive_distribution(x, diagonal_output=True)
+                return self._glm_predictive_samples(f_mu, f_var_diag, n_samples, False, generator, eps).mean(dim=0)
+            big = x.shape[0] * self.n_outputs * self._n_params_posterior * 4 > self._JACOBIAN_BYTES_MAX
+            full = self._glm_covariance_matrix_free(x) if big else None
+            if full is not None:
+                f_mu, f_var = full
+                # polarised off-diagonals can leave a node's matrix indefinite in the last bits: those nodes (if any) take the
+                # Jacobian route, 32 at a time
+                info = torch.linalg.cholesky_ex(f_var).info
+                bad = info.nonzero().squeeze(1)
+                for b0 in range(0, bad.numel(), 32):
+                    sel = bad[b0:b0 + 32]
+                    f_var[sel] = self._glm_predictive_distribution(x[sel])[1]
+            else:
+                f_mu, f_var = self._glm_predictive_distribution(x)
+            return self._glm_predictive_samples(f_mu, f_var, n_samples, diagonal_output, generator, eps).mean(dim=0)
+        # Laplace bridge with zero-mean correction (:630-660): reads the diagonal, the row sums and the total of f_var only
+        moments = self._bridge_moments_matrix_free(x)
+        if moments is None:
+            f_mu, f_var = self._glm_predictive_distribution(x)
+            moments = (f_mu, torch.diagonal(f_var, dim1=1, dim2=2), f_var.sum(-1), f_var.sum(dim=(1, 2)))
+        f_mu, f_var_diag, rows, total = moments  # (symmetric f_var: f_var.sum(-1) == f_var.sum(-2))
+        f_mu = f_mu - rows * f_mu.sum(-1).reshape(-1, 1) / total.reshape(-1, 1)
+        f_var_diag = f_var_diag - rows * rows / total.reshape(-1, 1)
+        K = f_mu.size(-1)
+        if link_approx == "bridge_norm":
+            f_var_diag_mean = f_var_diag.mean(dim=1)
+            f_var_diag_mean = f_var_diag_mean / torch.as_tensor([K / 2], device=self._device).sqrt()
+            f_mu = f_mu / f_var_diag_mean.sqrt().unsqueeze(-1)
+            f_var_diag = f_var_diag / f_var_diag_mean.unsqueeze(-1)
+        sum_exp = torch.exp(-f_mu).sum(dim=1).unsqueeze(-1)
+        alpha = (1 - 2 / K + f_mu.exp() / K ** 2 * sum_exp) / f_var_diag
+        return torch.nan_to_num(alpha / alpha.sum(dim=1).unsqueeze(-1), nan=1.0)
+
+    def _glm_predictive_samples(self, f_mu, f_var, n_samples, diagonal_output=False, generator=None, eps=None):
+        """softmax of samples of N(f_mu, f_var): laplace/baselaplace.py:667-709 + utils.normal_samples (:329-369)."""
+        if diagonal_output:
+            f_var = torch.diagonal(f_var, dim1=1, dim2=2)
+        C = f_mu.shape[1]
+        if eps is None:
+            eps = torch.randn((C, n_samples), device=f_mu.device, dtype=f_mu.dtype, generator=generator)
+        eps = eps.to(f_mu.device)
+        if f_var.ndim == 2:
+            scaled = f_var.sqrt().unsqueeze(-1) * eps.unsqueeze(0)
+        else:
+            scaled = torch.matmul(torch.linalg.cholesky(f_var), eps.unsqueeze(0))
+        return torch.softmax((f_mu.unsqueeze(-1) + scaled).permute((2, 0, 1)), dim=-1)
+
+
+class ParametricLaplace(_GLMLinkMixin, BaseLaplace):
     def _init_H(self):
         raise NotImplementedError
 
@@ -457,71 +528,6 @@ class ParametricLaplace(BaseLaplace):
         if len(mus) == 1:
             return mus[0], fvars[0]
         return torch.cat(mus), torch.cat(fvars)
-
-    def _glm_forward_call(self, x, link_approx, n_samples, diagonal_output, generator, eps):
-        """laplace/baselaplace.py:570-665 (classification branches)."""
-        if link_approx == "probit":  # reads the diagonal of f_var only (laplace/baselaplace.py:610-616)
-            f_mu, f_var_diag = self._glm_predictive_distribution(x, diagonal_output=True)
-            kappa = 1 / torch.sqrt(1.0 + pi / 8 * f_var_diag)
-            return torch.softmax(kappa * f_mu, dim=-1)
-        if link_approx == "mc":
-            if diagonal_output:  # samples of N(f_mu, diag f_var): the diagonal is all that is read (:667-709)
-                f_mu, f_var_diag = self._glm_predictive_distribution(x, diagonal_output=True)
-                return self._glm_predictive_samples(f_mu, f_var_diag, n_samples, False, generator, eps).mean(dim=0)
-            big = x.shape[0] * self.n_outputs * self._n_params_posterior * 4 > self._JACOBIAN_BYTES_MAX
-            full = self._glm_covariance_matrix_free(x) if big else None
-            if full is not None:
-                f_mu, f_var = full
-                # polarised off-diagonals can leave a node's matrix indefinite in the last bits: those nodes (if any) take the
-                # Jacobian route, 32 at a time
-                info = torch.linalg.cholesky_ex(f_var).info
-                bad = info.nonzero().squeeze(1)
-                for b0 in range(0, bad.numel(), 32):
-                    sel = bad[b0:b0 + 32]
-                    f_var[sel] = self._glm_predictive_distribution(x[sel])[1]
-            else:
-                f_mu, f_var = self._glm_predictive_distribution(x)
-            return self._glm_predictive_samples(f_mu, f_var, n_samples, diagonal_output, generator, eps).mean(dim=0)
-        # Laplace bridge with zero-mean correction (:630-660): reads the diagonal, the row sums and the total of f_var only
-        moments = self._bridge_moments_matrix_free(x)
-        if moments is None:
-            f_mu, f_var = self._glm_predictive_distribution(x)
-            moments = (f_mu, torch.diagonal(f_var, dim1=1, dim2=2), f_var.sum(-1), f_var.sum(dim=(1, 2)))
-        f_mu, f_var_diag, rows, total = moments  # (symmetric f_var: f_var.sum(-1) == f_var.sum(-2))
-        f_mu = f_mu - rows * f_mu.sum(-1).reshape(-1, 1) / total.reshape(-1, 1)
-        f_var_diag = f_var_diag - rows * rows / total.reshape(-1, 1)
-        K = f_mu.size(-1)
-        if link_approx == "bridge_norm":
-            f_var_diag_mean = f_var_diag.mean(dim=1)
-            f_var_diag_mean = f_var_diag_mean / torch.as_tensor([K / 2], device=self._device).sqrt()
-            f_mu = f_mu / f_var_diag_mean.sqrt().unsqueeze(-1)
-            f_var_diag = f_var_diag / f_var_diag_mean.unsqueeze(-1)
-        sum_exp = torch.exp(-f_mu).sum(dim=1).unsqueeze(-1)
-        alpha = (1 - 2 / K + f_mu.exp() / K ** 2 * sum_exp) / f_var_diag
-        return torch.nan_to_num(alpha / alpha.sum(dim=1).unsqueeze(-1), nan=1.0)
-
-    def _glm_predictive_samples(self, f_mu, f_var, n_samples, diagonal_output=False, generator=None, eps=None):
-        """softmax of samples of N(f_mu, f_var): laplace/baselaplace.py:667-709 + utils.normal_samples (:329-369)."""
-        if diagonal_output:
-            f_var = torch.diagonal(f_var, dim1=1, dim2=2)
-        C = f_mu.shape[1]
-        if eps is None:
-            eps = torch.randn((C, n_samples), device=f_mu.device, dtype=f_mu.dtype, generator=generator)
-        eps = eps.to(f_mu.device)
-        if f_var.ndim == 2:
-            scaled = f_var.sqrt().unsqueeze(-1) * eps.unsqueeze(0)
-        else:
-            scaled = torch.matmul(torch.linalg.cholesky(f_var), eps.unsqueeze(0))
-        return torch.softmax((f_mu.unsqueeze(-1) + scaled).permute((2, 0, 1)), dim=-1)
-
-    @property
-    def log_likelihood(self) -> torch.Tensor:
-        """laplace/baselaplace.py:895-922: -H_factor * loss for classification."""
-        factor = -self._H_factor
-        if self.likelihood == "regression":
-            c = self.n_data * self.n_outputs * log(self.sigma_noise * (2 * pi) ** 0.5)
-            return factor * self.loss - c
-        return factor * self.loss
 
     @property
     def scatter(self) -> torch.Tensor:
@@ -1785,6 +1791,9 @@ def Laplace(model: nn.Module, likelihood: str, subset_of_weights: str = "last_la
     """String-keyed factory with the reference's call signature (laplace/laplace.py:13-47)."""
     if subset_of_weights == "subnetwork" and hessian_structure not in ["full", "diag"]:
         raise ValueError("Subnetwork Laplace requires a full or diagonal Hessian approximation!")
+    if hessian_structure == "gp" and subset_of_weights != "all":
+        raise NotImplementedError("FunctionalLLLaplace (a GP posterior over the last layer) is not implemented; "
+                                  "use subset_of_weights='all'")
     laplace_map = {sub._key: sub for sub in _all_subclasses(BaseLaplace) if hasattr(sub, "_key")}
     key = (subset_of_weights, hessian_structure)
     if key not in laplace_map:
