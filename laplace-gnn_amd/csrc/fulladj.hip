@@ -2,7 +2,7 @@
 //     Gamma = d(1/2 logdet(f H + Delta)) / dH = (f / 2) (f H + Delta)^-1        [P, P], symmetric
 // (FullLaplace, laplace/baselaplace.py:1377-1505; the curvature it differentiates: laplace/curvature/curvature.py:374-410 with the
 // fork's attached Jacobians, :89-130; the loop that asks for it: gnn/marglik_training.py:197-216 under --hessian_structure full,
-// gnn/utils.py:57-59).  One pass over Z = J Gamma gives both inputs of adjgrad.hip's tangent / reverse chain,
+// gnn/utils.py:57-59).  One pass over Z = J Gamma gives both inputs of adjgrad_ext.hip's tangent / reverse chain,
 //     K_n = (J_n Gamma) J_n^T   [C, C]            R_n = 2 Lambda_n (J_n Gamma)   [C, P],   Lambda_n = diag(p) - p p^T,
 // without Z ever reaching memory.
 #include "lgnn_internal.h"
@@ -20,7 +20,7 @@ constexpr int FZLD = FHALF + 1;  // odd stride of the staged accumulator half: r
 // columns (the K loop's staging buffers are reused, 33 KB in all), and per half
 //   R[q, col]      = 2 p_c (Z[q, col] - sum_k p_k Z[(m, k), col])                      one store per element, q = (m, c)
 //   K_n[a, b]     += sum_col Z[(m, a), col] J[(m, b), col]                              one wave reduction per (m, a, b)
-// K_n's partial sums over the column blocks are combined with float atomics (as adjgrad.hip's other accumulators): K_n is
+// K_n's partial sums over the column blocks are combined with float atomics (as the adjacency gradient's other accumulators): K_n is
 // zeroed by the launcher, and the order of the P / 64 additions per entry is not fixed.  R needs the complete K_n only through
 // out_bar (diag_ext_sample_kernel, which runs after this kernel), so one pass is enough.  p = softmax of the model's own logits
 // at idx, computed as diag_ext_sample_kernel computes it; a sample with an id outside [0, N) gets p = 0 (R = 0).

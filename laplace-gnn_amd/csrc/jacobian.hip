@@ -17,8 +17,6 @@
 
 namespace lgnn {
 
-void* blas_handle(hipStream_t s);  // eigh.hip: the process-wide rocBLAS handle, bound to `s`
-
 namespace {
 
 // GCN: planes[(m, c)][v][c] = P[idx[m], v] for the entries v of row idx[m] of P; one wave per sample.

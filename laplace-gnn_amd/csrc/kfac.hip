@@ -714,7 +714,7 @@ int batch_epilogue(lgnn_ctx* h, const int64_t* idx, int64_t M, hipStream_t s) {
   return 0;
 }
 
-// The GCN top layer of one batch for a caller outside the accumulate (adjgrad.hip): active rows (flags in ws.active, list in
+// The GCN top layer of one batch for a caller outside the accumulate (adjgrad_gcn.hip): active rows (flags in ws.active, list in
 // ws.act_list / ws.act_count) and the class-major planes g[c][n][:] of ALL C classes for those rows -- rows that are not
 // active are NOT written.  Needs batch_prologue's probabilities / multiplicities; the Gram it also forms goes to a scratch.
 int kfac_top_planes(lgnn_ctx* h, const int64_t* idx, int64_t M, bool fork_exact, float* g, hipStream_t s) {

@@ -647,5 +647,7 @@ int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* ou
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127
 int launch_full_directions(const float* J, const float* Gamma, const int64_t* idx, const float* logits, int64_t N,
                            int64_t mc, int64_t C, int64_t P, float* R, float* Kn, hipStream_t s);
+// ---- eigh.hip ---------------------------------------------------------------------------
+void* blas_handle(hipStream_t s);  // the process-wide rocblas_handle, bound to `s`
 
 }  // namespace lgnn

@@ -8,7 +8,7 @@
 // needs d(-marglik)/dA_hat on ALL N^2 pairs:  grad_A = scaling B^T G,  grad_B = scaling G A^T.
 //
 // Three pieces live here:
-//  * the dense-grid terms of the adjacency gradient (adjgrad.hip's chain with a dense [N, N] target instead of the stored
+//  * the dense-grid terms of the adjacency gradient (adjgrad_gcn.hip's / adjgrad_diag.hip's chains with a dense [N, N] target instead of the stored
 //    entries and a candidate list): every per-pair term <U[a], V[b]> summed over planes becomes a tile GEMM on the fp32
 //    matrix cores (dense_nt_kernel, v_mfma_f32_32x32x2_f32; rows restricted to a device list where the term lives on a few
 //    rows only -- the active rows of a batch, the batch rows of the seed term), the diagonal posterior's per-sample term

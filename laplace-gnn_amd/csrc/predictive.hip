@@ -28,8 +28,6 @@
 
 namespace lgnn {
 
-void* blas_handle(hipStream_t s);  // eigh.hip
-
 namespace {
 
 constexpr int PJT = 64;   // feature columns of the tile per thread (the bias column is one more register)

@@ -30,6 +30,7 @@ import torch.distributed as dist
 from torch import nn
 from torch.nn.utils import parameters_to_vector
 
+from .adjgrad import _adjacency_candidates, _adjgrad_drive, _adjgrad_scope, _dense_scope  # noqa: F401  (re-exported)
 from .curvature import HipGGN
 from .data import TensorBatchLoader
 from .matrix import Kron, KronDecomposed
@@ -141,54 +142,6 @@ class BaseLaplace:
 
 def _is_zero_number(v) -> bool:
     return isinstance(v, (int, float)) and v == 0
-
-
-def _adjacency_candidates(eng, candidates, sym: bool):
-    """Candidate pairs (i, j) of ``neg_marglik_adj_grad`` -> (a, b, accumulator) in the propagation matrix's coordinates, or
-    None.  The device kernels index rows with these pairs: validated before the cast to int32 (one host round trip; this is not
-    the per-batch path).  Stored pairs are not candidates: their gradient comes back with the stored entries (a GCN stores its
-    diagonal, gnn/models/models.py:23; GraphSAGE's diagonal entries are genuine non-edges of the reference's dense adj.grad,
-    gnn/models/models.py:47)."""
-    if candidates is None:
-        return None
-    ci, cj = candidates[0].to(eng.device).to(torch.int64), candidates[1].to(eng.device).to(torch.int64)
-    Nn = eng.num_nodes
-    if ci.numel():
-        if bool(((ci < 0) | (ci >= Nn) | (cj < 0) | (cj >= Nn)).any()):
-            raise ValueError(f"candidate pairs must index nodes in [0, {Nn})")
-        sr, sc = eng.export_adj()  # row-major sorted
-        skey, ckey = sr * Nn + sc, ci * Nn + cj
-        pos = torch.searchsorted(skey, ckey).clamp(max=max(skey.numel() - 1, 0))
-        if skey.numel() and bool((skey[pos] == ckey).any()):
-            raise ValueError("candidate pairs must not be stored entries of the adjacency")
-    if sym:  # (adj + adj^T) / 2 feeds the model: both orientations are needed
-        ci, cj = torch.cat([ci, cj]), torch.cat([cj, ci])
-    # entry (i, j) of the adjacency is entry (a = j, b = i) of the GCN propagation matrix D A^T D and entry
-    # (a = i, b = j) of GraphSAGE's A / rowsum
-    ca, cb = (cj, ci) if eng.kind == "gcn" else (ci, cj)
-    return (ca.to(torch.int32).contiguous(), cb.to(torch.int32).contiguous(),
-            torch.zeros(ci.shape[0], dtype=torch.float32, device=eng.device))
-
-
-def _adjgrad_scope(eng, what: str, depth: bool = False):
-    """1-layer models: GCN only (the reference's Banana configurations).  ``depth``: also refuse models deeper than two layers
-    here (the Kronecker and diagonal fronts leave that to the device entry points)."""
-    if len(eng.dims) == 2 and eng.kind != "gcn":
-        raise NotImplementedError(f"{what}: 1-layer GraphSAGE is not covered (1-layer GCN, 2-layer GCN / GraphSAGE)")
-    if depth and len(eng.dims) not in (2, 3):
-        raise NotImplementedError(f"{what}: 1- and 2-layer GCN / 2-layer GraphSAGE on the HIP backend")
-
-
-def _dense_scope(eng, what: str):
-    """``dense=True`` of ``neg_marglik_adj_grad``: the all-pairs gradient (LoRASTEGCN) covers plain 2-layer GCN models on the
-    HIP backend, and N x N floats must fit the workspace limit and int32 indexing."""
-    if eng is None or getattr(eng, "kind", None) != "gcn" or eng.num_layers != 2 or eng.has_extras:
-        raise NotImplementedError(f"{what}(dense=True): plain 2-layer GCN models (no res / norm) on the HIP backend")
-    N = eng.num_nodes
-    limit = getattr(eng, "_ws_limit", None) or (32 << 30)
-    if N * N >= 2 ** 31 or 4 * N * N > limit:
-        raise NotImplementedError(f"{what}(dense=True): an N x N gradient of {N} nodes exceeds the workspace limit "
-                                  f"({limit} bytes) or int32 indexing")
 
 
 class _GLMLinkMixin:
@@ -934,42 +887,11 @@ class KronLaplace(ParametricLaplace):
         gB, gA = self._logdet_factor_gradients()
         gB = [0.5 * g for g in gB]  # neg marglik = H_factor * loss + 1/2 (logdet P - logdet P_0 + scatter)
         gA = [0.5 * g for g in gA]
-        if dense:
-            N = eng.num_nodes
-            G = torch.zeros(N, N, dtype=torch.float32, device=eng.device)
-            out_bar = torch.zeros(N, eng.dims[-1], dtype=torch.float32, device=eng.device)
-            rank, world = _dist_info(process_group)
-            for t, (X, y) in enumerate(train_loader):
-                if t % world != rank:
-                    continue
-                eng.adjgrad_batch_dense(X.to(eng.device), y.to(eng.device), gB, out_bar, G,
-                                        fork_exact=getattr(self.backend, "fork_exact_seed", True), loss_scale=self._H_factor)
-            if world > 1:
-                all_reduce_flat_([G, out_bar], process_group)
-            a_scale = len(train_loader) / len(train_loader.dataset)
-            return value, eng.adjgrad_finish_dense(out_bar, gA, a_scale, G)
-        grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
-        out_bar = torch.zeros(eng.num_nodes, eng.dims[-1], dtype=torch.float32, device=eng.device)
-        rank, world = _dist_info(process_group)
-        sym = bool(getattr(self.model, "symmetric", False))
-        cand = _adjacency_candidates(eng, candidates, sym)
-        for t, (X, y) in enumerate(train_loader):
-            if t % world != rank:
-                continue
-            eng.adjgrad_batch(X.to(eng.device), y.to(eng.device), gB, grad_P, out_bar,
-                              fork_exact=getattr(self.backend, "fork_exact_seed", True), loss_scale=self._H_factor, cand=cand)
-        if world > 1:
-            all_reduce_flat_([grad_P, out_bar] + ([cand[2]] if cand is not None else []), process_group)
         a_scale = len(train_loader) / len(train_loader.dataset)
-        rows, cols = eng.export_adj()
-        if cand is None:
-            grad = eng.adjgrad_finish(out_bar, gA, a_scale, grad_P)
-            return value, torch.stack([rows, cols]), grad
-        grad, gc = eng.adjgrad_finish(out_bar, gA, a_scale, grad_P, cand=cand)
-        if sym:
-            K = candidates.shape[1]
-            gc = 0.5 * (gc[:K] + gc[K:])
-        return value, torch.stack([rows, cols]), grad, gc
+        return (value, *_adjgrad_drive(eng, train_loader, process_group, candidates, bool(getattr(self.model, "symmetric", False)),
+                                       dense, batch="adjgrad_batch", finish="adjgrad_finish", weight=gB, per_sample=False,
+                                       finish_args=(gA, a_scale), fork_exact=getattr(self.backend, "fork_exact_seed", True),
+                                       loss_scale=self._H_factor))
 
     @property
     def log_det_posterior_precision(self) -> torch.Tensor:
@@ -1237,46 +1159,9 @@ class DiagLaplace(ParametricLaplace):
         value = -self.log_marginal_likelihood()
         f = self._H_factor
         gamma = (0.5 * f / self.posterior_precision).to(torch.float32).contiguous()  # d(1/2 logdet P) / dH_p
-        N, F, C = eng.num_nodes, eng.dims[0], eng.dims[-1]
-        grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
-        out_bar = torch.zeros(N, C, dtype=torch.float32, device=eng.device)
-        # (a 1-layer model has no hidden layer: the device calls take a null h1_bar)
-        h1_bar = torch.zeros(N, eng.dims[1], dtype=torch.float32, device=eng.device) if len(eng.dims) != 2 else None
-        e_bar = torch.zeros(N, F + 1, dtype=torch.float32, device=eng.device)
-        rank, world = _dist_info(process_group)
-        sym = bool(getattr(self.model, "symmetric", False))
-        cand = _adjacency_candidates(eng, candidates, sym)
-        eng.set_likelihood("classification")
-        if dense:
-            G = torch.zeros(N, N, dtype=torch.float32, device=eng.device)
-            for X, y in train_loader:
-                M = X.shape[0]
-                lo, hi = M * rank // world, M * (rank + 1) // world
-                if hi > lo:
-                    eng.diag_adjgrad_batch_dense(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), gamma, out_bar, h1_bar,
-                                                 e_bar, G, loss_scale=f)
-            if world > 1:
-                all_reduce_flat_([G, out_bar, h1_bar, e_bar], process_group)
-            return value, eng.diag_adjgrad_finish_dense(out_bar, h1_bar, e_bar, G)
-        for X, y in train_loader:
-            # every term is a sum over samples: inside a job every rank takes its slice of every batch (a Cora-shaped loader has
-            # ONE batch); a candidate pair sees a repeated node id through each slice's own multiplicity
-            M = X.shape[0]
-            lo, hi = M * rank // world, M * (rank + 1) // world
-            if hi > lo:
-                eng.diag_adjgrad_batch(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), gamma, grad_P, out_bar, h1_bar, e_bar,
-                                       loss_scale=f, cand=cand)
-        if world > 1:
-            all_reduce_flat_([t for t in (grad_P, out_bar, h1_bar, e_bar) if t is not None]
-                             + ([cand[2]] if cand is not None else []), process_group)
-        rows, cols = eng.export_adj()
-        if cand is None:
-            return value, torch.stack([rows, cols]), eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P)
-        grad, gc = eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P, cand=cand)
-        if sym:
-            K = candidates.shape[1]
-            gc = 0.5 * (gc[:K] + gc[K:])
-        return value, torch.stack([rows, cols]), grad, gc
+        return (value, *_adjgrad_drive(eng, train_loader, process_group, candidates, bool(getattr(self.model, "symmetric", False)),
+                                       dense, batch="diag_adjgrad_batch", finish="diag_adjgrad_finish", weight=gamma,
+                                       per_sample=True, loss_scale=f))
 
     def _scale_samples(self, eps):  # laplace/baselaplace.py:1912-1919: samples * posterior_scale
         return eps * (1.0 / self.posterior_precision.sqrt()).reshape(1, -1)
@@ -1628,33 +1513,9 @@ class FullLaplace(ParametricLaplace):
         value = -self.log_marginal_likelihood()
         f = self._H_factor
         Gamma = self._adj_gamma()
-        N, F, C = eng.num_nodes, eng.dims[0], eng.dims[-1]
-        grad_P = torch.zeros(eng.nnz, dtype=torch.float32, device=eng.device)
-        out_bar = torch.zeros(N, C, dtype=torch.float32, device=eng.device)
-        # (a 1-layer model has no hidden layer: the device calls take a null h1_bar)
-        h1_bar = torch.zeros(N, eng.dims[1], dtype=torch.float32, device=eng.device) if len(eng.dims) != 2 else None
-        e_bar = torch.zeros(N, F + 1, dtype=torch.float32, device=eng.device)
-        rank, world = _dist_info(process_group)
-        sym = bool(getattr(self.model, "symmetric", False))
-        cand = _adjacency_candidates(eng, candidates, sym)
-        eng.set_likelihood("classification")
-        for X, y in train_loader:
-            M = X.shape[0]
-            lo, hi = M * rank // world, M * (rank + 1) // world
-            if hi > lo:
-                eng.full_adjgrad_batch(X[lo:hi].to(eng.device), y[lo:hi].to(eng.device), Gamma, grad_P, out_bar, h1_bar, e_bar,
-                                       loss_scale=f, cand=cand)
-        if world > 1:
-            all_reduce_flat_([t for t in (grad_P, out_bar, h1_bar, e_bar) if t is not None]
-                             + ([cand[2]] if cand is not None else []), process_group)
-        rows, cols = eng.export_adj()
-        if cand is None:
-            return value, torch.stack([rows, cols]), eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P)
-        grad, gc = eng.diag_adjgrad_finish(out_bar, h1_bar, e_bar, grad_P, cand=cand)
-        if sym:
-            K = candidates.shape[1]
-            gc = 0.5 * (gc[:K] + gc[K:])
-        return value, torch.stack([rows, cols]), grad, gc
+        return (value, *_adjgrad_drive(eng, train_loader, process_group, candidates, bool(getattr(self.model, "symmetric", False)),
+                                       False, batch="full_adjgrad_batch", finish="diag_adjgrad_finish", weight=Gamma,
+                                       per_sample=True, loss_scale=f))
 
 
 class SubnetLaplace(ParametricLaplace):

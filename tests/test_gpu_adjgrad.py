@@ -1,4 +1,4 @@
-"""SURVEY.md 8(f)-4 on the GPU: ``KronLaplace.neg_marglik_adj_grad`` (csrc/adjgrad.hip through the C ABI) against
+"""SURVEY.md 8(f)-4 on the GPU: ``KronLaplace.neg_marglik_adj_grad`` (csrc/adjgrad*.hip through the C ABI) against
 (a) the reference's ``model.adj.grad`` after ``(-log_marginal_likelihood()).backward()`` on its STEGCN / STEGraphSAGE (goldens generated
 by oracle/make_golden.py from the reference's own autograd) and (b) the CPU oracle's hand-written reverse chain on
 seeded mid-size inputs (class chunks under a small workspace cap, repeated node ids, upstream vs fork-exact seeds).

@@ -1,5 +1,5 @@
 """The adjacency gradient of the marginal likelihood under the FULL posterior (``FullLaplace.neg_marglik_adj_grad``;
-lgnn_full_adjgrad_batch / lgnn_full_directions, csrc/fulladj.hip + the shared tangent / reverse chains of csrc/adjgrad.hip):
+lgnn_full_adjgrad_batch / lgnn_full_directions, csrc/fulladj.hip + the shared tangent / reverse chains of csrc/adjgrad_{ext,sage,onelayer}.hip):
 
 1. the new entry point with a diagonal Gamma against the reference's own ``model.adj.grad`` goldens of DiagLaplace (1e-5, the bar
    of the diagonal tests for the same chain);

@@ -1,5 +1,5 @@
 """One-layer models on the GPU: the adjacency gradient of the marginal likelihood of a one-layer GCN under
-the diagonal, Kronecker and full posterior (csrc/adjgrad.hip: the ``onelayer_*`` route) against (a) the reference's own
+the diagonal, Kronecker and full posterior (csrc/adjgrad_onelayer.hip: the ``onelayer_*`` route) against (a) the reference's own
 ``model.adj.grad`` goldens (tests/golden/onelayer/, tools/make_onelayer_golden.py) and (b) the fp64 restatement
 (tests/onelayer_restatement.py, pinned to the same goldens on the CPU), the structure-learning loop of ``lg.STEGCN(..., 1, ...)``
 against goldens of the reference's loop, the matrix-free GLM predictive of one-layer GCN / GraphSAGE models
