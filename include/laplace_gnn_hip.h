@@ -169,6 +169,25 @@ LGNN_API int lgnn_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, float* out
 /* all-node logits [N, C] (what forward() indexes into) */
 LGNN_API int lgnn_forward_all(lgnn_ctx* h, float* out /* [N, C] */, void* stream);
 
+/* ---- sampled forward: the logits of S parameter samples at a batch, in one pass ---------------------------------------
+ * Replaces the loop of the sampling predictive (laplace/baselaplace.py:1160-1199 _nn_predictive_samples, reached from mc_eval,
+ * gnn/marglik_training.py:341-353: per sample vector_to_parameters + model(indices), a forward over all N nodes).
+ *   theta : [S, n_params] row major, each row in the Laplace parameter order: W_0 [dims[1], in_0] row major, b_0, W_1, b_1
+ *           (a 1-layer model: W, b).  Rows need no alignment.
+ *   out   : [S, M, C]; out[s, m, :] = the logits the model would give at node idx[m] if sample s were written into it; with
+ *           LGNN_SAMPLED_SOFTMAX their softmax.  Every batch row is one output row (a repeated id is computed twice).
+ * The bound weights, the cached forward and every other cache are neither read nor changed; what the call keeps (P X with the
+ * bias column, the needed-row list, the second Linear's products of a chunk of samples) lives in buffers of its own, counted
+ * by lgnn_device_bytes.  The samples go in chunks sized so that those products stay under lgnn_set_workspace_limit.  No
+ * float atomics: two calls on the same inputs agree bit for bit, and a sample's numbers do not depend on its chunk.
+ * Enqueues only.  Ids outside [0, num_nodes) raise the sticky flag lgnn_check_async_errors reports and give zero rows.
+ * Plain GCN / GraphSAGE with 1 or 2 layers, relu or tanh, any widths; a model bound with res / norm or with more than two
+ * layers is refused with a message naming the case.                                                                      */
+#define LGNN_SAMPLED_SOFTMAX 1u
+LGNN_API int lgnn_sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* theta /* [S, P] row major */,
+                                  int64_t S, uint32_t flags /* LGNN_SAMPLED_SOFTMAX */, float* out /* [S, M, C] */,
+                                  void* stream);
+
 /* ---- training-mode forward and its backward to the parameters --------------------------------------------------------
  * Replaces what autograd does for the weight update of the driver's loop (gnn/marglik_training.py:165-186: model.train();
  * f = model(train_indices); loss = criterion(f, train_labels); loss.backward(); optimizer.step()) on BaseGNN.forward in

@@ -17,6 +17,7 @@ LIK_CLASSIFICATION, LIK_REGRESSION = 0, 1
 NORM_NONE, NORM_LAYER, NORM_BATCH = 0, 1, 2
 FLAG_FORK_EXACT_SEED, FLAG_NO_FUSE, FLAG_NO_PATHS, FLAG_FORCE_PATHS = 1, 2, 4, 8
 GP_INDEPENDENT, GP_MATCHED, GP_FROM_JACOBIANS = 1, 2, 4
+SAMPLED_SOFTMAX = 1
 
 # name -> (restype, argtypes); mirrors include/laplace_gnn_hip.h one to one
 _vp, _i64, _i32, _u32 = C.c_void_p, C.c_int64, C.c_int, C.c_uint32
@@ -44,6 +45,7 @@ SIGNATURES = {
     "lgnn_set_workspace_limit": (_i32, [_vp, _i64]),
     "lgnn_forward": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "lgnn_forward_all": (_i32, [_vp, _vp, _vp]),
+    "lgnn_sampled_forward": (_i32, [_vp, _vp, _i64, _vp, _i64, _u32, _vp, _vp]),
     "lgnn_train_forward": (_i32, [_vp, _vp, _i64, _pp, C.c_float, _vp, _vp]),
     "lgnn_train_backward": (_i32, [_vp, _vp, _pp, _pp, _pp, _pp, _pp, _pp, _vp]),
     "lgnn_kfac_accumulate": (_i32, [_vp, _vp, _vp, _i64, _i64, _u32, _pp, _pp, _vp, _vp]),

@@ -393,6 +393,7 @@ extern "C" int lgnn_bind_model(lgnn_ctx* h, int num_layers, const int64_t* dims,
   h->ws.planes_a_zero_bytes = 0;
   h->fc.x_valid = false;  // a new X / new widths: nothing survives
   h->fc.px_valid = false;
+  h->sf.in_valid = false;
   h->fc.gram_valid[0] = false;
   h->tr.input_valid = false;
   return lgnn_invalidate(h);

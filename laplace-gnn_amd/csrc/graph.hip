@@ -392,7 +392,7 @@ int graph_update(lgnn_ctx* h, const int64_t* fi, const int64_t* fj, const uint8_
   h->sym = new_same;
   LGNN_CALL(graph_values(h, new_same, s));
   // everything cached from the graph
-  h->fc.valid = false; h->fc.aux_valid = false; h->fc.px_valid = false;
+  h->fc.valid = false; h->fc.aux_valid = false; h->fc.px_valid = false; h->sf.in_valid = false;
   h->tr.tape_valid = false; h->tr.input_valid = false;
   for (int l = 0; l < kMaxLayers; ++l) h->fc.gram_valid[l] = (l == 0 && h->kind == LGNN_KIND_GCN) ? h->fc.gram_valid[0] : false;
   h->n_long = -1; h->n_long_fwd = -1; h->n_top_multi = 0; h->n_top_slices = 0; h->n_long_tasks = 0; h->two_hop = -1.0; h->two_hop_max = -1.0; h->pair_hop_max = -1.0;

@@ -256,6 +256,24 @@ struct TrainState {
   }
 };
 
+// ---- sampled forward (sampled.hip) --------------------------------------------------------------------------------------
+// Buffers of lgnn_sampled_forward alone.  The entry never reserves a Workspace or ForwardCache buffer: a captured fit holds
+// raw pointers into those.  in0 depends on the graph and X only (in_valid is dropped where ForwardCache::px_valid is).
+struct SampledState {
+  bool in_valid = false;
+  int64_t ldk = 0;     // row stride of in0: in_0 + 1 rounded up to 4 floats
+  DevBuf in0;          // [N, ldk]: GCN [P X | rowsum(P) | 0 ..], GraphSAGE [X | P X | 1 | 0 ..] (the last used column meets the bias)
+  DevBuf need;         // uint8 [N]: the row is needed by the call's evaluation nodes
+  DevBuf rows;         // int32 [max(N, M)]: the needed rows R, sorted (1 layer: the batch's ids, -1 where invalid)
+  DevBuf count;        // int32: |R| (device)
+  DevBuf rpos;         // int32 [N]: position of a needed row in R
+  DevBuf z;            // fp32 [S_chunk, N, C or 2 C]: the second Linear's products of a chunk of samples
+  DevBuf select_tmp;   // rocPRIM select scratch
+  template <class F> void each_buf(F&& f) const {
+    f(in0); f(need); f(rows); f(count); f(rpos); f(z); f(select_tmp);
+  }
+};
+
 }  // namespace lgnn
 
 struct lgnn_ctx {
@@ -324,13 +342,14 @@ struct lgnn_ctx {
   int64_t ev_planes = 0;
   lgnn::BatchCache bcache;
   lgnn::TrainState tr;
+  lgnn::SampledState sf;
   // every DevBuf the context owns (the batch cache reports its own bytes: lgnn_batch_cache_stats)
   template <class F> void each_buf(F&& f) const {
     for (int l = 0; l < lgnn::kMaxLayers; ++l) { f(Wt[l]); f(Wrt[l]); f(Wcomb[l]); f(bcomb[l]); }
     f(A_rowptr); f(A_col); f(AT_rowptr); f(AT_col); f(val_fwd); f(val_bwd); f(deg_scale);
     f(long_rows); f(long_slot); f(long_tasks); f(hub); f(long_rows_fwd);
     f(top_multi); f(top_tasks); f(top_task_count); f(top_cnt); f(top_offs); f(top_hub_tiles);
-    fc.each_buf(f); ws.each_buf(f); tr.each_buf(f);
+    fc.each_buf(f); ws.each_buf(f); tr.each_buf(f); sf.each_buf(f);
   }
   ~lgnn_ctx();  // the timing events and the batch cache; the buffers free themselves
 };
@@ -642,6 +661,10 @@ int subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64
 int gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int flags, float* K, int64_t ldk,
               hipStream_t s);
 int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, hipStream_t s);
+// ---- sampled.hip ------------------------------------------------------------------------
+// out [S, M, C] = the logits (flags & LGNN_SAMPLED_SOFTMAX: their softmax) of S parameter vectors theta [S, n_params] at idx
+int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* theta, int64_t S, uint32_t flags, float* out,
+                    hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------
 // full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127

@@ -332,6 +332,17 @@ class HipCurvatureInterface:
     def peek_async_errors(self):
         self.engine.peek_async_errors()
 
+    def sampled_forward_in_scope(self, n_params: int) -> bool:
+        """Whether ``sampled_forward`` serves parameter vectors of this width: a plain 1- or 2-layer model all of whose
+        parameters are the posterior's."""
+        eng = self.engine
+        return not self.last_layer and eng.sampled_forward_in_scope and int(n_params) == eng.n_params
+
+    def sampled_forward(self, x: torch.Tensor, theta: torch.Tensor, softmax: bool = False) -> torch.Tensor:
+        """[S, M, C]: the model's logits (or their softmax) at ``x`` under each parameter vector of ``theta`` [S, P], without
+        writing the parameters (``lgnn_sampled_forward``): what laplace/baselaplace.py:1160-1199 loops over."""
+        return self.engine.sampled_forward(x, theta, softmax=softmax)
+
     def jacobians(self, x: torch.Tensor, enable_backprop: bool = False):
         """(Js [M, C, P], f [M, C]) as CurvatureInterface.jacobians (laplace/curvature/curvature.py:89-130); the
         M * C backward passes run as planes through the HIP engine (csrc/jacobian.hip).  No autograd graph."""

@@ -432,6 +432,28 @@ class GraphEngine:
         _lib.check(self.lib.lgnn_forward_all(self._h, out.data_ptr(), _stream(self.device)), "lgnn_forward_all")
         return out
 
+    @property
+    def sampled_forward_in_scope(self) -> bool:
+        """Whether ``sampled_forward`` covers the bound model: plain GCN / GraphSAGE (no res / norm) with 1 or 2 layers."""
+        return self._bound is not None and not self.has_extras and self.num_layers <= 2
+
+    def sampled_forward(self, idx: torch.Tensor, theta: torch.Tensor, softmax: bool = False) -> torch.Tensor:
+        """[S, M, C]: the logits (``softmax``: their softmax) the model would give at ``idx`` under each of the S parameter
+        vectors ``theta`` [S, n_params] (Laplace parameter order), in one pass (``lgnn_sampled_forward``, csrc/sampled.hip).
+        The bound parameters are not written and the cached forward stays valid.  Models with res / norm or more than two
+        layers are refused by the library."""
+        self._sync_versions()
+        idx = idx.contiguous()
+        theta = theta.detach().to(self.device, torch.float32).contiguous()
+        if theta.dim() != 2 or theta.shape[1] != self.n_params:
+            raise ValueError(f"theta must be [S, {self.n_params}], got {tuple(theta.shape)}")
+        S, M = theta.shape[0], idx.shape[0]
+        out = torch.empty(S, M, self.dims[-1], dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_sampled_forward(self._h, _dev_ptr(idx, torch.int64, "idx"), M, theta.data_ptr(), S,
+                                                 _lib.SAMPLED_SOFTMAX if softmax else 0, out.data_ptr(),
+                                                 _stream(self.device)), "lgnn_sampled_forward")
+        return out
+
     # -- training-mode forward / backward (lgnn_train_forward / lgnn_train_backward, csrc/train.hip) ------------------------
     def train_forward(self, idx: torch.Tensor, masks=None, p: float = 0.0) -> torch.Tensor:
         """Logits [M, C] of the training-mode forward (gnn/models/base_gnn.py:136-161 with dropout): ``masks`` is one uint8

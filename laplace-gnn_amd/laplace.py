@@ -203,7 +203,10 @@ class _GLMLinkMixin:
             scaled = f_var.sqrt().unsqueeze(-1) * eps.unsqueeze(0)
         else:
             scaled = torch.matmul(torch.linalg.cholesky(f_var), eps.unsqueeze(0))
-        return torch.softmax((f_mu.unsqueeze(-1) + scaled).permute((2, 0, 1)), dim=-1)
+        f_samples = (f_mu.unsqueeze(-1) + scaled).permute((2, 0, 1))
+        if self.likelihood == "regression":  # (reached through predictive_samples only: the samples themselves)
+            return f_samples
+        return torch.softmax(f_samples, dim=-1)
 
 
 class ParametricLaplace(_GLMLinkMixin, BaseLaplace):
@@ -319,8 +322,9 @@ class ParametricLaplace(_GLMLinkMixin, BaseLaplace):
         pass
 
     # ---- posterior samples and the sampling ("nn", link_approx="mc") predictive the GNN driver evaluates with
-    # (gnn/marglik_training.py:338-352 -> laplace/baselaplace.py:1183-1199): theta ~ N(mean, P^-1), one full-graph
-    # forward per sample through the HIP engine (the in-place parameter writes invalidate its cache), softmax, mean.
+    # (gnn/marglik_training.py:338-352 -> laplace/baselaplace.py:1183-1199): theta ~ N(mean, P^-1), softmax, mean.  Plain
+    # 1- / 2-layer models: all samples in one pass on the device, nothing written (csrc/sampled.hip); otherwise one
+    # full-graph forward per sample (the in-place parameter writes invalidate the engine's cache).
     def sample(self, n_samples: int = 100, generator: torch.Generator | None = None, eps: torch.Tensor | None = None):
         """``eps`` (n_samples x n_params standard normal draws) may be passed instead of a generator so that
         results are reproducible across devices."""
@@ -354,9 +358,49 @@ class ParametricLaplace(_GLMLinkMixin, BaseLaplace):
                 f_mu, f_var = self._glm_predictive_distribution(x)
                 return f_mu, (torch.diagonal(f_var, dim1=-2, dim2=-1) if diagonal_output else f_var)
             return self._glm_forward_call(x, link_approx, n_samples, diagonal_output, generator, eps)
+        # the reduction of _nn_predictive_samples over chunks of samples: [S, M, C] need not exist
+        samples = self.sample(n_samples, generator=generator, eps=eps)
+        S = samples.shape[0]
+        chunk = max(1, min(S, self._NN_CHUNK_FLOATS // max(1, x.shape[0] * int(self.n_outputs or 1))))
+        if chunk >= S:
+            outs = self._nn_forward_samples(x, samples)
+            if regression:  # mean and variance over the parameter samples (:1060-1066)
+                return outs.mean(dim=0), outs.var(dim=0)
+            return outs.mean(dim=0)
+        # chunks meet as (count, mean, sum of squared deviations from the mean): the variance never subtracts two large sums
+        n, mean, m2 = 0, None, None
+        for s0 in range(0, S, chunk):
+            outs = self._nn_forward_samples(x, samples[s0:s0 + chunk])
+            nb, mean_b = outs.shape[0], outs.mean(dim=0)
+            m2_b = ((outs - mean_b) ** 2).sum(dim=0) if regression else None
+            if mean is None:
+                n, mean, m2 = nb, mean_b, m2_b
+                continue
+            delta = mean_b - mean
+            if regression:
+                m2 = m2 + m2_b + delta * delta * (n * nb / (n + nb))
+            mean = mean + delta * (nb / (n + nb))
+            n += nb
+        if regression:
+            return mean, m2 / (n - 1)
+        return mean
+
+    _NN_CHUNK_FLOATS = 1 << 27  # floats of a chunk of sampled outputs [S_chunk, M, C] in ``__call__(pred_type="nn")``
+
+    def _nn_device_route(self) -> bool:
+        """Whether the backend evaluates parameter samples without writing them into the model (``sampled_forward``: plain
+        1- or 2-layer GCN / GraphSAGE on the HIP engine, posterior over all of the model's parameters)."""
+        be = self.backend
+        scope = getattr(be, "sampled_forward_in_scope", None)
+        return scope is not None and hasattr(be, "sampled_forward") and bool(scope(self.n_params))
+
+    def _nn_forward_samples(self, x, samples):
+        """[S, M, C]: the model's outputs at ``x`` under each row of ``samples`` [S, n_params]; classification: their softmax."""
+        regression = self.likelihood == "regression"
+        if self._nn_device_route():  # one pass on the device, the parameters are never written
+            return self.backend.sampled_forward(x, samples, softmax=not regression)
         from torch.nn.utils import vector_to_parameters
         outs = []
-        samples = self.sample(n_samples, generator=generator, eps=eps)
         try:
             for theta in samples:
                 vector_to_parameters(theta, self.params)
@@ -364,10 +408,29 @@ class ParametricLaplace(_GLMLinkMixin, BaseLaplace):
                 outs.append(f if regression else torch.softmax(f, dim=-1))
         finally:
             vector_to_parameters(self.mean.clone(), self.params)  # the parameters must not alias self.mean afterwards
-        outs = torch.stack(outs)
-        if regression:  # mean and variance over the parameter samples (:1060-1066)
-            return outs.mean(dim=0), outs.var(dim=0)
-        return outs.mean(dim=0)
+        return torch.stack(outs)
+
+    @torch.no_grad()
+    def _nn_predictive_samples(self, x, n_samples: int = 100, generator: torch.Generator | None = None,
+                               eps: torch.Tensor | None = None):
+        """laplace/baselaplace.py:1160-1181: [S, M, C] outputs of the model under S posterior samples (classification: their
+        softmax).  ``eps``: [n_samples, n_params] standard normal draws instead of the generator."""
+        return self._nn_forward_samples(x.to(self._device), self.sample(n_samples, generator=generator, eps=eps))
+
+    @torch.no_grad()
+    def predictive_samples(self, x, pred_type: str = "glm", n_samples: int = 100, diagonal_output: bool = False,
+                           generator: torch.Generator | None = None, eps: torch.Tensor | None = None):
+        """Samples of the posterior predictive [n_samples, M, C] (laplace/baselaplace.py:1074-1120).  ``"glm"``: samples of the
+        linearised model's ``N(f_mu, f_var)`` through the link (``diagonal_output``: of its diagonal); ``"nn"``: the network
+        under parameter samples.  ``eps`` replaces the random draws ([n_outputs, n_samples] for "glm", [n_samples, n_params]
+        for "nn")."""
+        if pred_type not in ("glm", "nn"):
+            raise ValueError("Only glm and nn supported as prediction types.")
+        if pred_type == "nn":
+            return self._nn_predictive_samples(x, n_samples, generator=generator, eps=eps)
+        x = x.to(self._device)
+        f_mu, f_var = self._glm_predictive_distribution(x)
+        return self._glm_predictive_samples(f_mu, f_var, n_samples, diagonal_output, generator, eps)
 
     # ---- GLM predictive ("next" row 8(f)-3) ---------------------------------------------------------------------
     def functional_variance(self, Js: torch.Tensor) -> torch.Tensor:
@@ -1297,18 +1360,28 @@ class _LastLayerHead:
                                     diagonal_output=diagonal_output, generator=generator, eps=eps, **kwargs)
         if link_approx != "mc":
             raise ValueError("Only mc link approximation is supported for nn prediction type.")
-        x = x.to(self._device)
         theta = self.sample(n_samples, generator=generator, eps=eps)  # [S, C D + C]
+        outs = [p.mean(dim=0) for p in self._nn_sample_chunks(x.to(self._device), theta)]
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def _nn_sample_chunks(self, x, theta):
+        """The per-sample softmax [S, m, C] of the head samples ``theta``, one chunk of evaluation nodes at a time."""
         S = theta.shape[0]
         C, D = self._head.weight.shape
         Ws, bs = theta[:, :C * D].reshape(S, C, D), theta[:, C * D:]
         chunk = max(1, self._LL_CHUNK_FLOATS // max(S * C, D))
-        outs = []
         for s0 in range(0, max(int(x.shape[0]), 1), chunk):
             phi, s, _ = self.backend.lastlayer_features(x[s0:s0 + chunk])
             f = torch.einsum("nd,scd->snc", phi, Ws) + s.reshape(1, -1, 1) * bs.unsqueeze(1)
-            outs.append(torch.softmax(f, dim=-1).mean(dim=0))
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+            yield torch.softmax(f, dim=-1)
+
+    @torch.no_grad()
+    def _nn_predictive_samples(self, x, n_samples: int = 100, generator: torch.Generator | None = None,
+                               eps: torch.Tensor | None = None):
+        """[S, M, C]: the softmax under each HEAD sample (what ``__call__(pred_type="nn")`` averages); nothing is written."""
+        theta = self.sample(n_samples, generator=generator, eps=eps)
+        outs = list(self._nn_sample_chunks(x.to(self._device), theta))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
 
 class KronLLLaplace(_LastLayerHead, KronLaplace):
