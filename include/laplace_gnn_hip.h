@@ -624,12 +624,19 @@ LGNN_API int lgnn_glm_variance_ext(lgnn_ctx* h, const int64_t* idx, int64_t M, c
 /* ---- decomposition of the fitted factors ("next" row: KronLaplace.fit -> Kron.decompose) ----------
  * Replaces the per-factor torch.linalg.eigh calls of laplace/utils/matrix.py:118-145 (symeig,
  * laplace/utils/utils.py:193-226) by one call for all factors: n <= 256 -- a one-workgroup Householder tridiagonalisation
- * per factor (all factors side by side), rocSOLVER's divide and conquer on the tridiagonal matrices (one chain per factor on
- * side streams joined back into `stream`), a back-transformation kernel; larger n -- ONE strided-batched rocSOLVER syevd.
+ * per factor (all factors side by side), a one-workgroup divide and conquer on the tridiagonal matrices (lgnn_tridiag_eig
+ * below), a back-transformation kernel; 256 < n <= 512 (n % 4 == 0) -- the same with rocSOLVER's divide and conquer (one
+ * chain per factor on side streams joined back into `stream`); larger n -- ONE strided-batched rocSOLVER syevd.
  * A: device fp32 [batch][n][n], symmetric, overwritten with the eigenvectors: ROW j of matrix b is the unit eigenvector of
  * eigenvalue W[b][j]; W: device fp32 [batch][n], ascending; info: device int32 [batch] (0 = converged).  Asynchronous on
- * `stream`; no graph handle involved.    */
+ * (n <= 256: 1 = a NaN or Inf in the factor).  Asynchronous on `stream`; no graph handle involved.    */
 LGNN_API int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W, int32_t* info, void* stream);
+
+/* The divide and conquer step of the n <= 256 route on its own (csrc/eigh.hip, tridiag_dc_kernel): eigenpairs of `batch`
+ * symmetric tridiagonal matrices, diagonal d [batch][n] and off-diagonal e [batch][n] (the last entry of each row unused),
+ * device fp32, in place: d <- eigenvalues ascending, ROW j of Z [batch][n][n] <- unit eigenvector j; info[b] = 1 where d or e
+ * holds a NaN or Inf (d and Z of that matrix are left alone), else 0.  1 <= n <= 256.  Asynchronous on `stream`.     */
+LGNN_API int lgnn_tridiag_eig(float* d, float* e, int64_t n, int64_t batch, float* Z, int32_t* info, void* stream);
 
 /* ---- kNN initial graph (the reference's `--init_graph knng` configurations) ----------------------
  * Replaces torch_geometric.nn.knn_graph(X, k, loop=False, cosine=False) inside get_knn_graph (gnn/utils.py:355-369, handed

@@ -87,6 +87,7 @@ SIGNATURES = {
     "lgnn_glm_variance_ext": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp]),
     "lgnn_symeig_batched": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "lgnn_tridiag_eig": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "lgnn_jacobians": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_jacobians_subset": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_subnet_full_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),

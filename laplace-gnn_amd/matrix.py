@@ -62,7 +62,8 @@ def _symeig_group_hip(mats: list) -> list:
 def symeig_batched_hip(mats: list, cache: dict | None = None, keys: list | None = None) -> list:
     """Eigendecompose several symmetric PSD factors on the GPU (``lgnn_symeig_batched``): per-factor ``torch.linalg.eigh`` is
     a serial chain of ~100 single-workgroup kernels (3.3 ms per 256 x 256 factor).  Factors of up to 256 rows go through ONE
-    call (hand-written tridiagonalisation, all factors side by side: the four arxiv factors in 2 ms), larger ones one call
+    call (hand-written tridiagonalisation, divide and conquer and back-transform, three launches with all factors side by
+    side: the four arxiv factors in 1.5 ms), larger ones one call
     each (padding a 64 x 64 factor to 1 433 would cost a second large decomposition).  ``cache`` / ``keys``: a dict owned by
     the caller and one hashable key (or None) per factor -- a large factor whose key is in the cache is served from it, a
     keyed one that is not gets stored (the ``_LARGE_EIG_KEEP`` most recent entries stay); factors without a key are always
@@ -71,7 +72,8 @@ def symeig_batched_hip(mats: list, cache: dict | None = None, keys: list | None 
     A factor H (n x n) smaller than the largest of its call (m x m) is embedded as blockdiag(H, -mean_eig(H) I): the blocks never couple (Householder reflectors and the divide and
     conquer splits keep exact zeros), D's eigenpairs sort first, H's are the last n rows restricted to the
     first n columns.  Returns [(eigenvalues, eigenvectors)] with ``symeig``'s conventions (ascending, clamped
-    at 0, NaNs zeroed, eigenvectors in columns); non-convergence falls back to ``symeig`` for that factor."""
+    at 0, NaNs zeroed, eigenvectors in columns); a factor whose status is not 0 (a NaN or Inf in it on the hand-written path,
+    non-convergence on the library's) falls back to ``symeig``."""
     out = [None] * len(mats)
     small = [b for b, H in enumerate(mats) if H.shape[0] <= _SMALL_EIG]
     if small:
