@@ -21,8 +21,6 @@ int sgemm_rm(hipStream_t s, int64_t R, int64_t Nout, int64_t K, float alpha, con
              int64_t ldb, float beta, float* Cm, int64_t ldc);
 // The Kronecker chains' top layer (C = dims[L] classes): g [C][N][C] = P^T scatter(seeds) and the flags ws.active of its rows
 int launch_seed_planes(lgnn_ctx* h, float* g, hipStream_t s);
-// ws.act_list / ws.act_count = the compacted list of the rows flagged in ws.active
-int compact_active_rows(lgnn_ctx* h, hipStream_t s);
 // gradP (stored entries; skipped when null) and grad_cand (K pairs) += <seeds of a batch row a, g1bar[b]>, classes [c0, c0 + cc)
 int launch_seed_sddmm(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* g1bar, int64_t c0, int64_t cc, float* grad_P,
                       const int32_t* cand_a, const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s);

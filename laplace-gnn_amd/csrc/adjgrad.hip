@@ -327,7 +327,7 @@ __global__ void adj_grad_symmetrize_kernel(const int32_t* __restrict__ a_rowptr,
   }
 }
 
-// GCN top layer, all N rows (kfac.hip's unfused seed SpMM restated here with the planes of a class chunk only)
+// GCN top layer, all N rows (kfac_top.hip's unfused seed SpMM restated here with the planes of a class chunk only)
 __global__ void seed_planes_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                    const float* __restrict__ val, int64_t N, int64_t C, const int32_t* __restrict__ pos,
                                    const float* __restrict__ seeds, float* __restrict__ g, uint8_t* __restrict__ active) {
@@ -446,13 +446,6 @@ int launch_seed_planes(lgnn_ctx* h, float* g, hipStream_t s) {
                      h->dims[h->L], h->ws.pos.as<int32_t>(), h->ws.seeds.as<float>(), g, h->ws.active.as<uint8_t>());
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
-}
-
-int compact_active_rows(lgnn_ctx* h, hipStream_t s) {
-  LGNN_CALL(h->ws.act_list.reserve(size_t(h->N) * 4));
-  LGNN_CALL(h->ws.act_count.reserve(64));
-  return compact_flags(h->ws.active.as<uint8_t>(), h->N, h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(),
-                       h->ws.select_tmp, s);
 }
 
 int launch_seed_sddmm(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* g1bar, int64_t c0, int64_t cc, float* grad_P,

@@ -1,5 +1,5 @@
 // Batch-structure cache: what a KFAC accumulate derives from the graph and a batch's node ids alone (lgnn_internal.h,
-// BatchEntry).  Host code only -- the lists are built by the kernels of kfac.hip / paths.hip into the workspace exactly as
+// BatchEntry).  Host code only -- the lists are built by the kernels of kfac_top.hip / paths.hip into the workspace exactly as
 // without the cache, and copied into an entry of their exact size the second time a tag is seen.
 //
 // The training loop of the reference builds its loader once (gnn/marglik_training.py:125-127, shuffle=False) and calls

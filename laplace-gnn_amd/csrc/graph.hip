@@ -266,6 +266,15 @@ int compact_flags(const uint8_t* flags, int64_t n, int32_t* out, int32_t* count_
   return 0;
 }
 
+int compact_rows(lgnn_ctx* h, const uint8_t* flags, DevBuf& list, DevBuf& count, hipStream_t s) {
+  LGNN_CALL(list.reserve(size_t(h->N) * 4));
+  LGNN_CALL(count.reserve(64));
+  return compact_flags(flags, h->N, list.as<int32_t>(), count.as<int32_t>(), h->ws.select_tmp, s);
+}
+
+int compact_active_rows(lgnn_ctx* h, hipStream_t s) {
+  return compact_rows(h, h->ws.active.as<uint8_t>(), h->ws.act_list, h->ws.act_count, s);
+}
 
 // Degree scales and the fp32 values of P / P^T for the CSRs in h->A / h->AT (`same`: A^T aliases A), and the P / P^T views.
 int graph_values(lgnn_ctx* h, bool same, hipStream_t s) {

@@ -328,7 +328,7 @@ struct lgnn_ctx {
   int64_t n_long = -1;             // -1: not looked at yet
   int64_t n_long_tasks = 0;
   lgnn::DevBuf long_rows, long_slot, long_tasks, hub;
-  // top-layer kernel (kfac.hip): hubs with more than kTopSlice entries are cut into slices; their node ids, count, and the
+  // top-layer kernel (kfac_top.hip): hubs with more than kTopSlice entries are cut into slices; their node ids, count, and the
   // number of slices over all of them (host copies); per-batch task list and partial tiles
   lgnn::DevBuf top_multi, top_tasks, top_task_count, top_cnt, top_offs, top_hub_tiles;
   int64_t n_top_multi = 0, n_top_slices = 0;
@@ -424,7 +424,11 @@ int launch_backgemm(const BackGemmArgs& g, hipStream_t s);
 int launch_relu_mask_bits(const float* h, int64_t ld, int64_t N, int64_t H, uint32_t* bits, hipStream_t s);
 // out[0:count) = sorted indices i with flags[i] != 0; *count_dev = count   (graph.hip, rocPRIM select)
 int compact_flags(const uint8_t* flags, int64_t n, int32_t* out, int32_t* count_dev, DevBuf& tmp, hipStream_t s);
-int kfac_top_planes(lgnn_ctx* h, const int64_t* idx, int64_t M, bool fork_exact, float* g, hipStream_t s);  // kfac.hip
+// the reserve-plus-select half of a row list: list / count = the sorted ids of the rows flagged in flags [N] (graph.hip) ...
+int compact_rows(lgnn_ctx* h, const uint8_t* flags, DevBuf& list, DevBuf& count, hipStream_t s);
+// ... for the workspace's own triple: ws.act_list / ws.act_count = the compacted list of the rows flagged in ws.active
+int compact_active_rows(lgnn_ctx* h, hipStream_t s);
+int kfac_top_planes(lgnn_ctx* h, const int64_t* idx, int64_t M, bool fork_exact, float* g, hipStream_t s);  // kfac_top.hip
 int exclusive_scan_i32(int32_t* in, int32_t* out, int64_t n, DevBuf& tmp, hipStream_t s);  // graph.hip, rocPRIM
 
 // ---- graph.hip -----------------------------------------------------------------------
@@ -534,7 +538,7 @@ int long_rows_fwd_ensure(lgnn_ctx* h, hipStream_t s);  // the list of long rows 
 // hub[plane][slot][0:width) = sum_j val[j] * in[plane][col[j]][0:width) for the long rows of P^T
 int launch_long_rows_spmm(lgnn_ctx* h, const float* val, const float* in, int64_t in_ld, int64_t in_plane_stride,
                           int64_t nplanes, int64_t width, hipStream_t s);
-// ---- kfac.hip ---------------------------------------------------------------------------
+// ---- kfac.hip (its kernels and launchers: kfac_seed.hip, kfac_top.hip; what those three share: kfac.h) ----------
 struct KfacPlan {
   bool seeds_on_the_fly;       // GCN top layer rebuilds the seed blocks from probabilities + logits
   bool sage_compact;           // GraphSAGE top level over the batch nodes only (compacted backward GEMM + fused MODE 1)
@@ -558,6 +562,7 @@ struct KfacShare { int64_t begin, end, count; };  // parts [begin, end) of `coun
 int kfac_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, int64_t n_train, uint32_t flags,
                     int64_t class_begin, int64_t class_end, float* const* A_out, float* const* B_out, float* loss_out,
                     hipStream_t s, const KfacFisherOpts* fisher = nullptr, const KfacShare* share = nullptr);
+// kfac_seed.hip: the start and the end of every batch
 int batch_prologue(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, bool want_seeds, bool fork_exact,
                    float* loss_out, hipStream_t s, const void* y_seed = nullptr, float resid_scale = 1.0f,
                    const int64_t* guard_ids = nullptr);  // guard_ids: the ids a cache entry was built from (compared on the device)

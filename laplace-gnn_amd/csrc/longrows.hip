@@ -108,7 +108,7 @@ int long_rows_ensure(lgnn_ctx* h, hipStream_t s) {
   LGNN_CALL(h->long_tasks.reserve(tasks.size() * 4));
   LGNN_HIP_CHECK(hipMemcpyAsync(h->long_tasks.p, tasks.data(), tasks.size() * 4, hipMemcpyHostToDevice, s));
   LGNN_HIP_CHECK(hipStreamSynchronize(s));
-  // hubs the top-layer kernel cuts into slices of kTopSlice entries (kfac.hip)
+  // hubs the top-layer kernel cuts into slices of kTopSlice entries (kfac_top.hip)
   std::vector<int32_t> ids(static_cast<size_t>(n)), multi;
   LGNN_HIP_CHECK(hipMemcpyAsync(ids.data(), h->long_rows.p, size_t(n) * 4, hipMemcpyDeviceToHost, s));
   LGNN_HIP_CHECK(hipStreamSynchronize(s));

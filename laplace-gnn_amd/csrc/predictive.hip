@@ -438,10 +438,7 @@ int glm_variance(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1m, i
     LGNN_HIP_CHECK(hipMemsetAsync(h->ws.active.p, 0, size_t(N), s));
     hipLaunchKernelGGL(pred_mark_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col,
                        h->ws.active.as<uint8_t>(), bad);
-    LGNN_CALL(h->ws.act_list.reserve(size_t(N) * 4));
-    LGNN_CALL(h->ws.act_count.reserve(64));
-    LGNN_CALL(compact_flags(h->ws.active.as<uint8_t>(), N, h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(),
-                            h->ws.select_tmp, s));
+    LGNN_CALL(compact_active_rows(h, s));
     int32_t nneed = 0;
     LGNN_HIP_CHECK(hipMemcpyAsync(&nneed, h->ws.act_count.p, 4, hipMemcpyDeviceToHost, s));
     LGNN_HIP_CHECK(hipStreamSynchronize(s));  // the size of R has to reach the host
@@ -552,10 +549,7 @@ int glm_variance_ext(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* W1
   LGNN_HIP_CHECK(hipMemsetAsync(h->ws.active.p, 0, size_t(N), s));
   hipLaunchKernelGGL(pred_mark_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col,
                      h->ws.active.as<uint8_t>(), bad);
-  LGNN_CALL(h->ws.act_list.reserve(size_t(N) * 4));
-  LGNN_CALL(h->ws.act_count.reserve(64));
-  LGNN_CALL(compact_flags(h->ws.active.as<uint8_t>(), N, h->ws.act_list.as<int32_t>(), h->ws.act_count.as<int32_t>(),
-                          h->ws.select_tmp, s));
+  LGNN_CALL(compact_active_rows(h, s));
   int32_t nneed = 0;
   LGNN_HIP_CHECK(hipMemcpyAsync(&nneed, h->ws.act_count.p, 4, hipMemcpyDeviceToHost, s));
   LGNN_HIP_CHECK(hipStreamSynchronize(s));  // the size of the table has to reach the host

@@ -4,7 +4,7 @@
 //     G_n[c, k] = sum_e w_e V_{m_e}[k, c]       over the entries e = (m_e, w_e) of row n of R = P^T[:, batch]
 //               = d_ck sum_e w_e alpha_c^e + sum_e (w_e (-beta)_c^e) u_k^e + (w_e (-gamma)_c^e) p_k^e
 //
-// (the seed block is diagonal plus rank two: kfac.hip, seed_spmm_gram_kernel).  seed_spmm_gram_kernel rebuilds the coefficients
+// (the seed block is diagonal plus rank two: kfac_top.hip, seed_spmm_gram_kernel).  seed_spmm_gram_kernel rebuilds the coefficients
 // of every (node, neighbour) pair from the probabilities and logits, finds the batch neighbours by walking the row of P^T with
 // ballots and writes the tile row by row through LDS: ~300 vector instructions per pair on an issue-bound wave.  Here
 //   * the coefficient rows (alpha | -beta | -gamma) and the rows (u, p) come from path_tables_kernel's tables (paths.hip),
