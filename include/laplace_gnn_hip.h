@@ -431,6 +431,40 @@ LGNN_API int lgnn_gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const
                             float* K, int64_t ldk, void* stream);
 LGNN_API int lgnn_gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, void* stream);
 
+/* ---- low-rank Laplace: products of the Jacobian and of the GGN with a block of parameter directions ----------------
+ * What LowRankLaplace (laplace/baselaplace.py:1679-1835) asks of its backend is eig_lowrank (laplace/curvature/
+ * asdfghjkl.py:212-236: power iteration on Hessian-vector products, one vector at a time).  Here the curvature is the GGN of
+ * lgnn_full_accumulate and a product takes a block V [k, P] of directions on the device; a direction is a contiguous row of
+ * P floats (the layout of theta in lgnn_sampled_forward), parameters in lgnn_jacobians' order.
+ *   lgnn_jvp_block:  out [M, C, k]: out[m, c, i] = <J[m, c, :], V[i, :]>  (written, never accumulated)
+ *   lgnn_ggn_matmat: G [k, P]: G[i, :] += sum_n J_n^T Lambda_n J_n V[i, :], Lambda_n = diag(p_n) - p_n p_n^T (regression:
+ *                    the identity, no interface factor, as lgnn_subnet_full_accumulate);
+ *                    *loss_out += loss(model(idx), y) without the interface factor, as lgnn_full_accumulate
+ *     LGNN_GGN_FROM_JACOBIANS     take the general route on any model (cross-check, timing baseline)
+ * 1- and 2-layer GCN / GraphSAGE (relu or tanh) without res / norm: no Jacobian and no [rows, H k] intermediate reaches memory.
+ * With in0 = [P X | rowsum P] (GCN) or [X | P X | 1] (GraphSAGE), R the rows the batch reads and D = act'(s), per direction
+ * (dW0, db0, dW1, db1): q[r] = (D[r] . (in0[r] [dW0 | db0]^T)) W1^T + h[r] dW1^T on v_mfma_f32_32x32x2_f32 with D and W1 applied
+ * while the tile is on chip (lgnn_sampled_forward's product, linearised); u[n] = sum_b P[n, b] (q[b] + db1); w[n] = Lambda_n u[n];
+ * qbar[b] = sum_n P[n, b] w[n] as a gather over P^T's rows; g_b1 = sum_n rho_n w[n]; g_W1 = sum_r qbar[r]^T h[r]; sbar[r] = D[r] .
+ * (qbar[r] W1) built in the prologue of the MFMA product [g_W0 | g_b0] = sum_r sbar[r]^T in0[r].  R is split into slabs whose
+ * partial [k, P] outputs a second pass adds in slab order.  The directions go in chunks that keep q, u, w, qbar and the partials
+ * under the workspace limit.  Every other model, and any model under LGNN_GGN_FROM_JACOBIANS: chunks of lgnn_jacobians' rows,
+ * U = J_c V^T on the fp32 matrix cores, Lambda applied to U, G += (Lambda U)^T J_c.  The P x P matrix is never formed.  No float
+ * atomics in the products: every element of out / G has one writer and a fixed summation order, two calls on the same input
+ * return the same bits.  Invalid ids: zero rows and the sticky flag, as lgnn_jacobians (lgnn_check_async_errors).  With kernel
+ * timing enabled lgnn_ggn_matmat records four event pairs per chunk (structured: forward + gather, curvature, qbar + bias, outer
+ * products + finish; general: J V^T, Lambda, (Lambda U)^T J, the addition into G), lgnn_jvp_block one.
+ *   lgnn_block_gram:  out [ka, kb] = A B^T for blocks of directions A [ka, P], B [kb, P] (written, never accumulated): the
+ *                    Gram and Rayleigh-Ritz matrices of the block eigensolver on the same fp32 MFMA NT GEMM as lgnn_gp_kernel
+ *                    (split-K partials added in slab order; A == B gives an exactly symmetric result).                     */
+#define LGNN_GGN_FROM_JACOBIANS 1
+LGNN_API int lgnn_block_gram(lgnn_ctx* h, const float* A, int64_t ka, const float* B, int64_t kb, int64_t P, float* out,
+                             void* stream);
+LGNN_API int lgnn_jvp_block(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* V /* [k, P] */, int64_t k,
+                            float* out /* [M, C, k] */, void* stream);
+LGNN_API int lgnn_ggn_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* V /* [k, P] */, int64_t k,
+                             int flags, float* G /* [k, P] */, float* loss_out, void* stream);
+
 /* ---- gradient of the negative log marginal likelihood w.r.t. the adjacency ("next" row 8(f)-4) --------------
  * Replaces what autograd does for ``neg_marglik.backward()`` into ``model.adj`` (gnn/marglik_training.py:197-216):
  * back through KronDecomposed.logdet / log_marginal_likelihood (laplace/utils/matrix.py:371-394,

@@ -10,9 +10,9 @@ from .curvature import HipCurvatureInterface, HipEF, HipGGN  # noqa: F401
 from .data import TensorBatchLoader, batches_of_rank, units_of_rank  # noqa: F401
 from .engine import GraphEngine  # noqa: F401
 from .knn import get_knn_graph, knn, knn_candidates, knn_graph  # noqa: F401
-from . import subnetmask  # noqa: F401
+from . import lowrank, subnetmask  # noqa: F401
 from .laplace import (BaseLaplace, DiagLaplace, DiagLLLaplace, DiagSubnetLaplace, FullLaplace, FullLLLaplace,  # noqa: F401
-                      FullSubnetLaplace, KronLaplace, KronLLLaplace, Laplace, ParametricLaplace, SubnetLaplace,
+                      FullSubnetLaplace, KronLaplace, KronLLLaplace, Laplace, LowRankLaplace, ParametricLaplace, SubnetLaplace,
                       all_reduce_flat_)
 from .gp import FunctionalLaplace  # noqa: F401
 from .matrix import Kron, KronDecomposed, symeig  # noqa: F401
@@ -25,4 +25,4 @@ __all__ = ["GraphEngine", "HipGGN", "HipEF", "HipCurvatureInterface", "Laplace",
            "TensorBatchLoader", "batches_of_rank", "units_of_rank", "all_reduce_flat_", "knn", "knn_graph", "get_knn_graph",
            "knn_candidates", "SubnetLaplace", "FullSubnetLaplace", "DiagSubnetLaplace", "subnetmask", "SubnetMask",
            "RandomSubnetMask", "LargestMagnitudeSubnetMask", "LargestVarianceDiagLaplaceSubnetMask", "ParamNameSubnetMask",
-           "ModuleNameSubnetMask", "LastLayerSubnetMask", "FunctionalLaplace"]
+           "ModuleNameSubnetMask", "LastLayerSubnetMask", "FunctionalLaplace", "LowRankLaplace"]

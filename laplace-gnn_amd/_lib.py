@@ -17,6 +17,7 @@ LIK_CLASSIFICATION, LIK_REGRESSION = 0, 1
 NORM_NONE, NORM_LAYER, NORM_BATCH = 0, 1, 2
 FLAG_FORK_EXACT_SEED, FLAG_NO_FUSE, FLAG_NO_PATHS, FLAG_FORCE_PATHS = 1, 2, 4, 8
 GP_INDEPENDENT, GP_MATCHED, GP_FROM_JACOBIANS = 1, 2, 4
+GGN_FROM_JACOBIANS = 1
 SAMPLED_SOFTMAX = 1
 
 # name -> (restype, argtypes); mirrors include/laplace_gnn_hip.h one to one
@@ -93,6 +94,9 @@ SIGNATURES = {
     "lgnn_subnet_full_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_gp_kernel": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "lgnn_gp_jvp": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_block_gram": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "lgnn_jvp_block": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "lgnn_ggn_matmat": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "lgnn_knn": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
 }
 

@@ -318,15 +318,11 @@ __global__ __launch_bounds__(256) void gp_jvp_kernel(const float* __restrict__ T
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------
-struct NtProblem {
-  const float* A; int64_t lda, a_bs;
-  const float* B; int64_t ldb, b_bs;
-  float* Out; int64_t ldo, o_es, o_bs;
-  int64_t Ra, Rb, K, batch;
-};
+}  // namespace
 
 // Split-K when the output has fewer tiles than the chip has CUs and K is long (the general route: K = P): partial outputs
-// [z][slab][Ra][Rb] in ws.gp_part, added in slab order by gp_splitk_sum_kernel.
+// [z][slab][Ra][Rb] in ws.gp_part, added in slab order by gp_splitk_sum_kernel.  (NtProblem: lgnn_internal.h; ggnmat.hip
+// calls this too.)
 int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s) {
   if (p.Ra <= 0 || p.Rb <= 0 || p.batch <= 0) return 0;
   LGNN_REQUIRE(p.K > 0, "NT product with empty K");
@@ -363,6 +359,8 @@ int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s) {
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+namespace {
 
 int launch_rowdot(const float* A, int64_t lda, int64_t a_bs, const float* B, int64_t ldb, int64_t b_bs, int64_t K, int64_t R,
                   int64_t batch, float* out, int64_t o_bs, hipStream_t s) {

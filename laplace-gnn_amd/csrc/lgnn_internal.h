@@ -158,6 +158,12 @@ struct Workspace {
   // contraction's output Kt [(c, e)][ma mb], Phi Phi^T [ma][mb], W_pair [(c, e)][z'], split-K partials, and the two chunks of
   // Jacobian rows of the general route
   DevBuf gp_tab_a, gp_tab_b, gp_phi_a, gp_phi_b, gp_g, gp_kt, gp_s, gp_wpair, gp_part, gp_jac_a, gp_jac_b;
+  // GGN-times-block products (ggnmat.hip): a chunk of Jacobian rows [mc C, P], U = J V^T [mc C, k], W^T [k, mc C] and the
+  // chunk's product [k, P]
+  DevBuf ggn_jac, ggn_u, ggn_wt, ggn_tmp;
+  // ... and of its structured route: q and qbar [kc][|R|][Cz] (u and w [kc][M][C] share ggn_u / ggn_wt), the slab partials
+  // [slabs][kc][P]
+  DevBuf ggn_q, ggn_qbar, ggn_part;
   template <class F> void each_buf(F&& f) const {
     for (int l = 0; l < kMaxLayers; ++l) { f(gram_scratch[l]); f(gram_scratch_res[l]); }
     f(pos); f(seeds); f(probs); f(mult); f(planes_a); f(planes_b); f(misc); f(jac); f(top); f(active); f(val_act);
@@ -169,7 +175,7 @@ struct Workspace {
     f(dense_stored); f(dense_rows);
     f(subnet_keys); f(subnet_ord); f(subnet_iota); f(subnet_tmp); f(subnet_plan); f(subnet_x);
     f(gp_tab_a); f(gp_tab_b); f(gp_phi_a); f(gp_phi_b); f(gp_g); f(gp_kt); f(gp_s); f(gp_wpair); f(gp_part); f(gp_jac_a);
-    f(gp_jac_b);
+    f(gp_jac_b); f(ggn_jac); f(ggn_u); f(ggn_wt); f(ggn_tmp); f(ggn_q); f(ggn_qbar); f(ggn_part);
   }
 };
 
@@ -666,10 +672,39 @@ int subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64
 int gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int flags, float* K, int64_t ldk,
               hipStream_t s);
 int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, hipStream_t s);
+// Out_z[i * ldo + j * o_es] = sum_k A_z[i, k] B_z[j, k] for z < batch (A_z = A + z a_bs: [Ra, K] with row stride lda, B_z
+// likewise, Out_z = Out + z o_bs) on the fp32 matrix cores; no float atomics (split-K partials in ws.gp_part, added in order)
+struct NtProblem {
+  const float* A; int64_t lda, a_bs;
+  const float* B; int64_t ldb, b_bs;
+  float* Out; int64_t ldo, o_es, o_bs;
+  int64_t Ra, Rb, K, batch;
+};
+int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s);
+// ---- ggnmat.hip -------------------------------------------------------------------------
+// out [M, C, k] = J V^T;  G [k, P] += sum_n J_n^T Lambda_n J_n V^T and *loss_out += loss, for V [k, P]
+int jvp_block(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* V, int64_t k, float* out, hipStream_t s);
+int ggn_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* V, int64_t k, int flags, float* G,
+               float* loss_out, hipStream_t s);
 // ---- sampled.hip ------------------------------------------------------------------------
 // out [S, M, C] = the logits (flags & LGNN_SAMPLED_SOFTMAX: their softmax) of S parameter vectors theta [S, n_params] at idx
 int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* theta, int64_t S, uint32_t flags, float* out,
                     hipStream_t s);
+// its pieces, shared with ggnmat.hip: in0 (SampledState::in0 / ldk), the needed-row list of a batch (SampledState::rows /
+// count / rpos) and the CSR gather of step (c)
+int sampled_ensure_input(lgnn_ctx* h, hipStream_t s);
+int sampled_needed_rows(lgnn_ctx* h, const int64_t* idx, int64_t M, hipStream_t s);
+struct GatherArgs {
+  const int64_t* idx; int64_t M, N;
+  const int32_t* rowptr; const int32_t* col; const float* val;
+  const int32_t* rpos;
+  const float* z; int64_t rcap, Cz, C;
+  int sage, cw;                     // cw: lanes per entry group, the smallest power of two >= min(C, 64)
+  const float* theta; int64_t P, offb;
+  int64_t ns;                       // samples of the chunk
+  float* out;                       // the chunk's [ns, M, C]
+};
+int launch_sampled_gather(const GatherArgs& g, hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------
 // full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127

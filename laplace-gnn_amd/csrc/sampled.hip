@@ -218,17 +218,6 @@ __global__ __launch_bounds__(256) void sampled_hidden_kernel(HiddenArgs g) {
   }
 }
 
-struct GatherArgs {
-  const int64_t* idx; int64_t M, N;
-  const int32_t* rowptr; const int32_t* col; const float* val;
-  const int32_t* rpos;
-  const float* z; int64_t rcap, Cz, C;
-  int sage, cw;                     // cw: lanes per entry group, the smallest power of two >= min(C, 64)
-  const float* theta; int64_t P, offb;
-  int64_t ns;                       // samples of the chunk
-  float* out;                       // the chunk's [ns, M, C]
-};
-
 // (c) one wave per (sample, batch row): 64 / cw groups of lanes share the row's entries (entry p to group p % groups), the
 // groups' partial sums meet in a fixed butterfly order
 __global__ __launch_bounds__(256) void sampled_gather_kernel(GatherArgs g) {
@@ -284,6 +273,8 @@ __global__ __launch_bounds__(256) void sampled_softmax_kernel(const int64_t* __r
   for (int64_t c = lane; c < C; c += 64) o[c] = expf(o[c] - mx) * inv;
 }
 
+}  // namespace
+
 // in0: what the first Linear multiplies, seen from an output row, with the bias' column.  The graph and X only.
 int sampled_ensure_input(lgnn_ctx* h, hipStream_t s) {
   SampledState& sf = h->sf;
@@ -305,7 +296,41 @@ int sampled_ensure_input(lgnn_ctx* h, hipStream_t s) {
   return 0;
 }
 
-}  // namespace
+// (a) R = the rows the evaluation nodes read, deduplicated and sorted (sf.rows, sf.count on the device), and where each of
+// them stands in R (sf.rpos); 1 layer: R is the batch itself
+int sampled_needed_rows(lgnn_ctx* h, const int64_t* idx, int64_t M, hipStream_t s) {
+  SampledState& sf = h->sf;
+  const int64_t N = h->N;
+  const bool two = h->L == 2, sage = h->kind == LGNN_KIND_SAGE;
+  int* bad = h->ws.flags.as<int>() + 2;  // "node index outside [0, num_nodes)" (lgnn_check_async_errors)
+  LGNN_CALL(sf.rows.reserve(size_t(std::max(N, M)) * 4));
+  LGNN_CALL(sf.count.reserve(4));
+  int32_t* rows = sf.rows.as<int32_t>();
+  int32_t* count = sf.count.as<int32_t>();
+  if (two) {
+    LGNN_CALL(sf.need.reserve(size_t(N)));
+    LGNN_CALL(sf.rpos.reserve(size_t(N) * 4));
+    LGNN_HIP_CHECK(hipMemsetAsync(sf.need.p, 0, size_t(N), s));
+    hipLaunchKernelGGL(sampled_mark_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col,
+                       sage ? 1 : 0, sf.need.as<uint8_t>(), bad);
+    LGNN_HIP_CHECK(hipGetLastError());
+    LGNN_CALL(compact_flags(sf.need.as<uint8_t>(), N, rows, count, sf.select_tmp, s));
+    hipLaunchKernelGGL(sampled_positions_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, rows, count, N,
+                       sf.rpos.as<int32_t>());
+    LGNN_HIP_CHECK(hipGetLastError());
+  } else {
+    hipLaunchKernelGGL(sampled_batch_rows_kernel, dim3(unsigned(cdiv(M, 256))), dim3(256), 0, s, idx, M, N, rows, count, bad);
+    LGNN_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+int launch_sampled_gather(const GatherArgs& g, hipStream_t s) {
+  LGNN_REQUIRE(cdiv(g.ns * g.M, 4) < (int64_t(1) << 31), "too many (sample, node) pairs per chunk");
+  hipLaunchKernelGGL(sampled_gather_kernel, dim3(unsigned(cdiv(g.ns * g.M, 4))), dim3(256), 0, s, g);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 
 int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* theta, int64_t S, uint32_t flags, float* out,
                     hipStream_t s) {
@@ -324,29 +349,11 @@ int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* the
   const int64_t off1 = H * Fp + H, offb = two ? off1 + C * ld1 : C * Fp;
   const int64_t P = h->n_params;
   LGNN_REQUIRE(P == offb + C, "parameter count of the bound model");
-  int* bad = h->ws.flags.as<int>() + 2;  // "node index outside [0, num_nodes)" (lgnn_check_async_errors)
   LGNN_CALL(sampled_ensure_input(h, s));
-  LGNN_CALL(sf.rows.reserve(size_t(std::max(N, M)) * 4));
-  LGNN_CALL(sf.count.reserve(4));
+  LGNN_CALL(sampled_needed_rows(h, idx, M, s));
   int32_t* rows = sf.rows.as<int32_t>();
   int32_t* count = sf.count.as<int32_t>();
   const int64_t rcap = two ? N : M;  // host-known bound of |R|
-  if (two) {
-    // (a) R = the rows the evaluation nodes read, deduplicated and sorted, and where each of them stands in R
-    LGNN_CALL(sf.need.reserve(size_t(N)));
-    LGNN_CALL(sf.rpos.reserve(size_t(N) * 4));
-    LGNN_HIP_CHECK(hipMemsetAsync(sf.need.p, 0, size_t(N), s));
-    hipLaunchKernelGGL(sampled_mark_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col,
-                       sage ? 1 : 0, sf.need.as<uint8_t>(), bad);
-    LGNN_HIP_CHECK(hipGetLastError());
-    LGNN_CALL(compact_flags(sf.need.as<uint8_t>(), N, rows, count, sf.select_tmp, s));
-    hipLaunchKernelGGL(sampled_positions_kernel, dim3(unsigned(cdiv(N, 256))), dim3(256), 0, s, rows, count, N,
-                       sf.rpos.as<int32_t>());
-    LGNN_HIP_CHECK(hipGetLastError());
-  } else {
-    hipLaunchKernelGGL(sampled_batch_rows_kernel, dim3(unsigned(cdiv(M, 256))), dim3(256), 0, s, idx, M, N, rows, count, bad);
-    LGNN_HIP_CHECK(hipGetLastError());
-  }
   // chunks of samples: z [chunk, N, Cz] stays under the workspace limit (1 layer: no z, the product is the output)
   int64_t chunk = std::min<int64_t>(S, 32768);
   if (two) {
@@ -384,8 +391,7 @@ int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* the
       g.sage = sage ? 1 : 0; g.cw = cw;
       g.theta = theta + s0 * P; g.P = P; g.offb = offb;
       g.ns = ns; g.out = out_c;
-      hipLaunchKernelGGL(sampled_gather_kernel, dim3(unsigned(cdiv(ns * M, 4))), dim3(256), 0, s, g);
-      LGNN_HIP_CHECK(hipGetLastError());
+      LGNN_CALL(launch_sampled_gather(g, s));
     }
     if (flags & LGNN_SAMPLED_SOFTMAX) {
       hipLaunchKernelGGL(sampled_softmax_kernel, dim3(unsigned(cdiv(ns * M, 4))), dim3(256), 0, s, idx, M, N, ns * M, C, out_c);

@@ -64,8 +64,14 @@ class HipCurvatureInterface:
     def __init__(self, model: nn.Module, likelihood: str, last_layer: bool = False,
                  subnetwork_indices: torch.LongTensor | None = None, dict_key_x: str = "input_ids",
                  dict_key_y: str = "labels", stochastic: bool = False, fork_exact_seed: bool = True,
-                 num_samples: int = 1, generator: torch.Generator | None = None):
+                 num_samples: int = 1, generator: torch.Generator | None = None, low_rank: int = 10,
+                 lowrank_tol: float | None = None, lowrank_max_iters: int | None = None, lowrank_seed: int = 0):
         assert likelihood in ["regression", "classification"]
+        # eig_lowrank (HipGGN): ``low_rank`` is the reference's name and default (laplace/curvature/asdfghjkl.py:185); the
+        # solver's tolerance (None: lowrank.DEFAULT_TOL), sweep budget (None: 10 * low_rank) and start-block seed
+        self.low_rank = int(low_rank)
+        self.lowrank_tol, self.lowrank_max_iters, self.lowrank_seed = lowrank_tol, lowrank_max_iters, int(lowrank_seed)
+        self.lowrank_info = None
         self.likelihood = likelihood
         self.model = model
         self.last_layer = last_layer
@@ -412,6 +418,51 @@ class HipGGN(HipCurvatureInterface):
         self._refuse_gp("gp_jvp")
         return self.engine.gp_jvp(x, v)
 
+    def jvp_block(self, x: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
+        """``einsum("bcp,kp->bck", J(x), V)`` for a block of directions ``V`` [k, P] as a fresh [M, C, k] tensor."""
+        self._refuse_gp("jvp_block")
+        return self.engine.jvp_block(x, V)
+
+    def ggn_matmat(self, loader_or_batches, V: torch.Tensor, from_jacobians: bool = False):
+        """``(V @ H [k, P], loss)`` for the GGN ``H = sum_n J_n^T Lambda_n J_n`` of all batches ``(X, y)`` of a loader (or any
+        iterable of them) -- the matrix ``full`` would return, never formed (``lgnn_ggn_matmat``).  The product is additive
+        over batches; the batch boundaries are the loader's.  Loss and H carry ``factor`` the way ``full`` applies it."""
+        self._refuse_gp("ggn_matmat")
+        eng = self.engine
+        eng.set_likelihood(self.likelihood)
+        V = V.detach().to(eng.device, torch.float32).contiguous()
+        G = torch.zeros_like(V)
+        loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
+        for X, y in loader_or_batches:
+            eng.ggn_matmat_(G, loss, X.to(eng.device), y.to(eng.device), V, from_jacobians=from_jacobians)
+        if self.likelihood != "regression" and self.factor != 1.0:
+            G = self.factor * G
+        return G, self.factor * loss[0]
+
+    def eig_lowrank(self, train_loader, tol: float | None = None, max_iters: int | None = None, seed: int | None = None):
+        """``(eigenvectors [P, K'], eigenvalues [K'], loss)``: the ``low_rank`` leading eigenpairs of the GGN over all
+        weights with eigenvalue > 1e-6, and the loss of the loader -- AsdfghjklHessian.eig_lowrank (laplace/curvature/
+        asdfghjkl.py:212-236) with block subspace iteration on ``ggn_matmat`` in place of power iteration on Hessian-vector
+        products (lowrank.py).  One sweep is one product over all batches; the solver's sweep count and residuals are left
+        in ``self.lowrank_info``.  ``tol`` / ``max_iters`` / ``seed`` override the constructor's values for this call."""
+        from . import lowrank
+        self._refuse_gp("eig_lowrank")
+        eng = self.engine
+        batches = [(X.to(eng.device), y.to(eng.device)) for X, y in train_loader]
+        state = {"loss": None}
+
+        def matmat(Q):
+            G, loss = self.ggn_matmat(batches, Q)
+            state["loss"] = loss
+            return G
+
+        res = lowrank.subspace_eig(
+            matmat, eng.n_params, self.low_rank, eng.device, tol=self.lowrank_tol if tol is None else tol,
+            max_iters=self.lowrank_max_iters if max_iters is None else max_iters,
+            seed=self.lowrank_seed if seed is None else seed, gram=eng.block_gram)
+        self.lowrank_info = res
+        return res.eigenvectors, res.eigenvalues, state["loss"]
+
 
 class HipEF(HipCurvatureInterface):
     """Empirical Fisher backend; the counterpart of ``CurvlinopsEF`` / ``EFInterface`` (laplace/curvature/curvlinops.py:
@@ -440,6 +491,12 @@ class HipEF(HipCurvatureInterface):
         rs = 2.0 if self.likelihood == "regression" else 1.0
         eng.ef_accumulate(x, y, y, rs, self.factor, diag=None if full else H, full=H if full else None, loss=loss)
         return self.factor * loss[0], H
+
+    def ggn_matmat(self, *args, **kwargs):
+        raise NotImplementedError("ggn_matmat is a product with the GGN: HipGGN only (HipEF holds the empirical Fisher)")
+
+    def eig_lowrank(self, *args, **kwargs):
+        raise NotImplementedError("eig_lowrank runs on the GGN product: HipGGN only (HipEF holds the empirical Fisher)")
 
     def diag(self, x: torch.Tensor, y: torch.Tensor, **kwargs: Any):
         return self._ef(x, y, full=False)

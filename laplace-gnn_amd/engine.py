@@ -748,6 +748,50 @@ class GraphEngine:
                                         out.data_ptr(), _stream(self.device)), "lgnn_gp_jvp")
         return out
 
+    # -- low-rank Laplace (csrc/ggnmat.hip) -----------------------------------------------------------------------
+    def _directions(self, V: torch.Tensor) -> torch.Tensor:
+        """A block of parameter directions: fp32 [k, n_params] on the device, one contiguous row per direction."""
+        V = V.detach().to(self.device, torch.float32).contiguous()
+        if V.dim() != 2 or V.shape[0] == 0 or V.shape[1] != self.n_params:
+            raise ValueError(f"V must be [k, {self.n_params}] with k >= 1, got {tuple(V.shape)}")
+        return V
+
+    def jvp_block(self, idx: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
+        """``out[m, c, i] = <J[m, c, :], V[i, :]>`` for ``V`` [k, n_params] (``lgnn_jvp_block``): [M, C, k]."""
+        self._sync_versions()
+        idx, V = idx.contiguous(), self._directions(V)
+        M, k = idx.shape[0], V.shape[0]
+        out = torch.empty(M, self.dims[-1], k, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_jvp_block(self._h, _dev_ptr(idx, torch.int64, "idx"), M, V.data_ptr(), k, out.data_ptr(),
+                                           _stream(self.device)), "lgnn_jvp_block")
+        return out
+
+    def block_gram(self, A: torch.Tensor, B: torch.Tensor | None = None) -> torch.Tensor:
+        """``A B^T`` [ka, kb] of two blocks of directions [k, P] on the library's NT GEMM (``lgnn_block_gram``): fixed summation
+        order, exactly symmetric for ``B is None`` (= A)."""
+        A = A.contiguous()
+        B = A if B is None else B.contiguous()
+        if A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[1]:
+            raise ValueError(f"blocks must be [k, P] with the same P, got {tuple(A.shape)} and {tuple(B.shape)}")
+        out = torch.empty(A.shape[0], B.shape[0], dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_block_gram(self._h, _dev_ptr(A, torch.float32, "A"), A.shape[0],
+                                            _dev_ptr(B, torch.float32, "B"), B.shape[0], A.shape[1], out.data_ptr(),
+                                            _stream(self.device)), "lgnn_block_gram")
+        return out
+
+    def ggn_matmat_(self, G: torch.Tensor, loss_buf: torch.Tensor, idx, y, V: torch.Tensor, from_jacobians: bool = False):
+        """``G[i, :] += sum_n J_n^T Lambda_n J_n V[i, :]`` for ``V`` [k, n_params], ``loss_buf += `` raw loss sum
+        (``lgnn_ggn_matmat``); the P x P matrix is never formed.  ``from_jacobians``: the library's flag of that name."""
+        self._sync_versions()
+        idx, V = idx.contiguous(), self._directions(V)
+        if tuple(G.shape) != tuple(V.shape) or not G.is_contiguous():
+            raise ValueError(f"G must be contiguous [{V.shape[0]}, {V.shape[1]}], got {tuple(G.shape)}")
+        rc = self.lib.lgnn_ggn_matmat(
+            self._h, _dev_ptr(idx, torch.int64, "idx"), self._labels(y, idx.shape[0]), idx.shape[0], V.data_ptr(), V.shape[0],
+            _lib.GGN_FROM_JACOBIANS if from_jacobians else 0, _dev_ptr(G, torch.float32, "G"), loss_buf.data_ptr(),
+            _stream(self.device))
+        _lib.check(rc, "lgnn_ggn_matmat")
+
     # -- subnetwork Laplace (csrc/subnet.hip) ---------------------------------------------------------------------
     def _subnet(self, subnet: torch.Tensor) -> torch.Tensor:
         """int64 [S] on the device.  The indices address the Laplace parameter vector (the columns of ``jacobians``); the
