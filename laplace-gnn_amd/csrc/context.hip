@@ -6,6 +6,7 @@
 // them (gnn/models/base_gnn.py:136-161).  Here it runs once per weight version and is cached,
 // together with the raw input Grams in_l^T in_l of the KFAC A factors (kfac.py:819-875), which are
 // batch independent for the same reason.
+#include "closedform.h"
 #include "lgnn_internal.h"
 
 namespace lgnn {
@@ -310,6 +311,41 @@ int forward_ensure_aux(lgnn_ctx* h, hipStream_t s) {
     LGNN_CALL(launch_act_deriv(h->fc.hact_p[0], h->fc.hact_ld[0], h->N, H, h->act, h->fc.dact0.as<float>(), s));
   }
   h->fc.aux_valid = true;
+  return 0;
+}
+
+// ---- closedform.h: the cache's buffers as the closed forms' operands (after forward_ensure_aux) --------------------------
+int feat_views(lgnn_ctx* h, int layer, FeatView& f) {
+  f.nrows = h->N;
+  // what Linear `layer` multiplies, seen from an output node: propagated input (GCN) or cat (GraphSAGE)
+  if (h->kind == LGNN_KIND_GCN) {
+    f.base = h->fc.prop_in[layer].as<float>();
+    f.ld = h->fc.prop_ld[layer];
+    f.width = h->dims[layer];
+    f.bias_col = h->fc.rowsum.as<float>();
+  } else {
+    f.base = h->fc.lin_in_p[layer];
+    f.ld = h->fc.lin_in_ld[layer];
+    f.width = h->in_dim[layer];
+    f.bias_col = nullptr;
+  }
+  return 0;
+}
+
+bool closed_form_model(const lgnn_ctx* h) { return h->L <= 2 && !h->extras(); }
+
+int closed_form_view(lgnn_ctx* h, ClosedForm& cf) {
+  LGNN_REQUIRE(h->L >= 1 && closed_form_model(h), "closed form: 1- and 2-layer models without res / norm");
+  const int L = h->L;
+  cf.L = L; cf.sage = h->kind == LGNN_KIND_SAGE ? 1 : 0;
+  cf.N = h->N; cf.in0 = h->in_dim[0]; cf.H = L == 2 ? h->dims[1] : 0; cf.C = h->dims[L]; cf.in_last = h->in_dim[L - 1];
+  cf.P = h->n_params; cf.off_last = L == 2 ? cf.H * cf.in0 + cf.H : 0;
+  cf.rowptr = h->P.rowptr; cf.col = h->P.col; cf.val = h->P.val;
+  LGNN_CALL(feat_views(h, 0, cf.E0));
+  LGNN_CALL(feat_views(h, L - 1, cf.PhiL));
+  cf.dact = L == 2 ? h->fc.dact0.as<float>() : nullptr;
+  cf.W1 = L == 2 ? h->W[1] : nullptr;
+  cf.w1_ld = L == 2 ? h->in_dim[1] : 0;
   return 0;
 }
 

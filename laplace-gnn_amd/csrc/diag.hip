@@ -1,4 +1,4 @@
-// Diagonal GGN and last-layer full GGN of one mini-batch, without materialising Jacobians.
+// Diagonal GGN of one mini-batch, without materialising Jacobians.
 //
 // Reference: GGNInterface.diag (laplace/curvature/curvature.py:412-432) builds Js[M, C, P] with
 // torch.func.jacrev (:89-130; 3.4 GB for the Cora-shaped config) and contracts
@@ -14,12 +14,14 @@
 //        diag(W_0)[j,i] = sum_n qbb[n,j] T^2 + 2 qab[n,j] S T + qaa[n,j] S^2
 //        q**[n,j] = w*_j^T Lambda_n w*_j with w_j the j-th column of the self / neighbour half of W_1.
 // The reference cannot construct models with more than 2 layers (live breakpoint at
-// gnn/models/base_gnn.py:109), so L <= 2 covers everything it can run.
+// gnn/models/base_gnn.py:109), so L <= 2 covers everything it can run; deeper models and models with res / norm contract
+// chunks of explicit Jacobians (diag_from_jacobians).
 //
-// Last-layer full GGN (laplace/curvature/curvature.py:132-167, 374-410):
-//   H = sum_n Lambda_n (x) phi~ phi~^T = blockdiag_c( sum_n p_nc phi~ phi~^T ) - Z^T Z,  z_n = p_n (x) phi~_n,
-// i.e. one large fp32 MFMA Gram (2 M P^2 flops) plus C small weighted Grams.
+// The file holds the kernels, one launcher per kernel and the driver diag_accumulate.  The empirical / Monte-Carlo Fisher's
+// diagonal (fisher.hip) is the same sum with other weights: it calls the launchers diag.h declares.
+#include "closedform.h"
 #include "device_utils.h"
+#include "diag.h"
 #include "lgnn_internal.h"
 
 namespace lgnn {
@@ -71,31 +73,6 @@ __global__ void q_kernel(const float* __restrict__ probs, int64_t M, int64_t C, 
     q[M * d + t] = ssn;
     q[2 * M * d + t] = sss;
   }
-}
-
-// Empirical Fisher: the per-sample gradient of the first layer is diag(rho_n) T_n (+ diag(rho_s) S_n), rho[j] = sum_k r_k w_kj,
-// so its square has the GGN kernel's form with q(neigh,neigh) = scale rho_n^2, q(self,neigh) = scale rho_s rho_n,
-// q(self,self) = scale rho_s^2; the last layer's weights are scale r_k^2.
-__global__ void q_ef_kernel(const float* __restrict__ r, int64_t M, int64_t C, const float* __restrict__ W1, int64_t ldw,
-                            int64_t d, int64_t off_self, int64_t off_neigh, int has_self, float scale, float* __restrict__ q) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= M * d) return;
-  const int64_t m = t / d, j = t - m * d;
-  float rn = 0.f, rs = 0.f;
-  for (int64_t k = 0; k < C; ++k) {
-    const float rk = r[m * C + k];
-    rn += rk * W1[k * ldw + off_neigh + j];
-    if (has_self) rs += rk * W1[k * ldw + off_self + j];
-  }
-  q[t] = scale * rn * rn;
-  if (has_self) {
-    q[M * d + t] = scale * rs * rn;
-    q[2 * M * d + t] = scale * rs * rs;
-  }
-}
-__global__ void ef_last_weights_kernel(const float* __restrict__ r, int64_t n, float scale, float* __restrict__ w) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t < n) w[t] = scale * r[t] * r[t];
 }
 
 // Classification batches of the closed-form diagonal: what batch_prologue + q_kernel did in five launches (mark, clear,
@@ -727,91 +704,6 @@ __global__ void diag_last_layer_kernel(const float* __restrict__ probs, const in
   else atomicAdd(&diag_b[k], acc);
 }
 
-// ---- last-layer full GGN as weighted Grams over class pairs -----------------------------------------------------
-// H = sum_n Lambda_n (x) phi~_n phi~_n^T: block (c, c') of H is the weighted Gram Phi~^T diag(Lambda[:, c, c']) Phi~ -- symmetric
-// in (c, c') AND inside the block.  Only the pairs c <= c' and the upper half of every block are computed (a quarter
-// of the P x P products; the formulation through Z^T Z, Z = [p_c phi~], computed half).
-// pair index q <-> (c, c'), c <= c', row major
-__device__ __forceinline__ void pair_of(int64_t q, int64_t C, int64_t& c, int64_t& c2) {
-  c = 0;
-  while (q >= C - c) { q -= C - c; ++c; }
-  c2 = c + q;
-}
-// Phi[m][j] = phi~ of batch row m (j < D features, j == D bias scale), zero padded to ldp
-__global__ void ll_build_phi_kernel(const int64_t* __restrict__ idx, int64_t M, FeatView Phi, int64_t ldp,
-                                    float* __restrict__ out) {
-  const int64_t total = M * ldp;
-  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-  for (int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t m = t / ldp, j = t - m * ldp;
-    out[t] = j <= Phi.width ? feat(Phi, idx[m], j) : 0.f;
-  }
-}
-// w = Lambda[m, c, c'] = [c == c'] p_c - p_c p_c'.  rs[q][m] = sqrt|w| (row scale of the Gram), ws[q][m] = w * s_m (signed,
-// times the bias scale of the row: the bias column of a block is sum_m w s_m phi~_m), zsign[q] = +1 (c == c') / -1
-__global__ void ll_pair_weights_kernel(const float* __restrict__ probs, const int64_t* __restrict__ idx, FeatView Phi,
-                                       int64_t M, int64_t C, int64_t q0, float* __restrict__ rs, float* __restrict__ ws,
-                                       float* __restrict__ zsign) {
-  const int64_t q = blockIdx.y;  // index inside the chunk of pairs that starts at q0
-  int64_t c, c2;
-  pair_of(q0 + q, C, c, c2);
-  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-  for (int64_t m = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; m < M; m += stride) {
-    const float pc = probs[m * C + c], pc2 = probs[m * C + c2];
-    const float w = (c == c2 ? pc : 0.f) - pc * pc2;
-    rs[q * M + m] = sqrtf(fabsf(w));
-    ws[q * M + m] = w * feat(Phi, idx[m], Phi.width);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) zsign[q] = c == c2 ? 1.f : -1.f;
-}
-// S[q] [D x D] (upper 32 x 32 sub-tiles valid) and Sb[q] [D + 1] (bias column) -> upper triangle of H.
-// H index of (class c, column a): a < D -> c * D + a, a == D (bias) -> C * D + c.
-// One workgroup per (32 x 32 tile (ti <= tj) of the block, pair): the tile goes through LDS so that the block's (ti, tj)
-// part and -- for c < c' or an off-diagonal tile -- its mirror image (tj, ti) are both written with coalesced rows.
-__global__ __launch_bounds__(256) void ll_place_tiles_kernel(const float* __restrict__ S, int64_t D, int64_t C, int64_t q0,
-                                                             float* __restrict__ Hout) {
-  __shared__ float t[32][33];
-  const int64_t P = C * D + C;
-  int64_t c, c2;
-  pair_of(q0 + blockIdx.z, C, c, c2);
-  const int64_t ti = blockIdx.y, tj = blockIdx.x;
-  if (ti > tj) return;
-  const float* __restrict__ Sq = S + int64_t(blockIdx.z) * D * D;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  for (int r = ty; r < 32; r += 8) {
-    const int64_t i = ti * 32 + r, j = tj * 32 + tx;
-    t[r][tx] = (i < D && j < D) ? Sq[i * D + j] : 0.f;
-  }
-  __syncthreads();
-  // block element (i, j) -> H[c D + i][c2 D + j]   (c <= c2: always in the upper triangle for c < c2; for c == c2 keep i <= j)
-  for (int r = ty; r < 32; r += 8) {
-    const int64_t i = ti * 32 + r, j = tj * 32 + tx;
-    if (i < D && j < D && (c < c2 || i <= j)) Hout[(c * D + i) * P + c2 * D + j] += t[r][tx];
-  }
-  if (ti < tj && c < c2) {  // the block is symmetric: element (j, i) of it equals (i, j); rows j of H, coalesced over i
-    for (int r = ty; r < 32; r += 8) {
-      const int64_t j = tj * 32 + r, i = ti * 32 + tx;
-      if (i < D && j < D) Hout[(c * D + j) * P + c2 * D + i] += t[tx][r];
-    }
-  }
-}
-// bias column of every block: H[(c, a)][(bias c2)] and H[(c2, a)][(bias c)] for a < D, H[bias c][bias c2]
-__global__ void ll_place_bias_kernel(const float* __restrict__ Sb, int64_t D, int64_t C, int64_t q0, int64_t nq,
-                                     float* __restrict__ Hout) {
-  const int64_t D1 = D + 1, P = C * D + C;
-  const int64_t total = nq * D1;
-  const int64_t stride = int64_t(gridDim.x) * blockDim.x;
-  for (int64_t tq = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; tq < total; tq += stride) {
-    const int64_t q = tq / D1, a = tq - q * D1;
-    int64_t c, c2;
-    pair_of(q0 + q, C, c, c2);
-    const float v = Sb[tq];
-    if (a == D) { Hout[(C * D + c) * P + C * D + c2] += v; continue; }  // (bias c, bias c2), c <= c2
-    Hout[(c * D + a) * P + C * D + c2] += v;                            // ((c, a), bias c2): row < column always
-    if (c != c2) Hout[(c2 * D + a) * P + C * D + c] += v;               // ((c2, a), bias c)
-  }
-}
-
 // Generic depth: diag[p] += sum_m sum_{c,k} J[m,c,p] Lambda_m[c,k] J[m,k,p] from a chunk of explicit Jacobians
 // J [mc, C, P] (jacobian.hip); Lambda_m = diag(p_m) - p_m p_m^T (laplace/curvature/curvature.py:365-372, 428), so
 // per sample: sum_c p_c t_c^2 - (sum_c p_c t_c)^2 with t_c = J[m,c,p].  regression (H_lik = None, :429-430): sum_c t_c^2.
@@ -853,71 +745,124 @@ int diag_from_jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* diag_
   return 0;
 }
 
-// ---- empirical / Monte-Carlo Fisher from per-sample gradients (EFInterface, laplace/curvature/curvature.py:435-504;
-// GGNInterface with stochastic=True, :343-364): G[m, p] = sum_c r[m, c] J[m, c, p] with the functional gradient
-// r = resid_scale * (softmax(f) - onehot(y_seed))  resp.  resid_scale * (f - y_seed) for the regression likelihood.
-__global__ void ef_resid_kernel(const float* __restrict__ probs, const float* __restrict__ logits,
-                                const int64_t* __restrict__ idx, const void* __restrict__ yseed, int64_t mc, int64_t C,
-                                int64_t N, int regression, float resid_scale, float* __restrict__ r, int* __restrict__ bad) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= mc * C) return;
-  const int64_t m = t / C, c = t - m * C;
-  const int64_t n = idx[m];
-  float v = 0.f;
-  if (n >= 0 && n < N) {
-    if (regression) v = logits[n * C + c] - static_cast<const float*>(yseed)[t];
-    else {
-      const int64_t ys = static_cast<const int64_t*>(yseed)[m];
-      if (ys < 0 || ys >= C) *bad = 2;
-      v = probs[t] - (c == ys ? 1.f : 0.f);
-    }
+const TileReduce kNoReduce{nullptr, 0, 0, 0, 0, nullptr, nullptr, -1};
+
+// LGNN_DIAG_SLAB: samples per workgroup slab, clamped to [1, cap]; unset: the launch's own choice
+int64_t slab_or_env(int64_t chosen, int64_t cap) {
+  if (const char* e = getenv("LGNN_DIAG_SLAB")) return std::max<int64_t>(1, std::min<int64_t>(cap, atoll(e)));
+  return chosen;
+}
+// LGNN_DIAG_STAGED forces the register-staged first-layer kernel for GCN too (tests compare the two)
+bool staged_forced() { return getenv("LGNN_DIAG_STAGED") != nullptr; }
+
+// GCN, narrow inputs: diag_first_layer_mfma_kernel, partial tiles flushed with float atomics
+int launch_first_layer_mfma(lgnn_ctx* h, const FeatView& E, const int64_t* idx, int64_t M, const float* q, float* diag_out,
+                            hipStream_t s) {
+  const int64_t H = h->dims[1], in0 = h->in_dim[0];
+  const unsigned gx = unsigned(cdiv(E.width + 1, 256)), gy = unsigned(cdiv(H, 64));
+  const int64_t sl = slab_or_env(std::max<int64_t>(4, std::min<int64_t>(64, cdiv(M * gx * gy, 512))), 64);
+  hipLaunchKernelGGL((diag_first_layer_mfma_kernel<8, 3>), dim3(gx, gy, unsigned(cdiv(M, sl))), dim3(256), 0, s,
+                     h->P.rowptr, h->P.col, h->P.val, idx, M, sl, E.base, E.ld, E.width, h->N,
+                     h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// GCN, wide inputs (ncb >= 4 column blocks): owned output tiles, long slabs, plain-store partials in ws.jac; `red` names them
+// for the fixed-order reduction that rides on the last-layer launch (no atomics)
+int launch_first_layer_tile(lgnn_ctx* h, const FeatView& E, int64_t ncb, const int64_t* idx, int64_t M, const float* q,
+                            float* diag_out, hipStream_t s, TileReduce& red) {
+  const int64_t H = h->dims[1], in0 = h->in_dim[0];
+  const int64_t gyt = cdiv(H, 64);
+  int64_t nsl = std::max<int64_t>(1, std::min<int64_t>(cdiv(256, ncb * gyt), cdiv(M, 16)));  // ~ one workgroup per CU
+  const int64_t sl = slab_or_env(std::min<int64_t>(kTileSlabMax, cdiv(M, nsl)), kTileSlabMax);
+  nsl = cdiv(M, sl);
+  const int64_t part_ld = ncb * kTileCols;
+  LGNN_CALL(h->ws.jac.reserve(size_t(nsl) * H * part_ld * 4));
+  float* part = h->ws.jac.as<float>();
+  hipLaunchKernelGGL(diag_first_layer_tile_kernel, dim3(unsigned(ncb * nsl), unsigned(gyt)), dim3(256), 0, s,
+                     h->P.rowptr, h->P.col, h->P.val, idx, M, sl, int(ncb), E.base, E.ld, E.width, h->N,
+                     h->fc.dact0.as<float>(), H, q, part, part_ld);
+  LGNN_HIP_CHECK(hipGetLastError());
+  red = TileReduce{part, part_ld, int(nsl), H, E.width, diag_out, diag_out + H * in0, 0};
+  return 0;
+}
+
+// diag_last_layer_kernel; a pending tile reduction (red.z0 >= 0) becomes extra z-slices of the launch
+int launch_last_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int64_t slab, const float* wgt, float* out, TileReduce red,
+                      hipStream_t s) {
+  const int64_t C = h->dims[h->L];
+  FeatView Phi;
+  feat_views(h, h->L - 1, Phi);
+  dim3 grid{unsigned(cdiv(Phi.width + 1, 256)), unsigned(C), unsigned(cdiv(M, slab))};
+  if (red.z0 >= 0) {
+    red.z0 = int(grid.z);
+    const int64_t blocks = cdiv(red.H * ((red.F + 4) / 4), 256);
+    grid.z += unsigned(cdiv(blocks, int64_t(grid.x) * grid.y));
   }
-  r[t] = resid_scale * v;
+  hipLaunchKernelGGL(diag_last_layer_kernel, grid, dim3(256), 0, s, h->ws.probs.as<float>(), idx, M, C, slab, Phi, out,
+                     out + C * Phi.width, wgt, red);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
 }
-__global__ __launch_bounds__(256) void grads_from_jac_kernel(const float* __restrict__ J, const float* __restrict__ r,
-                                                             int64_t mc, int64_t C, int64_t P, float* __restrict__ G) {
-  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  const int64_t m = blockIdx.y;
-  if (p >= P) return;
-  const float* __restrict__ Jm = J + m * C * P + p;
-  float acc = 0.f;
-  for (int64_t c = 0; c < C; ++c) acc += r[m * C + c] * Jm[c * P];
-  G[m * P + p] = acc;
-}
-__global__ __launch_bounds__(256) void sumsq_rows_kernel(const float* __restrict__ G, int64_t mc, int64_t P, float scale,
-                                                         float* __restrict__ diag) {
-  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (p >= P) return;
-  const int64_t m_begin = int64_t(blockIdx.y) * 32, m_end = min(mc, m_begin + 32);
-  float acc = 0.f;
-  for (int64_t m = m_begin; m < m_end; ++m) { const float g = G[m * P + p]; acc += g * g; }
-  atomicAdd(&diag[p], scale * acc);
+
+// The first layer of a 2-layer model: the matrix-core kernels for GCN, the register-staged kernel for GraphSAGE (its self path
+// needs three q rows and the node's own rows per closing entry) and under LGNN_DIAG_STAGED.  off: where the last layer's
+// block starts in diag_out; red: the tile kernel's partials, still to be added up.
+int first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int64_t slab, bool staged, const float* q, float* diag_out,
+                hipStream_t s, TileReduce& red, int64_t& off) {
+  red = kNoReduce;
+  off = 0;
+  if (h->L != 2) return 0;
+  if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the diagonal path (bench.py roofline)
+  if (staged) {
+    LGNN_CALL(launch_diag_first_layer_staged(h, idx, M, slab, q, diag_out, s));
+  } else {
+    // GCN: E = [P X | rowsum(P) | 0] is one padded matrix (context.hip build_px)
+    FeatView E;
+    feat_views(h, 0, E);
+    LGNN_REQUIRE(E.ld >= E.width + 1 && E.ld % 4 == 0, "internal: P X without its bias column");
+    const int64_t ncb = cdiv(E.width + 1, kTileCols);
+    if (ncb >= 4 && h->dims[1] % 4 == 0) LGNN_CALL(launch_first_layer_tile(h, E, ncb, idx, M, q, diag_out, s, red));
+    else LGNN_CALL(launch_first_layer_mfma(h, E, idx, M, q, diag_out, s));
+  }
+  if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += M; }
+  off = h->dims[1] * h->in_dim[0] + h->dims[1];
+  return 0;
 }
 
 }  // namespace
 
-int feat_views(lgnn_ctx* h, int layer, FeatView& f) {
-  f.nrows = h->N;
-  // what Linear `layer` multiplies, seen from an output node: propagated input (GCN) or cat (GraphSAGE)
-  if (h->kind == LGNN_KIND_GCN) {
-    f.base = h->fc.prop_in[layer].as<float>();
-    f.ld = h->fc.prop_ld[layer];
-    f.width = h->dims[layer];
-    f.bias_col = h->fc.rowsum.as<float>();
-  } else {
-    f.base = h->fc.lin_in_p[layer];
-    f.ld = h->fc.lin_in_ld[layer];
-    f.width = h->in_dim[layer];
-    f.bias_col = nullptr;
-  }
+// Samples per workgroup slab of the staged first-layer and the last-layer kernel.  A thread walks its slab's samples and
+// their neighbours one after the other (dependent loads: a latency chain), so small problems want short slabs -- Cora shape:
+// 0.42 -> 0.2 ms with 16 instead of 64 -- while every slab costs one atomic per output element: aim for `target` workgroups.
+// (measured at the Cora shape: 1 024 - 2 048 workgroups are the optimum -- fewer lengthen the per-workgroup chain,
+//  more multiply the float atomics of the flush: 0.13 ms at 2 048, 0.26 ms at 8 192)
+int64_t diag_slab(const lgnn_ctx* h, int64_t M, int64_t target) {
+  int64_t tiles = 1;
+  if (h->L == 2) tiles = cdiv(h->in_dim[0] + 1, 64) * cdiv(h->dims[1], 64);
+  return std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, target)));
+}
+
+int launch_diag_first_layer_staged(lgnn_ctx* h, const int64_t* idx, int64_t M, int64_t slab, const float* q, float* diag_out,
+                                   hipStream_t s) {
+  const int64_t H = h->dims[1], in0 = h->in_dim[0];
+  FeatView E;
+  feat_views(h, 0, E);
+  const dim3 grid{unsigned(cdiv(E.width + 1, 64)), unsigned(cdiv(H, 64)), unsigned(cdiv(M, slab))};
+  if (h->kind == LGNN_KIND_SAGE)
+    hipLaunchKernelGGL(diag_first_layer_kernel<1>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab, E,
+                       h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
+  else
+    hipLaunchKernelGGL(diag_first_layer_kernel<0>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab, E,
+                       h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
+  LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-int launch_ll_build_phi(const int64_t* idx, int64_t M, const FeatView& Phi, int64_t ldp, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(ll_build_phi_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M * ldp, 256), 8192))), dim3(256), 0, s, idx, M,
-                     Phi, ldp, out);
-  LGNN_HIP_CHECK(hipGetLastError());
-  return 0;
+int launch_diag_last_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int64_t slab, const float* wgt, float* out,
+                           hipStream_t s) {
+  return launch_last_layer(h, idx, M, slab, wgt, out, kNoReduce, s);
 }
 
 int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags, float* diag_out,
@@ -928,7 +873,7 @@ int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, u
   const int L = h->L;
   const int64_t C = h->dims[L];
   const bool regression = h->lik == LGNN_LIK_REGRESSION;
-  if (L > 2 || h->extras() || getenv("LGNN_JAC_PLANES") != nullptr) {
+  if (!closed_form_model(h) || getenv("LGNN_JAC_PLANES") != nullptr) {
     // deeper models (the reference builds them once the breakpoint at gnn/models/base_gnn.py:109 is removed): per-sample
     // Jacobians in chunks + the contraction with Lambda; no closed form
     LGNN_CALL(forward_ensure(h, s));
@@ -942,339 +887,40 @@ int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, u
   // (Lambda = I, no probabilities) keeps the shared prologue
   const bool light = !regression;
   if (!light) LGNN_CALL(batch_prologue(h, idx, y, M, false, false, loss_out, s));
-  // regression: Lambda = I, i.e. q = sum_k w_kj^2 and unit weights in the last layer (the interface's factor is the caller's)
-  const float* probs = regression ? nullptr : h->ws.probs.as<float>();
-  // Samples per workgroup slab.  A thread walks its slab's samples and their neighbours one after the other (dependent
-  // loads: a latency chain), so small problems want short slabs -- Cora shape: 0.42 -> 0.2 ms with 16 instead of 64 --
-  // while every slab costs one atomic per output element: aim for ~2048 workgroups.
-  int64_t tiles = 1;
-  if (h->L == 2) tiles = cdiv(h->in_dim[0] + 1, 64) * cdiv(h->dims[1], 64);
-  // (measured at the Cora shape: 1 024 - 2 048 workgroups are the optimum -- fewer lengthen the per-workgroup chain,
-  //  more multiply the float atomics of the flush: 0.13 ms at 2 048, 0.26 ms at 8 192)
-  int64_t slab = std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, 2048)));
-  // First-layer kernel: the matrix-core kernels for GCN, the register-staged kernel of round 2 for GraphSAGE (its self path
-  // needs three q rows and the node's own rows per closing entry).  LGNN_DIAG_STAGED forces the staged kernel for GCN too
-  // (tests compare the two).
-  const bool staged = getenv("LGNN_DIAG_STAGED") != nullptr || h->kind == LGNN_KIND_SAGE;
+  const bool staged = staged_forced() || h->kind == LGNN_KIND_SAGE;
   // the matrix-core kernels size their own slabs; behind them the last-layer kernel takes longer slabs, fewer atomics
   // (~768 workgroups, three per CU)
-  if (!staged) slab = std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, 768)));
-  if (const char* e = getenv("LGNN_DIAG_SLAB")) slab = std::max<int64_t>(1, std::min<int64_t>(64, atoll(e)));
-  const unsigned nslab = unsigned(cdiv(M, slab));
+  const int64_t slab = slab_or_env(diag_slab(h, M, staged ? 2048 : 768), 64);
 
-  int64_t off = 0;
-  TileReduce red{nullptr, 0, 0, 0, 0, nullptr, nullptr, -1};
-  {
-    const int64_t H = L == 2 ? h->dims[1] : 0, in0 = h->in_dim[0];
-    const int has_self = h->kind == LGNN_KIND_SAGE ? 1 : 0;
-    LGNN_CALL(h->ws.misc.reserve(size_t(3) * M * H * 4 + size_t(M) * C * 4));
-    float* q = h->ws.misc.as<float>();
-    if (light) {
-      LGNN_CALL(h->ws.probs.reserve(size_t(M) * C * 4));
-      probs = h->ws.probs.as<float>();
-      LGNN_REQUIRE(4 * C * 4 <= 60 * 1024, "too many classes for the prologue kernel");
-      hipLaunchKernelGGL(diag_prologue_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M, 4), 4096))), dim3(256),
-                         size_t(4 * C) * 4, s, h->fc.out.as<float>(), C, idx, static_cast<const int64_t*>(y), M, h->N,
-                         L == 2 ? h->W[1] : nullptr, L == 2 ? h->in_dim[1] : 0, H, int64_t(0), has_self ? H : int64_t(0),
-                         has_self, h->ws.probs.as<float>(), q, loss_out, h->ws.flags.as<int>());
-      LGNN_HIP_CHECK(hipGetLastError());
-    } else if (L == 2) {
-      hipLaunchKernelGGL(q_kernel, dim3(unsigned(cdiv(M * H, 256))), dim3(256), 0, s, probs, M, C, h->W[1],
-                         h->in_dim[1], H, int64_t(0), has_self ? H : int64_t(0), has_self, q);
-    }
-    if (L == 2) {
-      FeatView E;
-      feat_views(h, 0, E);
-      const dim3 grid{unsigned(cdiv(E.width + 1, 64)), unsigned(cdiv(H, 64)), nslab};
-      if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the diagonal path (bench.py roofline)
-      if (staged) {
-        if (has_self)
-          hipLaunchKernelGGL(diag_first_layer_kernel<1>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab,
-                             E, h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-        else
-          hipLaunchKernelGGL(diag_first_layer_kernel<0>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab,
-                             E, h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-      } else {
-        // GCN: the matrix-core kernels; E = [P X | rowsum(P) | 0] is one padded matrix (context.hip build_px)
-        LGNN_REQUIRE(E.ld >= E.width + 1 && E.ld % 4 == 0, "internal: P X without its bias column");
-        const int64_t ncb = cdiv(E.width + 1, kTileCols);
-        if (ncb >= 4 && H % 4 == 0) {
-          // wide inputs: owned output tiles, long slabs, plain-store partials + a fixed-order reduction (no atomics)
-          const int64_t gyt = cdiv(H, 64);
-          int64_t nsl = std::max<int64_t>(1, std::min<int64_t>(cdiv(256, ncb * gyt), cdiv(M, 16)));  // ~ one workgroup per CU
-          int64_t sl = std::min<int64_t>(kTileSlabMax, cdiv(M, nsl));
-          if (const char* e = getenv("LGNN_DIAG_SLAB")) sl = std::max<int64_t>(1, std::min<int64_t>(kTileSlabMax, atoll(e)));
-          nsl = cdiv(M, sl);
-          const int64_t part_ld = ncb * kTileCols;
-          LGNN_CALL(h->ws.jac.reserve(size_t(nsl) * H * part_ld * 4));
-          float* part = h->ws.jac.as<float>();
-          hipLaunchKernelGGL(diag_first_layer_tile_kernel, dim3(unsigned(ncb * nsl), unsigned(gyt)), dim3(256), 0, s,
-                             h->P.rowptr, h->P.col, h->P.val, idx, M, sl, int(ncb), E.base, E.ld, E.width, h->N,
-                             h->fc.dact0.as<float>(), H, q, part, part_ld);
-          LGNN_HIP_CHECK(hipGetLastError());
-          if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += M; }
-          red = TileReduce{part, part_ld, int(nsl), H, E.width, diag_out, diag_out + H * in0, 0};
-          off = H * in0 + H;
-          goto first_layer_done;
-        }
-        const unsigned gx = unsigned(cdiv(E.width + 1, 256)), gy = unsigned(cdiv(H, 64));
-        int64_t sl = std::max<int64_t>(4, std::min<int64_t>(64, cdiv(M * gx * gy, 512)));
-        if (const char* e = getenv("LGNN_DIAG_SLAB")) sl = std::max<int64_t>(1, std::min<int64_t>(64, atoll(e)));
-        hipLaunchKernelGGL((diag_first_layer_mfma_kernel<8, 3>), dim3(gx, gy, unsigned(cdiv(M, sl))), dim3(256), 0, s,
-                           h->P.rowptr, h->P.col, h->P.val, idx, M, sl, E.base, E.ld, E.width, h->N,
-                           h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-      }
-      LGNN_HIP_CHECK(hipGetLastError());
-      if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += M; }
-      off = H * in0 + H;
-    }
-  }
-first_layer_done:
-  {
-    FeatView Phi;
-    feat_views(h, L - 1, Phi);
-    const int64_t slab_last = slab;
-    dim3 grid{unsigned(cdiv(Phi.width + 1, 256)), unsigned(C), unsigned(cdiv(M, slab_last))};
-    if (red.z0 >= 0) {  // the tile kernel's partials are added up by extra z-slices of this launch
-      red.z0 = int(grid.z);
-      const int64_t blocks = cdiv(red.H * ((red.F + 4) / 4), 256);
-      grid.z += unsigned(cdiv(blocks, int64_t(grid.x) * grid.y));
-    }
-    const float* wgt = nullptr;
-    if (regression) {
-      const int64_t Hq = L == 2 ? h->dims[1] : 0;
-      LGNN_CALL(h->ws.misc.reserve(size_t(3) * M * Hq * 4 + size_t(M) * C * 4));
-      float* ones = h->ws.misc.as<float>() + 3 * M * Hq;
-      LGNN_CALL(launch_fill_i32(reinterpret_cast<int32_t*>(ones), M * C, 0x3f800000, s));  // 1.0f
-      wgt = ones;
-    }
-    hipLaunchKernelGGL(diag_last_layer_kernel, grid, dim3(256), 0, s, h->ws.probs.as<float>(), idx, M, C, slab_last, Phi,
-                       diag_out + off, diag_out + off + C * Phi.width, wgt, red);
+  const int64_t H = L == 2 ? h->dims[1] : 0;
+  const int has_self = h->kind == LGNN_KIND_SAGE ? 1 : 0;
+  LGNN_CALL(h->ws.misc.reserve(size_t(3) * M * H * 4 + size_t(M) * C * 4));
+  float* q = h->ws.misc.as<float>();
+  if (light) {
+    LGNN_CALL(h->ws.probs.reserve(size_t(M) * C * 4));
+    LGNN_REQUIRE(4 * C * 4 <= 60 * 1024, "too many classes for the prologue kernel");
+    hipLaunchKernelGGL(diag_prologue_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M, 4), 4096))), dim3(256),
+                       size_t(4 * C) * 4, s, h->fc.out.as<float>(), C, idx, static_cast<const int64_t*>(y), M, h->N,
+                       L == 2 ? h->W[1] : nullptr, L == 2 ? h->in_dim[1] : 0, H, int64_t(0), has_self ? H : int64_t(0),
+                       has_self, h->ws.probs.as<float>(), q, loss_out, h->ws.flags.as<int>());
     LGNN_HIP_CHECK(hipGetLastError());
+  } else if (L == 2) {
+    // regression: Lambda = I, i.e. q = sum_k w_kj^2 and unit weights in the last layer (the interface's factor is the caller's)
+    hipLaunchKernelGGL(q_kernel, dim3(unsigned(cdiv(M * H, 256))), dim3(256), 0, s, static_cast<const float*>(nullptr), M, C,
+                       h->W[1], h->in_dim[1], H, int64_t(0), has_self ? H : int64_t(0), has_self, q);
   }
+  TileReduce red;
+  int64_t off;
+  LGNN_CALL(first_layer(h, idx, M, slab, staged, q, diag_out, s, red, off));
+  const float* wgt = nullptr;
+  if (regression) {
+    float* ones = q + 3 * M * H;
+    LGNN_CALL(launch_fill_i32(reinterpret_cast<int32_t*>(ones), M * C, 0x3f800000, s));  // 1.0f
+    wgt = ones;
+  }
+  LGNN_CALL(launch_last_layer(h, idx, M, slab, wgt, diag_out + off, red, s));
   if (!light) LGNN_CALL(batch_epilogue(h, idx, M, s));
   return 0;
-}
-
-int gram_rows_sgemm(const float* G, int64_t rows, int64_t P, float scale, float* out, hipStream_t s);  // jacobian.hip
-int ef_grads_closed_form(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* r, float* G, hipStream_t s);  // jacobian.hip
-
-// Full GGN over all weights (GGNInterface.full, laplace/curvature/curvature.py:374-410; the reference's default backend
-// applies a matrix-free GGN to the P columns of the identity, curvlinops/ggn.py:44-75 via laplace/curvature/
-// curvlinops.py:110-140): H = sum_n J_n^T Lambda_n J_n with Lambda_n = S_n S_n^T, S[k, c] = sqrt(p_c) (d_kc - p_k), so
-// H = X^T X for the rows X[(n, c), :] = sum_k S_n[k, c] J[n, k, :] = sqrt(p_c) (J[n, c, :] - sum_k p_k J[n, k, :]) -- one
-// in-place row mixing pass over a chunk of device Jacobians, then the fp32 MFMA Gram kernel (upper sub-tiles) straight
-// into the caller's H.  Regression (H_lik = None): X = J.
-__global__ __launch_bounds__(256) void ggn_mix_rows_kernel(float* __restrict__ J, const float* __restrict__ probs,
-                                                           int64_t mc, int64_t C, int64_t P) {
-  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  const int64_t m = blockIdx.y;
-  if (p >= P) return;
-  float* __restrict__ Jm = J + m * C * P + p;
-  const float* __restrict__ pm = probs + m * C;
-  float t = 0.f;
-  for (int64_t k = 0; k < C; ++k) t += pm[k] * Jm[k * P];
-  for (int64_t c = 0; c < C; ++c) Jm[c * P] = sqrtf(pm[c]) * (Jm[c * P] - t);
-}
-
-int full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out, float* loss_out,
-                    hipStream_t s) {
-  LGNN_REQUIRE(M > 0 && idx && y && H_out && loss_out, "empty batch or null pointers");
-  LGNN_REQUIRE(h->L >= 1, "no model bound");
-  LGNN_CALL(forward_ensure(h, s));
-  const int64_t C = h->dims[h->L], P = h->n_params;
-  LGNN_REQUIRE(P * P < (int64_t(1) << 40), "full GGN: P x P does not fit");
-  LGNN_CALL(batch_prologue(h, idx, y, M, false, false, loss_out, s));
-  const int64_t mc_max = std::max<int64_t>(1, std::min<int64_t>(M, (h->ws_limit / 4) / std::max<int64_t>(C * P * 4, 1)));
-  LGNN_CALL(h->ws.jac.reserve(size_t(mc_max) * C * P * 4));
-  float* J = h->ws.jac.as<float>();
-  for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
-    const int64_t mc = std::min(mc_max, M - m0);
-    LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
-    if (h->lik != LGNN_LIK_REGRESSION) {
-      hipLaunchKernelGGL(ggn_mix_rows_kernel, dim3(unsigned(cdiv(P, 256)), unsigned(mc)), dim3(256), 0, s, J,
-                         h->ws.probs.as<float>() + m0 * C, mc, C, P);
-      LGNN_HIP_CHECK(hipGetLastError());
-    }
-    LGNN_CALL(launch_gram(J, P, mc * C, P, H_out, s));
-  }
-  LGNN_CALL(launch_symmetrize_upper(H_out, P, s));
-  LGNN_CALL(batch_epilogue(h, idx, M, s));
-  return 0;
-}
-
-int ef_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y_seed, const void* y_loss, int64_t M, float resid_scale,
-                  float scale, float* diag_out, float* full_out, float* grads_out, float* loss_out, hipStream_t s) {
-  LGNN_REQUIRE(M > 0 && idx && y_seed, "empty batch or null pointers");
-  LGNN_REQUIRE(h->L >= 1, "no model bound");
-  LGNN_REQUIRE(diag_out || full_out || grads_out, "nothing to compute");
-  LGNN_REQUIRE(!y_loss || loss_out, "loss requested without an output");
-  LGNN_CALL(forward_ensure(h, s));
-  const int64_t C = h->dims[h->L], P = h->n_params, N = h->N;
-  LGNN_CALL(batch_prologue(h, idx, y_loss ? y_loss : y_seed, M, false, false, y_loss ? loss_out : nullptr, s));
-  if (diag_out && !full_out && !grads_out && h->L <= 2 && !h->extras() && getenv("LGNN_JAC_PLANES") == nullptr) {
-    // diagonal only, <= 2 layers: the closed form of the diagonal GGN with other weights -- no Jacobians at all
-    LGNN_CALL(forward_ensure_aux(h, s));
-    const int L = h->L;
-    const int64_t H = L == 2 ? h->dims[1] : 0;
-    LGNN_CALL(h->ws.misc.reserve(size_t(3) * M * std::max<int64_t>(H, 1) * 4 + size_t(2) * M * C * 4));
-    float* q = h->ws.misc.as<float>();
-    float* r = q + 3 * M * std::max<int64_t>(H, 1);
-    float* wl = r + M * C;
-    hipLaunchKernelGGL(ef_resid_kernel, dim3(unsigned(cdiv(M * C, 256))), dim3(256), 0, s, h->ws.probs.as<float>(),
-                       h->fc.out.as<float>(), idx, y_seed, M, C, N, h->lik == LGNN_LIK_REGRESSION ? 1 : 0, resid_scale, r,
-                       h->ws.flags.as<int>());
-    hipLaunchKernelGGL(ef_last_weights_kernel, dim3(unsigned(cdiv(M * C, 256))), dim3(256), 0, s, r, M * C, scale, wl);
-    LGNN_HIP_CHECK(hipGetLastError());
-    int64_t tiles = 1;
-    if (L == 2) tiles = cdiv(h->in_dim[0] + 1, 64) * cdiv(H, 64);
-    const int64_t slab = std::max<int64_t>(8, std::min<int64_t>(64, cdiv(M * tiles, 2048)));
-    const unsigned nslab = unsigned(cdiv(M, slab));
-    int64_t off = 0;
-    if (L == 2) {
-      const int64_t in0 = h->in_dim[0];
-      const int has_self = h->kind == LGNN_KIND_SAGE ? 1 : 0;
-      hipLaunchKernelGGL(q_ef_kernel, dim3(unsigned(cdiv(M * H, 256))), dim3(256), 0, s, r, M, C, h->W[1], h->in_dim[1], H,
-                         int64_t(0), has_self ? H : int64_t(0), has_self, scale, q);
-      FeatView E;
-      feat_views(h, 0, E);
-      const dim3 grid{unsigned(cdiv(E.width + 1, 64)), unsigned(cdiv(H, 64)), nslab};
-      if (has_self)
-        hipLaunchKernelGGL(diag_first_layer_kernel<1>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab, E,
-                           h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-      else
-        hipLaunchKernelGGL(diag_first_layer_kernel<0>, grid, dim3(256), 0, s, h->P.rowptr, h->P.col, h->P.val, idx, M, slab, E,
-                           h->fc.dact0.as<float>(), H, q, diag_out, diag_out + H * in0);
-      LGNN_HIP_CHECK(hipGetLastError());
-      off = H * in0 + H;
-    }
-    FeatView Phi;
-    feat_views(h, L - 1, Phi);
-    hipLaunchKernelGGL(diag_last_layer_kernel, dim3(unsigned(cdiv(Phi.width + 1, 256)), unsigned(C), nslab), dim3(256), 0, s,
-                       h->ws.probs.as<float>(), idx, M, C, slab, Phi, diag_out + off, diag_out + off + C * Phi.width, wl,
-                       TileReduce{nullptr, 0, 0, 0, 0, nullptr, nullptr, -1});
-    LGNN_HIP_CHECK(hipGetLastError());
-    LGNN_CALL(batch_epilogue(h, idx, M, s));
-    return 0;
-  }
-  // <= 2 layers: the gradients come straight from the closed form (M * P floats); deeper models contract Jacobians
-  const bool closed = h->L <= 2 && !h->extras() && getenv("LGNN_JAC_PLANES") == nullptr;
-  const int64_t jrows = closed ? 0 : C;
-  const int64_t mc_max = std::max<int64_t>(1, std::min<int64_t>(M, (h->ws_limit / 4) / std::max<int64_t>((jrows + 1) * P * 4, 1)));
-  LGNN_CALL(h->ws.jac.reserve(size_t(mc_max) * (jrows + 1) * P * 4 + size_t(mc_max) * C * 4));
-  float* J = h->ws.jac.as<float>();
-  float* G = J + mc_max * jrows * P;
-  float* r = G + mc_max * P;
-  for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
-    const int64_t mc = std::min(mc_max, M - m0);
-    if (!closed) LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
-    const void* ys = h->lik == LGNN_LIK_REGRESSION ? static_cast<const void*>(static_cast<const float*>(y_seed) + m0 * C)
-                                                   : static_cast<const void*>(static_cast<const int64_t*>(y_seed) + m0);
-    hipLaunchKernelGGL(ef_resid_kernel, dim3(unsigned(cdiv(mc * C, 256))), dim3(256), 0, s, h->ws.probs.as<float>() + m0 * C,
-                       h->fc.out.as<float>(), idx + m0, ys, mc, C, N, h->lik == LGNN_LIK_REGRESSION ? 1 : 0, resid_scale, r,
-                       h->ws.flags.as<int>());
-    if (closed) LGNN_CALL(ef_grads_closed_form(h, idx + m0, mc, r, G, s));
-    else hipLaunchKernelGGL(grads_from_jac_kernel, dim3(unsigned(cdiv(P, 256)), unsigned(mc)), dim3(256), 0, s, J, r, mc, C, P, G);
-    LGNN_HIP_CHECK(hipGetLastError());
-    if (grads_out) LGNN_HIP_CHECK(hipMemcpyAsync(grads_out + m0 * P, G, size_t(mc) * P * 4, hipMemcpyDeviceToDevice, s));
-    if (diag_out)
-      hipLaunchKernelGGL(sumsq_rows_kernel, dim3(unsigned(cdiv(P, 256)), unsigned(cdiv(mc, 32))), dim3(256), 0, s, G, mc, P,
-                         scale, diag_out);
-    if (full_out) LGNN_CALL(gram_rows_sgemm(G, mc, P, scale, full_out, s));
-    LGNN_HIP_CHECK(hipGetLastError());
-  }
-  LGNN_CALL(batch_epilogue(h, idx, M, s));
-  return 0;
-}
-
-// phi~ of the batch rows: out [M, D + 1] = [last layer's input features at the node | bias scale]
-// (last_layer_jacobians, laplace/curvature/curvature.py:132-167: J_n = [I_C (x) phi_n^T | s_n I_C])
-int lastlayer_features(lgnn_ctx* h, const int64_t* idx, int64_t M, float* out, float* f_out, hipStream_t s) {
-  LGNN_REQUIRE(M > 0 && idx && out, "empty batch or null pointers");
-  LGNN_CALL(forward_ensure_aux(h, s));
-  FeatView Phi;
-  feat_views(h, h->L - 1, Phi);
-  const int64_t D1 = Phi.width + 1;
-  LGNN_CALL(launch_ll_build_phi(idx, M, Phi, D1, out, s));
-  if (f_out)
-    LGNN_CALL(launch_gather_rows(h->fc.out.as<float>(), h->dims[h->L], h->N, idx, M, h->dims[h->L], f_out,
-                                 h->ws.flags.as<int>() + 2, s));
-  return 0;
-}
-
-// Pair-major accumulation: S [Q][D][D] (upper sub-tiles of each block) and Sb [Q][D + 1] are the CALLER's buffers and are
-// added to -- a fit accumulates all its batches there and places them into H once (lastlayer_pairs_place), instead of one
-// placement (1.2 GB of read-modify-write) + mirror pass per batch; a data-parallel caller all-reduces the pair buffers,
-// half the bytes of H.
-int lastlayer_pairs_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* S, float* Sb,
-                               float* loss_out, hipStream_t s) {
-  LGNN_REQUIRE(M > 0 && idx && y && S && Sb && loss_out, "empty batch or null pointers");
-  LGNN_REQUIRE(h->lik == LGNN_LIK_CLASSIFICATION, "last-layer full GGN kernels: classification likelihood");
-  LGNN_CALL(forward_ensure_aux(h, s));
-  const int L = h->L;
-  const int64_t C = h->dims[L];
-  LGNN_CALL(batch_prologue(h, idx, y, M, false, false, loss_out, s));
-  const float* probs = h->ws.probs.as<float>();
-  FeatView Phi;
-  feat_views(h, L - 1, Phi);
-  const int64_t D = Phi.width, D1 = D + 1;
-  const int64_t Q = C * (C + 1) / 2, ldp = cdiv(D1, 4) * 4;
-  // chunks of pairs: the row-scale / weight vectors [qc][M] live in the workspace
-  const int64_t per_pair = (2 * M + 1) * 4;
-  const int64_t qc_max = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(Q, 32768), h->ws_limit / per_pair));
-  LGNN_CALL(h->ws.planes_a.reserve(size_t(M) * ldp * 4 + size_t(qc_max) * (2 * M + 1) * 4));
-  h->ws.planes_a_zero_ptr = nullptr;
-  float* PhiM = h->ws.planes_a.as<float>();
-  float* rs = PhiM + M * ldp;
-  float* wsg = rs + qc_max * M;
-  float* zsign = wsg + qc_max * M;
-  LGNN_CALL(launch_ll_build_phi(idx, M, Phi, ldp, PhiM, s));
-  for (int64_t q0 = 0; q0 < Q; q0 += qc_max) {
-    const int64_t qc = std::min(qc_max, Q - q0);
-    hipLaunchKernelGGL(ll_pair_weights_kernel, dim3(unsigned(std::min<int64_t>(cdiv(M, 256), 64)), unsigned(qc)),
-                       dim3(256), 0, s, probs, idx, Phi, M, C, q0, rs, wsg, zsign);
-    LGNN_HIP_CHECK(hipGetLastError());
-    // S[q] += sign_q * (diag(rs_q) Phi)^T (diag(rs_q) Phi) over the D feature columns
-    if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the last-layer path (bench.py roofline)
-    LGNN_CALL(launch_gram_batched(PhiM, ldp, M, D, S + q0 * D * D, D * D, qc, rs, zsign, 1.0f, s));
-    if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += qc; }
-    // bias column: Sb[q][j] += sum_m w_qm s_m phi~[m][j], one library GEMM [qc x M] * [M x D1]
-    LGNN_CALL(ll_bias_gemm(wsg, PhiM, Sb + q0 * D1, qc, M, D1, ldp, s, 1.0f));
-  }
-  LGNN_CALL(batch_epilogue(h, idx, M, s));
-  return 0;
-}
-
-// H_out [P, P] += the blocks of the pair-major accumulators (upper triangle), then the mirror pass
-int lastlayer_pairs_place(lgnn_ctx* h, const float* S, const float* Sb, float* H_out, hipStream_t s) {
-  LGNN_REQUIRE(S && Sb && H_out && h->L > 0, "null pointers / no model bound");
-  const int64_t C = h->dims[h->L], D = h->in_dim[h->L - 1], P = C * D + C;
-  const int64_t Q = C * (C + 1) / 2;
-  const unsigned nt = unsigned(cdiv(D, 32));
-  for (int64_t q0 = 0; q0 < Q; q0 += 32768) {
-    const int64_t qc = std::min<int64_t>(32768, Q - q0);
-    hipLaunchKernelGGL(ll_place_tiles_kernel, dim3(nt, nt, unsigned(qc)), dim3(256), 0, s, S + q0 * D * D, D, C, q0, H_out);
-  }
-  hipLaunchKernelGGL(ll_place_bias_kernel, dim3(unsigned(std::min<int64_t>(cdiv(Q * (D + 1), 256), 4096))), dim3(256), 0, s,
-                     Sb, D, C, int64_t(0), Q, H_out);
-  LGNN_HIP_CHECK(hipGetLastError());
-  LGNN_CALL(launch_symmetrize_upper(H_out, P, s));
-  return 0;
-}
-
-// One batch straight into H (the entry point of the first round): pair buffers from the workspace, zeroed, accumulated,
-// placed and mirrored in this call.
-int lastlayer_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out,
-                              float* loss_out, hipStream_t s) {
-  LGNN_REQUIRE(M > 0 && idx && y && H_out && loss_out, "empty batch or null pointers");
-  LGNN_REQUIRE(h->L > 0, "no model bound");
-  const int64_t C = h->dims[h->L], D = h->in_dim[h->L - 1], D1 = D + 1, Q = C * (C + 1) / 2;
-  LGNN_CALL(h->ws.planes_b.reserve(size_t(Q) * (D * D + D1) * 4));
-  float* S = h->ws.planes_b.as<float>();
-  float* Sb = S + Q * D * D;
-  LGNN_HIP_CHECK(hipMemsetAsync(S, 0, size_t(Q) * (D * D + D1) * 4, s));
-  LGNN_CALL(lastlayer_pairs_accumulate(h, idx, y, M, S, Sb, loss_out, s));
-  return lastlayer_pairs_place(h, S, Sb, H_out, s);
 }
 
 }  // namespace lgnn

@@ -38,6 +38,7 @@
 //
 // lgnn_block_gram: A B^T of two blocks of directions through the same NT GEMM -- the Gram and Rayleigh-Ritz matrices of the
 // eigensolver (lowrank.py), bit-reproducible and exactly symmetric for A == B.
+#include "closedform.h"
 #include "lgnn_internal.h"
 
 #include <climits>
@@ -581,8 +582,6 @@ __global__ __launch_bounds__(256) void ggn_place_kernel(const float* __restrict_
   out[mc * k + i0 + i] = U[t];
 }
 
-bool structured_model(const lgnn_ctx* h) { return h->L <= 2 && !h->extras() && h->X != nullptr; }
-
 // the shapes and operands both structured drivers read (sampled.hip's parameter layout)
 struct StructModel {
   bool two, sage;
@@ -760,7 +759,7 @@ int ggn_matmat_structured(lgnn_ctx* h, const int64_t* idx, int64_t M, const floa
 int jvp_block(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* V, int64_t k, float* out, hipStream_t s) {
   LGNN_REQUIRE(h->L > 0, "no model bound");
   LGNN_REQUIRE(k > 0 && k < 65536 && M < (int64_t(1) << 31), "block size or batch size out of range");
-  if (structured_model(h)) return jvp_block_structured(h, idx, M, V, k, out, s);
+  if (closed_form_model(h) && h->X != nullptr) return jvp_block_structured(h, idx, M, V, k, out, s);
   return jvp_block_general(h, idx, M, V, k, out, s);
 }
 
@@ -771,7 +770,8 @@ int ggn_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const 
   LGNN_REQUIRE(k > 0 && k < 65536 && M < (int64_t(1) << 31), "block size or batch size out of range");
   LGNN_CALL(forward_ensure(h, s));
   LGNN_CALL(batch_prologue(h, idx, y, M, false, false, loss_out, s));
-  if (structured_model(h) && !(flags & LGNN_GGN_FROM_JACOBIANS)) LGNN_CALL(ggn_matmat_structured(h, idx, M, V, k, G, s));
+  const bool structured = closed_form_model(h) && h->X != nullptr && !(flags & LGNN_GGN_FROM_JACOBIANS);
+  if (structured) LGNN_CALL(ggn_matmat_structured(h, idx, M, V, k, G, s));
   else LGNN_CALL(ggn_matmat_general(h, idx, M, V, k, G, s));
   LGNN_CALL(batch_epilogue(h, idx, M, s));
   return 0;

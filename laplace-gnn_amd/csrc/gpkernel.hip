@@ -10,7 +10,7 @@
 //   GraphSAGE  Ts_n[h, :] = d_a[h] [cat_0[a] | 1],   Tn_n[h, :] = sum_u P[a, u] d_u[h] [cat_0[u] | 1],   W_1 = [Ws | Wn]
 //   K[(n, c), (m, e)] = sum_h sum_{al, be} W^al[c, h] W^be[e, h] <T^al_n[h, :], T^be_m[h, :]> + [c == e] (<phi_n, phi_m> + s_n s_m)
 // (a) gp_table_kernel writes the tables T [z = (al, h)][n][ld] of a chunk of samples (the first-layer loop of
-//     jac_closed_form_kernel without the class scaling) and launch_ll_build_phi (diag.hip) the rows [phi_n | s_n];
+//     jac_closed_form_kernel without the class scaling) and launch_ll_build_phi (lastlayer_full.hip) the rows [phi_n | s_n];
 // (b) gp_nt_gemm_kernel, a batched NT GEMM on the fp32 matrix cores, forms G [z' = (al, be, h)][n][m] and Phi Phi^T;
 // (c) launch_gemm (kernels.hip) contracts the classes: Kt [(c, e)][(n, m)] = W_pair [(c, e), z'] G [z', (n, m)];
 // (d) the placement kernels write the caller's layout and add the last layer's term.
@@ -24,6 +24,7 @@
 // in slab order, launch_gemm runs with no_atomics.  Two calls on the same input return the same bits.  The fp32 MFMA is
 // bit for bit a k-ordered fmaf chain, so <x, y> and <y, x> agree; with the same index pointer on both sides only the upper
 // chunk pairs are computed and the lower triangle is a copy of the upper, so K(a, a) is exactly symmetric on every route.
+#include "closedform.h"
 #include "lgnn_internal.h"
 
 #include <cmath>
@@ -40,32 +41,26 @@ bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) ==
 
 // ---- (a) tables --------------------------------------------------------------------------------------------------------
 // T[(z * Mc + m) * ld + i], i <= in0 (i == in0: the bias entry), columns (in0, ld) zeroed; GCN: z = h; GraphSAGE: z = h
-// (self table), H + h (neighbour table).  Samples with an id outside [0, N): zero rows and the sticky flag.
-__global__ __launch_bounds__(256) void gp_table_kernel(const int64_t* __restrict__ idx, int64_t Mc, int64_t N,
-                                                       const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                       const float* __restrict__ val, int sage, int64_t in0, int64_t H,
-                                                       const float* __restrict__ E0, int64_t e0_ld,
-                                                       const float* __restrict__ e0_bias /* null: 1 */,
-                                                       const float* __restrict__ dact, int64_t ld, float* __restrict__ T,
-                                                       int* __restrict__ bad) {
+// (self table), H + h (neighbour table): the entries Ts / Tn of closedform.h.  Samples with an id outside [0, N): zero rows
+// and the sticky flag.
+__global__ __launch_bounds__(256) void gp_table_kernel(const int64_t* __restrict__ idx, int64_t Mc, LGNN_CF_PARAMS, int64_t ld,
+                                                       float* __restrict__ T, int* __restrict__ bad) {
+  const ClosedForm cf = LGNN_CF_VIEW;
   const int64_t m = blockIdx.x;
   const int64_t a = idx[m];
+  const int64_t H = cf.H;
   const int64_t t0 = int64_t(blockIdx.y) * blockDim.x + threadIdx.x, tstep = int64_t(gridDim.y) * blockDim.x;
-  const bool valid = a >= 0 && a < N;
+  const bool valid = a >= 0 && a < cf.N;
   if (!valid && t0 == 0) bad[1] = 1;
-  const int32_t ps = valid ? rowptr[a] : 0, pe = valid ? rowptr[a + 1] : 0;
+  const int32_t ps = valid ? cf.rowptr[a] : 0, pe = valid ? cf.rowptr[a + 1] : 0;
   for (int64_t t = t0; t < H * ld; t += tstep) {
     const int64_t hh = t / ld, i = t - hh * ld;
     float tn = 0.f, ts = 0.f;
-    if (valid && i <= in0) {
-      for (int32_t p = ps; p < pe; ++p) {
-        const int64_t u = col[p];
-        const float e = i < in0 ? E0[u * e0_ld + i] : (e0_bias ? e0_bias[u] : 1.f);
-        tn = fmaf(val[p] * dact[u * H + hh], e, tn);
-      }
-      if (sage) ts = dact[a * H + hh] * (i < in0 ? E0[a * e0_ld + i] : 1.f);
+    if (valid && i <= cf.in0) {
+      tn = cf_neigh(cf, ps, pe, hh, i);
+      if (cf.sage) ts = cf_self(cf, a, hh, i);
     }
-    if (sage) {
+    if (cf.sage) {
       T[(hh * Mc + m) * ld + i] = ts;
       T[((H + hh) * Mc + m) * ld + i] = tn;
     } else {
@@ -381,51 +376,31 @@ int launch_mirror(float* K, int64_t D, int64_t ld, int64_t planes, int64_t plane
   return 0;
 }
 
-bool structured_model(const lgnn_ctx* h) { return h->L <= 2 && !h->extras(); }
-
-// what the structured route reads from the bound model (the operands of jacobians_closed_form, jacobian.hip)
+// the structured route's view of the bound model: the closed form's operands and the table geometry
 struct GpModel {
-  int L; bool sage;
-  int64_t N, C, H, in0, in_last, P, off_last;
+  ClosedForm cf;
   int64_t Z, Zp;      // tables per sample, table pairs (0 for one-layer models)
   int64_t ld, ldp;    // row strides of the tables and of the [phi | s] rows
-  const float* E0; int64_t e0_ld; const float* e0_bias;
-  const float* dact; const float* W1; int64_t w1_ld;
-  FeatView Phi;
 };
 
 int gp_model(lgnn_ctx* h, GpModel& g) {
-  const int L = h->L;
-  g.L = L; g.sage = h->kind == LGNN_KIND_SAGE;
-  g.N = h->N; g.C = h->dims[L]; g.H = L == 2 ? h->dims[1] : 0; g.in0 = h->in_dim[0]; g.in_last = h->in_dim[L - 1];
-  g.P = h->n_params; g.off_last = L == 2 ? g.H * g.in0 + g.H : 0;
-  g.Z = L == 2 ? (g.sage ? 2 : 1) * g.H : 0;
-  g.Zp = L == 2 ? (g.sage ? 4 : 1) * g.H : 0;
-  g.ld = cdiv(g.in0 + 1, 4) * 4;
-  g.ldp = cdiv(g.in_last + 1, 4) * 4;
-  g.E0 = g.sage ? h->fc.lin_in_p[0] : h->fc.prop_in[0].as<float>();
-  g.e0_ld = g.sage ? h->fc.lin_in_ld[0] : h->fc.prop_ld[0];
-  g.e0_bias = g.sage ? nullptr : h->fc.rowsum.as<float>();
-  g.dact = L == 2 ? h->fc.dact0.as<float>() : nullptr;
-  g.W1 = L == 2 ? h->W[1] : nullptr;
-  g.w1_ld = L == 2 ? h->in_dim[1] : 0;
-  LGNN_CALL(feat_views(h, L - 1, g.Phi));
+  LGNN_CALL(closed_form_view(h, g.cf));
+  const ClosedForm& cf = g.cf;
+  g.Z = cf.L == 2 ? (cf.sage ? 2 : 1) * cf.H : 0;
+  g.Zp = cf.L == 2 ? (cf.sage ? 4 : 1) * cf.H : 0;
+  g.ld = cdiv(cf.in0 + 1, 4) * 4;
+  g.ldp = cdiv(cf.in_last + 1, 4) * 4;
   return 0;
 }
 
 // tables and [phi | s] rows of the samples idx[0..mc)
 int build_tables(lgnn_ctx* h, const GpModel& g, const int64_t* idx, int64_t mc, float* T, float* Phi, hipStream_t s) {
   LGNN_REQUIRE(mc < (int64_t(1) << 31), "too many samples");
-  LGNN_CALL(launch_ll_build_phi(idx, mc, g.Phi, g.ldp, Phi, s));
-  if (g.Z == 0) {  // one-layer model: the ids are checked here, nothing else looks at them
-    hipLaunchKernelGGL(gp_table_kernel, dim3(unsigned(mc), 1), dim3(64), 0, s, idx, mc, g.N, h->P.rowptr, h->P.col, h->P.val, 0,
-                       g.in0, int64_t(0), g.E0, g.e0_ld, g.e0_bias, g.dact, g.ld, T, h->ws.flags.as<int>());
-    LGNN_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  const unsigned per = unsigned(std::max<int64_t>(1, std::min<int64_t>(cdiv(g.H * g.ld, 256), cdiv(2048, mc))));
-  hipLaunchKernelGGL(gp_table_kernel, dim3(unsigned(mc), per), dim3(256), 0, s, idx, mc, g.N, h->P.rowptr, h->P.col, h->P.val,
-                     g.sage ? 1 : 0, g.in0, g.H, g.E0, g.e0_ld, g.e0_bias, g.dact, g.ld, T, h->ws.flags.as<int>());
+  LGNN_CALL(launch_ll_build_phi(idx, mc, g.cf.PhiL, g.ldp, Phi, s));
+  // (one-layer model: no table, one wave per sample checks the ids -- nothing else looks at them)
+  const unsigned per = g.Z == 0 ? 1u : unsigned(std::max<int64_t>(1, std::min<int64_t>(cdiv(g.cf.H * g.ld, 256), cdiv(2048, mc))));
+  hipLaunchKernelGGL(gp_table_kernel, dim3(unsigned(mc), per), dim3(g.Z == 0 ? 64 : 256), 0, s, idx, mc, LGNN_CF_ARGS(g.cf), g.ld, T,
+                     h->ws.flags.as<int>());
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -440,15 +415,16 @@ int gp_kernel_structured(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const in
   LGNN_CALL(forward_ensure_aux(h, s));
   GpModel g;
   LGNN_CALL(gp_model(h, g));
+  const ClosedForm& cf = g.cf;
   const bool indep = (flags & LGNN_GP_INDEPENDENT) != 0, matched = (flags & LGNN_GP_MATCHED) != 0;
   const bool same = idx_a == idx_b && Ma == Mb;
-  const int64_t C = g.C, Q = indep ? C : C * C;
+  const int64_t C = cf.C, Q = indep ? C : C * C;
   Workspace& w = h->ws;
   StageTimer tm{h, s};
   if (g.Zp > 0) {
     LGNN_CALL(w.gp_wpair.reserve(size_t(Q) * g.Zp * 4));
-    hipLaunchKernelGGL(gp_wpair_kernel, dim3(unsigned(cdiv(Q * g.Zp, 256))), dim3(256), 0, s, g.W1, g.w1_ld, g.H, C,
-                       g.sage ? 1 : 0, indep ? 1 : 0, w.gp_wpair.as<float>());
+    hipLaunchKernelGGL(gp_wpair_kernel, dim3(unsigned(cdiv(Q * g.Zp, 256))), dim3(256), 0, s, cf.W1, cf.w1_ld, cf.H, C,
+                       cf.sage ? 1 : 0, indep ? 1 : 0, w.gp_wpair.as<float>());
     LGNN_HIP_CHECK(hipGetLastError());
   }
   GemmEpilogue ep;
@@ -479,11 +455,11 @@ int gp_kernel_structured(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const in
       if (!same) LGNN_CALL(build_tables(h, g, idx_b + m0, mc, Tb, Pb, s));
       LGNN_CALL(tm.mark());
       LGNN_CALL(tm.mark());
-      const int64_t slab = g.H * mc * g.ld;  // one (al) group of tables
-      for (int64_t ab = 0; g.Zp > 0 && ab < (g.sage ? 4 : 1); ++ab)
-        LGNN_CALL(launch_rowdot(Ta + (ab >> 1) * slab, g.ld, mc * g.ld, Tb + (ab & 1) * slab, g.ld, mc * g.ld, g.in0 + 1, mc, g.H,
-                                w.gp_g.as<float>() + ab * g.H * mc, mc, s));
-      LGNN_CALL(launch_rowdot(Pa, g.ldp, 0, Pb, g.ldp, 0, g.in_last + 1, mc, 1, w.gp_s.as<float>(), 0, s));
+      const int64_t slab = cf.H * mc * g.ld;  // one (al) group of tables
+      for (int64_t ab = 0; g.Zp > 0 && ab < (cf.sage ? 4 : 1); ++ab)
+        LGNN_CALL(launch_rowdot(Ta + (ab >> 1) * slab, g.ld, mc * g.ld, Tb + (ab & 1) * slab, g.ld, mc * g.ld, cf.in0 + 1, mc, cf.H,
+                                w.gp_g.as<float>() + ab * cf.H * mc, mc, s));
+      LGNN_CALL(launch_rowdot(Pa, g.ldp, 0, Pb, g.ldp, 0, cf.in_last + 1, mc, 1, w.gp_s.as<float>(), 0, s));
       LGNN_CALL(tm.mark());
       LGNN_CALL(tm.mark());
       if (g.Zp > 0)
@@ -528,19 +504,19 @@ int gp_kernel_structured(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const in
       LGNN_CALL(tm.mark());
       const int64_t pairs = ma * mb;
       LGNN_CALL(tm.mark());
-      for (int64_t ab = 0; g.Zp > 0 && ab < (g.sage ? 4 : 1); ++ab) {
+      for (int64_t ab = 0; g.Zp > 0 && ab < (cf.sage ? 4 : 1); ++ab) {
         NtProblem p{};
-        p.A = Ta + (ab >> 1) * g.H * ma * g.ld; p.lda = g.ld; p.a_bs = ma * g.ld;
-        p.B = Tb + (ab & 1) * g.H * mb * g.ld; p.ldb = g.ld; p.b_bs = mb * g.ld;
-        p.Out = w.gp_g.as<float>() + ab * g.H * pairs; p.ldo = mb; p.o_es = 1; p.o_bs = pairs;
-        p.Ra = ma; p.Rb = mb; p.K = g.in0 + 1; p.batch = g.H;
+        p.A = Ta + (ab >> 1) * cf.H * ma * g.ld; p.lda = g.ld; p.a_bs = ma * g.ld;
+        p.B = Tb + (ab & 1) * cf.H * mb * g.ld; p.ldb = g.ld; p.b_bs = mb * g.ld;
+        p.Out = w.gp_g.as<float>() + ab * cf.H * pairs; p.ldo = mb; p.o_es = 1; p.o_bs = pairs;
+        p.Ra = ma; p.Rb = mb; p.K = cf.in0 + 1; p.batch = cf.H;
         LGNN_CALL(launch_nt_gemm(h, p, s));
       }
       {
         NtProblem p{};
         p.A = Pa; p.lda = g.ldp; p.B = Pb; p.ldb = g.ldp;
         p.Out = w.gp_s.as<float>(); p.ldo = mb; p.o_es = 1;
-        p.Ra = ma; p.Rb = mb; p.K = g.in_last + 1; p.batch = 1;
+        p.Ra = ma; p.Rb = mb; p.K = cf.in_last + 1; p.batch = 1;
         LGNN_CALL(launch_nt_gemm(h, p, s));
       }
       LGNN_CALL(tm.mark());
@@ -635,7 +611,7 @@ int gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_
   const int64_t C = h->dims[h->L];
   if (flags & LGNN_GP_MATCHED) LGNN_REQUIRE(Ma == Mb, "LGNN_GP_MATCHED needs as many samples on both sides");
   else LGNN_REQUIRE(ldk >= ((flags & LGNN_GP_INDEPENDENT) ? Mb : Mb * C), "row stride of K too small");
-  if (structured_model(h) && !(flags & LGNN_GP_FROM_JACOBIANS)) return gp_kernel_structured(h, idx_a, Ma, idx_b, Mb, flags, K, ldk, s);
+  if (closed_form_model(h) && !(flags & LGNN_GP_FROM_JACOBIANS)) return gp_kernel_structured(h, idx_a, Ma, idx_b, Mb, flags, K, ldk, s);
   return gp_kernel_general(h, idx_a, Ma, idx_b, Mb, flags, K, ldk, s);
 }
 
@@ -643,7 +619,7 @@ int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* ou
   LGNN_REQUIRE(h->L > 0, "no model bound");
   Workspace& w = h->ws;
   const int64_t C = h->dims[h->L], P = h->n_params;
-  if (!structured_model(h)) {  // a chunked matvec over lgnn_jacobians' rows
+  if (!closed_form_model(h)) {  // a chunked matvec over lgnn_jacobians' rows
     const int64_t mc_max = std::max<int64_t>(1, std::min<int64_t>(M, h->ws_limit / 2 / (C * P * 4)));
     LGNN_CALL(w.gp_jac_a.reserve(size_t(mc_max) * C * P * 4));
     for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
@@ -656,6 +632,7 @@ int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* ou
   LGNN_CALL(forward_ensure_aux(h, s));
   GpModel g;
   LGNN_CALL(gp_model(h, g));
+  const ClosedForm& cf = g.cf;
   LGNN_REQUIRE(g.Z * 4 <= 48 * 1024, "hidden width exceeds the staging area");
   const int64_t tab_row = std::max<int64_t>(g.Z, 1) * g.ld + g.ldp;
   const int64_t mc_max = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, 1 << 20), h->ws_limit / (tab_row * 4)));
@@ -665,8 +642,8 @@ int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* ou
     const int64_t mc = std::min(mc_max, M - m0);
     LGNN_CALL(build_tables(h, g, idx + m0, mc, w.gp_tab_a.as<float>(), w.gp_phi_a.as<float>(), s));
     hipLaunchKernelGGL(gp_jvp_kernel, dim3(unsigned(mc)), dim3(256), size_t(std::max<int64_t>(g.Z, 1)) * 4, s,
-                       w.gp_tab_a.as<float>(), mc, g.ld, g.in0, std::max<int64_t>(g.H, 1), g.Z, g.W1, g.w1_ld,
-                       w.gp_phi_a.as<float>(), g.ldp, g.in_last, C, g.off_last, v, out + m0 * C);
+                       w.gp_tab_a.as<float>(), mc, g.ld, cf.in0, std::max<int64_t>(cf.H, 1), g.Z, cf.W1, cf.w1_ld,
+                       w.gp_phi_a.as<float>(), g.ldp, cf.in_last, C, cf.off_last, v, out + m0 * C);
     LGNN_HIP_CHECK(hipGetLastError());
   }
   return 0;

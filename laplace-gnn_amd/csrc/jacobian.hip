@@ -11,8 +11,11 @@
 //     layer  dW_l[(m,c)] = g_l^T in_l   [out_l x in_l]      db_l[(m,c)] = column sums of g_l
 //     down   g_{l-1} = P^T (act'(h_l) * (g_l W_l))          (GraphSAGE: act'(h_l) * (dcat[:, :d] + P^T dcat[:, d:]))
 // The result is as large as the reference's (M*C*P floats); samples are processed in chunks that fit the workspace cap.
+// 1- and 2-layer models without res / norm skip the planes: closed form (closedform.h).  full_accumulate, the all-weights
+// full GGN, consumes whole chunks of these rows and sits at the end of the file.
 #include <rocblas/rocblas.h>
 
+#include "closedform.h"
 #include "lgnn_internal.h"
 
 namespace lgnn {
@@ -61,180 +64,54 @@ __global__ __launch_bounds__(256) void plane_colsum_kernel(const float* __restri
 
 }  // namespace
 
-// row major C[Q, D1] = A[Q, M] * B[M, D1] (ld ldp): the bias column of the last-layer pair Grams (diag.hip)
-int ll_bias_gemm(const float* Wq, const float* Phi, float* Sb, int64_t Q, int64_t M, int64_t D1, int64_t ldp,
-                 hipStream_t s, float beta) {
-  rocblas_handle blas = static_cast<rocblas_handle>(blas_handle(s));
-  LGNN_REQUIRE(blas != nullptr, "rocBLAS handle");
-  const float one = 1.f, zero = beta;
-  // column-major view: C^T[D1, Q] = B^T[D1, M] * A^T[M, Q]
-  const rocblas_status st = rocblas_sgemm(blas, rocblas_operation_none, rocblas_operation_none, rocblas_int(D1),
-                                          rocblas_int(Q), rocblas_int(M), &one, Phi, rocblas_int(ldp), Wq, rocblas_int(M),
-                                          &zero, Sb, rocblas_int(D1));
-  if (st != rocblas_status_success) { set_error("rocblas_sgemm failed"); return 3; }
-  return 0;
-}
-
-// out[P, P] += scale * G^T G for row-major G [rows, P] (the full empirical / MC Fisher of a chunk of per-sample gradients)
-int gram_rows_sgemm(const float* G, int64_t rows, int64_t P, float scale, float* out, hipStream_t s) {
-  rocblas_handle blas = static_cast<rocblas_handle>(blas_handle(s));
-  LGNN_REQUIRE(blas != nullptr, "rocBLAS handle");
-  const float one = 1.f;
-  // column-major view of G: [P, rows] with ld = P;  out = G_cm G_cm^T (symmetric: row / column major coincide)
-  const rocblas_status st = rocblas_sgemm(blas, rocblas_operation_none, rocblas_operation_transpose, rocblas_int(P),
-                                          rocblas_int(P), rocblas_int(rows), &scale, G, rocblas_int(P), G, rocblas_int(P), &one,
-                                          out, rocblas_int(P));
-  if (st != rocblas_status_success) { set_error("rocblas_sgemm failed"); return 3; }
-  return 0;
-}
-
-// Closed-form Jacobians of 1- and 2-layer models: no planes over all N nodes, no GEMM with K = N.  With a = idx[m],
-// E[v] = [what the first Linear multiplies at node v | 1-column] and d_v = act'(h_1[v]):
-//   last layer   d f_c / d W_last = e_c (x) phi_a,   d f_c / d b_last = s_a e_c            (phi, s: feat_views of diag.hip)
-//   first layer  GCN      : d f_c / d W_0[h, :] = w_c[h] sum_u P[a,u] d_u[h] (P X)[u, :],  bias: ... rowsum(P)[u]
-//                GraphSAGE: d f_c / d W_0[h, :] = ws_c[h] d_a[h] cat_0[a, :] + wn_c[h] sum_u P[a,u] d_u[h] cat_0[u, :],  bias: ... 1
-// One workgroup per sample: T_self / T_neigh [H x (in_0 + 1)] tiles are built once from the ~15 neighbours and every
-// class row of J is a row scaling of them -- the kernel is bound by writing J (M * C * P floats, like the reference's).
-__global__ __launch_bounds__(256) void jac_closed_form_kernel(
-    const int64_t* __restrict__ idx, int64_t M, int64_t N, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-    const float* __restrict__ val, int L, int sage, int64_t in0, int64_t H, int64_t C,
-    const float* __restrict__ E0, int64_t e0_ld, const float* __restrict__ e0_bias /* null: 1 */,
-    const float* __restrict__ dact, const float* __restrict__ W1, int64_t w1_ld,
-    const float* __restrict__ PhiL, int64_t phil_ld, int64_t phil_w, const float* __restrict__ phil_bias /* null: 1 */,
-    int64_t P, float* __restrict__ J, int* __restrict__ bad) {
+// Closed-form Jacobians of 1- and 2-layer models (closedform.h): no planes over all N nodes, no GEMM with K = N.
+// One workgroup row per sample: the entries Ts / Tn [H x (in_0 + 1)] are built once from the ~15 neighbours and every class row
+// of J is a row scaling of them -- the kernel is bound by writing J (M * C * P floats, like the reference's).
+__global__ __launch_bounds__(256) void jac_closed_form_kernel(const int64_t* __restrict__ idx, LGNN_CF_PARAMS,
+                                                              float* __restrict__ J, int* __restrict__ bad) {
+  const ClosedForm cf = LGNN_CF_VIEW;
   const int64_t m = blockIdx.x;
   const int64_t a = idx[m];
+  const int64_t C = cf.C, P = cf.P, H = cf.H, in0 = cf.in0, in_last = cf.in_last;
   float* __restrict__ Jm = J + m * C * P;
   const int64_t t0 = int64_t(blockIdx.y) * blockDim.x + threadIdx.x, tstep = int64_t(gridDim.y) * blockDim.x;
-  if (a < 0 || a >= N) {
+  if (a < 0 || a >= cf.N) {
     if (t0 == 0) bad[1] = 1;
     for (int64_t t = t0; t < C * P; t += tstep) Jm[t] = 0.f;
     return;
   }
-  const int64_t in_last = phil_w;  // columns of the last weight
-  const int64_t off_last = L == 2 ? H * in0 + H : 0;
   // last layer: row c of J holds phi_a in its own block, zeros in the other classes' blocks, s_a at its bias entry
   for (int64_t t = t0; t < C * (C * in_last + C); t += tstep) {
     const int64_t c = t / (C * in_last + C), q = t - c * (C * in_last + C);
     float v = 0.f;
-    if (q < C * in_last) { if (q / in_last == c) v = PhiL[a * phil_ld + (q - c * in_last)]; }
-    else if (q - C * in_last == c) v = phil_bias ? phil_bias[a] : 1.f;
-    Jm[c * P + off_last + q] = v;
+    if (q < C * in_last) { if (q / in_last == c) v = feat_at(cf.PhiL, a, q - c * in_last); }
+    else if (q - C * in_last == c) v = feat_at(cf.PhiL, a, in_last);
+    Jm[c * P + cf.off_last + q] = v;
   }
-  if (L == 1) return;
+  if (cf.L == 1) return;
   // first layer: element (h, i) with i <= in0 (i == in0: the bias entry of unit h)
-  const int32_t ps = rowptr[a], pe = rowptr[a + 1];
+  const int32_t ps = cf.rowptr[a], pe = cf.rowptr[a + 1];
   const int64_t in1 = in0 + 1;
   for (int64_t t = t0; t < H * in1; t += tstep) {
     const int64_t hh = t / in1, i = t - hh * in1;
-    float tn = 0.f;
-    for (int32_t p = ps; p < pe; ++p) {
-      const int64_t u = col[p];
-      const float e = i < in0 ? E0[u * e0_ld + i] : (e0_bias ? e0_bias[u] : 1.f);
-      tn = fmaf(val[p] * dact[u * H + hh], e, tn);
-    }
+    const float tn = cf_neigh(cf, ps, pe, hh, i);
     float ts = 0.f;
-    if (sage) ts = dact[a * H + hh] * (i < in0 ? E0[a * e0_ld + i] : 1.f);
+    if (cf.sage) ts = cf_self(cf, a, hh, i);
     const int64_t dst = i < in0 ? hh * in0 + i : H * in0 + hh;
-    for (int64_t c = 0; c < C; ++c) {
-      const float v = sage ? W1[c * w1_ld + hh] * ts + W1[c * w1_ld + H + hh] * tn : W1[c * w1_ld + hh] * tn;
-      Jm[c * P + dst] = v;
-    }
+    for (int64_t c = 0; c < C; ++c) Jm[c * P + dst] = cf_class_row(cf, c, hh, ts, tn);
   }
 }
 
 static int jacobians_closed_form(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out, hipStream_t s) {
   LGNN_CALL(forward_ensure_aux(h, s));
-  const int L = h->L;
-  const int64_t N = h->N, C = h->dims[L], H = L == 2 ? h->dims[1] : 0, in0 = h->in_dim[0], P = h->n_params;
-  const bool sage = h->kind == LGNN_KIND_SAGE;
+  ClosedForm cf;
+  LGNN_CALL(closed_form_view(h, cf));
   int* bad = h->ws.flags.as<int>();
-  if (f_out) LGNN_CALL(launch_gather_rows(h->fc.out.as<float>(), C, N, idx, M, C, f_out, bad + 2, s));
-  // first-layer feature rows: GCN (P X)[u] with the bias entry rowsum(P)[u]; GraphSAGE cat_0[u] with 1
-  const float* E0 = sage ? h->fc.lin_in_p[0] : h->fc.prop_in[0].as<float>();
-  const int64_t e0_ld = sage ? h->fc.lin_in_ld[0] : h->fc.prop_ld[0];
-  const float* e0_bias = sage ? nullptr : h->fc.rowsum.as<float>();
-  // last-layer feature row seen from the batch node
-  const float* PhiL = sage ? h->fc.lin_in_p[L - 1] : h->fc.prop_in[L - 1].as<float>();
-  const int64_t phil_ld = sage ? h->fc.lin_in_ld[L - 1] : h->fc.prop_ld[L - 1];
-  const float* phil_bias = sage ? nullptr : h->fc.rowsum.as<float>();
+  if (f_out) LGNN_CALL(launch_gather_rows(h->fc.out.as<float>(), cf.C, cf.N, idx, M, cf.C, f_out, bad + 2, s));
   LGNN_REQUIRE(M < (int64_t(1) << 31), "too many samples");
   // enough workgroups per sample to fill the chip at small M
-  const unsigned per = unsigned(std::max<int64_t>(1, std::min<int64_t>(cdiv(std::max<int64_t>(H * (in0 + 1), C * (C * h->in_dim[L - 1] + C)), 256), cdiv(2048, M))));
-  hipLaunchKernelGGL(jac_closed_form_kernel, dim3(unsigned(M), per), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col, h->P.val, L,
-                     sage ? 1 : 0, in0, H, C, E0, e0_ld, e0_bias, L == 2 ? h->fc.dact0.as<float>() : nullptr,
-                     L == 2 ? h->W[1] : nullptr, L == 2 ? h->in_dim[1] : 0, PhiL, phil_ld, h->in_dim[L - 1], phil_bias, P, J, bad);
-  LGNN_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-// Per-sample loss gradients G[m, :] = sum_c r[m, c] J[m, c, :] of 1- and 2-layer models straight from the closed form (the
-// empirical / MC Fisher's rows, laplace/curvature/curvature.py:169-210): with rho_s[h] = sum_c r_c ws_c[h], rho_n[h] =
-// sum_c r_c wn_c[h] the first layer's gradient is rho_s[h] T_self[h, :] + rho_n[h] T_neigh[h, :], the last layer's is
-// r (x) phi_a -- M * P floats instead of the M * C * P of the Jacobians.
-__global__ __launch_bounds__(256) void ef_grads_closed_form_kernel(
-    const int64_t* __restrict__ idx, int64_t M, int64_t N, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-    const float* __restrict__ val, int L, int sage, int64_t in0, int64_t H, int64_t C,
-    const float* __restrict__ E0, int64_t e0_ld, const float* __restrict__ e0_bias /* null: 1 */,
-    const float* __restrict__ dact, const float* __restrict__ W1, int64_t w1_ld,
-    const float* __restrict__ PhiL, int64_t phil_ld, int64_t phil_w, const float* __restrict__ phil_bias /* null: 1 */,
-    const float* __restrict__ r, int64_t P, float* __restrict__ G) {
-  const int64_t m = blockIdx.x;
-  const int64_t a = idx[m];
-  float* __restrict__ Gm = G + m * P;
-  const float* __restrict__ rm = r + m * C;
-  const int64_t t0 = int64_t(blockIdx.y) * blockDim.x + threadIdx.x, tstep = int64_t(gridDim.y) * blockDim.x;
-  if (a < 0 || a >= N) {  // flagged by the batch prologue
-    for (int64_t t = t0; t < P; t += tstep) Gm[t] = 0.f;
-    return;
-  }
-  const int64_t in_last = phil_w;
-  const int64_t off_last = L == 2 ? H * in0 + H : 0;
-  for (int64_t t = t0; t < C * in_last + C; t += tstep) {
-    float v;
-    if (t < C * in_last) { const int64_t k = t / in_last; v = rm[k] * PhiL[a * phil_ld + (t - k * in_last)]; }
-    else v = rm[t - C * in_last] * (phil_bias ? phil_bias[a] : 1.f);
-    Gm[off_last + t] = v;
-  }
-  if (L == 1) return;
-  const int32_t ps = rowptr[a], pe = rowptr[a + 1];
-  const int64_t in1 = in0 + 1;
-  for (int64_t t = t0; t < H * in1; t += tstep) {
-    const int64_t hh = t / in1, i = t - hh * in1;
-    float rs = 0.f, rn = 0.f;
-    for (int64_t c = 0; c < C; ++c) {
-      const float rc = rm[c];
-      if (sage) { rs = fmaf(rc, W1[c * w1_ld + hh], rs); rn = fmaf(rc, W1[c * w1_ld + H + hh], rn); }
-      else rn = fmaf(rc, W1[c * w1_ld + hh], rn);
-    }
-    float tn = 0.f;
-    for (int32_t p = ps; p < pe; ++p) {
-      const int64_t u = col[p];
-      const float e = i < in0 ? E0[u * e0_ld + i] : (e0_bias ? e0_bias[u] : 1.f);
-      tn = fmaf(val[p] * dact[u * H + hh], e, tn);
-    }
-    float v = rn * tn;
-    if (sage) v = fmaf(rs, dact[a * H + hh] * (i < in0 ? E0[a * e0_ld + i] : 1.f), v);
-    Gm[i < in0 ? hh * in0 + i : H * in0 + hh] = v;
-  }
-}
-
-int ef_grads_closed_form(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* r, float* G, hipStream_t s) {
-  LGNN_REQUIRE(h->L >= 1 && h->L <= 2, "closed-form gradients: 1- and 2-layer models");
-  LGNN_CALL(forward_ensure_aux(h, s));
-  const int L = h->L;
-  const int64_t N = h->N, C = h->dims[L], H = L == 2 ? h->dims[1] : 0, in0 = h->in_dim[0], P = h->n_params;
-  const bool sage = h->kind == LGNN_KIND_SAGE;
-  const float* E0 = sage ? h->fc.lin_in_p[0] : h->fc.prop_in[0].as<float>();
-  const int64_t e0_ld = sage ? h->fc.lin_in_ld[0] : h->fc.prop_ld[0];
-  const float* bias_col = sage ? nullptr : h->fc.rowsum.as<float>();
-  const float* PhiL = sage ? h->fc.lin_in_p[L - 1] : h->fc.prop_in[L - 1].as<float>();
-  const int64_t phil_ld = sage ? h->fc.lin_in_ld[L - 1] : h->fc.prop_ld[L - 1];
-  LGNN_REQUIRE(M < (int64_t(1) << 31), "too many samples");
-  const unsigned per = unsigned(std::max<int64_t>(1, std::min<int64_t>(cdiv(std::max<int64_t>(H * (in0 + 1), C * h->in_dim[L - 1] + C), 256), cdiv(4096, M))));
-  hipLaunchKernelGGL(ef_grads_closed_form_kernel, dim3(unsigned(M), per), dim3(256), 0, s, idx, M, N, h->P.rowptr, h->P.col,
-                     h->P.val, L, sage ? 1 : 0, in0, H, C, E0, e0_ld, bias_col, L == 2 ? h->fc.dact0.as<float>() : nullptr,
-                     L == 2 ? h->W[1] : nullptr, L == 2 ? h->in_dim[1] : 0, PhiL, phil_ld, h->in_dim[L - 1], bias_col, r, P, G);
+  const unsigned per = unsigned(std::max<int64_t>(1, std::min<int64_t>(cdiv(std::max<int64_t>(cf.H * (cf.in0 + 1), cf.C * (cf.C * cf.in_last + cf.C)), 256), cdiv(2048, M))));
+  hipLaunchKernelGGL(jac_closed_form_kernel, dim3(unsigned(M), per), dim3(256), 0, s, idx, LGNN_CF_ARGS(cf), J, bad);
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -244,7 +121,7 @@ int jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out
   // 1- and 2-layer models: closed form (LGNN_JAC_PLANES=1 forces the generic plane route, which deeper models use)
   const bool force_planes = getenv("LGNN_JAC_PLANES") != nullptr;
   // (models with res / norm have no closed form: the norm's row-local backward sits between the layers)
-  if (h->L <= 2 && !force_planes && !h->extras()) return jacobians_closed_form(h, idx, M, J, f_out, s);
+  if (closed_form_model(h) && !force_planes) return jacobians_closed_form(h, idx, M, J, f_out, s);
   LGNN_CALL(forward_ensure(h, s));
   const int64_t N = h->N;
   const int L = h->L;
@@ -355,6 +232,50 @@ int jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out
       }
     }
   }
+  return 0;
+}
+
+// Full GGN over all weights (GGNInterface.full, laplace/curvature/curvature.py:374-410; the reference's default backend
+// applies a matrix-free GGN to the P columns of the identity, curvlinops/ggn.py:44-75 via laplace/curvature/
+// curvlinops.py:110-140): H = sum_n J_n^T Lambda_n J_n with Lambda_n = S_n S_n^T, S[k, c] = sqrt(p_c) (d_kc - p_k), so
+// H = X^T X for the rows X[(n, c), :] = sum_k S_n[k, c] J[n, k, :] = sqrt(p_c) (J[n, c, :] - sum_k p_k J[n, k, :]) -- one
+// in-place row mixing pass over a chunk of device Jacobians, then the fp32 MFMA Gram kernel (upper sub-tiles) straight
+// into the caller's H.  Regression (H_lik = None): X = J.
+__global__ __launch_bounds__(256) void ggn_mix_rows_kernel(float* __restrict__ J, const float* __restrict__ probs,
+                                                           int64_t mc, int64_t C, int64_t P) {
+  const int64_t p = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  const int64_t m = blockIdx.y;
+  if (p >= P) return;
+  float* __restrict__ Jm = J + m * C * P + p;
+  const float* __restrict__ pm = probs + m * C;
+  float t = 0.f;
+  for (int64_t k = 0; k < C; ++k) t += pm[k] * Jm[k * P];
+  for (int64_t c = 0; c < C; ++c) Jm[c * P] = sqrtf(pm[c]) * (Jm[c * P] - t);
+}
+
+int full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out, float* loss_out,
+                    hipStream_t s) {
+  LGNN_REQUIRE(M > 0 && idx && y && H_out && loss_out, "empty batch or null pointers");
+  LGNN_REQUIRE(h->L >= 1, "no model bound");
+  LGNN_CALL(forward_ensure(h, s));
+  const int64_t C = h->dims[h->L], P = h->n_params;
+  LGNN_REQUIRE(P * P < (int64_t(1) << 40), "full GGN: P x P does not fit");
+  LGNN_CALL(batch_prologue(h, idx, y, M, false, false, loss_out, s));
+  const int64_t mc_max = std::max<int64_t>(1, std::min<int64_t>(M, (h->ws_limit / 4) / std::max<int64_t>(C * P * 4, 1)));
+  LGNN_CALL(h->ws.jac.reserve(size_t(mc_max) * C * P * 4));
+  float* J = h->ws.jac.as<float>();
+  for (int64_t m0 = 0; m0 < M; m0 += mc_max) {
+    const int64_t mc = std::min(mc_max, M - m0);
+    LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
+    if (h->lik != LGNN_LIK_REGRESSION) {
+      hipLaunchKernelGGL(ggn_mix_rows_kernel, dim3(unsigned(cdiv(P, 256)), unsigned(mc)), dim3(256), 0, s, J,
+                         h->ws.probs.as<float>() + m0 * C, mc, C, P);
+      LGNN_HIP_CHECK(hipGetLastError());
+    }
+    LGNN_CALL(launch_gram(J, P, mc * C, P, H_out, s));
+  }
+  LGNN_CALL(launch_symmetrize_upper(H_out, P, s));
+  LGNN_CALL(batch_epilogue(h, idx, M, s));
   return 0;
 }
 

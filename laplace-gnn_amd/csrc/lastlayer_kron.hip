@@ -6,7 +6,7 @@
 // and GGNInterface.diag on last_layer_jacobians (laplace/curvature/curvature.py:132-167, 412-432).
 //
 // Per batch sample n the logits are f_n = W phi_n + s_n b (GraphSAGE: phi_n = [h_n | (A_bar h)_n], s_n = 1; GCN:
-// phi_n = (A_hat h)_n, s_n = rowsum(A_hat)_n -- feat_views of diag.hip), so with the KFAC seeds V_n [C, C] of kfac_seed.hip
+// phi_n = (A_hat h)_n, s_n = rowsum(A_hat)_n -- feat_views of closedform.h), so with the KFAC seeds V_n [C, C] of kfac_seed.hip
 //   A   [D, D] += Phi^T Phi / n_train              (fp32 MFMA Gram of the gathered rows, kernels.hip)
 //   B   [C, C] += sum_n V_n V_n^T
 //   B_b [C, C] += sum_n s_n^2 V_n V_n^T            (the exact bias block; equals B for GraphSAGE)
@@ -21,6 +21,7 @@
 // -- C^2 work per sample from seven C-vectors; no seed block is ever written.
 #include <algorithm>
 
+#include "closedform.h"
 #include "device_utils.h"
 #include "lgnn_internal.h"
 

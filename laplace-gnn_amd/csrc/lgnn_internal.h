@@ -504,9 +504,6 @@ int launch_gram_scaled(const float* X, int64_t ld, int64_t R, int64_t D, float* 
 // nz weighted Grams over the same rows: out[z] += scale * zscale[z] * X^T diag(row_scale[z]^2) X (upper sub-tiles)
 int launch_gram_batched(const float* X, int64_t ld, int64_t R, int64_t D, float* out, int64_t out_zstride, int64_t nz,
                         const float* row_scale, const float* zscale, float scale, hipStream_t s);
-// row major Sb[Q, D1] = Wq[Q, M] * Phi[M, D1] (rocBLAS; jacobian.hip)
-int ll_bias_gemm(const float* Wq, const float* Phi, float* Sb, int64_t Q, int64_t M, int64_t D1, int64_t ldp, hipStream_t s,
-                 float beta = 0.f);  // Sb = Wq Phi + beta Sb
 // lower triangle <- upper triangle
 int launch_symmetrize_upper(float* H, int64_t D, hipStream_t s);
 // out[i,j] += scale * scratch[min(i,j), max(i,j)]
@@ -626,32 +623,17 @@ int ensure_wt(lgnn_ctx* h, hipStream_t s);           // transposed weights (forw
 // gcn2_forward.hip: small plain 2-layer GCN, forward + auxiliary products through the cached P X
 bool gcn2_small_forward_supported(const lgnn_ctx* h);
 int gcn2_forward_through_px(lgnn_ctx* h, hipStream_t s);
-// ---- diag.hip ---------------------------------------------------------------------------
-// What a Linear multiplies, seen from an output node, plus its bias column: the rows the diagonal and last-layer kernels gather
-struct FeatView {  // E[v, i]: i < width -> base[v*ld + i]; i == width -> bias column
-  const float* base;
-  int64_t ld;
-  int64_t width;
-  const float* bias_col;  // per-node scale (rowsum) or nullptr for the constant 1
-  int64_t nrows;          // node ids outside [0, nrows) (flagged by the batch prologue) read as zero rows
-};
-__device__ __forceinline__ float feat(const FeatView& f, int64_t v, int64_t i) {
-  if (v < 0 || v >= f.nrows) return 0.f;
-  if (i < f.width) return f.base[v * f.ld + i];
-  return f.bias_col ? f.bias_col[v] : 1.f;
-}
-int feat_views(lgnn_ctx* h, int layer, FeatView& f);  // needs forward_ensure_aux
-// out [M, ldp] = [phi_n | s_n | 0 ...] of the batch rows (ll_build_phi_kernel)
-int launch_ll_build_phi(const int64_t* idx, int64_t M, const FeatView& Phi, int64_t ldp, float* out, hipStream_t s);
+// ---- diag.hip (its kernels' launchers, which fisher.hip calls too: diag.h) --------------------------------------------------
 int diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, uint32_t flags, float* diag_out,
                     float* loss_out, hipStream_t s);
+// ---- lastlayer_full.hip (launch_ll_build_phi takes a FeatView: declared in closedform.h) ----------------------------------
 int lastlayer_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out,
                               float* loss_out, hipStream_t s);
 int lastlayer_pairs_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* S, float* Sb,
                                float* loss_out, hipStream_t s);
 int lastlayer_features(lgnn_ctx* h, const int64_t* idx, int64_t M, float* out, float* f_out, hipStream_t s);
 int lastlayer_pairs_place(lgnn_ctx* h, const float* S, const float* Sb, float* H_out, hipStream_t s);
-int full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out, float* loss_out, hipStream_t s);
+// ---- fisher.hip ---------------------------------------------------------------------------
 int ef_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y_seed, const void* y_loss, int64_t M, float resid_scale,
                   float scale, float* diag_out, float* full_out, float* grads_out, float* loss_out, hipStream_t s);
 // ---- lastlayer_kron.hip -----------------------------------------------------------------
@@ -661,6 +643,8 @@ int lastlayer_diag_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, in
                               hipStream_t s);
 // ---- jacobian.hip -----------------------------------------------------------------------
 int jacobians(lgnn_ctx* h, const int64_t* idx, int64_t M, float* J, float* f_out, hipStream_t s);
+// all-weights full GGN from chunks of those rows: H_out [P, P] += sum_n J_n^T Lambda_n J_n
+int full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, float* H_out, float* loss_out, hipStream_t s);
 // ---- subnet.hip -------------------------------------------------------------------------
 // columns subnet[0..S) (device, caller's order) of the Jacobians: J [M, C, S]
 int jacobians_subset(lgnn_ctx* h, const int64_t* idx, int64_t M, const int64_t* subnet, int64_t S, float* J, float* f_out,

@@ -6,7 +6,7 @@
 //   * 1- and 2-layer GCN / GraphSAGE without res / norm: the closed form of jac_closed_form_kernel (jacobian.hip) evaluated
 //     for the selected columns only.  A first-layer column (h, i) is one pass over the deg(a) neighbours of the sample and its
 //     C class rows are a scaling by W1[:, h]; a last-layer column is one feature of the sample.  M C S floats are written
-//     instead of M C P.  For the GGN the Hessian square root of ggn_mix_rows_kernel (diag.hip) is applied while the column
+//     instead of M C P.  For the GGN the Hessian square root of ggn_mix_rows_kernel (jacobian.hip) is applied while the column
 //     is built: with p = softmax(f_a), the mixed rows of a first-layer column are sqrt(p_c) (W1[c, h] - sum_k p_k W1[k, h]) t
 //     (GraphSAGE: the self and the neighbour half of W1 each), those of a last-layer column (c', d) are
 //     sqrt(p_c) (delta_cc' - p_c') phi[d].  sum_k p_k W1[k, :] and sqrt(p) are staged in LDS once per sample.
@@ -18,6 +18,7 @@
 // floats, so the columns are processed in the order of their vector index -- which is (kind, unit, input column) order: W_0 row
 // major, b_0, W_last row major, b_last -- and every value is written through the sorted column's position in the caller's
 // list.  The outputs are in the caller's order; nothing is permuted afterwards.
+#include "closedform.h"
 #include "lgnn_internal.h"
 
 #include <rocprim/rocprim.hpp>
@@ -64,16 +65,15 @@ __global__ void subnet_plan_kernel(const int64_t* __restrict__ keys, const int32
 }
 
 // X[(m C + c) ld + dst] for the planned columns of sample m; columns [S, ld) are zeroed.  probs == null: the Jacobian's own
-// rows (the arithmetic of jac_closed_form_kernel, product by product); otherwise the rows mixed with the Hessian square root.
-// Dynamic LDS: 2 C + w1_ld floats.
-__global__ __launch_bounds__(256) void subnet_closed_form_kernel(
-    const int64_t* __restrict__ idx, int64_t N, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-    const float* __restrict__ val, int sage, int64_t in0, int64_t H, int64_t C, const float* __restrict__ E0, int64_t e0_ld,
-    const float* __restrict__ e0_bias /* null: 1 */, const float* __restrict__ dact, const float* __restrict__ W1,
-    int64_t w1_ld, const float* __restrict__ PhiL, int64_t phil_ld, const float* __restrict__ phil_bias /* null: 1 */,
-    const SubCol* __restrict__ plan, int64_t S, int64_t ld, const float* __restrict__ probs, float* __restrict__ X,
-    int* __restrict__ bad) {
+// rows -- the entries jac_closed_form_kernel writes, from the same device functions (closedform.h), so the bits agree;
+// otherwise the rows mixed with the Hessian square root.  Dynamic LDS: 2 C + w1_ld floats.
+__global__ __launch_bounds__(256) void subnet_closed_form_kernel(const int64_t* __restrict__ idx, LGNN_CF_PARAMS,
+                                                                 const SubCol* __restrict__ plan, int64_t S, int64_t ld,
+                                                                 const float* __restrict__ probs, float* __restrict__ X,
+                                                                 int* __restrict__ bad) {
   extern __shared__ float lds[];
+  const ClosedForm cf = LGNN_CF_VIEW;
+  const int64_t C = cf.C, H = cf.H;
   float* __restrict__ sp = lds;          // sqrt(p_c)
   float* __restrict__ pr = lds + C;      // p_c
   float* __restrict__ wbar = lds + 2 * C;  // sum_k p_k W1[k, :]  (GraphSAGE: both halves)
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void subnet_closed_form_kernel(
   const int64_t a = idx[m];
   float* __restrict__ Xm = X + m * C * ld;
   const int64_t t0 = int64_t(blockIdx.y) * blockDim.x + threadIdx.x, tstep = int64_t(gridDim.y) * blockDim.x;
-  if (a < 0 || a >= N) {
+  if (a < 0 || a >= cf.N) {
     if (t0 == 0) bad[1] = 1;
     for (int64_t t = t0; t < C * ld; t += tstep) Xm[t] = 0.f;
     return;
@@ -90,15 +90,15 @@ __global__ __launch_bounds__(256) void subnet_closed_form_kernel(
   if (mix) {
     const float* __restrict__ pm = probs + m * C;
     for (int64_t c = threadIdx.x; c < C; c += blockDim.x) { const float p = pm[c]; pr[c] = p; sp[c] = sqrtf(p); }
-    if (W1)
-      for (int64_t q = threadIdx.x; q < w1_ld; q += blockDim.x) {
+    if (cf.W1)
+      for (int64_t q = threadIdx.x; q < cf.w1_ld; q += blockDim.x) {
         float t = 0.f;
-        for (int64_t k = 0; k < C; ++k) t = fmaf(pm[k], W1[k * w1_ld + q], t);
+        for (int64_t k = 0; k < C; ++k) t = fmaf(pm[k], cf.W1[k * cf.w1_ld + q], t);
         wbar[q] = t;
       }
     __syncthreads();
   }
-  const int32_t ps = rowptr[a], pe = rowptr[a + 1];
+  const int32_t ps = cf.rowptr[a], pe = cf.rowptr[a + 1];
   for (int64_t j = t0; j < ld; j += tstep) {
     SubCol sc;
     sc.kind = 4; sc.unit = 0; sc.col = 0; sc.dst = int32_t(j);  // padding: a zero column in place
@@ -106,31 +106,22 @@ __global__ __launch_bounds__(256) void subnet_closed_form_kernel(
     float* __restrict__ out = Xm + sc.dst;
     if (sc.kind <= 1) {
       const int64_t hh = sc.unit;
-      const bool w = sc.kind == 0;
-      const int64_t i = sc.col;
-      float tn = 0.f;
-      for (int32_t p = ps; p < pe; ++p) {
-        const int64_t u = col[p];
-        const float e = w ? E0[u * e0_ld + i] : (e0_bias ? e0_bias[u] : 1.f);
-        tn = fmaf(val[p] * dact[u * H + hh], e, tn);
-      }
+      const int64_t i = sc.kind == 0 ? int64_t(sc.col) : cf.in0;  // in0: the bias entry of unit hh
+      const float tn = cf_neigh(cf, ps, pe, hh, i);
       float ts = 0.f;
-      if (sage) ts = dact[a * H + hh] * (w ? E0[a * e0_ld + i] : 1.f);
+      if (cf.sage) ts = cf_self(cf, a, hh, i);
       if (!mix) {
-        for (int64_t c = 0; c < C; ++c) {
-          const float v = sage ? W1[c * w1_ld + hh] * ts + W1[c * w1_ld + H + hh] * tn : W1[c * w1_ld + hh] * tn;
-          out[c * ld] = v;
-        }
+        for (int64_t c = 0; c < C; ++c) out[c * ld] = cf_class_row(cf, c, hh, ts, tn);
       } else {
-        const float bs = wbar[hh], bn = sage ? wbar[H + hh] : 0.f;
+        const float bs = wbar[hh], bn = cf.sage ? wbar[H + hh] : 0.f;
         for (int64_t c = 0; c < C; ++c) {
-          const float v = sage ? (W1[c * w1_ld + hh] - bs) * ts + (W1[c * w1_ld + H + hh] - bn) * tn
-                               : (W1[c * w1_ld + hh] - bs) * tn;
+          const float v = cf.sage ? (cf.W1[c * cf.w1_ld + hh] - bs) * ts + (cf.W1[c * cf.w1_ld + H + hh] - bn) * tn
+                                  : (cf.W1[c * cf.w1_ld + hh] - bs) * tn;
           out[c * ld] = sp[c] * v;
         }
       }
     } else if (sc.kind <= 3) {
-      const float phi = sc.kind == 2 ? PhiL[a * phil_ld + sc.col] : (phil_bias ? phil_bias[a] : 1.f);
+      const float phi = sc.kind == 2 ? cf.PhiL.base[a * cf.PhiL.ld + sc.col] : (cf.PhiL.bias_col ? cf.PhiL.bias_col[a] : 1.f);
       const int64_t cq = sc.unit;
       if (!mix) {
         for (int64_t c = 0; c < C; ++c) out[c * ld] = c == cq ? phi : 0.f;
@@ -171,8 +162,6 @@ __global__ __launch_bounds__(256) void subnet_gather_kernel(const float* __restr
   for (int64_t c = 0; c < C; ++c) Xm[c * ld + dst] = sqrtf(pm[c]) * (Jm[c * P] - t);
 }
 
-bool closed_form_model(const lgnn_ctx* h) { return h->L <= 2 && !h->extras(); }
-
 // ws.subnet_keys / ws.subnet_ord: the caller's indices in increasing order and their positions in the caller's list;
 // closed-form models: ws.subnet_plan, the decoded columns
 int subnet_prepare(lgnn_ctx* h, const int64_t* subnet, int64_t S, hipStream_t s) {
@@ -203,24 +192,14 @@ int subnet_prepare(lgnn_ctx* h, const int64_t* subnet, int64_t S, hipStream_t s)
 // the planned columns of samples idx[0..mc) into X [mc C, ld]; needs forward_ensure_aux and subnet_prepare
 int launch_subnet_closed_form(lgnn_ctx* h, const int64_t* idx, int64_t mc, int64_t S, int64_t ld, const float* probs,
                               float* X, hipStream_t s) {
-  const int L = h->L;
-  const int64_t N = h->N, C = h->dims[L], H = L == 2 ? h->dims[1] : 0, in0 = h->in_dim[0];
-  const bool sage = h->kind == LGNN_KIND_SAGE;
-  // the operands of jacobians_closed_form (jacobian.hip)
-  const float* E0 = sage ? h->fc.lin_in_p[0] : h->fc.prop_in[0].as<float>();
-  const int64_t e0_ld = sage ? h->fc.lin_in_ld[0] : h->fc.prop_ld[0];
-  const float* bias_col = sage ? nullptr : h->fc.rowsum.as<float>();
-  const float* PhiL = sage ? h->fc.lin_in_p[L - 1] : h->fc.prop_in[L - 1].as<float>();
-  const int64_t phil_ld = sage ? h->fc.lin_in_ld[L - 1] : h->fc.prop_ld[L - 1];
-  const int64_t w1_ld = L == 2 ? h->in_dim[1] : 0;
+  ClosedForm cf;
+  LGNN_CALL(closed_form_view(h, cf));
   LGNN_REQUIRE(mc < (int64_t(1) << 31), "too many samples");
-  const size_t lds = size_t(2 * C + w1_ld) * 4;
+  const size_t lds = size_t(2 * cf.C + cf.w1_ld) * 4;
   LGNN_REQUIRE(lds <= 48 * 1024, "subnetwork: classes + hidden width exceed the staging area");
   const unsigned per = unsigned(std::max<int64_t>(1, std::min<int64_t>(cdiv(ld, 256), cdiv(2048, mc))));
-  hipLaunchKernelGGL(subnet_closed_form_kernel, dim3(unsigned(mc), per), dim3(256), lds, s, idx, N, h->P.rowptr, h->P.col,
-                     h->P.val, sage ? 1 : 0, in0, H, C, E0, e0_ld, bias_col, L == 2 ? h->fc.dact0.as<float>() : nullptr,
-                     L == 2 ? h->W[1] : nullptr, w1_ld, PhiL, phil_ld, bias_col, h->ws.subnet_plan.as<SubCol>(), S, ld, probs,
-                     X, h->ws.flags.as<int>());
+  hipLaunchKernelGGL(subnet_closed_form_kernel, dim3(unsigned(mc), per), dim3(256), lds, s, idx, LGNN_CF_ARGS(cf),
+                     h->ws.subnet_plan.as<SubCol>(), S, ld, probs, X, h->ws.flags.as<int>());
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }
