@@ -16,9 +16,6 @@ int launch_sddmm(const Csr& m, int64_t nrows, const int32_t* rows, const int32_t
 int launch_sddmm_coo(const int32_t* ca, const int32_t* cb, int64_t K, const float* L, int64_t l_ld, int64_t l_stride,
                      const float* R, int64_t r_ld, int64_t r_stride, int64_t width, int64_t nplanes, const uint8_t* a_active,
                      float* out, hipStream_t s);
-// C_rm[R, Nout] = alpha * A_rm[R, K] * B_rm[K, Nout] + beta * C_rm (rocBLAS)
-int sgemm_rm(hipStream_t s, int64_t R, int64_t Nout, int64_t K, float alpha, const float* A, int64_t lda, const float* B,
-             int64_t ldb, float beta, float* Cm, int64_t ldc);
 // The Kronecker chains' top layer (C = dims[L] classes): g [C][N][C] = P^T scatter(seeds) and the flags ws.active of its rows
 int launch_seed_planes(lgnn_ctx* h, float* g, hipStream_t s);
 // gradP (stored entries; skipped when null) and grad_cand (K pairs) += <seeds of a batch row a, g1bar[b]>, classes [c0, c0 + cc)

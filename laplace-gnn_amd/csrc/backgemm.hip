@@ -353,12 +353,7 @@ template <int KH>
 int backgemm_pc_launch(const BackGemmArgs& g, hipStream_t s) {
   constexpr int H = 4 * KH, KP = 2 * H + 4;
   const size_t smem = size_t(2) * (PC_ROWS * KP + PC_ROWS * META_LD) * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&backgemm_pc_kernel<KH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024));
-    attr_set = true;
-  }
+  LGNN_CALL(lds_opt_in<&backgemm_pc_kernel<KH>>(100 * 1024));
   const int64_t worst = cdiv(g.N, PC_ROWS) * g.planes;
   const unsigned grid = unsigned(std::max<int64_t>(1, std::min<int64_t>(worst, 256)));
   hipLaunchKernelGGL(backgemm_pc_kernel<KH>, dim3(grid), dim3(PC_THREADS), smem, s, g);

@@ -993,15 +993,11 @@ extern "C" int lgnn_symeig_batched(float* A, int64_t n, int64_t batch, float* W,
     LGNN_CALL(scratch().info.reserve(size_t(batch) * 4));
     const size_t smem = size_t(2 * SNB * n + SRG * n + 3 * n + 2 * SNB) * 4;
     LGNN_REQUIRE(smem <= 160 * 1024, "symeig: panel does not fit the LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-      LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tridiag_stream_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set = true;
-    }
+    LGNN_CALL(lds_opt_in<&tridiag_stream_kernel>(160 * 1024));
     LGNN_HIP_CHECK(hipMemsetAsync(scratch().v.p, 0, size_t(batch) * n * n * 4, s));  // (the trailing block's reflectors start at column n - 256)
     hipLaunchKernelGGL(tridiag_stream_kernel, dim3(unsigned(batch)), dim3(1024), smem, s, A, int(n), int(n - TN),
                        scratch().d.as<float>(), scratch().e.as<float>(), scratch().v.as<float>(), scratch().tau.as<float>());
+    LGNN_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(tridiag256_kernel, dim3(unsigned(batch)), dim3(1024), 0, s, A, TN, scratch().d.as<float>(), scratch().e.as<float>(),
                        scratch().v.as<float>(), scratch().tau.as<float>(), int(n), int(n - TN), int(n));
     LGNN_HIP_CHECK(hipGetLastError());

@@ -376,12 +376,7 @@ int seed_spmm_gram_launch(lgnn_ctx* h, bool fork_exact, float* g, int64_t cb, in
   // + 64 floats: an MFMA operand read of the last row may run past it (those lanes are masked)
   const size_t smem = std::max(per_wave * waves + 256, size_t(NT) * 256 * 4);
   LGNN_REQUIRE(smem <= 158 * 1024, "too many classes for the seed SpMM kernel (use class ranges)");
-  static bool attr_set = false;  // more than 64 KiB of dynamic LDS needs an explicit opt-in
-  if (!attr_set) {
-    LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&seed_spmm_gram_kernel<NBLK>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-    attr_set = true;
-  }
+  LGNN_CALL(lds_opt_in<&seed_spmm_gram_kernel<NBLK>>(158 * 1024));
   const int per_cu = int(std::max<size_t>(1, std::min<size_t>(2048 / (64 * waves), (158 * 1024) / smem)));
   const int fe = h->lik == LGNN_LIK_REGRESSION ? 2 : (fork_exact ? 1 : 0);
   LGNN_CALL(long_rows_ensure(h, s));

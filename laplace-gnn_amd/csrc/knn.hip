@@ -391,9 +391,7 @@ extern "C" int lgnn_knn(const float* X, int64_t N, int64_t F, int64_t ld, int k,
   hipLaunchKernelGGL(knn_norms_kernel, dim3(unsigned(cdiv(N, 4))), dim3(256), 0, s, X, N, F, ld, nrm, nmax);
   LGNN_HIP_CHECK(hipGetLastError());
   FilterArgs fa{X, N, F, ld, nrm, cand, rej, int(splits), keep, vec ? 1 : 0};
-  // (per call: the attribute belongs to the current device, and this entry has no context that remembers one)
-  LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_filter_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(kFilterLds)));
+  LGNN_CALL(lds_opt_in<&knn_filter_kernel>(int(kFilterLds)));
   hipLaunchKernelGGL(knn_filter_kernel, dim3(unsigned(tiles), unsigned(splits)), dim3(256), kFilterLds, s, fa);
   LGNN_HIP_CHECK(hipGetLastError());
   RerankArgs ra{X, N, F, ld, nrm, nmax, cand, rej, int(splits), keep, k, nbr, dist, flag};

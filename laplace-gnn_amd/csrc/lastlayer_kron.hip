@@ -273,12 +273,7 @@ int lastlayer_kron_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, in
   while (SC > 4 && smem_of(SC) > 158 * 1024) SC /= 2;
   const size_t smem = smem_of(SC);
   LGNN_REQUIRE(smem <= 158 * 1024, "too many classes for the last-layer Kronecker kernel");
-  static bool attr_set = false;  // more than 64 KiB of dynamic LDS needs an explicit opt-in
-  if (!attr_set) {
-    LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ll_kron_rows_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
-    attr_set = true;
-  }
+  LGNN_CALL(lds_opt_in<&ll_kron_rows_kernel>(158 * 1024));
   // ~512 workgroups (two per CU) of whole chunks: every workgroup ends with C^2 float atomics per factor
   const int64_t slab = cdiv(std::max<int64_t>(SC, cdiv(M, 512)), SC) * SC;
   hipLaunchKernelGGL(ll_kron_rows_kernel, dim3(unsigned(cdiv(M, slab))), dim3(256), smem, s, h->fc.out.as<float>(), int(C),

@@ -1,6 +1,7 @@
 // Internal declarations shared by the HIP translation units of liblaplace_gnn_hip.so.
 // gfx950 (MI355X / CDNA4) only: wave64, fp32-input MFMA, 160 KiB LDS per CU.
 #pragma once
+#include <atomic>
 #include <cstring>  // rocprim's texture iterator needs host memset declared first
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,6 +39,21 @@ void set_error(const std::string& msg);
   } while (0)
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// More than 64 KiB of dynamic LDS needs an explicit opt-in, and the attribute belongs to the current device's copy of the
+// kernel: set it the first time `Kernel` is launched on a device (`bytes`: the kernel's fixed upper bound), remembered in one
+// bit per device.  Two threads that race set it twice, which is harmless; a device id beyond the mask sets it on every call.
+template <auto Kernel>
+int lds_opt_in(int bytes) {
+  static std::atomic<uint64_t> done{0};
+  int dev = 0;
+  LGNN_HIP_CHECK(hipGetDevice(&dev));
+  const uint64_t bit = dev < 64 ? uint64_t(1) << dev : 0;
+  if (done.load(std::memory_order_acquire) & bit) return 0;
+  LGNN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done.fetch_or(bit, std::memory_order_release);
+  return 0;
+}
 
 // Grow-only device buffer (no allocation in steady state).  It owns its memory: the destructor frees it, so a member of a
 // context struct needs no entry in a release list, and a function's temporary may be left through LGNN_CALL / LGNN_HIP_CHECK /
@@ -696,5 +712,9 @@ int launch_full_directions(const float* J, const float* Gamma, const int64_t* id
                            int64_t mc, int64_t C, int64_t P, float* R, float* Kn, hipStream_t s);
 // ---- eigh.hip ---------------------------------------------------------------------------
 void* blas_handle(hipStream_t s);  // the process-wide rocblas_handle, bound to `s`
+// ---- adjgrad.hip ------------------------------------------------------------------------
+// C_rm[R, Nout] = alpha * A_rm[R, K] * B_rm[K, Nout] + beta * C_rm (rocBLAS on blas_handle(s))
+int sgemm_rm(hipStream_t s, int64_t R, int64_t Nout, int64_t K, float alpha, const float* A, int64_t lda, const float* B,
+             int64_t ldb, float beta, float* Cm, int64_t ldc);
 
 }  // namespace lgnn

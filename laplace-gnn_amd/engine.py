@@ -1020,50 +1020,37 @@ class GraphEngine:
         Jacobian (see include/laplace_gnn_hip.h lgnn_glm_variance for the operand conventions).  ``out_map`` = E [Cm, C]:
         the variances of the linear map E f instead, [M, Cm]; S1 / QB1sq / kappa are then the caller's mapped operands
         (lgnn_glm_variance_mapped)."""
-        self._sync_versions()
-        idx = idx.contiguous()
-        M, C = idx.shape[0], self.dims[-1]
-        Cm = C if out_map is None else int(out_map.shape[0])
-        f_mu = torch.empty(M, C, dtype=torch.float32, device=self.device)
-        f_var = torch.empty(M, Cm, dtype=torch.float32, device=self.device)
-        keep = [t.contiguous().to(torch.float32) if t is not None else None for t in (QA0, QB0, S0, QA1, S1, QB1sq, kappa)]
-        ptr = [None if t is None else _dev_ptr(t, torch.float32, "posterior operand") for t in keep]
-        if out_map is None:
-            rc = self.lib.lgnn_glm_variance(self._h, _dev_ptr(idx, torch.int64, "idx"), M, *ptr, f_mu.data_ptr(),
-                                            f_var.data_ptr(), _stream(self.device))
-            _lib.check(rc, "lgnn_glm_variance")
-            return f_mu, f_var
-        if out_map.ndim != 2 or out_map.shape[1] != C:
-            raise ValueError(f"out_map must be [rows, {C}]")
-        W1m = (out_map.to(device=self.device, dtype=torch.float32) @ self._bound[1][-1].detach().to(torch.float32)).contiguous()
-        rc = self.lib.lgnn_glm_variance_mapped(self._h, _dev_ptr(idx, torch.int64, "idx"), M, W1m.data_ptr(), Cm, *ptr,
-                                               f_mu.data_ptr(), f_var.data_ptr(), _stream(self.device))
-        _lib.check(rc, "lgnn_glm_variance_mapped")
-        return f_mu, f_var
+        return self._glm_variance(idx, (QA0, QB0, S0, QA1, S1, QB1sq, kappa), out_map, ext=False)
 
     def glm_variance_ext(self, idx: torch.Tensor, S0, S1, kappa, QA0=None, QB0=None, QA1=None, QB1sq=None, Sr=None, QAr=None,
                          QBr=None, out_map=None):
         """``glm_variance`` for 2-layer models built with res / norm (and, through the same route, plain ones): one entry
         with or without ``out_map`` (lgnn_glm_variance_ext).  ``Sr`` [H, F + 1] (and ``QAr`` / ``QBr`` under a Kronecker
         posterior) are the operands of the res.0 block; None for a model without res."""
+        return self._glm_variance(idx, (QA0, QB0, S0, QA1, S1, QB1sq, kappa, QAr, QBr, Sr), out_map, ext=True)
+
+    def _glm_variance(self, idx, operands, out_map, ext):
+        """The one call behind ``glm_variance`` (lgnn_glm_variance, with ``out_map`` lgnn_glm_variance_mapped) and
+        ``glm_variance_ext`` (lgnn_glm_variance_ext, which takes a null head for the model's own classes)."""
         self._sync_versions()
         idx = idx.contiguous()
         M, C = idx.shape[0], self.dims[-1]
-        Cm, W1m = 0, None
+        head = []
         if out_map is not None:
             if out_map.ndim != 2 or out_map.shape[1] != C:
                 raise ValueError(f"out_map must be [rows, {C}]")
-            Cm = int(out_map.shape[0])
             W1m = (out_map.to(device=self.device, dtype=torch.float32) @ self._bound[1][-1].detach().to(torch.float32)).contiguous()
+            head = [W1m.data_ptr(), int(out_map.shape[0])]
+        elif ext:
+            head = [None, 0]
         f_mu = torch.empty(M, C, dtype=torch.float32, device=self.device)
-        f_var = torch.empty(M, Cm or C, dtype=torch.float32, device=self.device)
-        keep = [t.contiguous().to(torch.float32) if t is not None else None
-                for t in (QA0, QB0, S0, QA1, S1, QB1sq, kappa, QAr, QBr, Sr)]
+        f_var = torch.empty(M, C if out_map is None else out_map.shape[0], dtype=torch.float32, device=self.device)
+        keep = [t.contiguous().to(torch.float32) if t is not None else None for t in operands]
         ptr = [None if t is None else _dev_ptr(t, torch.float32, "posterior operand") for t in keep]
-        rc = self.lib.lgnn_glm_variance_ext(self._h, _dev_ptr(idx, torch.int64, "idx"), M,
-                                            None if W1m is None else W1m.data_ptr(), Cm, *ptr, f_mu.data_ptr(),
-                                            f_var.data_ptr(), _stream(self.device))
-        _lib.check(rc, "lgnn_glm_variance_ext")
+        name = "lgnn_glm_variance_ext" if ext else ("lgnn_glm_variance" if out_map is None else "lgnn_glm_variance_mapped")
+        rc = getattr(self.lib, name)(self._h, _dev_ptr(idx, torch.int64, "idx"), M, *head, *ptr, f_mu.data_ptr(),
+                                     f_var.data_ptr(), _stream(self.device))
+        _lib.check(rc, name)
         return f_mu, f_var
 
     def check_async_errors(self):

@@ -144,13 +144,15 @@ def test_the_edge_graph_has_the_rows_the_kernel_cases_need():
 
 
 @pytest.mark.parametrize("shape", [(150, 136, 5), (20, 20, 3)], ids=["F150_H136_C5", "F20_H20_C3"])
-@pytest.mark.parametrize("norm,res", [("layer", True), ("layer", False), ("batch", True), (None, True)],
-                         ids=["ln_res", "ln", "bn_res", "res"])
+@pytest.mark.parametrize("norm,res", [("layer", True), ("layer", False), ("batch", True), (None, True), (None, False)],
+                         ids=["ln_res", "ln", "bn_res", "res", "plain"])
 @pytest.mark.parametrize("kind", ["gcn", "sage"])
 def test_kernel_edges_against_the_jacobian_route(kind, norm, res, shape):
     """Hp = 256 with two (GCN) / three (GraphSAGE) ragged column chunks and a padded X (F % 4 = 2) resp. Hp = 64 with 44 idle
     rows and LayerNorm reductions over 20 channels; rows with two staging passes, exactly 48 and 49 staged entries, a node
-    without edges and a repeated id.  Both posteriors, prior precision 2.0."""
+    without edges and a repeated id.  Both posteriors, prior precision 2.0.  ``plain``: the same graph through the plain entries
+    (lgnn_glm_variance): table rows under the Kronecker posterior, in-loop rows and E read in place (row stride of the
+    forward, not a multiple of 4 at F = 150) under the diagonal one."""
     import laplace_gnn_amd as lg
 
     F, H, C = shape
@@ -213,7 +215,8 @@ def test_every_link_of_a_res_layernorm_model_runs_without_jacobians():
 
 
 # ---- 6. flagged id -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["gcn_resln_small_3batch_s1", "sage_resln_small_3batch_s1"])
+@pytest.mark.parametrize("name", ["gcn_resln_small_3batch_s1", "sage_resln_small_3batch_s1", "gcn_mid_1batch_s0",
+                                  "sage_mid_2batch_s2"])
 def test_an_id_out_of_range_is_flagged_and_leaves_the_other_rows_alone(name):
     import laplace_gnn_amd as lg
     from laplace_gnn_amd._lib import HipLibraryError

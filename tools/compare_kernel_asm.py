@@ -7,7 +7,8 @@ Compiles the named files of both source directories to gfx950 assembly (``hipcc 
 flags; files with per-file flags take them through ``--flags``), cuts every kernel from its ``.globl`` line to
 ``.end_amdhsa_kernel``, drops comments, replaces the function index in local labels and the kernel's own mangled name, and
 compares the bodies line for line, kernel descriptor included.  ``--moved OLD=NEW1,NEW2``: every kernel of OLD must appear in
-exactly one of the NEW files; ``--same F``: the same file on both sides.  Prints one JSON document -- per old file and kernel
+exactly one of the NEW files; ``--same F``: the same file on both sides; ``--renamed OLD=NEW``: the kernel printed as OLD (as in
+the report: demangled, no namespaces, no argument list) is looked up under the name NEW (respelled template parameters).  Prints one JSON document -- per old file and kernel
 ``[result, compared lines, file that holds it now]`` -- and exits 1 unless everything is identical."""
 import argparse
 import json
@@ -66,28 +67,32 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--moved", action="append", default=[], metavar="OLD=NEW1,NEW2")
     ap.add_argument("--same", action="append", default=[], metavar="FILE")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW", help="kernel names as the report prints them")
     ap.add_argument("--flags", action="append", default=[], metavar="FILE=FLAG,FLAG", help="per-file flags of the Makefile")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     a = ap.parse_args()
     extra = {f.split("=", 1)[0]: f.split("=", 1)[1].split(",") for f in a.flags}
     filt = next((p for p in ("/opt/rocm/llvm/bin/llvm-cxxfilt", "/usr/bin/c++filt") if os.path.exists(p)), None)
     plan = [(m.split("=", 1)[0], m.split("=", 1)[1].split(",")) for m in a.moved] + [(f, [f]) for f in a.same]
+    renamed = dict(r.split("=", 1) for r in a.renamed)
     report, ok, total = {}, True, 0
     for old_name, new_names in plan:
         old = kernels(a.old, old_name, extra.get(old_name, []), a.hipcc)
         new = {n: kernels(a.new, n, extra.get(n, []), a.hipcc) for n in new_names}
         entry = report[old_name] = {}
+        by_short = {short(s, filt): s for n in new_names for s in new[n]}
+        now = lambda sym: by_short.get(renamed.get(short(sym, filt)), sym)
         for sym, body in sorted(old.items()):
-            holders = [n for n in new_names if sym in new[n]]
+            holders = [n for n in new_names if now(sym) in new[n]]
             if len(holders) != 1:
                 result, where = ("missing" if not holders else "duplicated"), holders
             else:
                 where = holders[0]
-                result = "identical" if new[where][sym] == body else "DIFFERENT"
+                result = "identical" if new[where][now(sym)] == body else "DIFFERENT"
             ok &= result == "identical"
             total += 1
             entry[short(sym, filt)] = [result, len(body), where]
-        added = sorted(short(s, filt) for n in new_names for s in new[n] if s not in old)
+        added = sorted(short(s, filt) for n in new_names for s in new[n] if s not in {now(o) for o in old})
         if added:
             ok = False
             entry["(kernels the old file does not have)"] = added

@@ -4,6 +4,9 @@
   --baseline M                   also time the Jacobian-chunk route on an M-node subset (probit), alternating with the
                                  matrix-free route on the same subset, and report their agreement at that size
   --json PATH                    append one JSON line per measurement
+  --train N                      fit on the first N training nodes only (the diagonal posterior of a res / norm model is fitted
+                                 from plane-route Jacobians, 91 ms per sample: 90 941 of them take hours; what la(x) costs
+                                 does not depend on N)
   --kinds / --posteriors / --links   restrict what is run (a profiler run wants one call)"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,6 +19,7 @@ ap.add_argument("--res", action="store_true")
 ap.add_argument("--norm", choices=["layer", "batch"], default=None)
 ap.add_argument("--baseline", type=int, default=0)
 ap.add_argument("--json", default=None)
+ap.add_argument("--train", type=int, default=0)
 ap.add_argument("--kinds", default="gcn,sage")
 ap.add_argument("--posteriors", default="kron,diag")
 ap.add_argument("--links", default="probit,bridge,bridge_norm,mc")
@@ -24,7 +28,7 @@ LINKS = {"probit": {}, "bridge": {}, "bridge_norm": {}, "mc": {"diagonal_output"
 
 
 def emit(**rec):
-    rec.update(res=args.res, norm=args.norm)
+    rec.update(res=args.res, norm=args.norm, train=args.train or len(tri))
     print(json.dumps(rec), flush=True)
     if args.json:
         with open(args.json, "a") as f:
@@ -43,6 +47,8 @@ def rel(a, b):
 
 
 w, ei, X, tri, try_ = bench.make_workload("arxiv", "cuda")
+if args.train:
+    tri, try_ = tri[:args.train], try_[:args.train]
 for kind in args.kinds.split(","):
     torch.manual_seed(0)
     model = (lg.GCN if kind == "gcn" else lg.GraphSAGE)(w["F"], w["H"], w["C"], 2, X, ei, symmetric=True, res=args.res,
