@@ -6,7 +6,7 @@
 //     K_n = (J_n Gamma) J_n^T   [C, C]            R_n = 2 Lambda_n (J_n Gamma)   [C, P],   Lambda_n = diag(p) - p p^T,
 // without Z ever reaching memory.
 #include "lgnn_internal.h"
-#include "gram256.h"
+#include "mfma_tile.h"  // f32x16
 
 namespace lgnn {
 namespace {

@@ -8,7 +8,7 @@
 // Structured route (1- and 2-layer GCN / GraphSAGE, relu or tanh, no res / norm): no Jacobian and no [rows, H k] intermediate
 // reaches memory.  Notation of sampled.hip: in0 = [P X | rowsum P] (GCN) or [X | P X | 1] (GraphSAGE), R the needed rows of the
 // batch, D = act'(s), W1 = [W1a | W1b] for GraphSAGE (z has Cz = 2 C columns, C for GCN).  Per direction i = (dW0, db0, dW1, db1):
-//   forward    q_i[r] = (D[r] . (in0[r] [dW0 | db0]^T)) W1^T + h[r] dW1^T             r in R      ggn_forward_kernel
+//   forward    q_i[r] = (D[r] . (in0[r] [dW0 | db0]^T)) W1^T + h[r] dW1^T             r in R      first_layer_kernel<FwdArgs>
 //              u_i[m] = sum_b P[n_m, b] (q_i[b] + db1)  (GraphSAGE: self half + gathered half + db1)   sampled.hip's gather
 //   curvature  w_i[m] = Lambda_m u_i[m]                                                            ggn_lambda_rows_kernel
 //   transpose  qbar_i[r] = sum_m P[n_m, r] w_i[m]  (GraphSAGE: and the self half)                     ggn_qbar_kernel
@@ -17,7 +17,7 @@
 //              sbar_i[r] = D[r] . (qbar_i[r] W1);  [g_W0 | g_b0] = sum_r sbar_i[r]^T in0[r]         ggn_tn_kernel, through W1
 // A sample's w depends on its node alone, so the samples of a repeated node enter qbar as (multiplicity) x (the first one's w):
 // qbar is a gather over P^T's rows with one writer per element.  One layer is the two outer products alone.
-// ggn_forward_kernel is step (b) of sampled.hip linearised: the first product on v_mfma_f32_32x32x2_f32 with the k directions
+// The forward product is step (b) of sampled.hip linearised, and is that kernel's text (its FwdArgs instance): the k directions
 // in the grid, D and the contraction with W1 applied while the 64 x 64 tile is in LDS, the h dW1^T term on the same
 // accumulators.  ggn_tn_kernel owns a 64 x 64 output tile per workgroup and walks its share of R's row tiles: it builds sbar
 // from qbar and W1 in its prologue (MFMA), multiplies sbar^T in0 on the same MFMA, and writes one partial tile per slab of R;
@@ -44,7 +44,7 @@
 #include <climits>
 
 #include "device_utils.h"
-#include "gram256.h"  // f32x16
+#include "mfma_tile.h"
 
 namespace lgnn {
 
@@ -158,176 +158,6 @@ int ggn_matmat_general(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* 
 
 
 // ======== structured route ================================================================================================
-constexpr int TB = 64, TLD = TB + 1, TZW = 128;  // tile edge, its LDS stride, columns of q per forward workgroup
-
-struct FwdArgs {
-  const float* in0; int64_t ldk;
-  const int32_t* rows; const int32_t* count;
-  const float* V; int64_t P;        // the chunk's first direction, floats between directions
-  int64_t Fp, H;                    // columns of the first Linear's weight, its rows (1 layer: the classes)
-  const float* dact; const float* h1; int64_t h1_ld;  // act'(s) [N, H], h [N, H] with row stride h1_ld
-  const float* W1; int64_t ld1, off1, C, Cz;          // the bound W1 (row stride ld1); dW1 of a direction at V_i + off1
-  float* q; int64_t rcap;           // q[(i * rcap + t) * Cz + c]   (1 layer: u[(i * rcap + m) * H + c])
-};
-
-// grid: (workers over the row tiles of R, directions of the chunk, windows of TZW columns of q)
-template <bool ONE>
-__global__ __launch_bounds__(256) void ggn_forward_kernel(FwdArgs g) {
-  __shared__ float stage[TZW * TLD];  // the first product's K stage (As | Bs), then the W1 / dW1 tile
-  __shared__ float Hs[TB * TLD];
-  __shared__ float bcol[TB];
-  __shared__ int rid[TB];
-  float* As = stage;
-  float* Bs = stage + TB * TLD;
-  float* Ws = stage;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wr = wave >> 1, wc = wave & 1;
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int64_t cnt = int64_t(*g.count);
-  const float* __restrict__ th = g.V + int64_t(blockIdx.y) * g.P;
-  const int64_t zw0 = int64_t(blockIdx.z) * TZW;
-  const int zrows = ONE ? 0 : int(g.Cz - zw0 < TZW ? g.Cz - zw0 : TZW);
-  const int srow = tid >> 2, sk = (tid & 3) * 16;
-  const int bj = tid >> 6, bk = tid & 63;
-  for (int64_t tile = blockIdx.x; tile * TB < cnt; tile += gridDim.x) {
-    const int64_t t0 = tile * TB;
-    int64_t arow = -1;
-    if (t0 + srow < cnt) arow = g.rows[t0 + srow];
-    const float* __restrict__ ap = g.in0 + (arow < 0 ? 0 : arow) * g.ldk;
-    __syncthreads();  // the previous tile's last reads of bcol / rid / the LDS tiles
-    if ((tid & 3) == 0) {
-      bcol[srow] = arow < 0 ? 0.f : ap[g.Fp];
-      rid[srow] = int(arow);
-    }
-    f32x16 zacc[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) zacc[i][r] = 0.f;
-    for (int64_t j0 = 0; j0 < g.H; j0 += TB) {
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-      float4 pa[4];
-      float pb[16];
-      auto fetch = [&](int64_t k0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int64_t k = k0 + sk + 4 * e;
-          pa[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (arow >= 0 && k < g.ldk) pa[e] = *reinterpret_cast<const float4*>(ap + k);  // (ldk % 4 == 0)
-        }
-        const int64_t k = k0 + bk;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int64_t j = j0 + bj + 4 * e;
-          pb[e] = (j < g.H && k < g.Fp) ? th[j * g.Fp + k] : 0.f;
-        }
-      };
-      fetch(0);
-      for (int64_t k0 = 0; k0 < g.Fp; k0 += TB) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float* d = As + srow * TLD + sk + 4 * e;
-          d[0] = pa[e].x; d[1] = pa[e].y; d[2] = pa[e].z; d[3] = pa[e].w;
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) Bs[(bj + 4 * e) * TLD + bk] = pb[e];
-        __syncthreads();
-        if (k0 + TB < g.Fp) fetch(k0 + TB);
-#pragma unroll
-        for (int kk = 0; kk < TB; kk += 2) {
-          const float a = As[(wr * 32 + l31) * TLD + kk + lh];
-          const float b = Bs[(wc * 32 + l31) * TLD + kk + lh];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
-      }
-      const int64_t jb = j0 + wc * 32 + l31;
-      const float bias = jb < g.H ? th[g.H * g.Fp + jb] : 0.f;
-      if constexpr (ONE) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int64_t t = t0 + row;
-          if (t < cnt && jb < g.H) g.q[(int64_t(blockIdx.y) * g.rcap + t) * g.H + jb] = fmaf(bcol[row], bias, acc[r]);
-        }
-      } else {
-        __syncthreads();  // every wave has read the last K stage: the region takes W1's tile
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int rr = rid[row];
-          const float d = (rr >= 0 && jb < g.H) ? g.dact[int64_t(rr) * g.H + jb] : 0.f;
-          Hs[row * TLD + wc * 32 + l31] = d * fmaf(bcol[row], bias, acc[r]);
-        }
-        const int64_t j = j0 + lane;
-        const int zpad = (zrows + 31) & ~31;
-        for (int cz = wave; cz < zpad; cz += 4) {
-          const int64_t c = zw0 + cz;
-          float v = 0.f;
-          if (c < g.Cz && j < g.H) v = g.W1[(c % g.C) * g.ld1 + (c / g.C) * g.H + j];
-          Ws[cz * TLD + lane] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int zb = wc + 2 * i;
-          if (zb * 32 < zrows) {  // (uniform in the wave)
-#pragma unroll
-            for (int kk = 0; kk < TB; kk += 2) {
-              const float a = Hs[(wr * 32 + l31) * TLD + kk + lh];
-              const float b = Ws[(zb * 32 + l31) * TLD + kk + lh];
-              zacc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, zacc[i], 0, 0, 0);
-            }
-          }
-        }
-        __syncthreads();  // the tiles take h and the direction's dW1
-        {
-          const int rr = rid[srow];
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int64_t jj = j0 + sk + e;
-            Hs[srow * TLD + sk + e] = (rr >= 0 && jj < g.H) ? g.h1[int64_t(rr) * g.h1_ld + jj] : 0.f;
-          }
-        }
-        for (int cz = wave; cz < zpad; cz += 4) {
-          const int64_t c = zw0 + cz;
-          float v = 0.f;
-          if (c < g.Cz && j < g.H) v = th[g.off1 + (c % g.C) * g.ld1 + (c / g.C) * g.H + j];
-          Ws[cz * TLD + lane] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int zb = wc + 2 * i;
-          if (zb * 32 < zrows) {
-#pragma unroll
-            for (int kk = 0; kk < TB; kk += 2) {
-              const float a = Hs[(wr * 32 + l31) * TLD + kk + lh];
-              const float b = Ws[(zb * 32 + l31) * TLD + kk + lh];
-              zacc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, zacc[i], 0, 0, 0);
-            }
-          }
-        }
-        // (the next tile of the hidden width starts with a barrier before it writes the regions again)
-      }
-    }
-    if constexpr (!ONE) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int64_t c = zw0 + (wc + 2 * i) * 32 + l31;
-        if ((wc + 2 * i) * 32 >= zrows || c >= g.Cz) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int64_t t = t0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (t < cnt) g.q[(int64_t(blockIdx.y) * g.rcap + t) * g.Cz + c] = zacc[i][r];
-        }
-      }
-    }
-  }
-}
-
 // w[i][m][:] = Lambda_m u[i][m][:] in place layout [kc][M][C]; one thread per (direction, sample)
 __global__ __launch_bounds__(256) void ggn_lambda_rows_kernel(const float* __restrict__ U, const float* __restrict__ probs,
                                                               const int64_t* __restrict__ idx, int64_t N, int64_t M, int64_t C,
@@ -434,15 +264,15 @@ __device__ __forceinline__ void tn_fetch(float (&v)[16], const float* __restrict
 }
 __device__ __forceinline__ void tn_store(float* __restrict__ dst, const float (&v)[16], int srow, int sk) {
 #pragma unroll
-  for (int e = 0; e < 16; ++e) dst[srow * TLD + sk + e] = v[e];
+  for (int e = 0; e < 16; ++e) dst[srow * SLDT + sk + e] = v[e];
 }
 // Wh[h][cz] = W1z[cz0 + cz][a0 + h], lanes along h
 __device__ __forceinline__ void tn_stage_w1(float* __restrict__ Wh, const TnArgs& g, int64_t cz0, int64_t a0, int wave, int lane) {
-  for (int cz = wave; cz < TB; cz += 4) {
+  for (int cz = wave; cz < SBM; cz += 4) {
     const int64_t c = cz0 + cz, hh = a0 + lane;
     float v = 0.f;
     if (c < g.acols && hh < g.H) v = g.W1[(c % g.C) * g.ld1 + (c / g.C) * g.H + hh];
-    Wh[lane * TLD + cz] = v;
+    Wh[lane * SLDT + cz] = v;
   }
 }
 
@@ -450,11 +280,11 @@ __device__ __forceinline__ void tn_stage_w1(float* __restrict__ Wh, const TnArgs
 // of the 64 x 64 tiles it stages; the next row tile's id and A values and this tile's B values travel in registers under the
 // products.  W1's tile is staged once per workgroup when the classes fit one chunk of 64.
 __global__ __launch_bounds__(256) void ggn_tn_kernel(TnArgs g) {
-  __shared__ float At[TB * TLD];
-  __shared__ float Bt[TB * TLD];
-  __shared__ float Wh[TB * TLD];
-  __shared__ float bcol[TB];
-  __shared__ int rid[TB];
+  __shared__ float At[SBM * SLDT];
+  __shared__ float Bt[SBM * SLDT];
+  __shared__ float Wh[SBM * SLDT];
+  __shared__ float bcol[SBM];
+  __shared__ int rid[SBM];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int l31 = lane & 31, lh = lane >> 5;
@@ -462,27 +292,26 @@ __global__ __launch_bounds__(256) void ggn_tn_kernel(TnArgs g) {
   const int64_t cnt = int64_t(*g.count);
   const int64_t i = blockIdx.y;
   const int64_t at = int64_t(blockIdx.z) / g.btiles, bt = int64_t(blockIdx.z) - at * g.btiles;
-  const int64_t a0 = at * TB, b0 = bt * TB;
+  const int64_t a0 = at * SBM, b0 = bt * SBM;
   const bool bias = g.bias_off >= 0 && bt == 0;
   const bool through = g.mode == 1;
-  const bool w1_once = through && g.acols <= TB;
+  const bool w1_once = through && g.acols <= SBM;
   const int64_t ac0 = through ? 0 : a0;  // first column of A this workgroup reads
   const float* __restrict__ Ai = g.A + i * g.a_ds;
   f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  acc_zero(acc);
   float bias_acc = 0.f;
   if (w1_once) tn_stage_w1(Wh, g, 0, a0, wave, lane);  // (the first tile's barriers come before its first read)
   int64_t tile = blockIdx.x;
   int32_t r_cur = -1;
   float qa[16];
-  if (tile * TB < cnt) {
-    r_cur = g.rows[tile * TB + srow < cnt ? tile * TB + srow : cnt - 1];
-    if (tile * TB + srow >= cnt) r_cur = -1;
-    tn_fetch(qa, Ai + (tile * TB + srow) * g.a_ld, ac0 + sk, g.acols, r_cur >= 0);
+  if (tile * SBM < cnt) {
+    r_cur = g.rows[tile * SBM + srow < cnt ? tile * SBM + srow : cnt - 1];
+    if (tile * SBM + srow >= cnt) r_cur = -1;
+    tn_fetch(qa, Ai + (tile * SBM + srow) * g.a_ld, ac0 + sk, g.acols, r_cur >= 0);
   }
-  for (; tile * TB < cnt; tile += gridDim.x) {
-    const int64_t t0 = tile * TB;
+  for (; tile * SBM < cnt; tile += gridDim.x) {
+    const int64_t t0 = tile * SBM;
     const bool rok = r_cur >= 0;
     float pb[16];
     tn_fetch(pb, g.B + int64_t(rok ? r_cur : 0) * g.b_ld, b0 + sk, g.bcols, rok);
@@ -497,7 +326,7 @@ __global__ __launch_bounds__(256) void ggn_tn_kernel(TnArgs g) {
     if (through && !w1_once) tn_stage_w1(Wh, g, 0, a0, wave, lane);
     // the next tile of this workgroup: its row and its A values
     {
-      const int64_t nt = (tile + gridDim.x) * TB + srow;
+      const int64_t nt = (tile + gridDim.x) * SBM + srow;
       r_cur = nt < cnt ? g.rows[nt] : -1;
       tn_fetch(qa, Ai + nt * g.a_ld, ac0 + sk, g.acols, r_cur >= 0);
     }
@@ -507,19 +336,13 @@ __global__ __launch_bounds__(256) void ggn_tn_kernel(TnArgs g) {
       float dv[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int r2 = rid[wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
+        const int r2 = rid[acc_row(wr * 32, lane, r)];
         dv[r] = (r2 >= 0 && hh < g.H) ? g.dact[int64_t(r2) * g.H + hh] : 0.f;
       }
       f32x16 sacc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
-#pragma unroll
-      for (int kk = 0; kk < TB; kk += 2) {
-        const float a = Bt[(wr * 32 + l31) * TLD + kk + lh];
-        const float b = Wh[(wc * 32 + l31) * TLD + kk + lh];
-        sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, sacc, 0, 0, 0);
-      }
-      for (int64_t cz0 = TB; cz0 < g.acols; cz0 += TB) {  // more than 64 class columns: the further chunks, staged in place
+      acc_zero(sacc);
+      tile_nt_step<SBM, SLDT>(Bt, wr * 32, Wh, wc * 32, lane, sacc);
+      for (int64_t cz0 = SBM; cz0 < g.acols; cz0 += SBM) {  // more than 64 class columns: the further chunks, staged in place
         __syncthreads();
         float qc[16];
         const int r2 = rid[srow];
@@ -527,39 +350,34 @@ __global__ __launch_bounds__(256) void ggn_tn_kernel(TnArgs g) {
         tn_store(Bt, qc, srow, sk);
         tn_stage_w1(Wh, g, cz0, a0, wave, lane);
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < TB; kk += 2) {
-          const float a = Bt[(wr * 32 + l31) * TLD + kk + lh];
-          const float b = Wh[(wc * 32 + l31) * TLD + kk + lh];
-          sacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, sacc, 0, 0, 0);
-        }
+        tile_nt_step<SBM, SLDT>(Bt, wr * 32, Wh, wc * 32, lane, sacc);
       }
       __syncthreads();  // every wave has read Bt (and Wh): Bt takes the B tile
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        At[row * TLD + wc * 32 + l31] = dv[r] * sacc[r];
+        const int row = acc_row(wr * 32, lane, r);
+        At[row * SLDT + wc * 32 + l31] = dv[r] * sacc[r];
       }
       tn_store(Bt, pb, srow, sk);
       __syncthreads();
     }
 #pragma unroll
-    for (int kk = 0; kk < TB; kk += 2) {
-      const float a = At[(kk + lh) * TLD + wr * 32 + l31];
-      const float b = Bt[(kk + lh) * TLD + wc * 32 + l31];
+    for (int kk = 0; kk < SBM; kk += 2) {
+      const float a = At[(kk + lh) * SLDT + wr * 32 + l31];
+      const float b = Bt[(kk + lh) * SLDT + wc * 32 + l31];
       acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
     }
-    if (bias && tid < TB)
-      for (int t = 0; t < TB; ++t) bias_acc = fmaf(At[t * TLD + tid], bcol[t], bias_acc);
+    if (bias && tid < SBM)
+      for (int t = 0; t < SBM; ++t) bias_acc = fmaf(At[t * SLDT + tid], bcol[t], bias_acc);
   }
   float* __restrict__ out = g.part + (int64_t(blockIdx.x) * g.kc + i) * g.P;
   const int64_t bb = b0 + wc * 32 + l31;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t aa = a0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int64_t aa = acc_row(a0 + wr * 32, lane, r);
     if (aa < g.adim && bb < g.bcols) out[g.ooff + (aa % g.amod) * g.old + (aa / g.amod) * g.ashift + bb] = acc[r];
   }
-  if (bias && tid < TB && a0 + tid < g.adim) out[g.bias_off + a0 + tid] = bias_acc;
+  if (bias && tid < SBM && a0 + tid < g.adim) out[g.bias_off + a0 + tid] = bias_acc;
 }
 
 // G[i][p] += the slabs' partials in slab order
@@ -606,16 +424,13 @@ int struct_forward(lgnn_ctx* h, const StructModel& m, const int64_t* idx, int64_
   FwdArgs a{};
   a.in0 = sf.in0.as<float>(); a.ldk = sf.ldk;
   a.rows = sf.rows.as<int32_t>(); a.count = sf.count.as<int32_t>();
-  a.V = Vc; a.P = m.P;
+  a.theta = Vc; a.P = m.P;
   a.Fp = m.Fp; a.H = m.two ? m.H : m.C;
   a.dact = m.two ? h->fc.dact0.as<float>() : nullptr;
   a.h1 = m.two ? h->fc.hact_p[0] : nullptr; a.h1_ld = m.two ? h->fc.hact_ld[0] : 0;
   a.W1 = m.two ? h->W[1] : nullptr; a.ld1 = m.ld1; a.off1 = m.off1; a.C = m.C; a.Cz = m.Cz;
-  a.q = m.two ? q : u; a.rcap = m.rcap;
-  const dim3 grid(unsigned(std::min<int64_t>(cdiv(m.rcap, TB), 512)), unsigned(kc), m.two ? unsigned(cdiv(m.Cz, TZW)) : 1u);
-  if (m.two) hipLaunchKernelGGL(ggn_forward_kernel<false>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(ggn_forward_kernel<true>, grid, dim3(256), 0, s, a);
-  LGNN_HIP_CHECK(hipGetLastError());
+  a.z = m.two ? q : u; a.rcap = m.rcap;
+  LGNN_CALL(launch_first_layer(a, m.two, kc, s));
   if (m.two) {
     int cw = 1;
     while (cw < 64 && cw < m.C) cw <<= 1;
@@ -691,8 +506,8 @@ int ggn_matmat_structured(lgnn_ctx* h, const int64_t* idx, int64_t M, const floa
   for (int64_t i0 = 0; i0 < k; i0 += kc_max) {
     const int64_t kc = std::min(kc_max, k - i0);
     // slabs of R's row tiles: about 1024 workgroups over the directions and output tiles (a function of the shapes alone)
-    const int64_t tiles = m.two ? cdiv(m.H, TB) * (cdiv(m.Fp, TB) + cdiv(m.Cz, TB)) : cdiv(m.C, TB) * cdiv(m.Fp, TB);
-    const int nslab = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMaxSlabs, cdiv(m.rcap, TB)),
+    const int64_t tiles = m.two ? cdiv(m.H, SBM) * (cdiv(m.Fp, SBM) + cdiv(m.Cz, SBM)) : cdiv(m.C, SBM) * cdiv(m.Fp, SBM);
+    const int nslab = int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMaxSlabs, cdiv(m.rcap, SBM)),
                                                                   cdiv(1024, kc * tiles))));
     LGNN_CALL(tm.mark());
     LGNN_CALL(struct_forward(h, m, idx, M, V + i0 * m.P, kc, q, u, s));
@@ -727,23 +542,23 @@ int ggn_matmat_structured(lgnn_ctx* h, const int64_t* idx, int64_t M, const floa
       t.A = qbar; t.a_ld = m.Cz; t.a_ds = m.rcap * m.Cz; t.acols = m.Cz; t.mode = 1;
       t.B = sf.in0.as<float>(); t.b_ld = sf.ldk; t.bcols = m.Fp;
       t.adim = m.H; t.ooff = 0; t.old = m.Fp; t.amod = big; t.ashift = 0; t.bias_off = m.H * m.Fp;
-      t.btiles = int(cdiv(m.Fp, TB));
-      hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(kc), unsigned(cdiv(m.H, TB) * t.btiles)), dim3(256), 0, s, t);
+      t.btiles = int(cdiv(m.Fp, SBM));
+      hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(kc), unsigned(cdiv(m.H, SBM) * t.btiles)), dim3(256), 0, s, t);
       LGNN_HIP_CHECK(hipGetLastError());
       // g_W1 = sum_r qbar^T h
       t.mode = 0;
       t.B = h->fc.hact_p[0]; t.b_ld = h->fc.hact_ld[0]; t.bcols = m.H;
       t.adim = m.Cz; t.ooff = m.off1; t.old = m.ld1; t.amod = m.C; t.ashift = m.H; t.bias_off = -1;
-      t.btiles = int(cdiv(m.H, TB));
-      hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(kc), unsigned(cdiv(m.Cz, TB) * t.btiles)), dim3(256), 0, s, t);
+      t.btiles = int(cdiv(m.H, SBM));
+      hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(kc), unsigned(cdiv(m.Cz, SBM) * t.btiles)), dim3(256), 0, s, t);
       LGNN_HIP_CHECK(hipGetLastError());
     } else {
       // one layer: [g_W | g_b] = sum_m w^T in0 over the batch rows
       t.A = wv; t.a_ld = m.C; t.a_ds = M * m.C; t.acols = m.C; t.mode = 0;
       t.B = sf.in0.as<float>(); t.b_ld = sf.ldk; t.bcols = m.Fp;
       t.adim = m.C; t.ooff = 0; t.old = m.Fp; t.amod = big; t.ashift = 0; t.bias_off = m.C * m.Fp;
-      t.btiles = int(cdiv(m.Fp, TB));
-      hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(kc), unsigned(cdiv(m.C, TB) * t.btiles)), dim3(256), 0, s, t);
+      t.btiles = int(cdiv(m.Fp, SBM));
+      hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(kc), unsigned(cdiv(m.C, SBM) * t.btiles)), dim3(256), 0, s, t);
       LGNN_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(ggn_finish_kernel, dim3(unsigned(std::min<int64_t>(cdiv(kc * m.P, 256), 8192))), dim3(256), 0, s, part,

@@ -30,12 +30,11 @@
 #include <cmath>
 
 #include "device_utils.h"
+#include "mfma_tile.h"  // f32x16
 
 namespace lgnn {
 
 namespace {
-
-using f32x16 = __attribute__((__vector_size__(16 * sizeof(float)))) float;
 
 bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -13,9 +13,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace lgnn {
+#include "mfma_tile.h"  // f32x16
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+namespace lgnn {
 
 template <int W> struct Tiles256;
 template <> struct Tiles256<0> {

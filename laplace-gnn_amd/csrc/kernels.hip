@@ -8,10 +8,9 @@
 // C/D: col = l&31, row = (reg&3) + 8*(reg>>2) + 4*(l>>5)   (cdna_hip_programming.md section 3).
 #include "lgnn_internal.h"
 #include "device_utils.h"
+#include "mfma_tile.h"  // f32x16
 
 namespace lgnn {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // =====================================================================================
 // SpMM: out[plane][r][0:width) = epi( self[r] + sum_j val[j] * in[plane][col[j]][0:width) )

@@ -40,7 +40,7 @@
 // order; two more units for the second-order term and the rounding of this very comparison).  A row that passes needs nothing
 // else; a row that turned nothing away (fewer than KC + 1 other points in every split) has g_rej = +inf and passes trivially.
 #include "device_utils.h"
-#include "gram256.h"  // f32x16
+#include "mfma_tile.h"
 #include "lgnn_internal.h"
 
 #include <cfloat>
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(FilterArgs a) {
   float ni[16], rej[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t i = i0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int64_t i = acc_row(i0 + wr * 32, lane, r);
     ni[r] = i < a.N ? a.nrm[i] : 0.f;
     rej[r] = INFINITY;
   }
@@ -194,8 +194,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(FilterArgs a) {
     const bool b_ok = j0 + srow < a.N;
     const float* __restrict__ bp = a.X + (b_ok ? j0 + srow : 0) * a.ld;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    acc_zero(acc);
     float va[4], vb[4];
     fetch(ap, a_ok, 0, va);
     fetch(bp, b_ok, 0, vb);
@@ -211,12 +210,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(FilterArgs a) {
         fetch(ap, a_ok, k0 + KK, va);
         fetch(bp, b_ok, k0 + KK, vb);
       }
-#pragma unroll
-      for (int kk = 0; kk < KK; kk += 2) {
-        const float x = As[(wr * 32 + (lane & 31)) * KLD + kk + (lane >> 5)];
-        const float y = Bs[(wc * 32 + (lane & 31)) * KLD + kk + (lane >> 5)];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x, y, acc, 0, 0, 0);
-      }
+      tile_nt_step<KK, KLD>(As, wr * 32, Bs, wc * 32, lane, acc);
     }
     // epilogue: g = n_i + n_j - 2 x_i.x_j against the row's threshold
     const int64_t j = j0 + wc * 32 + (lane & 31);
@@ -224,7 +218,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(FilterArgs a) {
       const float nj = a.nrm[j];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int t = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int t = acc_row(wr * 32, lane, r);
         const int64_t i = i0 + t;
         if (i >= a.N || i == j) continue;
         const float g = (ni[r] + nj) - 2.f * acc[r];
@@ -249,6 +243,7 @@ __global__ __launch_bounds__(256) void knn_filter_kernel(FilterArgs a) {
     float v = rej[r];
 #pragma unroll
     for (int o = 16; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    // (the row map of mfma_tile.h written out: this kernel's code is held instruction for instruction)
     if ((lane & 31) == 0) rejw[wc * KT + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)] = v;
   }
   __syncthreads();

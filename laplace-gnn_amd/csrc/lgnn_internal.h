@@ -705,6 +705,23 @@ struct GatherArgs {
   float* out;                       // the chunk's [ns, M, C]
 };
 int launch_sampled_gather(const GatherArgs& g, hipStream_t s);
+// The first-layer tile kernel of step (b): 64-row tiles of the needed rows, the first product's K stage and the hidden tile 64
+// wide (rows padded to 65 floats), windows of SZW columns of z per workgroup.  ggnmat.hip's transposed products stage the same
+// 64 x 64 tiles.
+constexpr int SBM = 64, SBH = 64, SBK = 64, SLDT = SBK + 1, SLDH = SBH + 1, SZW = 128;
+// Its linearised instance (ggnmat.hip): theta is a block of directions (dW0, db0, dW1, db1), and
+//   z_i[r] = (D[r] . (in0[r] [dW0 | db0]^T)) W1^T + h[r] dW1^T
+struct FwdArgs {
+  static constexpr bool linearised = true;
+  const float* in0; int64_t ldk;
+  const int32_t* rows; const int32_t* count;
+  const float* theta; int64_t P;    // the chunk's first direction, floats between directions
+  int64_t Fp, H;                    // columns of the first Linear's weight, its rows (1 layer: the classes)
+  const float* dact; const float* h1; int64_t h1_ld;  // D = act'(s) [N, H], h [N, H] with row stride h1_ld
+  const float* W1; int64_t ld1, off1, C, Cz;          // the bound W1 (row stride ld1); dW1 of a direction at theta_i + off1
+  float* z; int64_t rcap;           // z[(i * rcap + t) * Cz + c]   (1 layer: u[(i * rcap + m) * H + c])
+};
+int launch_first_layer(const FwdArgs& a, bool two, int64_t ndir, hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------
 // full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127

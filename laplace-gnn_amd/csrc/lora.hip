@@ -18,7 +18,7 @@
 //  * lgnn_lora_threshold: re-binarise adj0 + scaling B A against the engine's stored pattern, compacted flips on the device;
 //  * lgnn_lora_grad: grad_A / grad_B from the dense G in one pass over row tiles of G.
 #include "device_utils.h"
-#include "gram256.h"  // f32x16
+#include "mfma_tile.h"
 #include "lgnn_internal.h"
 
 namespace lgnn {
@@ -26,8 +26,8 @@ namespace lgnn {
 namespace {
 
 // ---- C[orow(t), b] += sum_c sum_k L_c[lrow(t), k] R_c[b, k]  (+ rowc[orow]) ------------------------------------------------
-// 64 x 64 output tile per workgroup, four waves of 32 x 32; K staged through LDS 16 wide (rows padded to 17 floats).  Lane l
-// supplies operand row l & 31 at k = kk + (l >> 5); the result of lane l is column l & 31, rows (r & 3) + 8 (r >> 2) + 4 (l >> 5).
+// 64 x 64 output tile per workgroup, four waves of 32 x 32 (mfma_tile.h); K staged through LDS 16 wide (rows padded to 17
+// floats).
 // Every output row of a launch belongs to one list entry: one writer per element, no atomics.
 constexpr int DT = 64, DKC = 16, DLD = DKC + 1;
 
@@ -50,8 +50,7 @@ __global__ __launch_bounds__(256) void dense_nt_kernel(DenseNtArgs g) {
   const int64_t sb = b0 + srow;
   const bool r_ok = sb < g.ncols;
   f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  acc_zero(acc);
   for (int64_t c = 0; c < g.nplanes; ++c) {
     const float* __restrict__ lp = g.L + c * g.l_stride + lrow * g.l_ld;
     const float* __restrict__ rp = g.R + c * g.r_stride + sb * g.r_ld;
@@ -65,19 +64,14 @@ __global__ __launch_bounds__(256) void dense_nt_kernel(DenseNtArgs g) {
         Rs[srow * DLD + sk + e] = (r_ok && kin) ? rp[k] : 0.f;
       }
       __syncthreads();
-#pragma unroll
-      for (int kk = 0; kk < DKC; kk += 2) {
-        const float a = Ls[(wr * 32 + (lane & 31)) * DLD + kk + (lane >> 5)];
-        const float b = Rs[(wc * 32 + (lane & 31)) * DLD + kk + (lane >> 5)];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-      }
+      tile_nt_step<DKC, DLD>(Ls, wr * 32, Rs, wc * 32, lane, acc);
     }
   }
   const int64_t b = b0 + wc * 32 + (lane & 31);
   if (b >= g.ncols) return;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int64_t t = t0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+    const int64_t t = acc_row(t0 + wr * 32, lane, r);
     if (t >= total) continue;
     const int64_t orow = g.orows ? int64_t(g.orows[t]) : t;
     float v = acc[r];
@@ -118,8 +112,7 @@ __global__ __launch_bounds__(256) void dense_diag_pair_kernel(const int64_t* __r
     const int64_t sj = j0 + srow;
     const bool j_ok = sj < H;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    acc_zero(acc);
     for (int64_t i0 = 0; i0 < F1; i0 += DKC) {
       __syncthreads();
 #pragma unroll
@@ -129,17 +122,12 @@ __global__ __launch_bounds__(256) void dense_diag_pair_kernel(const int64_t* __r
         Es[srow * DLD + sk + e] = !b_ok ? 0.f : (i < F ? PX[sb * ldx + i] : (i == F ? rowsum[sb] : 0.f));
       }
       __syncthreads();
-#pragma unroll
-      for (int kk = 0; kk < DKC; kk += 2) {
-        const float a = Ts[(wr * 32 + (lane & 31)) * DLD + kk + (lane >> 5)];
-        const float b = Es[(wc * 32 + (lane & 31)) * DLD + kk + (lane >> 5)];
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-      }
+      tile_nt_step<DKC, DLD>(Ts, wr * 32, Es, wc * 32, lane, acc);
     }
     if (bl < N) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int64_t j = j0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int64_t j = acc_row(j0 + wr * 32, lane, r);
         if (j < H) part = fmaf(acc[r], mask[bl * H + j], part);
       }
     }

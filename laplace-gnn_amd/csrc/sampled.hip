@@ -11,8 +11,8 @@
 //   1 layer    f_s[m] = in0[idx_m] [W_s | b_s]^T
 // Three steps per call, no host round trip:
 //   (a) the needed rows R (the columns of P's rows idx; GraphSAGE: and idx) as flags -> sorted list (compact_flags) -> positions;
-//   (b) sampled_hidden_kernel: a 64-row tile of R x one sample per workgroup pass.  The first product runs on
-//       v_mfma_f32_32x32x2_f32 (lane layout of dense_nt_kernel, lora.hip; K staged through LDS 64 wide, the next stage in
+//   (b) first_layer_kernel: a 64-row tile of R x one sample per workgroup pass.  The first product runs on
+//       v_mfma_f32_32x32x2_f32 (lane layout and tile step: mfma_tile.h; K staged through LDS 64 wide, the next stage in
 //       registers while the current one is multiplied; the B operand read from theta as stored: K contiguous, scalar loads --
 //       rows of theta are not 16-byte aligned in general); the hidden width is walked in tiles of 64; bias (times the row's
 //       bias column) and activation in registers, the tile goes to LDS and meets W1_s's 64 columns on the same MFMA while it
@@ -22,14 +22,12 @@
 // No float atomics: every output element has one writer and one summation order, which does not depend on the chunk the
 // sample runs in.  The samples go in chunks sized so that z stays under the workspace limit.
 #include "device_utils.h"
-#include "gram256.h"  // f32x16
+#include "mfma_tile.h"
 #include "lgnn_internal.h"
 
 namespace lgnn {
 
 namespace {
-
-constexpr int SBM = 64, SBH = 64, SBK = 64, SLDT = SBK + 1, SLDH = SBH + 1, SZW = 128;
 
 // in0[r, col] = rowsum(P)[r] (GCN) or 1 (GraphSAGE): the column the bias is multiplied with
 __global__ void sampled_bias_column_kernel(const int32_t* __restrict__ rowptr, const float* __restrict__ val, int64_t N,
@@ -80,6 +78,7 @@ __global__ void sampled_batch_rows_kernel(const int64_t* __restrict__ idx, int64
 }
 
 struct HiddenArgs {
+  static constexpr bool linearised = false;
   const float* in0; int64_t ldk;
   const int32_t* rows; const int32_t* count;
   const float* theta; int64_t P;   // the chunk's first sample, floats between samples
@@ -89,20 +88,25 @@ struct HiddenArgs {
   int act;
 };
 
-// (b).  grid: (workers over the row tiles, samples of the chunk, windows of SZW columns of z)
-template <bool ONE>
-__global__ __launch_bounds__(256) void sampled_hidden_kernel(HiddenArgs g) {
-  // As / Bs (the first product's K stage) and Ws (W1_s's tile) are never live at the same time: one region
+// (b).  grid: (workers over the row tiles, samples of the chunk, windows of SZW columns of z).  Two argument structs, one
+// text: HiddenArgs writes act(.) into the hidden tile and multiplies it with the sample's own W1_s; FwdArgs (the GGN's
+// forward product, ggnmat.hip) writes D . (.) instead, multiplies it with the bound W1, and then runs h dW1^T over the same
+// accumulators.
+template <class Args, bool ONE>
+__global__ __launch_bounds__(256) void first_layer_kernel(Args g) {
+  constexpr bool LIN = Args::linearised;
+  // As / Bs (the first product's K stage) and Ws (W1's tile) are never live at the same time: one region
   __shared__ float stage[SZW * SLDH];
   __shared__ float Hs[SBM * SLDH];
   __shared__ float bcol[SBM];
+  __shared__ int rid[LIN && !ONE ? SBM : 1];  // LIN: the tile rows' node ids, for D and h
   float* As = stage;
   float* Bs = stage + SBM * SLDT;
   float* Ws = stage;
   static_assert(SZW * SLDH >= (SBM + SBH) * SLDT, "the K stage fits the region of the W1 tile");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
-  const int l31 = lane & 31, lh = lane >> 5;
+  const int l31 = lane & 31;
   const int64_t cnt = int64_t(*g.count);
   const float* __restrict__ th = g.theta + int64_t(blockIdx.y) * g.P;
   const int64_t zw0 = int64_t(blockIdx.z) * SZW;
@@ -114,18 +118,18 @@ __global__ __launch_bounds__(256) void sampled_hidden_kernel(HiddenArgs g) {
     int64_t arow = -1;
     if (t0 + srow < cnt) arow = g.rows[t0 + srow];
     const float* __restrict__ ap = g.in0 + (arow < 0 ? 0 : arow) * g.ldk;
-    __syncthreads();  // the previous tile's last epilogue has read bcol
+    __syncthreads();  // the previous tile's last reads of bcol / rid / the LDS tiles
     // what the bias is multiplied with: rowsum(P) (GCN) or 1 (GraphSAGE); 0 for padding rows and invalid ids (a zero row)
-    if ((tid & 3) == 0) bcol[srow] = arow < 0 ? 0.f : ap[g.Fp];
+    if ((tid & 3) == 0) {
+      bcol[srow] = arow < 0 ? 0.f : ap[g.Fp];
+      if constexpr (LIN && !ONE) rid[srow] = int(arow);
+    }
     f32x16 zacc[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) zacc[i][r] = 0.f;
+    for (int i = 0; i < 2; ++i) acc_zero(zacc[i]);
     for (int64_t j0 = 0; j0 < g.H; j0 += SBH) {
       f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      acc_zero(acc);
       // the next K stage travels in registers while the matrix cores work on the current one
       float4 pa[4];
       float pb[16];
@@ -156,12 +160,7 @@ __global__ __launch_bounds__(256) void sampled_hidden_kernel(HiddenArgs g) {
         for (int e = 0; e < 16; ++e) Bs[(bj + 4 * e) * SLDT + bk] = pb[e];
         __syncthreads();
         if (k0 + SBK < g.Fp) fetch(k0 + SBK);
-#pragma unroll
-        for (int kk = 0; kk < SBK; kk += 2) {
-          const float a = As[(wr * 32 + l31) * SLDT + kk + lh];
-          const float b = Bs[(wc * 32 + l31) * SLDT + kk + lh];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-        }
+        tile_nt_step<SBK, SLDT>(As, wr * 32, Bs, wc * 32, lane, acc);
       }
       // bias in registers: this lane's column of the tile, the rows' bias columns from LDS
       const int64_t jb = j0 + wc * 32 + l31;
@@ -169,38 +168,52 @@ __global__ __launch_bounds__(256) void sampled_hidden_kernel(HiddenArgs g) {
       if constexpr (ONE) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int row = acc_row(wr * 32, lane, r);
           const int64_t t = t0 + row;
           if (t < cnt && jb < g.H) g.z[(int64_t(blockIdx.y) * g.rcap + t) * g.H + jb] = fmaf(bcol[row], bias, acc[r]);
         }
       } else {
-        __syncthreads();  // every wave has read the last K stage: the region takes W1_s's tile
+        const int64_t j = j0 + lane;
+        // Ws = 64 hidden columns (from j0) of the z window's rows of W1 = w + off; zacc += Hs Ws^T
+        auto times_w1 = [&](const float* __restrict__ w, int64_t off) {
+          for (int cz = wave; cz < ((zrows + 31) & ~31); cz += 4) {
+            const int64_t c = zw0 + cz;
+            float v = 0.f;
+            if (c < g.Cz && j < g.H) v = w[off + (c % g.C) * g.ld1 + (c / g.C) * g.H + j];
+            Ws[cz * SLDH + lane] = v;
+          }
+          __syncthreads();
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const int zb = wc + 2 * i;
+            if (zb * 32 < zrows) tile_nt_step<SBH, SLDH>(Hs, wr * 32, Ws, zb * 32, lane, zacc[i]);  // (uniform in the wave)
+          }
+        };
+        __syncthreads();  // every wave has read the last K stage: the region takes W1's tile
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int row = wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          Hs[row * SLDH + wc * 32 + l31] = act_apply(fmaf(bcol[row], bias, acc[r]), g.act);
-        }
-        const int64_t j = j0 + lane;
-        for (int cz = wave; cz < ((zrows + 31) & ~31); cz += 4) {
-          const int64_t c = zw0 + cz;
-          float v = 0.f;
-          if (c < g.Cz && j < g.H) v = th[g.off1 + (c % g.C) * g.ld1 + (c / g.C) * g.H + j];
-          Ws[cz * SLDH + lane] = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int zb = wc + 2 * i;
-          if (zb * 32 < zrows) {  // (uniform in the wave)
-#pragma unroll
-            for (int kk = 0; kk < SBH; kk += 2) {
-              const float a = Hs[(wr * 32 + l31) * SLDH + kk + lh];
-              const float b = Ws[(zb * 32 + l31) * SLDH + kk + lh];
-              zacc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, zacc[i], 0, 0, 0);
-            }
+          const int row = acc_row(wr * 32, lane, r);
+          const float s = fmaf(bcol[row], bias, acc[r]);
+          if constexpr (LIN) {
+            const int rr = rid[row];
+            const float d = (rr >= 0 && jb < g.H) ? g.dact[int64_t(rr) * g.H + jb] : 0.f;
+            Hs[row * SLDH + wc * 32 + l31] = d * s;
+          } else {
+            Hs[row * SLDH + wc * 32 + l31] = act_apply(s, g.act);
           }
         }
-        // (the next tile of the hidden width starts with a barrier before it writes the region again)
+        if constexpr (LIN) {
+          times_w1(g.W1, 0);
+          __syncthreads();  // the tiles take h and the direction's dW1
+          const int rr = rid[srow];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int64_t jj = j0 + sk + e;
+            Hs[srow * SLDH + sk + e] = (rr >= 0 && jj < g.H) ? g.h1[int64_t(rr) * g.h1_ld + jj] : 0.f;
+          }
+        }
+        times_w1(th, g.off1);
+        // (the next tile of the hidden width starts with a barrier before it writes the regions again)
       }
     }
     if constexpr (!ONE) {
@@ -210,12 +223,21 @@ __global__ __launch_bounds__(256) void sampled_hidden_kernel(HiddenArgs g) {
         if ((wc + 2 * i) * 32 >= zrows || c >= g.Cz) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int64_t t = t0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+          const int64_t t = acc_row(t0 + wr * 32, lane, r);
           if (t < cnt) g.z[(int64_t(blockIdx.y) * g.rcap + t) * g.Cz + c] = zacc[i][r];
         }
       }
     }
   }
+}
+
+template <class Args>
+int launch_first_layer_t(const Args& a, bool two, int64_t ndir, hipStream_t s) {
+  const dim3 grid(unsigned(std::min<int64_t>(cdiv(a.rcap, SBM), 512)), unsigned(ndir), two ? unsigned(cdiv(a.Cz, SZW)) : 1u);
+  if (two) hipLaunchKernelGGL((first_layer_kernel<Args, false>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((first_layer_kernel<Args, true>), grid, dim3(256), 0, s, a);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 // (c) one wave per (sample, batch row): 64 / cw groups of lanes share the row's entries (entry p to group p % groups), the
@@ -325,6 +347,8 @@ int sampled_needed_rows(lgnn_ctx* h, const int64_t* idx, int64_t M, hipStream_t 
   return 0;
 }
 
+int launch_first_layer(const FwdArgs& a, bool two, int64_t ndir, hipStream_t s) { return launch_first_layer_t(a, two, ndir, s); }
+
 int launch_sampled_gather(const GatherArgs& g, hipStream_t s) {
   LGNN_REQUIRE(cdiv(g.ns * g.M, 4) < (int64_t(1) << 31), "too many (sample, node) pairs per chunk");
   hipLaunchKernelGGL(sampled_gather_kernel, dim3(unsigned(cdiv(g.ns * g.M, 4))), dim3(256), 0, s, g);
@@ -376,11 +400,8 @@ int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* the
     a.off1 = off1; a.ld1 = ld1; a.C = C; a.Cz = Cz;
     a.z = two ? sf.z.as<float>() : out_c; a.rcap = rcap;
     a.act = h->act;
-    const dim3 grid(unsigned(std::min<int64_t>(cdiv(rcap, SBM), 512)), unsigned(ns), two ? unsigned(cdiv(Cz, SZW)) : 1u);
     if (h->timing) LGNN_CALL(record_event(h, s));
-    if (two) hipLaunchKernelGGL(sampled_hidden_kernel<false>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(sampled_hidden_kernel<true>, grid, dim3(256), 0, s, a);
-    LGNN_HIP_CHECK(hipGetLastError());
+    LGNN_CALL(launch_first_layer_t(a, two, ns, s));
     if (h->timing) LGNN_CALL(record_event(h, s));
     if (two) {
       GatherArgs g{};

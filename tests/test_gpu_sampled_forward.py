@@ -119,6 +119,8 @@ PARITY = {
     "sage_tanh": dict(SMALL, kind="sage", S=7, M=33, act="tanh"),
     "gcn_one_sample": dict(SMALL, kind="gcn", S=1, M=33),
     "sage_two_windows_of_z": dict(SMALL, kind="sage", C=70, S=2, M=33),  # 2 C = 140 columns of z: two windows of 128
+    # the same ragged second window (12 of 128 columns) over two row tiles of the needed rows, the second one ragged too
+    "sage_two_windows_two_row_tiles": dict(SMALL, kind="sage", N=96, H=10, C=70, S=2, M=33),
 }
 
 

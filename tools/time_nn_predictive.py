@@ -8,7 +8,7 @@ KronLaplace and DiagLaplace.  Median of ``--reps`` calls after ``--warmup``, dev
                               pair the lines of two such files (A: the earlier commit) and write one JSON document with the ratios
 
 Where the engine has the one-pass route (csrc/sampled.hip) one more call runs with the library's event timing on: the time of
-sampled_hidden_kernel alone, and its rate against 2 |R| F' H S flop and the fp32 MFMA peak."""
+the first-layer tile kernel (first_layer_kernel) alone, and its rate against 2 |R| F' H S flop and the fp32 MFMA peak."""
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
