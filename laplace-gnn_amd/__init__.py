@@ -20,9 +20,10 @@ from .subnetmask import (LargestMagnitudeSubnetMask, LargestVarianceDiagLaplaceS
                          LastLayerSubnetMask, ModuleNameSubnetMask, ParamNameSubnetMask, RandomSubnetMask, SubnetMask)
 from .models import GCN, STEGCN, GraphSAGE, LoRASTEGCN  # noqa: F401
 
-__all__ = ["GraphEngine", "HipGGN", "HipEF", "HipCurvatureInterface", "Laplace", "BaseLaplace", "ParametricLaplace",
-           "KronLaplace", "DiagLaplace", "FullLaplace", "FullLLLaplace", "KronLLLaplace", "DiagLLLaplace", "Kron", "KronDecomposed", "symeig", "GCN", "STEGCN", "LoRASTEGCN", "GraphSAGE",
-           "TensorBatchLoader", "batches_of_rank", "units_of_rank", "all_reduce_flat_", "knn", "knn_graph", "get_knn_graph",
-           "knn_candidates", "SubnetLaplace", "FullSubnetLaplace", "DiagSubnetLaplace", "subnetmask", "SubnetMask",
-           "RandomSubnetMask", "LargestMagnitudeSubnetMask", "LargestVarianceDiagLaplaceSubnetMask", "ParamNameSubnetMask",
-           "ModuleNameSubnetMask", "LastLayerSubnetMask", "FunctionalLaplace", "LowRankLaplace"]
+__all__ = ["BaseLaplace", "DiagLLLaplace", "DiagLaplace", "DiagSubnetLaplace", "FullLLLaplace", "FullLaplace",
+           "FullSubnetLaplace", "FunctionalLaplace", "GCN", "GraphEngine", "GraphSAGE", "HipCurvatureInterface", "HipEF",
+           "HipGGN", "Kron", "KronDecomposed", "KronLLLaplace", "KronLaplace", "Laplace", "LargestMagnitudeSubnetMask",
+           "LargestVarianceDiagLaplaceSubnetMask", "LastLayerSubnetMask", "LoRASTEGCN", "LowRankLaplace",
+           "ModuleNameSubnetMask", "ParamNameSubnetMask", "ParametricLaplace", "RandomSubnetMask", "STEGCN", "SubnetLaplace",
+           "SubnetMask", "TensorBatchLoader", "all_reduce_flat_", "batches_of_rank", "get_knn_graph", "knn", "knn_candidates",
+           "knn_graph", "subnetmask", "symeig", "units_of_rank"]

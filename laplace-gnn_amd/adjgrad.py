@@ -1,9 +1,11 @@
-"""Host side of ``neg_marglik_adj_grad``: candidate pairs, scope checks and the one driver behind the Kronecker, diagonal and
-full posteriors' fronts (laplace.py) -- buffers, rank sharding, the all-reduce, the finish and the candidates' tail.  The device
-side is csrc/adjgrad.hip and its per-family files."""
+"""Host side of ``neg_marglik_adj_grad``: candidate pairs, the prelude and scope checks, and the one driver behind the
+Kronecker, diagonal and full posteriors' fronts (laplace/kron.py, diag.py, full.py) -- buffers, rank sharding, the all-reduce,
+the finish and the candidates' tail.  The device side is csrc/adjgrad.hip and its per-family files."""
 from __future__ import annotations
 
 import torch
+
+from . import laplace as _front  # its _dist_info / all_reduce_flat_ are read at call time: the package imports this module
 
 
 def _adjacency_candidates(eng, candidates, sym: bool):
@@ -54,6 +56,31 @@ def _dense_scope(eng, what: str):
                                   f"({limit} bytes) or int32 indexing")
 
 
+def _adjgrad_prelude(la, name: str, under: str, fitted: bool, prior_precision, candidates, dense: bool, *, batch: str,
+                     dense_offered: bool = True, depth: bool = False):
+    """What ``neg_marglik_adj_grad`` of posterior ``name`` checks before its own value and weighting: a fit, the prior
+    overwrite, the likelihood, an engine with the ``batch`` entry, ``dense`` against ``candidates``, the family.  Returns eng."""
+    what = f"adjacency gradient under {under}"
+    if not fitted:
+        raise AttributeError("Laplace not fitted. Run fit() first.")
+    if prior_precision is not None:
+        la.prior_precision = prior_precision
+    if la.likelihood != "classification":
+        raise NotImplementedError("adjacency gradient: classification likelihood")
+    if dense and not dense_offered:
+        raise NotImplementedError(f"{what}: stored entries and candidates only "
+                                  "(dense=True is offered by KronLaplace and DiagLaplace)")
+    eng = getattr(la.backend, "engine", None)
+    if eng is None or not hasattr(eng, batch) or eng.kind not in ("gcn", "sage"):
+        raise NotImplementedError(f"{what}: 2-layer GCN / GraphSAGE on the HIP backend")
+    if dense:
+        if candidates is not None:
+            raise ValueError("dense=True covers every pair: no candidates")
+        _dense_scope(eng, f"{name}.neg_marglik_adj_grad")
+    _adjgrad_scope(eng, what, depth=depth)
+    return eng
+
+
 def _adjgrad_drive(eng, train_loader, process_group, candidates, sym: bool, dense: bool, *, batch: str, finish: str, weight,
                    per_sample: bool, finish_args=(), **batch_kwargs):
     """Everything of ``neg_marglik_adj_grad`` behind the posterior's own refusals, value and weighting: returns what follows
@@ -65,8 +92,6 @@ def _adjgrad_drive(eng, train_loader, process_group, candidates, sym: bool, dens
     ``finish_args`` -- and True for the diagonal and the full posterior, whose terms are sums over samples: every rank takes its
     slice of every batch (a Cora-shaped loader has ONE batch; a candidate pair sees a repeated node id through each slice's own
     multiplicity), and the adjoints ``h1_bar`` / ``e_bar`` travel from the batch calls to the finish."""
-    from .laplace import _dist_info, all_reduce_flat_  # (at call time: laplace.py imports this module)
-
     dev, N = eng.device, eng.num_nodes
     out_bar = torch.zeros(N, eng.dims[-1], dtype=torch.float32, device=dev)
     adjoints = []
@@ -81,7 +106,7 @@ def _adjgrad_drive(eng, train_loader, process_group, candidates, sym: bool, dens
         target = torch.zeros(eng.nnz, dtype=torch.float32, device=dev)  # d/dP on the stored entries
         cand = _adjacency_candidates(eng, candidates, sym)
         args, kwargs = (weight, target, out_bar, *adjoints), dict(batch_kwargs, cand=cand)
-    rank, world = _dist_info(process_group)
+    rank, world = _front._dist_info(process_group)
     if per_sample:
         eng.set_likelihood("classification")
     run = getattr(eng, batch)
@@ -94,8 +119,8 @@ def _adjgrad_drive(eng, train_loader, process_group, candidates, sym: bool, dens
         elif t % world == rank:
             run(X.to(dev), y.to(dev), *args, **kwargs)
     if world > 1:
-        all_reduce_flat_([b for b in (target, out_bar, *adjoints) if b is not None] + ([cand[2]] if cand is not None else []),
-                         process_group)
+        _front.all_reduce_flat_([b for b in (target, out_bar, *adjoints) if b is not None]
+                                + ([cand[2]] if cand is not None else []), process_group)
     done, fin = getattr(eng, finish), (out_bar, *(adjoints if per_sample else finish_args), target)
     if dense:
         return (done(*fin),)

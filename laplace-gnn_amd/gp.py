@@ -218,20 +218,7 @@ class FunctionalLaplace(_GLMLinkMixin, BaseLaplace):
         set."""
         if process_group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
             raise NotImplementedError("FunctionalLaplace: process_group sharding is not implemented")
-        if self.model.training:
-            self.model.eval()
-        dev = self._device
-        self.mean = parameters_to_vector(self.params).detach()
-        self.n_outputs = getattr(self.model, "n_outputs", None)
-        if self.n_outputs is None:
-            X0 = next(iter(train_loader))[0]
-            with torch.no_grad():
-                try:
-                    out = self.model(X0[:1].to(dev))
-                except (TypeError, AttributeError):
-                    out = self.model(X0.to(dev))
-            self.n_outputs = out.shape[-1]
-        setattr(self.model, "output_size", self.n_outputs)
+        dev = self._begin_fit(train_loader)
         self.batch_size = train_loader.batch_size
         if self.likelihood == "regression" and self.n_outputs > 1 and self.independent_outputs:
             warnings.warn("FunctionalLaplace with independent outputs is not recommended for multivariate regression: the "

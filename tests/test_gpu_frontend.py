@@ -903,3 +903,39 @@ def test_graphsage_neighbour_sampling_with_an_explicit_seed():
     for Fa, Fb in zip(la.H_facs.kfacs, lb.H_facs.kfacs):
         for a_, b_ in zip(Fa, Fb):
             assert rel(a_.cpu().numpy(), b_.cpu().numpy()) < 1e-5
+
+
+@pytest.mark.parametrize("cls", ["KronLaplace", "DiagLaplace", "FullLLLaplace", "KronLLLaplace", "DiagLLLaplace"])
+def test_in_place_accumulator_route_equals_the_generic_backend_route(cls):
+    """The fit loop's accumulator protocol (laplace/fit.py): ``fit(override=True)`` then ``fit(override=False)`` of every
+    posterior with an in-place route gives the H / H_facs, loss and n_data of the same posterior forced onto the generic
+    ``backend.kron`` / ``diag`` / ``full`` route (``_new_accumulator`` returning None).  2-layer GCN, 64 nodes, 40 training nodes
+    in batches of 24 + 16: two uneven batches, C = 3 classes."""
+    import laplace_gnn_amd as lg
+
+    N, F, H, C = 64, 8, 8, 3
+    gen = torch.Generator().manual_seed(11)
+    ei, X = torch.randint(0, N, (2, 256), generator=gen), torch.randn(N, F, generator=gen)
+    torch.manual_seed(1)
+    model = lg.GCN(F, H, C, 2, X, ei, symmetric=True).cuda().eval()
+    idx, y = torch.randperm(N, generator=gen)[:40].cuda(), torch.randint(0, C, (40,), generator=gen).cuda()
+    loader = lg.TensorBatchLoader(idx, y, batch_size=24)
+    fast, slow = getattr(lg, cls)(model, "classification"), getattr(lg, cls)(model, "classification")
+    made, new = [], fast._new_accumulator
+    fast._new_accumulator = lambda override: made.append(new(override)) or made[-1]
+    slow._new_accumulator = lambda override: None
+    for k, override in enumerate((True, False)):
+        fast.fit(loader, override=override)
+        slow.fit(loader, override=override)
+        assert len(made) == k + 1 and made[-1] is not None and fast._acc is None
+        assert fast.n_data == slow.n_data == 40 * (k + 1)
+        print(f"{cls} override={override}: loss {float(fast.loss):.6f} / {float(slow.loss):.6f}")
+        assert abs(float(fast.loss) - float(slow.loss)) <= RTOL * abs(float(slow.loss))
+        if hasattr(fast, "H_facs"):
+            pairs = [(a, b) for Ff, Fs in zip(fast.H_facs.kfacs, slow.H_facs.kfacs) for a, b in zip(Ff, Fs)]
+            assert len(pairs) == sum(len(Fs) for Fs in slow.H_facs.kfacs)
+        else:
+            pairs = [(fast.H, slow.H)]
+        for a, b in pairs:
+            assert a.shape == b.shape and rel(a.cpu().numpy(), b.cpu().numpy()) < RTOL
+    model.engine.check_async_errors()
