@@ -50,6 +50,11 @@ extern "C" {
 /* graph kinds: which propagation matrix the convolutions use */
 #define LGNN_KIND_GCN 0  /* D^-1/2 A^T D^-1/2, self loops added  (gnn/models/models.py:23-31, utils.py:106-112) */
 #define LGNN_KIND_SAGE 1 /* A / max(rowsum,1), self loops removed (gnn/models/models.py:47, layers.py:18-24)    */
+/* bit of `kind` in lgnn_create, GraphSAGE only: the diagonal is part of the graph.  STEGraphSAGE zeroes it once in its
+ * constructor (gnn/models/models.py:135) and its forward_adj never overwrites it again (models.py:160-180, against :114 of
+ * STEGCN), so adj[i, i] is a learnable entry: pairs (i, i) of the edge list are kept, lgnn_update_adjacency edits them, and a
+ * stored (i, i) is an ordinary entry of A and A^T (row sum deg + 1, layers.py:18-24).  A GCN context refuses the bit. */
+#define LGNN_KIND_SELF_LOOPS 0x100
 
 /* activations between layers (gnn/models/base_gnn.py:85, default "relu") */
 #define LGNN_ACT_RELU 0
@@ -92,7 +97,7 @@ LGNN_API int lgnn_create(lgnn_ctx** out, int64_t num_nodes, const int64_t* edge_
                 int kind, int symmetric, void* stream);
 LGNN_API void lgnn_destroy(lgnn_ctx* h);
 
-/* nnz of the stored 0/1 adjacency (incl. self loops for GCN).  host value. */
+/* nnz of the stored 0/1 adjacency (incl. self loops for GCN and for LGNN_KIND_SELF_LOOPS).  host value. */
 LGNN_API int64_t lgnn_nnz(const lgnn_ctx* h);
 LGNN_API int64_t lgnn_num_nodes(const lgnn_ctx* h);
 /* Rows of the backward propagation matrix with more than 64 stored entries (hubs): the 256-wide fused kernel receives
@@ -121,8 +126,9 @@ LGNN_API int lgnn_adj_to_edge_index(const lgnn_ctx* h, int64_t* edge_index_out, 
  * dense `adj` parameter (`adj_optimizer.step()`, gnn/marglik_training.py:211-221) and re-thresholding it on the next forward
  * (`BinarizeSTE` + `fill_diagonal_(1)` + `normalize_adj`, gnn/models/models.py:103-116, gnn/models/utils.py:42-112): here the
  * caller (laplace_gnn_amd.models.STEGCN) thresholds its continuous values and hands over the entries that changed side.
- * Diagonal pairs are ignored (a GCN's self loops are overwritten ones, GraphSAGE's zeros); a pair listed twice or an id out of
- * range is an error.  No re-ingest: the flips are sorted and merged into both CSRs, degrees and the values of the propagation
+ * Diagonal pairs are ignored (a GCN's self loops are overwritten ones, GraphSAGE's zeros) unless the context was created with
+ * LGNN_KIND_SELF_LOOPS: then (i, i) is inserted and removed like any other pair (on a symmetric graph it is its own mirror).  A
+ * pair listed twice or an id out of range is an error.  No re-ingest: the flips are sorted and merged into both CSRs, degrees and the values of the propagation
  * matrices are recomputed, everything cached from the graph (forward pass, P X, long-row lists) is dropped; what depends on
  * the features only survives.  Synchronises the stream (the new entry count has to reach the host).                       */
 LGNN_API int lgnn_update_adjacency(lgnn_ctx* h, const int64_t* rows, const int64_t* cols, const uint8_t* state,

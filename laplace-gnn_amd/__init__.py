@@ -18,12 +18,12 @@ from .gp import FunctionalLaplace  # noqa: F401
 from .matrix import Kron, KronDecomposed, symeig  # noqa: F401
 from .subnetmask import (LargestMagnitudeSubnetMask, LargestVarianceDiagLaplaceSubnetMask,  # noqa: F401
                          LastLayerSubnetMask, ModuleNameSubnetMask, ParamNameSubnetMask, RandomSubnetMask, SubnetMask)
-from .models import GCN, STEGCN, GraphSAGE, LoRASTEGCN  # noqa: F401
+from .models import GCN, STEGCN, GraphSAGE, LoRASTEGCN, STEGraphSAGE  # noqa: F401
 
 __all__ = ["BaseLaplace", "DiagLLLaplace", "DiagLaplace", "DiagSubnetLaplace", "FullLLLaplace", "FullLaplace",
            "FullSubnetLaplace", "FunctionalLaplace", "GCN", "GraphEngine", "GraphSAGE", "HipCurvatureInterface", "HipEF",
            "HipGGN", "Kron", "KronDecomposed", "KronLLLaplace", "KronLaplace", "Laplace", "LargestMagnitudeSubnetMask",
            "LargestVarianceDiagLaplaceSubnetMask", "LastLayerSubnetMask", "LoRASTEGCN", "LowRankLaplace",
-           "ModuleNameSubnetMask", "ParamNameSubnetMask", "ParametricLaplace", "RandomSubnetMask", "STEGCN", "SubnetLaplace",
-           "SubnetMask", "TensorBatchLoader", "all_reduce_flat_", "batches_of_rank", "get_knn_graph", "knn", "knn_candidates",
+           "ModuleNameSubnetMask", "ParamNameSubnetMask", "ParametricLaplace", "RandomSubnetMask", "STEGCN", "STEGraphSAGE",
+           "SubnetLaplace", "SubnetMask", "TensorBatchLoader", "all_reduce_flat_", "batches_of_rank", "get_knn_graph", "knn", "knn_candidates",
            "knn_graph", "subnetmask", "symeig", "units_of_rank"]

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, os.environ.get("LGNN_LIB_DIR", "lib"), "liblaplace_gnn_hip.so")
 
 KIND_GCN, KIND_SAGE = 0, 1
+KIND_SELF_LOOPS = 0x100  # bit of `kind` in lgnn_create (GraphSAGE): the diagonal is stored and editable
 ACT_RELU, ACT_TANH = 0, 1
 LIK_CLASSIFICATION, LIK_REGRESSION = 0, 1
 NORM_NONE, NORM_LAYER, NORM_BATCH = 0, 1, 2

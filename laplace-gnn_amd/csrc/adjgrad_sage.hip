@@ -12,6 +12,8 @@
 #include "adjgrad.h"
 #include "device_utils.h"
 
+#include <rocprim/rocprim.hpp>
+
 namespace lgnn {
 
 namespace {
@@ -228,14 +230,16 @@ __global__ void relu_mask_ld_kernel(float* __restrict__ x, const float* __restri
 //     gradP[(n, b)] += <h1dot[b], W1n[c]> + <H1[b], dW1n[c]>                   (W1 = [W1s | W1n]: self / neighbour halves)
 //     h1_bar[b] += P[n, b] dW1n[c],  h1_bar[n] += dW1s[c]
 //     px_bar[r] += (act'(h1[r]) * coef_r) dW0n,  coef_b = P[n, b] W1n[c],  coef_n = W1s[c]        (adjoint of P X, dW0 = [dW0s | dW0n])
-// candidate pairs (n, b') get the same first line for their b'.
+// candidate pairs (n, b') get the same first line for their b': the caller's list is ordered by row once per call
+// (sage_order_candidates), so a workgroup walks the slice [cand_ptr[n], cand_ptr[n + 1]) of the sorted positions cand_ord
+// instead of scanning all K pairs; the results land at the pairs' places in the caller's list.
 __global__ __launch_bounds__(256) void sage_diag_pair_kernel(const int64_t* __restrict__ idx, int64_t N, int64_t C, int64_t H,
                                                              int64_t F, int64_t P, const int32_t* __restrict__ rowptr,
                                                              const int32_t* __restrict__ col, const float* __restrict__ val,
                                                              const float* __restrict__ cat0, const float* __restrict__ cat1,
                                                              const float* __restrict__ dact, const float* __restrict__ W1,
-                                                             const float* __restrict__ R, const int32_t* __restrict__ ca,
-                                                             const int32_t* __restrict__ cb, int64_t K,
+                                                             const float* __restrict__ R, const int32_t* __restrict__ cand_ptr,
+                                                             const int32_t* __restrict__ cand_ord, const int32_t* __restrict__ cb,
                                                              float* __restrict__ grad_P, float* __restrict__ grad_cand,
                                                              float* __restrict__ h1_bar, float* __restrict__ px_bar,
                                                              int64_t px_ld) {
@@ -306,25 +310,27 @@ __global__ __launch_bounds__(256) void sage_diag_pair_kernel(const int64_t* __re
       __syncthreads();
     }
   }
-  // candidate pairs that start at n (a = n in the propagation matrix's coordinates)
-  for (int64_t k0 = 0; k0 < K; k0 += 256) {
-    const int64_t k = k0 + tid;
-    const bool mine = k < K && ca[k] == n;
-    // every wave walks its own matches; the dot product needs the whole workgroup, so collect the matches first
-    __shared__ int32_t match[256];
-    __shared__ int nmatch;
-    if (tid == 0) nmatch = 0;
-    __syncthreads();
-    if (mine) match[atomicAdd(&nmatch, 1)] = int32_t(k);
-    __syncthreads();
-    const int nm = nmatch;
-    for (int i = 0; i < nm; ++i) {
-      const int32_t kk = match[i];
-      const float d = pair_dot(cb[kk]);
-      if (tid == 0) atomicAdd(&grad_cand[kk], d);
-    }
-    __syncthreads();
+  // candidate pairs that start at n (a = n in the propagation matrix's coordinates): the row's slice of the sorted list
+  const int32_t k1 = cand_ptr ? cand_ptr[n + 1] : 0;
+  for (int32_t i = cand_ptr ? cand_ptr[n] : 0; i < k1; ++i) {
+    const int32_t kk = cand_ord[i];
+    const float d = pair_dot(cb[kk]);
+    if (tid == 0) atomicAdd(&grad_cand[kk], d);
   }
+}
+
+// cand_ptr[n] = the first position of the sorted rows that is >= n, n = 0 .. N: row n's candidates are [cand_ptr[n], cand_ptr[n + 1])
+__global__ void sage_cand_slices_kernel(const int32_t* __restrict__ rows, int64_t K, int64_t N, int32_t* __restrict__ cand_ptr) {
+  const int64_t n = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (n > N) return;
+  int64_t lo = 0, hi = K;
+  while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (rows[mid] < n) lo = mid + 1; else hi = mid; }
+  cand_ptr[n] = int32_t(lo);
+}
+
+__global__ void iota_i32_kernel(int32_t* __restrict__ v, int64_t n) {
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j < n) v[j] = int32_t(j);
 }
 
 __global__ void add_strided_kernel(float* __restrict__ x, int64_t ldx, const float* __restrict__ y, int64_t ldy, int64_t rows,
@@ -468,6 +474,32 @@ int sage_adjgrad_finish(lgnn_ctx* h, const float* out_bar, const float* gamma_A0
   return 0;
 }
 
+// The candidates' rows in increasing order (stable radix sort; the caller's order is arbitrary, symmetric models pass both
+// orientations concatenated): ws.cand_ord = the positions in the caller's list, ws.cand_ptr = every row's slice of them.  All 32
+// bits of the signed ids are sorted, so a row outside [0, N) lands before slice 0 or behind slice N - 1 and is never visited,
+// as it never matched a sample's node before.
+static int sage_order_candidates(lgnn_ctx* h, const int32_t* cand_a, int64_t K, hipStream_t s) {
+  Workspace& w = h->ws;
+  const int64_t N = h->N;
+  LGNN_REQUIRE(K < (int64_t(1) << 31), "adjacency gradient: too many candidates");
+  LGNN_CALL(w.cand_rows.reserve(size_t(K) * 4));
+  LGNN_CALL(w.cand_ord.reserve(size_t(K) * 4));
+  LGNN_CALL(w.cand_iota.reserve(size_t(K) * 4));
+  LGNN_CALL(w.cand_ptr.reserve(size_t(N + 1) * 4));
+  hipLaunchKernelGGL(iota_i32_kernel, dim3(unsigned(cdiv(K, 256))), dim3(256), 0, s, w.cand_iota.as<int32_t>(), K);
+  LGNN_HIP_CHECK(hipGetLastError());
+  size_t bytes = 0;
+  LGNN_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, cand_a, w.cand_rows.as<int32_t>(), w.cand_iota.as<int32_t>(),
+                                           w.cand_ord.as<int32_t>(), size_t(K), 0, 32, s));
+  LGNN_CALL(w.cand_tmp.reserve(bytes));
+  LGNN_HIP_CHECK(rocprim::radix_sort_pairs(w.cand_tmp.p, bytes, cand_a, w.cand_rows.as<int32_t>(), w.cand_iota.as<int32_t>(),
+                                           w.cand_ord.as<int32_t>(), size_t(K), 0, 32, s));
+  hipLaunchKernelGGL(sage_cand_slices_kernel, dim3(unsigned(cdiv(N + 1, 256))), dim3(256), 0, s, w.cand_rows.as<int32_t>(), K, N,
+                     w.cand_ptr.as<int32_t>());
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // (gamma [P]: diagonal posterior; Gamma [P, P]: full posterior; exactly one of them, see chunk_directions)
 int persample_adjgrad_batch_sage(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma,
                                  const float* Gamma, float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar,
@@ -491,13 +523,21 @@ int persample_adjgrad_batch_sage(lgnn_ctx* h, const int64_t* idx, const void* y,
   float* probs = h->ws.probs.as<float>();
   float* Kn = probs + chunk * C;
   const int64_t* yy = static_cast<const int64_t*>(y);
+  const int32_t* cand_ptr = nullptr;
+  const int32_t* cand_ord = nullptr;
+  if (K > 0) {
+    LGNN_REQUIRE(cand_a && cand_b && grad_cand, "null candidate pointers");
+    LGNN_CALL(sage_order_candidates(h, cand_a, K, s));
+    cand_ptr = h->ws.cand_ptr.as<int32_t>();
+    cand_ord = h->ws.cand_ord.as<int32_t>();
+  }
   for (int64_t m0 = 0; m0 < M; m0 += chunk) {
     const int64_t mc = std::min(chunk, M - m0);
     LGNN_CALL(jacobians(h, idx + m0, mc, J, nullptr, s));
     LGNN_CALL(chunk_directions(h, idx + m0, yy + m0, mc, J, gamma, Gamma, loss_scale, probs, Kn, R, out_bar, s));
     hipLaunchKernelGGL(sage_diag_pair_kernel, dim3(unsigned(mc * C)), dim3(256), size_t(6 * H + 4) * 4, s, idx + m0, N, C, H, F, P,
                        h->P.rowptr, h->P.col, h->P.val, h->fc.lin_in_p[0], h->fc.lin_in_p[1], h->fc.dact0.as<float>(), h->W[1], R,
-                       cand_a, cand_b, K, grad_P, grad_cand, h1_bar, e_bar, F + 1);
+                       cand_ptr, cand_ord, cand_b, grad_P, grad_cand, h1_bar, e_bar, F + 1);
     LGNN_HIP_CHECK(hipGetLastError());
   }
   return 0;

@@ -360,13 +360,17 @@ extern "C" int lgnn_create(lgnn_ctx** out, int64_t num_nodes, const int64_t* edg
                            int symmetric, void* stream) {
   if (!out) { set_error("null output handle"); return 2; }
   *out = nullptr;
+  const bool self_loops = (kind & LGNN_KIND_SELF_LOOPS) != 0;
+  kind &= ~LGNN_KIND_SELF_LOOPS;
   LGNN_REQUIRE(kind == LGNN_KIND_GCN || kind == LGNN_KIND_SAGE, "unknown graph kind");
+  LGNN_REQUIRE(!self_loops || kind == LGNN_KIND_SAGE, "self_loops: GraphSAGE graphs only (a GCN's diagonal is overwritten with ones)");
   LGNN_REQUIRE(num_edges == 0 || edge_index != nullptr, "edge_index is null");
   lgnn_ctx* h = new (std::nothrow) lgnn_ctx();
   if (!h) { set_error("out of host memory"); return 1; }
   h->N = num_nodes;
   h->kind = kind;
   h->sym = symmetric != 0;
+  h->self_loops = self_loops;
   int rc = graph_build(h, edge_index, num_edges, static_cast<hipStream_t>(stream));
   if (rc == 0) {
     rc = h->ws.pos.reserve(size_t(num_nodes) * 4);

@@ -17,7 +17,7 @@ namespace {
 constexpr uint64_t kSentinel = ~uint64_t(0);
 
 __global__ void make_keys_kernel(const int64_t* __restrict__ ei, int64_t E, int64_t N, int symmetric,
-                                 int add_loops, uint64_t* __restrict__ keys, int* __restrict__ bad) {
+                                 int add_loops, int keep_diag, uint64_t* __restrict__ keys, int* __restrict__ bad) {
   const int64_t stride = int64_t(gridDim.x) * blockDim.x;
   const int64_t per = symmetric ? 2 * E : E;
   for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < per + (add_loops ? N : 0); e += stride) {
@@ -28,12 +28,12 @@ __global__ void make_keys_kernel(const int64_t* __restrict__ ei, int64_t E, int6
         *bad = 1;
         key = kSentinel;
       } else {
-        key = (s == t) ? kSentinel : uint64_t(s) * uint64_t(N) + uint64_t(t);  // diagonal is overwritten
+        key = (s == t && !keep_diag) ? kSentinel : uint64_t(s) * uint64_t(N) + uint64_t(t);  // diagonal is overwritten
       }
     } else if (e < per) {
       int64_t s = ei[e - E], t = ei[E + e - E];
       if (s < 0 || s >= N || t < 0 || t >= N) key = kSentinel;
-      else key = (s == t) ? kSentinel : uint64_t(t) * uint64_t(N) + uint64_t(s);
+      else key = (s == t && !keep_diag) ? kSentinel : uint64_t(t) * uint64_t(N) + uint64_t(s);
     } else {
       uint64_t n = uint64_t(e - per);
       key = n * uint64_t(N) + n;  // GCN: fill_diagonal_(1)
@@ -153,15 +153,16 @@ __global__ void expand_keys_kernel(const int32_t* __restrict__ rowptr, const int
   for (int32_t p = rowptr[row] + lane; p < rowptr[row + 1]; p += 64) keys[p] = uint64_t(row) * uint64_t(N) + uint64_t(col[p]);
 }
 // flips (i, j, state) -> keys of the adjacency and of its transpose; the diagonal is not editable (a GCN's self loops are
-// overwritten ones, GraphSAGE's zeros: gnn/models/models.py:23, 47, 114): sentinel
-__global__ void flip_keys_kernel(const int64_t* __restrict__ fi, const int64_t* __restrict__ fj, int64_t K, int64_t N,
+// overwritten ones, GraphSAGE's zeros: gnn/models/models.py:23, 47, 114): sentinel -- unless `edit_diag` (a GraphSAGE context
+// with self loops, models.py:135, 160-180): then (i, i) is a pair like any other, and its own mirror
+__global__ void flip_keys_kernel(const int64_t* __restrict__ fi, const int64_t* __restrict__ fj, int64_t K, int64_t N, int edit_diag,
                                  uint64_t* __restrict__ keys, uint64_t* __restrict__ tkeys, int* __restrict__ bad) {
   const int64_t k = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (k >= K) return;
   const int64_t i = fi[k], j = fj[k];
   uint64_t a = kSentinel, b = kSentinel;
   if (i < 0 || i >= N || j < 0 || j >= N) *bad = 1;
-  else if (i != j) { a = uint64_t(i) * uint64_t(N) + uint64_t(j); b = uint64_t(j) * uint64_t(N) + uint64_t(i); }
+  else if (i != j || edit_diag) { a = uint64_t(i) * uint64_t(N) + uint64_t(j); b = uint64_t(j) * uint64_t(N) + uint64_t(i); }
   keys[k] = a; tkeys[k] = b;
 }
 __device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* __restrict__ a, int64_t n, uint64_t key) {
@@ -344,7 +345,8 @@ int graph_update(lgnn_ctx* h, const int64_t* fi, const int64_t* fj, const uint8_
   const dim3 rg(cdiv(N * 64, 256)), kg(cdiv(K, 256));
   hipLaunchKernelGGL(expand_keys_kernel, rg, dim3(256), 0, s, h->A.rowptr, h->A.col, N, kA.as<uint64_t>());
   hipLaunchKernelGGL(expand_keys_kernel, rg, dim3(256), 0, s, h->AT.rowptr, h->AT.col, N, kT.as<uint64_t>());
-  hipLaunchKernelGGL(flip_keys_kernel, kg, dim3(256), 0, s, fi, fj, K, N, fk.as<uint64_t>(), tk.as<uint64_t>(), d_flag);
+  hipLaunchKernelGGL(flip_keys_kernel, kg, dim3(256), 0, s, fi, fj, K, N, h->self_loops ? 1 : 0,
+                     fk.as<uint64_t>(), tk.as<uint64_t>(), d_flag);
   auto sort_pairs = [&](uint64_t* kin, uint64_t* kout, uint8_t* vout) -> int {
     size_t bytes = 0;
     LGNN_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, st, vout, size_t(K), 0, 64, s));
@@ -432,7 +434,7 @@ int graph_build(lgnn_ctx* h, const int64_t* ei, int64_t E, hipStream_t s) {
   int64_t nnz = 0;
   if (total > 0) {
     hipLaunchKernelGGL(make_keys_kernel, dim3(grid_for(total)), dim3(256), 0, s, ei, E, N, sym, loops,
-                       keys_a.as<uint64_t>(), d_bad);
+                       h->self_loops ? 1 : 0, keys_a.as<uint64_t>(), d_bad);
     LGNN_CALL(sort_keys(keys_a.as<uint64_t>(), keys_b.as<uint64_t>(), total, 64, tmp, s));
     // adjacent-unique == the clamp `adj[adj > 1] = 1`
     size_t bytes = 0;

@@ -180,6 +180,10 @@ struct Workspace {
   // ... and of its structured route: q and qbar [kc][|R|][Cz] (u and w [kc][M][C] share ggn_u / ggn_wt), the slab partials
   // [slabs][kc][P]
   DevBuf ggn_q, ggn_qbar, ggn_part;
+  // per-sample GraphSAGE adjacency gradient (adjgrad_sage.hip): the candidates' rows sorted (int32 [K]) with their positions
+  // in the caller's list (int32 [K]; cand_iota: the unsorted positions), the sort's scratch, and the slice of every row
+  // (int32 [N + 1])
+  DevBuf cand_rows, cand_ord, cand_iota, cand_tmp, cand_ptr;
   template <class F> void each_buf(F&& f) const {
     for (int l = 0; l < kMaxLayers; ++l) { f(gram_scratch[l]); f(gram_scratch_res[l]); }
     f(pos); f(seeds); f(probs); f(mult); f(planes_a); f(planes_b); f(misc); f(jac); f(top); f(active); f(val_act);
@@ -192,6 +196,7 @@ struct Workspace {
     f(subnet_keys); f(subnet_ord); f(subnet_iota); f(subnet_tmp); f(subnet_plan); f(subnet_x);
     f(gp_tab_a); f(gp_tab_b); f(gp_phi_a); f(gp_phi_b); f(gp_g); f(gp_kt); f(gp_s); f(gp_wpair); f(gp_part); f(gp_jac_a);
     f(gp_jac_b); f(ggn_jac); f(ggn_u); f(ggn_wt); f(ggn_tmp); f(ggn_q); f(ggn_qbar); f(ggn_part);
+    f(cand_rows); f(cand_ord); f(cand_iota); f(cand_tmp); f(cand_ptr);
   }
 };
 
@@ -303,6 +308,7 @@ struct lgnn_ctx {
   int64_t nnz = 0;
   int kind = 0;
   bool sym = false;
+  bool self_loops = false;  // LGNN_KIND_SELF_LOOPS: GraphSAGE keeps and edits the diagonal (STEGraphSAGE, gnn/models/models.py:135, 160-180)
   // stored 0/1 adjacency A (rows) and its transpose; AT aliases A when symmetric
   lgnn::Csr A, AT;
   lgnn::DevBuf A_rowptr, A_col, AT_rowptr, AT_col, val_fwd, val_bwd, deg_scale;

@@ -128,10 +128,17 @@ class GraphEngine:
     """Graph ingest + model binding + per-batch curvature accumulation on one GPU."""
     supports_shares = True  # kfac_accumulate(share=...): lgnn_kfac_accumulate_share
 
-    def __init__(self, edge_index: torch.Tensor, num_nodes: int, kind: str = "gcn", symmetric: bool = False):
+    def __init__(self, edge_index: torch.Tensor, num_nodes: int, kind: str = "gcn", symmetric: bool = False,
+                 self_loops: bool = False):
+        """``self_loops=True`` (GraphSAGE only): the pairs ``(i, i)`` of the edge list are kept and ``update_adjacency`` edits
+        them -- the graph of ``STEGraphSAGE``, whose diagonal is a learnable entry (gnn/models/models.py:135, 160-180).
+        ``export_adj``, ``nnz`` and ``export_propagation`` then include them; ``adj_to_edge_index`` drops the diagonal as ever."""
         self.lib = _lib.load()
         if kind not in KINDS:
             raise ValueError(f"kind must be one of {list(KINDS)}")
+        if self_loops and kind != "sage":
+            raise ValueError("self_loops=True: GraphSAGE engines only (a GCN's diagonal is overwritten with ones)")
+        self.self_loops = bool(self_loops)
         if edge_index.dim() != 2 or edge_index.shape[0] != 2:
             raise ValueError("edge_index must have shape [2, E]")
         ei = edge_index.contiguous()
@@ -143,7 +150,7 @@ class GraphEngine:
         with torch.cuda.device(self.device):
             rc = self.lib.lgnn_create(
                 C.byref(self._h), self.num_nodes, _dev_ptr(ei, torch.int64, "edge_index"), ei.shape[1],
-                KINDS[kind], int(bool(symmetric)), _stream(self.device))
+                KINDS[kind] | (_lib.KIND_SELF_LOOPS if self_loops else 0), int(bool(symmetric)), _stream(self.device))
         _lib.check(rc, "lgnn_create")
         self._bound = None  # keeps the bound tensors alive (borrowed pointers)
         self.dims = None

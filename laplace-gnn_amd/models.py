@@ -311,7 +311,118 @@ class GraphSAGE(BaseGNN):
         return self._engine
 
 
-class STEGCN(GCN):
+class _TrackedAdjacency:
+    """What ``STEGCN`` and ``STEGraphSAGE`` share: a continuous ``adj`` parameter on the TRACKED pairs only -- the stored
+    entries of the initial graph (1) and the caller's ``candidates`` (0), named by ``adj_index`` [2, n] (row-major sorted,
+    both orientations for a symmetric model) -- with the binarised graph held by the HIP engine.  ``_track_diagonal`` says
+    whether pairs ``(i, i)`` may be tracked (GraphSAGE: the diagonal is a learnable entry) or are dropped (GCN: the forward
+    overwrites it)."""
+    _track_diagonal = False
+
+    def _track(self, candidates):
+        """Registers ``adj_index`` and ``adj`` from the model's ``edge_index`` buffer and the candidate pairs."""
+        N = self.num_nodes
+
+        def pattern(pairs):
+            k = pairs[0] * N + pairs[1]
+            if self.symmetric:
+                k = torch.cat([k, pairs[1] * N + pairs[0]])
+            if not self._track_diagonal:
+                k = k[(k // N) != (k % N)]
+            return torch.unique(k)
+
+        ei = self.edge_index.cpu()
+        if self._track_diagonal:  # the initial graph itself has none (gnn/models/models.py:135)
+            ei = ei[:, ei[0] != ei[1]]
+        keys = pattern(ei)  # the stored pattern (duplicates clamp to one entry)
+        vals = torch.ones(keys.numel())
+        if candidates is not None and candidates.numel():
+            ck = pattern(candidates.cpu().to(torch.int64))
+            ck = ck[~torch.isin(ck, keys)]
+            keys, order = torch.sort(torch.cat([keys, ck]))
+            vals = torch.cat([vals, torch.zeros(ck.numel())])[order]
+        self.register_buffer("adj_index", torch.stack([keys // N, keys % N]))
+        self.adj = nn.Parameter(vals)  # (the Laplace parameter filter drops names containing 'adj', baselaplace.py:118-122)
+
+    def _train_pair_mask(self, train_nodes) -> torch.Tensor:
+        """bool [n]: the tracked pair joins two training nodes (gnn/models/utils.py:19-22)."""
+        is_train = torch.zeros(self.num_nodes, dtype=torch.bool)
+        is_train[torch.as_tensor(train_nodes).cpu().to(torch.int64)] = True
+        return is_train[self.adj_index[0]] & is_train[self.adj_index[1]]
+
+    def _keys(self) -> torch.Tensor:
+        return self.adj_index[0] * self.num_nodes + self.adj_index[1]
+
+    def _effective(self) -> torch.Tensor:
+        """What is thresholded: the values, or (adj + adj^T) / 2 of a symmetric model (models.py:105-106, 162-163)."""
+        v = self.adj.detach()
+        if not self.symmetric:
+            return v
+        keys = self._keys()
+        tpos = torch.searchsorted(keys, self.adj_index[1] * self.num_nodes + self.adj_index[0])
+        return 0.5 * (v + v[tpos])  # (the tracked pattern of a symmetric model contains both orientations)
+
+    def _tracked_dense(self) -> torch.Tensor:
+        out = torch.zeros(self.num_nodes, self.num_nodes, device=self.adj.device)
+        out[self.adj_index[0], self.adj_index[1]] = self.adj.detach()
+        return out
+
+    # -- the structure-learning step -----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def adj_backward(self, la, train_loader, process_group=None):
+        """``neg_marglik.backward()`` of the loop (gnn/marglik_training.py:212-216): ``adj.grad`` <- the gradient of the fitted
+        posterior's negative log marginal likelihood w.r.t. the tracked entries, through the normalisation of the propagation
+        matrix (a GCN's overwritten diagonal included), the STE (identity times ``grad_adj_mask``, gnn/models/utils.py:67-71)
+        and the symmetric parameterisation.  Accumulates into an existing ``.grad`` like autograd does.  Returns the negative
+        log marginal likelihood."""
+        eng = self.engine
+        keys = self._keys()
+        sr, sc = eng.export_adj()
+        skeys = sr * self.num_nodes + sc
+        stored = torch.isin(keys, skeys)  # tracked pairs the engine currently stores
+        ci, cj = self.adj_index[0][~stored], self.adj_index[1][~stored]
+        if self.symmetric:  # one orientation per unordered pair: the call returns the symmetrised value for both
+            half = ci <= cj
+            ci, cj = ci[half], cj[half]
+        cand = torch.stack([ci, cj]) if ci.numel() else None
+        res = la.neg_marglik_adj_grad(train_loader, process_group=process_group, candidates=cand)
+        value, _, gs = res[0], res[1], res[2]
+        g = torch.zeros_like(self.adj)
+        pos = torch.searchsorted(keys, skeys).clamp(max=max(keys.numel() - 1, 0))
+        hit = keys[pos] == skeys  # (a GCN's diagonal and untracked stored pairs -- none by construction -- are skipped)
+        g[pos[hit]] = gs[hit]
+        if cand is not None:
+            gc = res[3]
+            ckeys = ci * self.num_nodes + cj
+            g[torch.searchsorted(keys, ckeys)] = gc
+            if self.symmetric:
+                g[torch.searchsorted(keys, cj * self.num_nodes + ci)] = gc
+        if self.train_masked_update:
+            g = g * self.grad_adj_mask
+        self.adj.grad = g if self.adj.grad is None else self.adj.grad + g
+        return value
+
+    @torch.no_grad()
+    def apply_adj(self) -> int:
+        """After ``adj_optimizer.step()``: re-binarise the tracked values (``> threshold``, models.py:103-116, 160-180) and flip
+        the entries of the engine's graph whose side changed.  Returns the number of directed entries flipped."""
+        eng = self.engine
+        want = self._effective() > self.threshold
+        sr, sc = eng.export_adj()
+        have = torch.isin(self._keys(), sr * self.num_nodes + sc)
+        flip = want != have
+        n = int(flip.sum())
+        if n:
+            eng.update_adjacency(self.adj_index[0][flip], self.adj_index[1][flip], want[flip])
+            self._graph_edited(eng)
+        return n
+
+    def _graph_edited(self, eng):
+        """The buffer the engine is rebuilt from (``.to()`` / ``_apply``) follows the engine's graph."""
+        self.edge_index = eng.adj_to_edge_index()
+
+
+class STEGCN(_TrackedAdjacency, GCN):
     """The reference's structure-learning model (gnn/models/models.py:65-118) on a sparse pattern.
 
     The reference keeps a dense continuous ``adj`` parameter [N, N] (initialised with the 0/1 adjacency and the GCN's self
@@ -347,29 +458,10 @@ class STEGCN(GCN):
         self.threshold = float(threshold)
         self.sign_grad = False
         self.train_masked_update = bool(train_masked_update)
-        N = self.num_nodes
-        ei = self.edge_index.cpu()
-        keys = ei[0] * N + ei[1]
-        if symmetric:
-            keys = torch.cat([keys, ei[1] * N + ei[0]])
-        keys = torch.unique(keys[(keys // N) != (keys % N)])  # the stored off-diagonal pattern (duplicates clamp to one entry)
-        vals = torch.ones(keys.numel())
-        if candidates is not None and candidates.numel():
-            c = candidates.cpu().to(torch.int64)
-            ck = c[0] * N + c[1]
-            if symmetric:
-                ck = torch.cat([ck, c[1] * N + c[0]])
-            ck = torch.unique(ck[(ck // N) != (ck % N)])
-            ck = ck[~torch.isin(ck, keys)]
-            keys, order = torch.sort(torch.cat([keys, ck]))
-            vals = torch.cat([vals, torch.zeros(ck.numel())])[order]
-        self.register_buffer("adj_index", torch.stack([keys // N, keys % N]))
-        self.adj = nn.Parameter(vals)  # (the Laplace parameter filter drops names containing 'adj', baselaplace.py:118-122)
+        self._track(candidates)
         if self.train_masked_update:
             # soft mask of BinarizeSTE (models.py:94-98): 0.1 between two training nodes, 1 elsewhere
-            is_train = torch.zeros(N, dtype=torch.bool)
-            is_train[torch.as_tensor(train_nodes).cpu().to(torch.int64)] = True
-            both = is_train[self.adj_index[0]] & is_train[self.adj_index[1]]
+            both = self._train_pair_mask(train_nodes)
             self.register_buffer("grad_adj_mask", torch.where(both, torch.tensor(0.1), torch.tensor(1.0)))
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -391,78 +483,113 @@ class STEGCN(GCN):
                 self._engine = None
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
-    # -- helpers on the tracked pattern --------------------------------------------------------------------------------
-    def _keys(self) -> torch.Tensor:
-        return self.adj_index[0] * self.num_nodes + self.adj_index[1]
-
-    def _effective(self) -> torch.Tensor:
-        """What is thresholded: the values, or (adj + adj^T) / 2 of a symmetric model (models.py:105-106)."""
-        v = self.adj.detach()
-        if not self.symmetric:
-            return v
-        keys = self._keys()
-        tpos = torch.searchsorted(keys, self.adj_index[1] * self.num_nodes + self.adj_index[0])
-        return 0.5 * (v + v[tpos])  # (the tracked pattern of a symmetric model contains both orientations)
-
     def full_adj(self) -> torch.Tensor:
         """Dense binarised adjacency (models.py:99-101, with the propagated self loops), small graphs only."""
         return super().full_adj()
 
     def dense_adj(self) -> torch.Tensor:
         """The continuous parameter as the reference stores it (dense [N, N], untracked pairs 0, diagonal 1): small graphs."""
-        out = torch.zeros(self.num_nodes, self.num_nodes, device=self.adj.device)
-        out[self.adj_index[0], self.adj_index[1]] = self.adj.detach()
+        out = self._tracked_dense()
         out.fill_diagonal_(1.0)
         return out
 
-    # -- the structure-learning step -----------------------------------------------------------------------------------
-    @torch.no_grad()
-    def adj_backward(self, la, train_loader, process_group=None):
-        """``neg_marglik.backward()`` of the loop (gnn/marglik_training.py:212-216): ``adj.grad`` <- the gradient of the fitted
-        posterior's negative log marginal likelihood w.r.t. the tracked entries, through normalize_adj, the overwritten
-        diagonal, the STE (identity times ``grad_adj_mask``, gnn/models/utils.py:67-71) and the symmetric parameterisation.
-        Accumulates into an existing ``.grad`` like autograd does.  Returns the negative log marginal likelihood."""
-        eng = self.engine
-        keys = self._keys()
-        sr, sc = eng.export_adj()
-        skeys = sr * self.num_nodes + sc
-        stored = torch.isin(keys, skeys)  # tracked pairs the engine currently stores
-        ci, cj = self.adj_index[0][~stored], self.adj_index[1][~stored]
-        if self.symmetric:  # one orientation per unordered pair: the call returns the symmetrised value for both
-            half = ci < cj
-            ci, cj = ci[half], cj[half]
-        cand = torch.stack([ci, cj]) if ci.numel() else None
-        res = la.neg_marglik_adj_grad(train_loader, process_group=process_group, candidates=cand)
-        value, _, gs = res[0], res[1], res[2]
-        g = torch.zeros_like(self.adj)
-        pos = torch.searchsorted(keys, skeys).clamp(max=max(keys.numel() - 1, 0))
-        hit = keys[pos] == skeys  # (the diagonal and untracked stored pairs -- none by construction -- are skipped)
-        g[pos[hit]] = gs[hit]
-        if cand is not None:
-            gc = res[3]
-            ckeys = ci * self.num_nodes + cj
-            g[torch.searchsorted(keys, ckeys)] = gc
-            if self.symmetric:
-                g[torch.searchsorted(keys, cj * self.num_nodes + ci)] = gc
-        if self.train_masked_update:
-            g = g * self.grad_adj_mask
-        self.adj.grad = g if self.adj.grad is None else self.adj.grad + g
-        return value
 
-    @torch.no_grad()
-    def apply_adj(self) -> int:
-        """After ``adj_optimizer.step()``: re-binarise the tracked values (``> threshold``, models.py:103-116) and flip the
-        entries of the engine's graph whose side changed.  Returns the number of directed entries flipped."""
-        eng = self.engine
-        want = self._effective() > self.threshold
-        sr, sc = eng.export_adj()
-        have = torch.isin(self._keys(), sr * self.num_nodes + sc)
-        flip = want != have
-        n = int(flip.sum())
-        if n:
-            eng.update_adjacency(self.adj_index[0][flip], self.adj_index[1][flip], want[flip])
-            self.edge_index = eng.adj_to_edge_index()
-        return n
+class STEGraphSAGE(_TrackedAdjacency, GraphSAGE):
+    """The reference's GraphSAGE structure-learning model (gnn/models/models.py:121-183) on a sparse pattern: ``STEGCN``'s loop
+    with mean aggregation ``P = A / max(rowsum, 1)`` (gnn/models/layers.py:18-24) and a LEARNABLE diagonal.
+
+    The reference zeroes the diagonal of its dense ``adj`` once, in the constructor (models.py:135); its ``forward_adj``
+    binarises ``adj`` -- ``(adj + adj^T) / 2`` of a symmetric model -- and never overwrites the diagonal again (models.py:160-180,
+    against :114 of STEGCN).  So ``adj[i, i]`` is an ordinary entry: once it crosses the threshold node ``i`` averages over
+    itself as well.  Here the engine is built with ``self_loops=True`` and ``candidates`` may list pairs ``(i, i)``, tracked like
+    any other; entry ``(i, j)`` of ``adj`` is entry ``(a = i, b = j)`` of the propagation matrix.  With every pair listed --
+    the stored entries, every non-edge and the diagonal, ``adj.numel() == N * N`` -- this reproduces the reference's loop
+    (tests/golden/sageloop/steloop_sage_*.npz).
+
+    ``train_masked_update``: the gradient mask is the hard one of ``train_adj_mask`` (models.py:152-154) -- 0 between two
+    training nodes, ``(t, t)`` included, 1 elsewhere -- not STEGCN's 0.1.  ``num_sampled_nodes_per_hop`` is accepted and unused,
+    as in the reference (its sampling line is commented out, models.py:174-177).  Plain 2-layer models only: ``sign_grad=True``,
+    ``res=True``, a ``norm`` and other depths are refused here, as the adjacency gradient refuses them."""
+    _track_diagonal = True
+
+    def __init__(self, in_channels, hidden_channels, out_channels, num_layers, X, init_adj, num_sampled_nodes_per_hop=None,
+                 dropout_p: float = 0.5, act="relu", act_kwargs=None, threshold: float = 0.5, train_masked_update: bool = False,
+                 train_nodes=None, symmetric: bool = False, sign_grad: bool = False, candidates: Optional[torch.Tensor] = None,
+                 **kwargs):
+        if sign_grad:
+            raise NotImplementedError("sign_grad=True: the reference sums the signs of per-forward-call gradients "
+                                      "(gnn/models/utils.py:75-76); not reproducible from one accumulated gradient")
+        if kwargs.get("res"):
+            raise NotImplementedError("STEGraphSAGE: res=True is not covered (the GraphSAGE adjacency gradient takes plain "
+                                      "2-layer models)")
+        if kwargs.get("norm") not in (None, "none"):
+            raise NotImplementedError(f"STEGraphSAGE: norm={kwargs.get('norm')!r} is not covered (the GraphSAGE adjacency "
+                                      "gradient takes plain 2-layer models)")
+        if num_layers != 2:
+            raise NotImplementedError(f"STEGraphSAGE: num_layers={num_layers} is not covered (the GraphSAGE adjacency "
+                                      "gradient takes plain 2-layer models)")
+        if train_masked_update and train_nodes is None:
+            raise ValueError("'train_nodes' must be provided, to use train_masked_update.")  # models.py:149-151
+        kwargs.pop("update_adj", None)
+        kwargs.pop("sample_seed", None)
+        # (num_sampled_nodes_per_hop does not reach GraphSAGE's sampler: the reference's sampling line is commented out)
+        super().__init__(in_channels, hidden_channels, out_channels, num_layers, X, init_adj, dropout_p=dropout_p, act=act,
+                         act_kwargs=act_kwargs, symmetric=symmetric, **kwargs)
+        self.ste_num_sampled_nodes_per_hop = num_sampled_nodes_per_hop
+        self.threshold = float(threshold)
+        self.sign_grad = False
+        self.train_masked_update = bool(train_masked_update)
+        ei = self.edge_index
+        self.edge_index = ei[:, ei[0] != ei[1]].contiguous()  # init_adj.fill_diagonal_(0), models.py:135
+        self._track(candidates)
+        if self.train_masked_update:
+            both = self._train_pair_mask(train_nodes)  # train_adj_mask: hard 0 / 1 (gnn/models/utils.py:19-22)
+            self.register_buffer("grad_adj_mask", torch.where(both, torch.tensor(0.0), torch.tensor(1.0)))
+
+    @property
+    def engine(self) -> GraphEngine:
+        """The HIP context: a GraphSAGE graph that keeps and edits its diagonal (``self_loops=True``)."""
+        dev = self.convs[0].lin.weight.device
+        if self._engine is None:
+            if dev.type != "cuda":
+                raise RuntimeError("the HIP engine needs the model on a GPU: call model.to('cuda') first "
+                                   "(there is no CPU fallback)")
+            eng = GraphEngine(self.edge_index.to(dev), self.num_nodes, kind=self.kind, symmetric=self.symmetric,
+                              self_loops=True)
+            eng.bind(self.X.to(dev).contiguous(), [c.lin.weight for c in self.convs],
+                     [c.lin.bias for c in self.convs], act=self.act_name)
+            self._engine = eng
+        return self._engine
+
+    def _graph_edited(self, eng):
+        # (adj_to_edge_index drops the diagonal, gnn/utils.py:333-336: the rebuild needs the learned self loops)
+        self.edge_index = torch.stack(eng.export_adj()).contiguous()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        """A reference checkpoint's dense ``adj`` [N, N] (continuous values) is reduced to the tracked pairs, and the engine's
+        graph becomes its binarisation, diagonal included; this module's own checkpoints hold the tracked values as they are."""
+        key = prefix + "adj"
+        adj = state_dict.get(key)
+        if adj is not None and adj.dim() == 2:
+            if tuple(adj.shape) != (self.num_nodes, self.num_nodes):
+                error_msgs.append(f"adj has shape {tuple(adj.shape)}, expected ({self.num_nodes}, {self.num_nodes})")
+            else:
+                dense = adj.to(torch.float32)
+                ai = self.adj_index.to(dense.device)
+                state_dict[key] = dense[ai[0], ai[1]]
+                eff = 0.5 * (dense + dense.T) if self.symmetric else dense
+                on = eff > self.threshold
+                self.edge_index = on.nonzero().t().to(torch.int64).contiguous().to(self.edge_index.device)
+                self._engine = None
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
+
+    def full_adj(self) -> torch.Tensor:
+        """Dense binarised adjacency (models.py:156-158) including the learned self loops, small graphs only."""
+        return super().full_adj()
+
+    def dense_adj(self) -> torch.Tensor:
+        """The continuous parameter as the reference stores it (dense [N, N]): untracked pairs 0, the diagonal as tracked."""
+        return self._tracked_dense()
 
 
 class LoRASTEGCN(GCN):
