@@ -437,6 +437,32 @@ LGNN_API int lgnn_gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const
                             float* K, int64_t ldk, void* stream);
 LGNN_API int lgnn_gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, void* stream);
 
+/* ---- joint GLM predictive: the cross-node covariance J P^-1 J^T ------------------------------------------------------
+ * What _glm_predictive_distribution(joint=True) (laplace/baselaplace.py:1123-1158; the joint predictive :1223-1242) gets from
+ * functional_covariance -- KronLaplace :1638-1644 through laplace/utils/matrix.py (inv_square_form), DiagLaplace :1905-1910,
+ * FullLaplace :1491-1494 -- for a posterior that is block diagonal over the model's Linear layers, with J as lgnn_jacobians
+ * defines it.  idx_a [Ma], idx_b [Mb] int64 on the device; C = number of outputs.
+ *   K[(n C + c) ldk + (m C + e)] = sum_p sum_q J_a[n, c, p] (P^-1)[p, q] J_b[m, e, q]; written, never accumulated; ldk >= Mb C.
+ * QA, QB, S are HOST arrays of n_blocks device pointers, blocks in lgnn_jacobians' order (convs.* first, then res.*); n_blocks
+ * must be the model's number of Linear layers.  Per block l (weight [out_l, in_l], bias [out_l]):
+ *   S[l]  [out_l, in_l + 1]  inverse precisions, the last column is the bias (the S0 convention of lgnn_glm_variance);
+ *   Kronecker posterior: QA[l] [in_l, in_l], QB[l] [out_l, out_l], eigenvectors in columns, S[l][i, j] = 1 / (f lB_i lA_j +
+ *     delta_W), S[l][i, in_l] = 1 / (f lB_i + delta_b) in QB[l]'s basis: the block of P^-1 is (Q_B (x) Q_A) diag(S) (Q_B (x) Q_A)^T;
+ *   diagonal posterior: QA[l] = QB[l] = NULL and S[l] = 1 / precision of (W_l | b_l).
+ * 1- and 2-layer GCN / GraphSAGE without res / norm (relu or tanh): from the tables and feature rows of lgnn_gp_kernel, no
+ * Jacobian row is written (csrc/glmcov.hip has the stages and the flop count); every other model, and any model under
+ * LGNN_COV_FROM_JACOBIANS: chunks of lgnn_jacobians' rows, rotated block by block, one side scaled.  Chunks follow the
+ * workspace limit (a limit below one sample's buffers is an error); lgnn_glm_covariance_chunk_pairs: how many chunk pairs the last call computed.  No float atomics: two calls
+ * on the same input return the same bits; with idx_a == idx_b (the same pointer) only the upper chunk pairs are computed and K
+ * is exactly symmetric.  Invalid ids: zero rows / columns and the sticky flag (lgnn_check_async_errors).  Enqueues only.  With
+ * kernel timing enabled the structured route records five event pairs per chunk pair: tables, V (rotations and scales), NT
+ * GEMM, class contraction, placement.                                                                                      */
+#define LGNN_COV_FROM_JACOBIANS 1
+LGNN_API int lgnn_glm_covariance(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb,
+                                 int n_blocks, const float* const* QA, const float* const* QB, const float* const* S,
+                                 int flags, float* K, int64_t ldk, void* stream);
+LGNN_API int64_t lgnn_glm_covariance_chunk_pairs(lgnn_ctx* h);
+
 /* ---- low-rank Laplace: products of the Jacobian and of the GGN with a block of parameter directions ----------------
  * What LowRankLaplace (laplace/baselaplace.py:1679-1835) asks of its backend is eig_lowrank (laplace/curvature/
  * asdfghjkl.py:212-236: power iteration on Hessian-vector products, one vector at a time).  Here the curvature is the GGN of

@@ -19,6 +19,7 @@ NORM_NONE, NORM_LAYER, NORM_BATCH = 0, 1, 2
 FLAG_FORK_EXACT_SEED, FLAG_NO_FUSE, FLAG_NO_PATHS, FLAG_FORCE_PATHS = 1, 2, 4, 8
 GP_INDEPENDENT, GP_MATCHED, GP_FROM_JACOBIANS = 1, 2, 4
 GGN_FROM_JACOBIANS = 1
+COV_FROM_JACOBIANS = 1
 SAMPLED_SOFTMAX = 1
 
 # name -> (restype, argtypes); mirrors include/laplace_gnn_hip.h one to one
@@ -95,6 +96,8 @@ SIGNATURES = {
     "lgnn_subnet_full_accumulate": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "lgnn_gp_kernel": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "lgnn_gp_jvp": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "lgnn_glm_covariance": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _pp, _pp, _pp, _i32, _vp, _i64, _vp]),
+    "lgnn_glm_covariance_chunk_pairs": (_i64, [_vp]),
     "lgnn_block_gram": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "lgnn_jvp_block": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "lgnn_ggn_matmat": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),

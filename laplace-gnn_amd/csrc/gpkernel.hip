@@ -25,6 +25,7 @@
 // bit for bit a k-ordered fmaf chain, so <x, y> and <y, x> agree; with the same index pointer on both sides only the upper
 // chunk pairs are computed and the lower triangle is a copy of the upper, so K(a, a) is exactly symmetric on every route.
 #include "closedform.h"
+#include "gpkernel.h"
 #include "lgnn_internal.h"
 
 #include <cmath>
@@ -84,6 +85,7 @@ struct NtArgs {
   int64_t k_chunk;                     // split-K: slab sp covers [sp * k_chunk, (sp + 1) * k_chunk); a multiple of TBK
   int splits;                          // blockIdx.z = z * splits + sp
   int vecA, vecB;
+  int upper;                           // skip the tiles strictly below the diagonal (the caller mirrors the upper triangle)
 };
 
 __device__ __forceinline__ void nt_load_tile(const float* __restrict__ base, int64_t ld, int64_t rows, int64_t row0,
@@ -113,6 +115,7 @@ __device__ __forceinline__ void nt_load_tile(const float* __restrict__ base, int
 __global__ __launch_bounds__(256) void gp_nt_gemm_kernel(NtArgs g) {
   __shared__ float As[TBM][TBK + 1];
   __shared__ float Bs[TBN][TBK + 1];
+  if (g.upper && blockIdx.x > blockIdx.y) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int l31 = lane & 31, lhi = lane >> 5;
@@ -200,23 +203,25 @@ __global__ __launch_bounds__(256) void gp_rowdot_kernel(const float* __restrict_
 }
 
 // ---- (c) class pairs -----------------------------------------------------------------------------------------------------
-// Wp[q * Zp + (ab * H + h)] = W^al[c, h] W^be[e, h];  q = c * C + e, or q = c = e with diag_only; GCN: one (al, be);
+// Wp[q * ldw + (ab * H + h)] = W^al[c, h] W^be[e, h];  q = c * C + e, or q = c = e with diag_only; GCN: one (al, be);
 // GraphSAGE: ab = 2 al + be over the halves [Ws | Wn] of W_1
 __global__ void gp_wpair_kernel(const float* __restrict__ W1, int64_t w1_ld, int64_t H, int64_t C, int sage, int diag_only,
-                                float* __restrict__ Wp) {
+                                float* __restrict__ Wp, int64_t ldw) {
   const int64_t nab = sage ? 4 : 1, Zp = nab * H, Q = diag_only ? C : C * C;
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= Q * Zp) return;
   const int64_t q = t / Zp, zp = t - q * Zp, ab = zp / H, hh = zp - ab * H;
   const int64_t c = diag_only ? q : q / C, e = diag_only ? q : q - c * C;
-  Wp[t] = W1[c * w1_ld + (ab >> 1) * H + hh] * W1[e * w1_ld + (ab & 1) * H + hh];
+  Wp[q * ldw + zp] = W1[c * w1_ld + (ab >> 1) * H + hh] * W1[e * w1_ld + (ab & 1) * H + hh];
 }
 
 // ---- (d) placement -------------------------------------------------------------------------------------------------------
-// full layout: K[(n C + c) ldk + (m C + e)] = Kt[(c C + e) pairs + n mb + m] + [c == e] S[n mb + m]; one workgroup per
-// (64 columns m, class c, sample n): Kt is read along m and written along (m, e) through an LDS transpose of 32 classes e
+// full layout: K[(n C + c) ldk + (m C + e)] = Kt[(c C + e) pairs + n mb + m] + [c == e] S[c s_cs + n mb + m] + Add[(n C + c)
+// mb C + m C + e]; one workgroup per (64 columns m, class c, sample n): Kt is read along m and written along (m, e) through an
+// LDS transpose of 32 classes e.  S (s_cs = 0: one plane for every class) and Add are the joint GLM predictive's.
 __global__ __launch_bounds__(256) void gp_place_full_kernel(const float* __restrict__ Kt /* null: 0 */, int64_t pairs,
-                                                            const float* __restrict__ S, int64_t mb, int64_t C,
+                                                            const float* __restrict__ S /* null: 0 */, int64_t s_cs,
+                                                            const float* __restrict__ Add /* null: 0 */, int64_t mb, int64_t C,
                                                             float* __restrict__ K, int64_t ldk) {
   __shared__ float tile[32][65];
   const int64_t n = blockIdx.z, c = blockIdx.y, m0 = int64_t(blockIdx.x) * 64;
@@ -228,7 +233,7 @@ __global__ __launch_bounds__(256) void gp_place_full_kernel(const float* __restr
       float v = 0.f;
       if (e < C && m < mb) {
         if (Kt) v = Kt[(c * C + e) * pairs + n * mb + m];
-        if (e == c) v += S[n * mb + m];
+        if (S && e == c) v += S[c * s_cs + n * mb + m];
       }
       tile[ee][mm] = v;
     }
@@ -236,7 +241,8 @@ __global__ __launch_bounds__(256) void gp_place_full_kernel(const float* __restr
     for (int mm = t >> 5; mm < 64; mm += 8) {
       const int ee = t & 31;
       const int64_t e = e0 + ee, m = m0 + mm;
-      if (e < C && m < mb) K[(n * C + c) * ldk + m * C + e] = tile[ee][mm];
+      if (e < C && m < mb)
+        K[(n * C + c) * ldk + m * C + e] = Add ? tile[ee][mm] + Add[(n * C + c) * mb * C + m * C + e] : tile[ee][mm];
     }
     __syncthreads();
   }
@@ -323,11 +329,21 @@ int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s) {
   NtArgs g{};
   g.A = p.A; g.lda = p.lda; g.a_bs = p.a_bs; g.B = p.B; g.ldb = p.ldb; g.b_bs = p.b_bs;
   g.Ra = p.Ra; g.Rb = p.Rb; g.K = p.K;
+  g.upper = (p.upper_only && p.Ra == p.Rb) ? 1 : 0;
   g.vecA = (p.lda % 4 == 0) && (p.a_bs % 4 == 0) && aligned16p(p.A);
   g.vecB = (p.ldb % 4 == 0) && (p.b_bs % 4 == 0) && aligned16p(p.B);
   const int64_t tiles = cdiv(p.Ra, TBM) * cdiv(p.Rb, TBN) * p.batch;
   int64_t splits = 1, k_chunk = 0;
-  if (tiles < 256 && p.K >= 512) {
+  if (g.upper) {
+    // upper tiles only: a long K on few tiles is bound by one tile's time (M C = 2 560, K = 33 792: 210 tiles);
+    // slabs of K fill the chip
+    const int64_t nt = cdiv(p.Ra, TBM), work = nt * (nt + 1) / 2 * p.batch;
+    if (work < 512 && p.K >= 512) {
+      const int64_t want = std::min<int64_t>(cdiv(1024, work), cdiv(p.K, 128));
+      k_chunk = cdiv(cdiv(p.K, want), TBK) * TBK;
+      splits = cdiv(p.K, k_chunk);
+    }
+  } else if (tiles < 256 && p.K >= 512) {
     const int64_t want = std::min<int64_t>(cdiv(512, tiles), cdiv(p.K, 128));
     k_chunk = cdiv(cdiv(p.K, want), TBK) * TBK;
     splits = cdiv(p.K, k_chunk);
@@ -354,6 +370,25 @@ int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s) {
   return 0;
 }
 
+int launch_wpair(const float* W1, int64_t w1_ld, int64_t H, int64_t C, bool sage, bool diag_only, float* Wp, int64_t ldw,
+                 hipStream_t s) {
+  const int64_t total = (diag_only ? C : C * C) * (sage ? 4 : 1) * H;
+  if (total <= 0) return 0;
+  hipLaunchKernelGGL(gp_wpair_kernel, dim3(unsigned(cdiv(total, 256))), dim3(256), 0, s, W1, w1_ld, H, C, sage ? 1 : 0,
+                     diag_only ? 1 : 0, Wp, ldw);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_place_full(const float* Kt, int64_t pairs, const float* S, int64_t s_cs, const float* Add, int64_t ma, int64_t mb,
+                      int64_t C, float* K, int64_t ldk, hipStream_t s) {
+  LGNN_REQUIRE(C < 65536 && ma < 65536, "too many classes");
+  hipLaunchKernelGGL(gp_place_full_kernel, dim3(unsigned(cdiv(mb, 64)), unsigned(C), unsigned(ma)), dim3(256), 0, s, Kt, pairs,
+                     S, s_cs, Add, mb, C, K, ldk);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 namespace {
 
 int launch_rowdot(const float* A, int64_t lda, int64_t a_bs, const float* B, int64_t ldb, int64_t b_bs, int64_t K, int64_t R,
@@ -366,6 +401,8 @@ int launch_rowdot(const float* A, int64_t lda, int64_t a_bs, const float* B, int
   return 0;
 }
 
+}  // namespace
+
 int launch_mirror(float* K, int64_t D, int64_t ld, int64_t planes, int64_t plane, hipStream_t s) {
   if (D <= 1) return 0;
   const int64_t nt = cdiv(D, 32);
@@ -375,13 +412,7 @@ int launch_mirror(float* K, int64_t D, int64_t ld, int64_t planes, int64_t plane
   return 0;
 }
 
-// the structured route's view of the bound model: the closed form's operands and the table geometry
-struct GpModel {
-  ClosedForm cf;
-  int64_t Z, Zp;      // tables per sample, table pairs (0 for one-layer models)
-  int64_t ld, ldp;    // row strides of the tables and of the [phi | s] rows
-};
-
+// the structured route's view of the bound model (GpModel: gpkernel.h)
 int gp_model(lgnn_ctx* h, GpModel& g) {
   LGNN_CALL(closed_form_view(h, g.cf));
   const ClosedForm& cf = g.cf;
@@ -404,10 +435,7 @@ int build_tables(lgnn_ctx* h, const GpModel& g, const int64_t* idx, int64_t mc, 
   return 0;
 }
 
-struct StageTimer {  // lgnn_enable_kernel_timing: one event pair per stage (a)-(d) of every chunk pair, in that order
-  lgnn_ctx* h; hipStream_t s;
-  int mark() { return h->timing ? record_event(h, s) : 0; }
-};
+namespace {
 
 int gp_kernel_structured(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int flags, float* K,
                          int64_t ldk, hipStream_t s) {
@@ -422,9 +450,7 @@ int gp_kernel_structured(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const in
   StageTimer tm{h, s};
   if (g.Zp > 0) {
     LGNN_CALL(w.gp_wpair.reserve(size_t(Q) * g.Zp * 4));
-    hipLaunchKernelGGL(gp_wpair_kernel, dim3(unsigned(cdiv(Q * g.Zp, 256))), dim3(256), 0, s, cf.W1, cf.w1_ld, cf.H, C,
-                       cf.sage ? 1 : 0, indep ? 1 : 0, w.gp_wpair.as<float>());
-    LGNN_HIP_CHECK(hipGetLastError());
+    LGNN_CALL(launch_wpair(cf.W1, cf.w1_ld, cf.H, C, cf.sage != 0, indep, w.gp_wpair.as<float>(), g.Zp, s));
   }
   GemmEpilogue ep;
   ep.no_atomics = true;
@@ -531,9 +557,7 @@ int gp_kernel_structured(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const in
         hipLaunchKernelGGL(gp_place_planes_kernel, dim3(unsigned(cdiv(mb, 256)), unsigned(ma), unsigned(C)), dim3(256), 0, s, Kt,
                            pairs, w.gp_s.as<float>(), mb, K + n0 * ldk + m0, ldk, plane);
       } else {
-        LGNN_REQUIRE(C < 65536, "too many classes");
-        hipLaunchKernelGGL(gp_place_full_kernel, dim3(unsigned(cdiv(mb, 64)), unsigned(C), unsigned(ma)), dim3(256), 0, s, Kt,
-                           pairs, w.gp_s.as<float>(), mb, C, K + n0 * C * ldk + m0 * C, ldk);
+        LGNN_CALL(launch_place_full(Kt, pairs, w.gp_s.as<float>(), 0, nullptr, ma, mb, C, K + n0 * C * ldk + m0 * C, ldk, s));
       }
       LGNN_HIP_CHECK(hipGetLastError());
       LGNN_CALL(tm.mark());

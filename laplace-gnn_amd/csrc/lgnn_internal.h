@@ -174,6 +174,10 @@ struct Workspace {
   // contraction's output Kt [(c, e)][ma mb], Phi Phi^T [ma][mb], W_pair [(c, e)][z'], split-K partials, and the two chunks of
   // Jacobian rows of the general route
   DevBuf gp_tab_a, gp_tab_b, gp_phi_a, gp_phi_b, gp_g, gp_kt, gp_s, gp_wpair, gp_part, gp_jac_a, gp_jac_b;
+  // joint GLM predictive (glmcov.hip; it shares the gp_* buffers above): the rotated [phi | s] rows of the two chunks, the
+  // b side's C scaled copies, the rotated tables [n][l][z], V [(n, c)][k][l] of the two chunks, the first layer's term
+  // [(n, c)][(m, e)], the call's small operands (class pairs, M, Q^T, padded S) and the general route's rotation scratch
+  DevBuf cov_phit_a, cov_phit_b, cov_phis, cov_t2, cov_va, cov_vb, cov_add, cov_small, cov_scr;
   // GGN-times-block products (ggnmat.hip): a chunk of Jacobian rows [mc C, P], U = J V^T [mc C, k], W^T [k, mc C] and the
   // chunk's product [k, P]
   DevBuf ggn_jac, ggn_u, ggn_wt, ggn_tmp;
@@ -195,7 +199,8 @@ struct Workspace {
     f(dense_stored); f(dense_rows);
     f(subnet_keys); f(subnet_ord); f(subnet_iota); f(subnet_tmp); f(subnet_plan); f(subnet_x);
     f(gp_tab_a); f(gp_tab_b); f(gp_phi_a); f(gp_phi_b); f(gp_g); f(gp_kt); f(gp_s); f(gp_wpair); f(gp_part); f(gp_jac_a);
-    f(gp_jac_b); f(ggn_jac); f(ggn_u); f(ggn_wt); f(ggn_tmp); f(ggn_q); f(ggn_qbar); f(ggn_part);
+    f(gp_jac_b); f(cov_phit_a); f(cov_phit_b); f(cov_phis); f(cov_t2); f(cov_va); f(cov_vb); f(cov_add); f(cov_small);
+    f(cov_scr); f(ggn_jac); f(ggn_u); f(ggn_wt); f(ggn_tmp); f(ggn_q); f(ggn_qbar); f(ggn_part);
     f(cand_rows); f(cand_ord); f(cand_iota); f(cand_tmp); f(cand_ptr);
   }
 };
@@ -348,6 +353,7 @@ struct lgnn_ctx {
   lgnn::Workspace ws;
   int64_t ws_limit = int64_t(32) << 30;  // backward planes (ping + pong) per class chunk: 288 GB of HBM, keep chunks large
   // rows of P^T with more than kLongRow stored entries (hubs), built once on first use (longrows.hip)
+  int64_t cov_chunk_pairs = 0;     // chunk pairs the last lgnn_glm_covariance computed
   bool last_route_paths = false;   // the last KFAC accumulate took the two-hop path route
   int last_top_kernel = 0;         // ... and its top layer ran on 0: seed_spmm_gram_kernel, 1: top_tiles_kernel, 2: top_pairs_kernel
   double two_hop_max = -1.0;       // largest number of 2-hop paths starting at one node (same count pass)
@@ -678,6 +684,11 @@ int subnet_full_accumulate(lgnn_ctx* h, const int64_t* idx, const void* y, int64
 int gp_kernel(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int flags, float* K, int64_t ldk,
               hipStream_t s);
 int gp_jvp(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* v, float* out, hipStream_t s);
+// ---- glmcov.hip -------------------------------------------------------------------------
+// K = J(idx_a) P^-1 J(idx_b)^T for a block-diagonal Kronecker / diagonal posterior (lgnn_glm_covariance)
+int glm_covariance(lgnn_ctx* h, const int64_t* idx_a, int64_t Ma, const int64_t* idx_b, int64_t Mb, int n_blocks,
+                   const float* const* QA, const float* const* QB, const float* const* S, int flags, float* K, int64_t ldk,
+                   hipStream_t s);
 // Out_z[i * ldo + j * o_es] = sum_k A_z[i, k] B_z[j, k] for z < batch (A_z = A + z a_bs: [Ra, K] with row stride lda, B_z
 // likewise, Out_z = Out + z o_bs) on the fp32 matrix cores; no float atomics (split-K partials in ws.gp_part, added in order)
 struct NtProblem {
@@ -685,6 +696,7 @@ struct NtProblem {
   const float* B; int64_t ldb, b_bs;
   float* Out; int64_t ldo, o_es, o_bs;
   int64_t Ra, Rb, K, batch;
+  int upper_only = 0;  // Out_z is square and symmetric and the caller mirrors it: tiles strictly below the diagonal are skipped
 };
 int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s);
 // ---- ggnmat.hip -------------------------------------------------------------------------

@@ -349,6 +349,15 @@ class HipCurvatureInterface:
         writing the parameters (``lgnn_sampled_forward``): what laplace/baselaplace.py:1160-1199 loops over."""
         return self.engine.sampled_forward(x, theta, softmax=softmax)
 
+    def glm_covariance(self, xa: torch.Tensor, xb: torch.Tensor | None = None, *, QA, QB, S,
+                       from_jacobians: bool = False) -> torch.Tensor:
+        """``J(xa) P^-1 J(xb)^T`` [Ma C, Mb C] for a posterior that is block diagonal over the model's Linear layers -- what
+        ``functional_covariance`` contracts from explicit Jacobians (laplace/baselaplace.py:1638-1644, :1905-1910) -- as a
+        fresh tensor; ``xb=None``: the same nodes on both sides.  See ``GraphEngine.glm_covariance``."""
+        if self.last_layer or self._subnetwork_indices is not None:
+            raise NotImplementedError("glm_covariance serves posteriors over all weights (no last_layer, no subnetwork_indices)")
+        return self.engine.glm_covariance(xa, xb, QA=QA, QB=QB, S=S, from_jacobians=from_jacobians)
+
     def jacobians(self, x: torch.Tensor, enable_backprop: bool = False):
         """(Js [M, C, P], f [M, C]) as CurvatureInterface.jacobians (laplace/curvature/curvature.py:89-130); the
         M * C backward passes run as planes through the HIP engine (csrc/jacobian.hip).  No autograd graph."""

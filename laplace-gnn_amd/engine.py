@@ -1060,6 +1060,53 @@ class GraphEngine:
         _lib.check(rc, name)
         return f_mu, f_var
 
+    # -- joint GLM predictive (csrc/glmcov.hip) --------------------------------------------------------------------
+    def glm_covariance(self, idx_a: torch.Tensor, idx_b: torch.Tensor | None = None, *, QA, QB, S,
+                       from_jacobians: bool = False) -> torch.Tensor:
+        """``J(idx_a) P^-1 J(idx_b)^T`` [Ma C, Mb C] for a posterior that is block diagonal over the Linear layers
+        (``lgnn_glm_covariance``; see include/laplace_gnn_hip.h for the operands).  ``QA`` / ``QB`` / ``S``: one entry per block
+        in ``block_dims`` order -- ``S[l]`` [out_l, in_l + 1] inverse precisions (last column: the bias), ``QA[l]`` [in_l, in_l]
+        and ``QB[l]`` [out_l, out_l] eigenvectors in columns, or None / None for a diagonal block.  ``idx_b=None``: the same
+        tensor on both sides, and an exactly symmetric result.  No Jacobian is written where the model has a closed form;
+        ``from_jacobians`` forces the route over ``lgnn_jacobians`` rows."""
+        self._sync_versions()
+        same = idx_b is None or idx_b is idx_a
+        idx_a = idx_a.contiguous()
+        idx_b = idx_a if same else idx_b.contiguous()
+        nb = len(self.block_dims)
+        if not (len(QA) == len(QB) == len(S) == nb):
+            raise ValueError(f"QA, QB and S must have one entry per Linear layer ({nb}), got {len(QA)}, {len(QB)}, {len(S)}")
+        keep = []
+
+        def ptrs(ts, what, shape_of):
+            out = []
+            for l, t in enumerate(ts):
+                if t is None:
+                    out.append(None)
+                    continue
+                t = t.detach().to(self.device, torch.float32).contiguous()
+                if tuple(t.shape) != shape_of(l):
+                    raise ValueError(f"{what}[{l}] must be {shape_of(l)}, got {tuple(t.shape)}")
+                keep.append(t)
+                out.append(_dev_ptr(t, torch.float32, what).value)
+            return _lib.ptr_array(out)
+
+        qa = ptrs(QA, "QA", lambda l: (self.block_dims[l][0], self.block_dims[l][0]))
+        qb = ptrs(QB, "QB", lambda l: (self.block_dims[l][1], self.block_dims[l][1]))
+        sv = ptrs(S, "S", lambda l: (self.block_dims[l][1], self.block_dims[l][0] + 1))
+        Ma, Mb, C = idx_a.shape[0], idx_b.shape[0], self.dims[-1]
+        K = torch.empty(Ma * C, Mb * C, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lgnn_glm_covariance(self._h, _dev_ptr(idx_a, torch.int64, "idx_a"), Ma,
+                                                _dev_ptr(idx_b, torch.int64, "idx_b"), Mb, nb, qa, qb, sv,
+                                                _lib.COV_FROM_JACOBIANS if from_jacobians else 0, K.data_ptr(), Mb * C,
+                                                _stream(self.device)), "lgnn_glm_covariance")
+        del keep  # (enqueued on the current stream: the allocator hands the copies' memory out again in stream order)
+        return K
+
+    def glm_covariance_chunk_pairs(self) -> int:
+        """How many chunk pairs of the two index lists the last ``glm_covariance`` computed (chunks follow the workspace limit)."""
+        return int(self.lib.lgnn_glm_covariance_chunk_pairs(self._h))
+
     def check_async_errors(self):
         """Synchronise and raise if any batch since the last check contained an invalid node id or label."""
         _lib.check(self.lib.lgnn_check_async_errors(self._h, _stream(self.device)), "lgnn_check_async_errors")

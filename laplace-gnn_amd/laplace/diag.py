@@ -201,3 +201,20 @@ class DiagLaplace(ParametricLaplace):
 
     def functional_variance(self, Js):  # laplace/baselaplace.py:1901-1903
         return torch.einsum("ncp,p,nkp->nck", Js, 1.0 / self.posterior_precision, Js)
+
+    def _covariance_rows(self, J):  # laplace/baselaplace.py:1905-1910: einsum("np,p,mp->nm") one factor at a time
+        return J / self.posterior_precision
+
+    def _covariance_operands(self):
+        """Per Linear block ``S = 1 / precision`` of ``(W | b)``, no eigenbases."""
+        shapes = [tuple(p.shape) for p in self.params]
+        if len(shapes) % 2 or [len(sh) for sh in shapes] != [2, 1] * (len(shapes) // 2):
+            return None
+        inv = 1.0 / self.posterior_precision
+        o, S = 0, []
+        for out, din in shapes[::2]:
+            w = inv[o:o + out * din].view(out, din)
+            o += out * din
+            S.append(torch.cat([w, inv[o:o + out].view(out, 1)], dim=1))
+            o += out
+        return dict(QA=[None] * len(S), QB=[None] * len(S), S=S)

@@ -42,6 +42,9 @@ class FullLaplace(ParametricLaplace):
     def functional_variance(self, Js):  # :1488-1489
         return torch.einsum("ncp,pq,nkq->nck", Js, self.posterior_covariance, Js)
 
+    def _covariance_rows(self, J):  # :1491-1494: Js posterior_covariance Js^T, one factor at a time
+        return J @ self.posterior_covariance
+
     def _scale_samples(self, eps):  # :1497-1508: samples @ posterior_scale
         return eps @ self.posterior_scale
 
@@ -127,3 +130,6 @@ class FullLLLaplace(ParametricLaplace):
     def functional_variance(self, Js):  # laplace/lllaplace.py via FullLaplace.functional_variance (baselaplace.py:1488-1489)
         cov = torch.linalg.inv(self.posterior_precision.double()).float()  # (fp64 inverse: see FullLaplace.posterior_scale)
         return torch.einsum("ncp,pq,nkq->nck", Js, cov, Js)
+
+    def _covariance_rows(self, J):  # as FullLaplace (baselaplace.py:1491-1494) with the fp64 inverse above
+        return J @ torch.linalg.inv(self.posterior_precision.double()).float()

@@ -357,3 +357,40 @@ class KronLaplace(ParametricLaplace):
 
     def functional_variance(self, Js):  # laplace/baselaplace.py:1635-1636 (fp64 eigenpairs: see _eigh64)
         return self.posterior_precision_refined.inv_square_form(Js)
+
+    def _covariance_rows(self, J):  # the P^-1 W^T of inv_square_form (laplace/baselaplace.py:1638-1644, utils/matrix.py)
+        return self.posterior_precision_refined.bmm(J, exponent=-1)
+
+    def _covariance_operands(self):
+        """Per Linear block: ``QA`` / ``QB`` the refined eigenvectors of its factors, ``S = [1 / (f lB (x) lA + delta_W) |
+        1 / (f lB_b + delta_b)]``.  None under damping, and where a bias block's ``B`` factor is not a multiple of its weight
+        block's (the device rotates both with one ``Q_B``)."""
+        H = self._refined_decomposition()
+        if not isinstance(H, KronDecomposed) or H.damping or len(H.eigenvalues) % 2:
+            return None
+        nb = len(H.eigenvalues)
+        d = self._block_prior_precision(nb)
+        if d.numel() != nb:
+            return None
+        f = self._H_factor
+        QA, QB, S = [], [], []
+        for l in range(0, nb, 2):
+            if len(H.eigenvalues[l]) != 2 or len(H.eigenvalues[l + 1]) != 1:
+                return None
+            (lB, lA), (qB, qA) = H.eigenvalues[l], H.eigenvectors[l]
+            (lBb,), (qBb,) = H.eigenvalues[l + 1], H.eigenvectors[l + 1]
+            if not (qBb is qB or (qBb.shape == qB.shape and torch.equal(qBb, qB))):
+                # a multiple of the weight block's B (regression: sqrt(factor) there, factor here) has its eigenvectors up to
+                # the gauge: take Q_B if it diagonalises the bias block's factor to 1e-5 of its largest eigenvalue
+                if qBb.shape != qB.shape:
+                    return None
+                Q64 = self._eigh64(l, 0)[1]
+                D = Q64.T @ self.H_facs.kfacs[l + 1][0].double() @ Q64
+                lam = torch.diagonal(D)
+                if float((D - torch.diag(lam)).abs().max()) > 1e-5 * float(lam.abs().max()):
+                    return None
+                lBb = lam.clamp(min=0.0).float()
+            S.append(torch.cat([1.0 / (f * torch.outer(lB, lA) + d[l]), (1.0 / (f * lBb + d[l + 1])).unsqueeze(1)], dim=1))
+            QA.append(qA)
+            QB.append(qB)
+        return dict(QA=QA, QB=QB, S=S)

@@ -28,6 +28,9 @@ class _LastLayerHead:
     def _matrix_free_operands(self, out_map=None):
         return None  # (csrc/predictive.hip serves posteriors over all weights)
 
+    def _covariance_operands(self):
+        return None  # (csrc/glmcov.hip likewise: the joint predictive takes the head's explicit Jacobians)
+
     def neg_marglik_adj_grad(self, *args, **kwargs):
         raise NotImplementedError("adjacency gradient: posteriors over all weights (KronLaplace, DiagLaplace, FullLaplace)")
 
@@ -36,8 +39,11 @@ class _LastLayerHead:
 
     _LL_CHUNK_FLOATS = 1 << 27  # floats of a chunk's largest temporary ([M, C, C] covariances, [S, M, C] sampled logits)
 
-    def _glm_predictive_distribution(self, x, diagonal_output: bool = False):
-        """(f_mu [M, C], f_var [M, C, C] or its diagonal [M, C]) in closed form from the feature rows."""
+    def _glm_predictive_distribution(self, x, diagonal_output: bool = False, joint: bool = False):
+        """(f_mu [M, C], f_var [M, C, C] or its diagonal [M, C]) in closed form from the feature rows; ``joint``: the
+        cross-node covariance from the head's explicit Jacobians (``last_layer_jacobians``)."""
+        if joint:
+            return ParametricLaplace._glm_predictive_distribution(self, x, joint=True)
         C = self.n_outputs
         chunk = max(1, self._LL_CHUNK_FLOATS // max(C * C, self._head.weight.shape[1]))
         mus, fvars = [], []

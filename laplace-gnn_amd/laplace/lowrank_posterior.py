@@ -126,9 +126,12 @@ class LowRankLaplace(ParametricLaplace):
         return (torch.as_tensor(self.prior_precision).numel() == 1 and eng is not None and hasattr(eng, "jvp_block")
                 and len(eng.dims) in (2, 3) and not bool(getattr(eng, "has_extras", False)))
 
-    def _glm_predictive_distribution(self, x, diagonal_output: bool = False):
-        if not self._lowrank_matrix_free():
-            return super()._glm_predictive_distribution(x, diagonal_output=diagonal_output)
+    def _covariance_rows(self, J):  # the P^-1 J^T of functional_covariance (:1802-1810), transposed
+        return J / self.prior_precision_diag - ((J @ self.V) @ self.Kinv) @ self.V.T
+
+    def _glm_predictive_distribution(self, x, diagonal_output: bool = False, joint: bool = False):
+        if joint or not self._lowrank_matrix_free():
+            return super()._glm_predictive_distribution(x, diagonal_output=diagonal_output, joint=joint)
         be = self.backend
         prior = torch.as_tensor(self.prior_precision, dtype=torch.float32, device=self._device).reshape(())
         f_mu = be.engine.forward(x)

@@ -89,13 +89,15 @@ class _PredictiveMixin(_GLMLinkMixin):
     @torch.no_grad()
     def __call__(self, x, pred_type: str = "glm", link_approx: str = "probit", n_samples: int = 100,
                  diagonal_output: bool = False, generator: torch.Generator | None = None,
-                 eps: torch.Tensor | None = None, **kwargs):
-        """Posterior predictive (laplace/baselaplace.py:975-1072), classification.
+                 eps: torch.Tensor | None = None, joint: bool = False, **kwargs):
+        """Posterior predictive (laplace/baselaplace.py:975-1072).
 
         ``pred_type="glm"`` (default, with ``link_approx`` in probit / mc / bridge / bridge_norm): linearised model,
         ``f ~ N(f_mu, J P^-1 J^T)`` from explicit Jacobians (:1123-1158, :570-665).  ``pred_type="nn"`` with
         ``link_approx="mc"``: parameter samples, one forward each (:1183-1199).  ``eps`` replaces the random draws
-        (standard normal, [n_samples, n_params] for "nn", [n_outputs, n_samples] for "glm"/"mc")."""
+        (standard normal, [n_samples, n_params] for "nn", [n_outputs, n_samples] for "glm"/"mc").  ``joint=True`` (regression,
+        "glm"): the joint predictive over the evaluation nodes, ``(f_mu [M C], f_cov [M C, M C])`` (:618-625, :1123-1158);
+        classification does not read it (:618-620).  Other keyword arguments are accepted and ignored."""
         if pred_type not in ("glm", "nn"):
             raise ValueError("Only glm and nn supported as prediction types.")
         if link_approx not in ("mc", "probit", "bridge", "bridge_norm"):
@@ -105,6 +107,8 @@ class _PredictiveMixin(_GLMLinkMixin):
         x = x.to(self._device)
         regression = self.likelihood == "regression"
         if pred_type == "glm":
+            if regression and joint:  # N([f(x_1) .. f(x_M)], Cov): diagonal_output is not read (:622-625)
+                return self._glm_predictive_distribution(x, joint=True)
             if regression:  # (f_mu [M, C], f_var [M, C, C]) of the linearised model (:620-624)
                 f_mu, f_var = self._glm_predictive_distribution(x)
                 return f_mu, (torch.diagonal(f_var, dim1=-2, dim2=-1) if diagonal_output else f_var)
@@ -185,6 +189,78 @@ class _PredictiveMixin(_GLMLinkMixin):
     # ---- GLM predictive ("next" row 8(f)-3) ---------------------------------------------------------------------
     def functional_variance(self, Js: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
+
+    def _covariance_rows(self, J: torch.Tensor) -> torch.Tensor:
+        """``J P^-1`` [R, P] for rows ``J`` [R, P] of Jacobians: what the cross-node covariance multiplies with the other
+        side's rows."""
+        raise NotImplementedError
+
+    def functional_covariance(self, Js: torch.Tensor) -> torch.Tensor:
+        """``[M C, M C]`` joint covariance ``J P^-1 J^T`` of Jacobians ``Js`` [M, C, P] (laplace/baselaplace.py:1491-1494,
+        :1638-1644, :1905-1910), symmetrised (the two triangles differ in the last bit otherwise)."""
+        if Js.ndim != 3 or Js.shape[1:] != (self.n_outputs, self._n_params_posterior):
+            raise ValueError("Invalid Jacobians shape for Laplace posterior approx.")
+        J = Js.reshape(Js.shape[0] * Js.shape[1], Js.shape[2])
+        cov = self._covariance_rows(J) @ J.T
+        return 0.5 * (cov + cov.T)
+
+    def _covariance_operands(self):
+        """``dict(QA, QB, S)`` of ``GraphEngine.glm_covariance`` -- one entry per Linear block of the model -- for this
+        posterior, or None when the device route does not apply (the chunked Jacobian route in torch serves it then)."""
+        return None
+
+    def _glm_covariance_device(self, xa, xb):
+        """``J(xa) P^-1 J(xb)^T`` from ``lgnn_glm_covariance`` (csrc/glmcov.hip), or None: Kronecker and diagonal posteriors
+        over all weights, any model, either likelihood.  ``xb=None``: the same nodes on both sides."""
+        be = self.backend
+        eng = getattr(be, "engine", None)
+        if eng is None or not hasattr(be, "glm_covariance") or not hasattr(eng, "glm_covariance"):
+            return None
+        if getattr(be, "last_layer", False) or getattr(be, "subnetwork_indices", None) is not None:
+            return None
+        ops = self._covariance_operands()
+        if ops is None or len(ops["S"]) != len(eng.block_dims):
+            return None
+        return be.glm_covariance(xa, xb, **ops)
+
+    def _glm_covariance_jacobians(self, xa, xb):
+        """``(J(xa) P^-1 J(xb)^T, f(xa))`` from chunk pairs of the backend's Jacobians: three chunks of rows (one side, its
+        product with P^-1, the other side) stay under ``_JACOBIAN_BYTES_MAX``, so no ``[M, C, P]`` above it exists."""
+        C, P = self.n_outputs, self._n_params_posterior
+        same = xb is None
+        xb = xa if same else xb
+        Ma, Mb = int(xa.shape[0]), int(xb.shape[0])
+        chunk = max(1, self._JACOBIAN_BYTES_MAX // (3 * max(1, C * P * 4)))
+        K = torch.empty(Ma * C, Mb * C, device=self._device)
+        mus = []
+        for a0 in range(0, Ma, chunk):
+            Ja, f_mu = self.backend.jacobians(xa[a0:a0 + chunk], enable_backprop=False)
+            if Ja.shape[1:] != (C, P):
+                raise ValueError("Invalid Jacobians shape for Laplace posterior approx.")
+            mus.append(f_mu)
+            Ja = Ja.reshape(-1, P)
+            SJa = self._covariance_rows(Ja)
+            for b0 in range(a0 if same else 0, Mb, chunk):
+                if same and b0 == a0:
+                    blk = SJa @ Ja.T
+                    blk = 0.5 * (blk + blk.T)
+                else:
+                    blk = SJa @ self.backend.jacobians(xb[b0:b0 + chunk], enable_backprop=False)[0].reshape(-1, P).T
+                K[a0 * C:a0 * C + blk.shape[0], b0 * C:b0 * C + blk.shape[1]] = blk
+                if same and b0 != a0:
+                    K[b0 * C:b0 * C + blk.shape[1], a0 * C:a0 * C + blk.shape[0]] = blk.T
+            del Ja, SJa
+        return K, (mus[0] if len(mus) == 1 else torch.cat(mus))
+
+    @torch.no_grad()
+    def glm_covariance(self, x, x_other=None) -> torch.Tensor:
+        """``Cov[f(x), f(x_other)]`` [M C, M' C] of the linearised model, ``J(x) P^-1 J(x_other)^T``: the cross block between
+        two node lists (candidates against test nodes; the reference's ``functional_covariance`` only ever gives the square
+        block).  ``x_other=None``: the square block of ``x``, exactly symmetric.  Either likelihood."""
+        x = x.to(self._device)
+        x_other = None if x_other is None else x_other.to(self._device)
+        K = self._glm_covariance_device(x, x_other)
+        return K if K is not None else self._glm_covariance_jacobians(x, x_other)[0]
 
     def _matrix_free_operands(self, out_map=None):
         """Operands of ``GraphEngine.glm_variance`` for this posterior (mapped by ``out_map`` = E [Cm, C] where they depend on
@@ -268,9 +344,16 @@ class _PredictiveMixin(_GLMLinkMixin):
             covs.append(cov)
         return torch.cat(mus), torch.cat(covs)
 
-    def _glm_predictive_distribution(self, x, diagonal_output: bool = False):
+    def _glm_predictive_distribution(self, x, diagonal_output: bool = False, joint: bool = False):
         """(f_mu [M, C], f_var [M, C, C]) (laplace/baselaplace.py:1123-1158); ``diagonal_output``: f_var [M, C], matrix free
-        where the model family allows it."""
+        where the model family allows it; ``joint``: (f_mu [M C], f_cov [M C, M C]) over all evaluation nodes (:1145-1147),
+        on the device for Kronecker and diagonal posteriors over all weights."""
+        if joint:
+            f_cov = self._glm_covariance_device(x, None)
+            if f_cov is not None:
+                return self.backend.engine.forward(x).flatten(), f_cov
+            f_cov, f_mu = self._glm_covariance_jacobians(x, None)
+            return f_mu.flatten(), f_cov
         if diagonal_output:
             fast = self._glm_variance_matrix_free(x)
             if fast is not None:

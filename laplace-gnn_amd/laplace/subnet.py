@@ -86,6 +86,9 @@ class SubnetLaplace(ParametricLaplace):
     def _matrix_free_operands(self, out_map=None):
         return None  # the matrix-free predictive covers posteriors over all weights; here: Jacobian columns [M, C, S]
 
+    def _covariance_operands(self):
+        return None  # (likewise the joint predictive: chunk pairs of the selected columns)
+
     def state_dict(self) -> dict:
         state = super().state_dict()
         state["subnetwork_indices"] = self.subnetwork_indices
