@@ -178,11 +178,11 @@ int batch_cache_store_paths(lgnn_ctx* h, BatchEntry* e, int64_t cap, bool have_n
   LGNN_REQUIRE(cnt[1] >= 0 && int64_t(cnt[1]) <= std::max<int64_t>(h->nnz, 1) && cnt[2] >= 0 && cnt[2] <= N,
                "internal: path structure counts out of range");
   const size_t nr = size_t(cnt[1]), nn = size_t(cnt[2]);
-  size_t add = size_t(N + 1) * 4 + std::max<size_t>(np, 1) * 12;
+  size_t add = size_t(N + 2) * 4 + std::max<size_t>(np, 1) * 12;  // (pptr: N + 1 pointers and the list's wsum, paths.hip)
   add += size_t(N + 1) * 4 + std::max<size_t>(nr, 1) * 8;
   if (have_nodes) add += std::max<size_t>(nn, 1) * 4 + 4;
   bool ok = make_room(h, e, add, batch_cache_budget());
-  ok = ok && alloc_copy(e->pptr, ws.path_pptr.p, size_t(N + 1), s) == 0 && alloc_copy(e->pm, ws.path_pm.p, np, s) == 0 &&
+  ok = ok && alloc_copy(e->pptr, ws.path_pptr.p, size_t(N + 2), s) == 0 && alloc_copy(e->pm, ws.path_pm.p, np, s) == 0 &&
        alloc_copy(e->pv, ws.path_pv.p, np, s) == 0 && alloc_copy(e->pw, ws.path_pw.p, np, s) == 0;
   if (ok)
     ok = alloc_copy(e->rptr, ws.path_rptr.p, size_t(N + 1), s) == 0 && alloc_copy(e->r_m, ws.path_rm.p, nr, s) == 0 &&

@@ -152,6 +152,8 @@ struct Workspace {
   DevBuf path_alpha;  // GraphSAGE: the samples' alpha coefficients, class major [M][64] (weights of the one-hot paths)
   DevBuf path_pcnt, path_pptr, path_pm, path_pv, path_pw;  // the batch's paths per destination node (CSR over n)
   DevBuf path_flags, path_nodes, path_nnodes;              // nodes of the launch's range that have a path: flags, list, count
+  DevBuf path_scale, path_bgn;  // the fp16 Gram's PathScale block (paths.h) and the column-normalised copy of path_bg
+  DevBuf path_vsum;             // ... and, per row of the coefficient table, max_c sum_k |V[k, c]| of the row's seed block (bits)
   // the top layer's term lists (toppairs.hip): s_m [M]; per-node pair counts and their scan [N + 1]; the pairs (m, m', w w')
   DevBuf pair_s, pair_cnt, pair_ptr, pair_m, pair_m2, pair_w;
   DevBuf pair_part;  // top_pairs_kernel's partial sums, one row of upper tiles per workgroup
@@ -194,6 +196,7 @@ struct Workspace {
     f(act_list); f(act_count); f(select_tmp); f(flags); f(out_flags); f(out_list); f(out_count); f(val_act2);
     f(path_coef); f(path_up); f(path_bg); f(path_cnt); f(path_rptr); f(path_rm); f(path_rw); f(path_zeros); f(path_alpha);
     f(path_pcnt); f(path_pptr); f(path_pm); f(path_pv); f(path_pw); f(path_flags); f(path_nodes); f(path_nnodes);
+    f(path_scale); f(path_bgn); f(path_vsum);
     f(pair_s); f(pair_cnt); f(pair_ptr); f(pair_m); f(pair_m2); f(pair_w); f(pair_part);
     f(planes_c); f(adj_z0); f(adj_dir); f(lora_rows); f(lora_cols); f(lora_state); f(lora_count); f(lora_part);
     f(dense_stored); f(dense_rows);

@@ -35,10 +35,31 @@ struct YArgs {
   int unused_;              // (keeps the fields below at their kernel-argument offsets: hipcc merges the argument loads
                             //  by offset, and shifted by 4 bytes paths_fused_kernel spills more SGPRs)
   int no_bg;                // regression / nothing but the diagonal term: the beta / gamma products vanish
-  int gram_f32;             // LGNN_GRAM_F32: paths_fused_kernel's Gram on fp32 MFMAs instead of the bf16 pieces
+  int gram_f32;             // LGNN_GRAM_F32: paths_fused_kernel's Gram on fp32 MFMAs instead of the fp16 pieces
+  const float* scale;       // paths_fused_kernel: the launch's PathScale block (below); W1 and bg are its normalised copies then
 };
 // (the kernels take YArgs by value and hipcc merges the argument loads by offset, see unused_: the layout is part of the kernels)
-static_assert(sizeof(YArgs) == 240 && __builtin_offsetof(YArgs, no_bg) == 228, "YArgs: paths_fused_kernel's argument offsets");
+static_assert(sizeof(YArgs) == 248 && __builtin_offsetof(YArgs, no_bg) == 228, "YArgs: paths_fused_kernel's argument offsets");
+
+// What the fp16 Gram of paths_fused_kernel needs to know about the size of the tile values (floats; paths.hip fills it per
+// accumulate, on the stream).  Every term of Y[n][c, j] is linear in column j of W_1 (paths.hip's header), so column j is
+// NORMALISED by the power of two cn_j = 2^-floor(log2 max_c |W_1[c, j]|): the fused kernel reads W1n = W_1 diag(cn) and
+// bgn = bg diag(cn), builds Y diag(cn) with not one instruction more, and multiplies its Gram by 1 / (cn_i cn_j) at the flush.
+// All of it is exact (powers of two).  What is left is ONE bound per launch, from TWO triangle inequalities over a node's
+// paths (a mask bit is 0 or 1), one over a path's three terms, one over the rows k of the sample's seed block
+// V[k, c] = alpha_c d_kc - beta_c u_k - gamma_c p_k, of which a path's vector is V[:, c]^T W_1:
+//     |Y[n][c, j]| cn_j <= wsum * min(tri, vmax * w1max),     tri = amax * w1max + bgmax,
+//   wsum  = max_n sum_paths |w|                  (where the path list is built: the float behind pptr[N], see path_list_reserve)
+//   amax  = max_m max_c |alpha_c^m|,   w1max = max |W_1 diag(cn)| (< 2; GraphSAGE: both halves of W_1),
+//   bgmax = max_m (max_c |beta_c^m| max_j |bgn_b[m, j]| + max_c |gamma_c^m| max_j |bgn_g[m, j]|),
+//   vmax  = max_m max_c sum_k |V_m[k, c]|        (the tables kernels, per sample).
+// The second sees what the first cannot: where the softmax is sure of its class the three terms cancel (V is zero for a
+// one-hot p) and a tile value is rounding noise far below `tri`.  The fused kernel's fp32 sums carry that noise whatever the
+// exact value is, so the bound it scales by is  wsum * (min(tri, vmax * w1max) + 2^-12 tri):  2^-12 covers 4 096 terms of
+// 2^-24 relative error each, all of one sign.  The maxima are taken on the bit patterns of |x| (unsigned order = numeric
+// order, and a NaN is above everything): a non-finite operand gives a non-finite bound, and such a launch runs the fp32 role.
+constexpr int kScaleCn = 4, kScaleCinv = kScaleCn + 256, kScaleW1 = kScaleCinv + 256;  // offsets: cn [256], 1 / cn [256], W1n [C][H]
+// ([0] amax, [1] w1max, [2] bgmax, [3] vmax as bit patterns)
 
 // R, the path list and the node list of a batch as the launches below read them: the workspace's or a cache entry's
 struct PathLists {

@@ -28,6 +28,22 @@ namespace lgnn {
 
 namespace {
 
+// max_c sum_k |V[k, c]| of a sample's seed block V[k, c] = alpha_c d_kc - beta_c u_k - gamma_c p_k, as a bit pattern (a NaN is above
+// everything): what PathScale's vmax is the largest of (paths.h).  Lane c holds (alpha, beta, gamma)_c (zeros past C), lane k
+// holds u_k and p_k; every lane of the wave takes part.
+__device__ __forceinline__ uint32_t seed_column_sum_max(float al, float be, float ga, float u, float p, int C, int lane) {
+  float vs = 0.f;
+  for (int k = 0; k < C; ++k) {
+    const float uk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), k));
+    const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), k));
+    vs += fabsf((lane == k ? al : 0.f) - be * uk - ga * pk);
+  }
+  uint32_t b = __float_as_uint(vs) & 0x7fffffffu;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) b = max(b, uint32_t(__shfl_xor(int(b), o)));
+  return b;
+}
+
 // One wave per batch sample (first occurrences only; a node listed t times carries t in its R weights).
 // mode: 0 upstream seeds, 1 fork exact, 2 regression (V = sqrt(2) I).  The coefficient row holds the classes [cb, cb + 64) of the
 // call in slot order (coef_slot); slots of classes >= ce are zero.
@@ -35,7 +51,8 @@ __global__ __launch_bounds__(256) void path_tables_kernel(const float* __restric
                                                           const int64_t* __restrict__ idx, const int32_t* __restrict__ pos,
                                                           int64_t M, int64_t N, int C, int cb, int ce, int mode,
                                                           float* __restrict__ coef, float* __restrict__ up,
-                                                          const float* __restrict__ W1, int H, float* __restrict__ bg) {
+                                                          const float* __restrict__ W1, int H, float* __restrict__ bg,
+                                                          uint32_t* __restrict__ vsum) {
   const int lane = threadIdx.x & 63;
   const int64_t m = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -65,6 +82,10 @@ __global__ __launch_bounds__(256) void path_tables_kernel(const float* __restric
   cm[2 * kCoefStride + lane] = have ? -sga : 0.f;
   cm[3 * kCoefStride + lane] = 0.f;
   if (lane < C) { um[lane] = u; pm[lane] = own ? pk : 0.f; }
+  {  // (one entry per row of the coefficient table)
+    const uint32_t vb = seed_column_sum_max(al, be, ga, u, own ? pk : 0.f, C, lane);
+    if (lane == 0) vsum[m] = vb;
+  }
   // b_m = u_m^T W_1 and g_m = p_m^T W_1 (rows m and M + m of bg [2 M, H]; null: not wanted): u and p sit in the wave's lanes,
   // the C rows of W_1 (L2 resident) are read 16 bytes per lane -- four columns of both products per lane
   if (bg == nullptr) return;
@@ -112,6 +133,18 @@ __global__ __launch_bounds__(256) void path_r_kernel(const int64_t* __restrict__
   }
 }
 
+// *m = max(*m, bits).  Tens of thousands of waves meet on one word, and atomics on one address run one after the other (a
+// full arxiv batch: 0.37 ms for 20 000 of them): the value only grows, so a wave that reads a value no smaller than its own
+// has nothing to add, and almost none of them gets as far as the atomic.
+__device__ __forceinline__ void atomic_max_bits(uint32_t* m, uint32_t bits) {
+  if (bits > *reinterpret_cast<volatile uint32_t*>(m)) atomicMax(m, bits);
+}
+// *wsum = max(*wsum, the wave's sum of `wabs`) on the bit patterns (wabs >= 0 or NaN: PathScale in paths.h)
+__device__ __forceinline__ void path_wsum_max(float wabs, int lane, uint32_t* __restrict__ wsum) {
+  const uint32_t bits = __float_as_uint(wave_sum(wabs)) & 0x7fffffffu;
+  if (lane == 0) atomic_max_bits(wsum, bits);
+}
+
 // The batch's 2-hop paths per destination node, materialised once per batch (count, rocPRIM scan, fill): the irregular
 // three-level walk (row of P^T -> R pointers -> R entries) runs here with one wave per node and tens of thousands of waves
 // in flight, so that ybuild_kernel's own chain is just  pointer -> entries -> table rows.
@@ -123,7 +156,7 @@ __global__ __launch_bounds__(256) void path_list_kernel(const int32_t* __restric
                                                         const float* __restrict__ r_w, int32_t* __restrict__ pcnt,
                                                         const int32_t* __restrict__ pptr, int64_t cap,
                                                         int32_t* __restrict__ pm, int32_t* __restrict__ pv,
-                                                        float* __restrict__ pw) {
+                                                        float* __restrict__ pw, uint32_t* __restrict__ wsum) {
   const int lane = threadIdx.x & 63;
   const int64_t n = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -132,6 +165,7 @@ __global__ __launch_bounds__(256) void path_list_kernel(const int32_t* __restric
   }
   const int32_t s = rowptr[n], e = rowptr[n + 1];
   int32_t run = FILL ? pptr[n] : 0;
+  float wabs = 0.f;  // FILL: the lane's share of sum_paths |w| of this node (PathScale's wsum)
   for (int32_t base = s; base < e; base += 64) {
     int32_t v = 0, r0 = 0, cnt = 0;
     float pval = 0.f;
@@ -153,11 +187,13 @@ __global__ __launch_bounds__(256) void path_list_kernel(const int32_t* __restric
         pm[off + k] = r_m[r0 + k];
         pv[off + k] = v;
         pw[off + k] = pval * r_w[r0 + k];
+        wabs += fabsf(pval * r_w[r0 + k]);
       }
     }
     run += __shfl(incl, 63);
   }
   if (!FILL && lane == 0) pcnt[n] = run;
+  if constexpr (FILL) path_wsum_max(wabs, lane, wsum);
 }
 
 // ---- GraphSAGE: the same fused kernel over ONE-hop paths ----------------------------------------------------------------
@@ -175,7 +211,7 @@ __global__ __launch_bounds__(256) void sage_path_tables_kernel(const float* __re
                                                                const int64_t* __restrict__ idx, const int32_t* __restrict__ pos,
                                                                int64_t M, int64_t N, int C, int cb, int ce, int mode,
                                                                float* __restrict__ coef, float* __restrict__ up,
-                                                               float* __restrict__ alpha) {
+                                                               float* __restrict__ alpha, uint32_t* __restrict__ vsum) {
   const int lane = threadIdx.x & 63;
   const int64_t m = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (m >= M + C) return;
@@ -184,6 +220,7 @@ __global__ __launch_bounds__(256) void sage_path_tables_kernel(const float* __re
   if (m >= M) {  // the one-hot rows
     float* __restrict__ cm = coef + (2 * M + (m - M)) * kCoefRow;
     cm[lane] = 0.f; cm[kCoefStride + lane] = (have && c == int(m - M)) ? 1.f : 0.f; cm[2 * kCoefStride + lane] = 0.f; cm[3 * kCoefStride + lane] = 0.f;
+    if (lane == 0) vsum[2 * M + (m - M)] = 0u;
     return;
   }
   const int64_t n = idx[m];
@@ -207,6 +244,9 @@ __global__ __launch_bounds__(256) void sage_path_tables_kernel(const float* __re
   cn[lane] = sal; cn[kCoefStride + lane] = -sbe; cn[2 * kCoefStride + lane] = -sga; cn[3 * kCoefStride + lane] = 0.f;
   alpha[m * kCoefStride + lane] = al;  // class major: the weights of the one-hot alpha paths (sage_path_list_kernel)
   if (lane < C) { up[m * C + lane] = u; up[(M + m) * C + lane] = own ? pk : 0.f; }
+  // (per row of the coefficient table; the sample's seed block stands at its neighbour row: its self term has the same block)
+  const uint32_t vb = seed_column_sum_max(al, be, ga, u, own ? pk : 0.f, C, lane);
+  if (lane == 0) { vsum[2 * m] = 0u; vsum[2 * m + 1] = vb; }
 }
 
 // One wave per node n: its paths (see above).  Row n of P^T lists the samples' nodes v with P[v, n] != 0.
@@ -216,12 +256,14 @@ __global__ __launch_bounds__(256) void sage_path_list_kernel(const int32_t* __re
                                                              const int32_t* __restrict__ pos, const int32_t* __restrict__ mult,
                                                              const float* __restrict__ alpha, int32_t* __restrict__ pcnt,
                                                              const int32_t* __restrict__ pptr, int32_t* __restrict__ pm,
-                                                             int32_t* __restrict__ pv, float* __restrict__ pw) {
+                                                             int32_t* __restrict__ pv, float* __restrict__ pw,
+                                                             uint32_t* __restrict__ wsum) {
   const int lane = threadIdx.x & 63;
   const int64_t n = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
   const int32_t s = rowptr[n], e = rowptr[n + 1];
   int32_t run = FILL ? pptr[n] : 0;
+  float wabs = 0.f;  // (as in path_list_kernel)
   for (int32_t base = s; base < e; base += 64) {
     int32_t mv = INT32_MAX;
     float w = 0.f;
@@ -232,6 +274,7 @@ __global__ __launch_bounds__(256) void sage_path_list_kernel(const int32_t* __re
       if (in) {
         const int32_t o = run + __popcll(bal & ((uint64_t(1) << lane) - 1));
         pm[o] = 2 * mv + 1; pv[o] = int32_t(n); pw[o] = w * float(mult[mv]);
+        wabs += fabsf(w * float(mult[mv]));
       }
     }
     run += __popcll(bal);
@@ -240,15 +283,108 @@ __global__ __launch_bounds__(256) void sage_path_list_kernel(const int32_t* __re
   if (ms != INT32_MAX) {  // n is a batch node: its own beta / gamma path and the C one-hot alpha paths
     if constexpr (FILL) {
       const float tm = float(mult[ms]);
-      if (lane == 0) { pm[run] = 2 * ms; pv[run] = int32_t(n); pw[run] = tm; }
+      if (lane == 0) { pm[run] = 2 * ms; pv[run] = int32_t(n); pw[run] = tm; wabs += tm; }
       if (lane < C) {
         pm[run + 1 + lane] = int32_t(2 * M) + lane; pv[run + 1 + lane] = int32_t(n);
         pw[run + 1 + lane] = tm * alpha[int64_t(ms) * kCoefStride + lane];
+        wabs += fabsf(tm * alpha[int64_t(ms) * kCoefStride + lane]);
       }
     }
     run += 1 + C;
   }
   if (!FILL && lane == 0) pcnt[n] = run;
+  if constexpr (FILL) path_wsum_max(wabs, lane, wsum);
+}
+
+// ---- the scale of the fused kernel's fp16 Gram (PathScale in paths.h) -----------------------------------------------------
+// One workgroup of 256 threads, thread j = column j: cn_j and 1 / cn_j from the largest |W_1[c, j]| over the C rows of W1a (the
+// fused kernel's W_1 operand) and, GraphSAGE, of W1b (the self half, which reaches Y through the table rows of the one-hot
+// paths); the normalised copy W1n = W1a diag(cn) and the largest normalised entry of both; the launch's maxima start at zero here.
+__global__ __launch_bounds__(256) void path_colscale_kernel(const float* __restrict__ W1a, const float* __restrict__ W1b, int ld,
+                                                            int C, int H, float* __restrict__ sc) {
+  const int j = threadIdx.x;
+  uint32_t* __restrict__ bits = reinterpret_cast<uint32_t*>(sc);
+  if (j < 4) bits[j] = 0u;
+  __syncthreads();
+  // the column's entries in registers (C <= kCoefStride; unrolled, so that the loads are in flight together: one workgroup
+  // walking the rows one dependent load at a time took 19 us, latency and nothing else)
+  float va[kCoefStride], vb[kCoefStride];
+#pragma unroll
+  for (int c = 0; c < kCoefStride; ++c) {
+    const bool in = j < H && c < C;
+    va[c] = in ? W1a[int64_t(c) * ld + j] : 0.f;
+    vb[c] = in && W1b ? W1b[int64_t(c) * ld + j] : 0.f;
+  }
+  uint32_t mx = 0u;
+#pragma unroll
+  for (int c = 0; c < kCoefStride; ++c)
+    mx = max(mx, max(__float_as_uint(va[c]) & 0x7fffffffu, __float_as_uint(vb[c]) & 0x7fffffffu));
+  // cn = 2^(127 - eb) for the biased exponent eb of the column's maximum, kept inside fp32's normal range together with its
+  // inverse; a column of zeros (or of subnormals: its squares vanish in fp32) stays as it is
+  const uint32_t eb = mx >> 23, k = eb == 0u ? 127u : min(max(eb, 1u), 253u);
+  const float cn = __uint_as_float((254u - k) << 23);
+  sc[kScaleCn + j] = cn;
+  sc[kScaleCinv + j] = __uint_as_float(k << 23);
+  uint32_t wm = 0u;
+#pragma unroll
+  for (int c = 0; c < kCoefStride; ++c) {
+    const float v = va[c] * cn;
+    if (j < H && c < C) sc[kScaleW1 + int64_t(c) * H + j] = v;
+    wm = max(wm, max(__float_as_uint(v) & 0x7fffffffu, __float_as_uint(vb[c] * cn) & 0x7fffffffu));
+  }
+  if (wm) atomicMax(&bits[1], wm);
+}
+// A wave per row r of the coefficient table at a time (a sample; GraphSAGE: a sample index): its largest |alpha|, |beta|,
+// |gamma| over the 64 class slots (16 lanes per kind, 16 bytes per lane), its rows b_r, g_r of the table times cn -- written to
+// bgn, which the fused kernel reads in the table's place -- and their largest entries; the row's entry of `vsum`.  The waves
+// stride over the rows and keep their maxima in registers; a workgroup ends in three atomics at most.  bg == nullptr (regression): no beta / gamma term.
+__global__ __launch_bounds__(256) void path_bound_kernel(const float* __restrict__ coef, int64_t rows, const float* __restrict__ bg,
+                                                         float* __restrict__ bgn, int H, const uint32_t* __restrict__ vsum,
+                                                         float* __restrict__ sc) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t amax = 0u, xmax = 0u, vmax = 0u;
+  f32x4 cn = {0.f, 0.f, 0.f, 0.f};
+  if (4 * lane < H) cn = *reinterpret_cast<const f32x4*>(sc + kScaleCn + 4 * lane);
+  for (int64_t r = int64_t(blockIdx.x) * 4 + wave; r < rows; r += int64_t(gridDim.x) * 4) {
+    const f32x4 cf = *reinterpret_cast<const f32x4*>(coef + r * kCoefRow + 4 * lane);
+    uint32_t km = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) km = max(km, __float_as_uint(cf[q]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) km = max(km, uint32_t(__shfl_xor(int(km), o)));  // (within the kind's 16 lanes)
+    amax = max(amax, uint32_t(__shfl(int(km), 0)));
+    vmax = max(vmax, vsum[r]);
+    if (bg == nullptr) continue;
+    const float be = __uint_as_float(uint32_t(__shfl(int(km), 16))), ga = __uint_as_float(uint32_t(__shfl(int(km), 32)));
+    uint32_t bm = 0u, gm = 0u;
+    if (4 * lane < H) {
+      const f32x4 b4 = *reinterpret_cast<const f32x4*>(bg + r * H + 4 * lane) * cn;
+      const f32x4 g4 = *reinterpret_cast<const f32x4*>(bg + (rows + r) * H + 4 * lane) * cn;
+      *reinterpret_cast<f32x4*>(bgn + r * H + 4 * lane) = b4;
+      *reinterpret_cast<f32x4*>(bgn + (rows + r) * H + 4 * lane) = g4;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bm = max(bm, __float_as_uint(b4[q]) & 0x7fffffffu);
+        gm = max(gm, __float_as_uint(g4[q]) & 0x7fffffffu);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      bm = max(bm, uint32_t(__shfl_xor(int(bm), o)));
+      gm = max(gm, uint32_t(__shfl_xor(int(gm), o)));
+    }
+    // (0 * inf is NaN: a non-finite operand stays visible whatever it meets)
+    xmax = max(xmax, __float_as_uint(be * __uint_as_float(bm) + ga * __uint_as_float(gm)) & 0x7fffffffu);
+  }
+  __shared__ uint32_t red[3][4];
+  if (lane == 0) { red[0][wave] = amax; red[1][wave] = xmax; red[2][wave] = vmax; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    uint32_t* __restrict__ bits = reinterpret_cast<uint32_t*>(sc);
+    const uint32_t* v = red[threadIdx.x];
+    const int slot = threadIdx.x == 0 ? 0 : int(threadIdx.x) + 1;  // [0] amax, [2] bgmax, [3] vmax
+    atomic_max_bits(&bits[slot], max(max(v[0], v[1]), max(v[2], v[3])));
+  }
 }
 
 __global__ void path_flag_kernel(const int32_t* __restrict__ pptr, int64_t n0, int64_t n, uint8_t* __restrict__ flags) {
@@ -355,15 +491,19 @@ static int path_node_list(lgnn_ctx* h, PathLists& pl, int64_t nb, int64_t ne, hi
   pl.nodes = ws.path_nodes.as<int32_t>(); pl.nnodes = ws.path_nnodes.as<int32_t>();
   return compact_flags(ws.path_flags.as<uint8_t>(), n, ws.path_nodes.as<int32_t>(), ws.path_nnodes.as<int32_t>(), ws.select_tmp, s);
 }
-// The workspace's buffers of a path list of at most `cap` entries (`pl` points at them); pcnt[N] = 0, the scan's last input
+// The workspace's buffers of a path list of at most `cap` entries (`pl` points at them); pcnt[N] = 0, the scan's last input.
+// (A list that overflows `cap` is not filled and keeps wsum = 0: the fused kernel returns at once on it anyway.)
 static int path_list_reserve(lgnn_ctx* h, int64_t cap, PathLists& pl, hipStream_t s) {
   Workspace& ws = h->ws;
   LGNN_CALL(ws.path_pcnt.reserve(size_t(h->N + 1) * 4));
-  LGNN_CALL(ws.path_pptr.reserve(size_t(h->N + 1) * 4));
+  LGNN_CALL(ws.path_pptr.reserve(size_t(h->N + 2) * 4));  // (N + 1 pointers and the list's wsum, see below)
   LGNN_CALL(ws.path_pm.reserve(size_t(cap) * 4));
   LGNN_CALL(ws.path_pv.reserve(size_t(cap) * 4));
   LGNN_CALL(ws.path_pw.reserve(size_t(cap) * 4));
   LGNN_HIP_CHECK(hipMemsetAsync(ws.path_pcnt.as<int32_t>() + h->N, 0, 4, s));
+  // max_n sum_paths |w| of the list (PathScale in paths.h) is part of the list: the filling kernel leaves its bit pattern in
+  // the word behind the N + 1 pointers, and a cache entry's copy of pptr takes it along
+  LGNN_HIP_CHECK(hipMemsetAsync(ws.path_pptr.as<int32_t>() + h->N + 1, 0, 4, s));
   pl.pptr = ws.path_pptr.as<int32_t>(); pl.pm = ws.path_pm.as<int32_t>(); pl.pv = ws.path_pv.as<int32_t>();
   pl.pw = ws.path_pw.as<float>();
   return 0;
@@ -388,6 +528,25 @@ static YArgs path_args(lgnn_ctx* h, const PathLists& pl, int64_t cb, int64_t cap
   return y;
 }
 
+// The fused kernel's launch arguments from the batch's: the PathScale block of this accumulate (paths.h) and the normalised
+// copies of W_1 and the b / g table in ws.path_scale / ws.path_bgn, two small launches on the stream.  W1b: GraphSAGE's self half.
+static int path_scale_args(lgnn_ctx* h, YArgs& y, const float* W1b, int ld, hipStream_t s) {
+  Workspace& ws = h->ws;
+  const int64_t C = h->dims[2], H = y.H, rows = y.n_coef;
+  LGNN_CALL(ws.path_scale.reserve(size_t(kScaleW1 + C * H) * 4));
+  if (!y.no_bg) LGNN_CALL(ws.path_bgn.reserve(size_t(2 * rows) * H * 4));
+  float* sc = ws.path_scale.as<float>();
+  hipLaunchKernelGGL(path_colscale_kernel, dim3(1), dim3(256), 0, s, y.W1, W1b, ld, int(C), int(H), sc);
+  LGNN_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(path_bound_kernel, dim3(unsigned(std::min<int64_t>(cdiv(rows, 4), 1024))), dim3(256), 0, s, y.coef, rows,
+                     y.no_bg ? static_cast<const float*>(nullptr) : y.bg, ws.path_bgn.as<float>(), int(H),
+                     ws.path_vsum.as<uint32_t>(), sc);
+  LGNN_HIP_CHECK(hipGetLastError());
+  y.scale = sc; y.W1 = sc + kScaleW1; y.w1_ld = int(H);
+  if (!y.no_bg) y.bg = ws.path_bgn.as<float>();
+  return 0;
+}
+
 // B_0 scratch += sum over the class columns [cb, ce) of this batch (see the file header).  Needs batch_prologue's
 // probabilities / multiplicities / positions and the cached forward (logits, mask bits).
 int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_mode, int64_t cb, int64_t ce, float* scratch,
@@ -402,6 +561,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
   LGNN_CALL(ws.path_coef.reserve(size_t(M) * kCoefRow * 4));
   LGNN_CALL(ws.path_up.reserve(size_t(2 * M) * C * 4));
   LGNN_CALL(ws.path_bg.reserve(size_t(2 * M) * H * 4));
+  LGNN_CALL(ws.path_vsum.reserve(size_t(M) * 4));
   // the wave that owns a sample also forms its rows b_m, g_m of the [2 M, H] table (16-byte loads of W_1's rows: a weight tensor
   // that is not 16-byte aligned takes the small GEMM instead)
   const bool no_bg = seed_mode == 2;
@@ -409,7 +569,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
   hipLaunchKernelGGL(path_tables_kernel, dim3(unsigned(cdiv(M, 4))), dim3(256), 0, s, ws.probs.as<float>(),
                      h->fc.out.as<float>(), idx, ws.pos.as<int32_t>(), M, N, int(C), int(cb), int(ce), seed_mode,
                      ws.path_coef.as<float>(), ws.path_up.as<float>(), h->W[1], int(H),
-                     bg_in_tables ? ws.path_bg.as<float>() : static_cast<float*>(nullptr));
+                     bg_in_tables ? ws.path_bg.as<float>() : static_cast<float*>(nullptr), ws.path_vsum.as<uint32_t>());
   LGNN_HIP_CHECK(hipGetLastError());
   if (!no_bg && !bg_in_tables) {
     GemmEpilogue none;
@@ -459,12 +619,13 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     hipLaunchKernelGGL(path_list_kernel<false>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N,
                        ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>(), ws.path_pcnt.as<int32_t>(),
                        static_cast<const int32_t*>(nullptr), cap, static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                       static_cast<float*>(nullptr));
+                       static_cast<float*>(nullptr), static_cast<uint32_t*>(nullptr));
     LGNN_HIP_CHECK(hipGetLastError());
     LGNN_CALL(exclusive_scan_i32(ws.path_pcnt.as<int32_t>(), ws.path_pptr.as<int32_t>(), N + 1, ws.select_tmp, s));
     hipLaunchKernelGGL(path_list_kernel<true>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N,
                        ws.path_rptr.as<int32_t>(), ws.path_rm.as<int32_t>(), ws.path_rw.as<float>(), ws.path_pcnt.as<int32_t>(),
-                       ws.path_pptr.as<int32_t>(), cap, ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>());
+                       ws.path_pptr.as<int32_t>(), cap, ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>(),
+                       ws.path_pptr.as<uint32_t>() + N + 1);
     LGNN_HIP_CHECK(hipGetLastError());
     pl.rptr = ws.path_rptr.as<int32_t>(); pl.r_m = ws.path_rm.as<int32_t>(); pl.r_w = ws.path_rw.as<float>();
   }
@@ -495,7 +656,9 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
   }
   YArgs y = path_args(h, pl, cb, cap, nb, ne);
   y.W1 = h->W[1]; y.w1_ld = int(H); y.M = M; y.n_coef = M; y.no_bg = no_bg ? 1 : 0;
-  LGNN_CALL(launch_paths_fused(h, y, cb, ce, scratch, s));
+  YArgs yf = y;  // (the overflow route keeps W_1 and the table as they are)
+  LGNN_CALL(path_scale_args(h, yf, nullptr, int(H), s));
+  LGNN_CALL(launch_paths_fused(h, yf, cb, ce, scratch, s));
   return can_overflow ? launch_paths_overflow(h, y, cb, ce, scratch, s) : 0;
 }
 
@@ -514,9 +677,10 @@ int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int 
   LGNN_CALL(ws.path_up.reserve(size_t(2 * M) * C * 4));
   LGNN_CALL(ws.path_bg.reserve(size_t(2 * T) * H * 4));
   LGNN_CALL(ws.path_alpha.reserve(size_t(M) * kCoefStride * 4));
+  LGNN_CALL(ws.path_vsum.reserve(size_t(T) * 4));
   hipLaunchKernelGGL(sage_path_tables_kernel, dim3(unsigned(cdiv(M + C, 4))), dim3(256), 0, s, ws.probs.as<float>(),
                      h->fc.out.as<float>(), idx, ws.pos.as<int32_t>(), M, N, int(C), int(cb), int(ce), seed_mode,
-                     ws.path_coef.as<float>(), ws.path_up.as<float>(), ws.path_alpha.as<float>());
+                     ws.path_coef.as<float>(), ws.path_up.as<float>(), ws.path_alpha.as<float>(), ws.path_vsum.as<uint32_t>());
   LGNN_HIP_CHECK(hipGetLastError());
   // b rows [0, T): u^T [W_1s | W_1n] as rows (2 m, 2 m + 1), then W_1s[c', :]; g rows [T, 2 T): p^T [W_1s | W_1n], then zeros
   float* bg = ws.path_bg.as<float>();
@@ -536,17 +700,19 @@ int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int 
   hipLaunchKernelGGL(sage_path_list_kernel<false>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N, M, int(C),
                      ws.pos.as<int32_t>(), ws.mult.as<int32_t>(), ws.path_alpha.as<float>(), ws.path_pcnt.as<int32_t>(),
                      static_cast<const int32_t*>(nullptr), static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                     static_cast<float*>(nullptr));
+                     static_cast<float*>(nullptr), static_cast<uint32_t*>(nullptr));
   LGNN_HIP_CHECK(hipGetLastError());
   LGNN_CALL(exclusive_scan_i32(ws.path_pcnt.as<int32_t>(), ws.path_pptr.as<int32_t>(), N + 1, ws.select_tmp, s));
   hipLaunchKernelGGL(sage_path_list_kernel<true>, pgrid, dim3(256), 0, s, h->PT.rowptr, h->PT.col, h->PT.val, N, M, int(C),
                      ws.pos.as<int32_t>(), ws.mult.as<int32_t>(), ws.path_alpha.as<float>(), ws.path_pcnt.as<int32_t>(),
-                     ws.path_pptr.as<int32_t>(), ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>());
+                     ws.path_pptr.as<int32_t>(), ws.path_pm.as<int32_t>(), ws.path_pv.as<int32_t>(), ws.path_pw.as<float>(),
+                     ws.path_pptr.as<uint32_t>() + N + 1);
   LGNN_HIP_CHECK(hipGetLastError());
   LGNN_CALL(path_node_list(h, pl, nb, ne, s));
   YArgs y = path_args(h, pl, cb, cap, nb, ne);
   y.W1 = h->W[1] + H; y.w1_ld = int(2 * H);  // the neighbour half: the alpha term of the neighbour paths
   y.M = T; y.n_coef = T; y.no_bg = 0;        // (the one-hot alpha paths go through the beta product: never skipped)
+  LGNN_CALL(path_scale_args(h, y, h->W[1], int(2 * H), s));
   return launch_paths_fused(h, y, cb, ce, scratch, s);
 }
 

@@ -13,12 +13,14 @@
 //       coefficient goes in as three bf16 pieces along K, see PAlpha).  No LDS staging, no window, no restaging of hubs: the
 //       operands of step s + 1 are in flight while the MFMAs of step s issue, across node boundaries (a node's triples
 //       (m, v, w) arrive with ONE coalesced load a node ahead and are handed to the lanes with ds_bpermute).
-//       Y[n] = W_1 (.) T1 + Y2 (W_1's rows straight from L2) is split into three bf16 pieces HERE, once per value, and the
-//       pieces go to one of TWO LDS tiles (FusedShared; 18 16-byte stores per node) -- under LGNN_GRAM_F32 the fp32 values.
+//       Y[n] = W_1 (.) T1 + Y2 (W_1's rows straight from L2) comes out SCALED -- its columns by the powers of two that W_1 and
+//       the b / g table carry (PathScale in paths.h), all of it by the launch's s, which rides on the path weights (GramScale)
+//       -- and is split into two fp16 pieces HERE, once per value; the pieces go to one of TWO LDS tiles (FusedShared; 18
+//       16-byte stores per node: h1 goes out twice) -- under LGNN_GRAM_F32, or without a usable scale, the fp32 values.
 //   waves 4 .. 7, the GRAM waves: S += Y[n - 1]^T Y[n - 1] from the other tile into register-resident upper-triangular
 //       accumulators (the 36 sub-tiles of gram256.h, 9 per wave, as 34 tiles of 16 x 16: 136 accumulator registers), nothing
-//       else: their loop is LDS reads and MFMAs -- v_mfma_f32_16x16x32_bf16 on the pieces, 16 cycles each, so that a product
-//       wave's MFMA waits 16 cycles for this wave's turn on the pipe, not 32 (gram_split16_role).
+//       else: their loop is LDS reads and MFMAs -- v_mfma_f32_16x16x32_f16 on the pieces, 16 cycles each and two per 16 tile
+//       rows, so that a product wave's MFMA waits 16 cycles for this wave's turn on the pipe, not 32 (gram_f16_role).
 // ONE hand-off per node (LDS counters).  The product wave of a SIMD needs the matrix pipe for about a third of a node's cycles
 // and sleeps on memory part of the rest; the Gram wave is a dense MFMA stream that takes every slot the product wave leaves: the
 // two phases that round 3 ran back to back in every wave (7.7 ms per arxiv batch, matrix pipes 57 % busy) now overlap.
@@ -30,15 +32,22 @@ namespace {
 
 constexpr int kYStride = 272;  // floats per row of the fp32 tile: 256 + 16, so that the four rows of a Gram operand read (lanes
                                // 16 k .. 16 k + 15 read row k0 + k) fall on disjoint banks
-// The tile as bf16 PIECES (the default Gram role): a tile value y is y0 + y1 + y2, y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y -
-// y0 - y1) (see gram_split16_role).  A dword holds the same piece of two tile rows (row r in the low half, r + 1 in the high
+// The tile as fp16 PIECES (the default Gram role): a scaled tile value y is h0 + h1, h0 = fp16(y), h1 = fp16(y - h0) (see
+// gram_f16_role).  A dword holds the same piece of two tile rows (row r in the low half, r + 1 in the high
 // half); the tile rows come in GROUPS of four, g = row / 4, i.e. (chunk of 16 rows, lane group of the Gram's MFMA operand), and a
-// group is three PLANES (y2, y0, y1) of 256 columns x 2 dwords (rows 4 g, 4 g + 1 | rows 4 g + 2, 4 g + 3): 2 KiB each.  A Gram
-// lane reads the 8 bytes of its column from each plane (ds_read_b64; 16 lanes: 128 contiguous bytes); a product lane writes
-// the 32 bytes of its four columns to each plane (two ds_write_b128).  The 8 lanes one ds_write_b128 cycle serves are 32 bytes
+// group is three PLANES (h1, h0, h1 again) of 256 columns x 2 dwords (rows 4 g, 4 g + 1 | rows 4 g + 2, 4 g + 3): 2 KiB each.
+// A Gram lane reads the 8 bytes of its column from each plane (ds_read_b64; 16 lanes: 128 contiguous bytes) and so holds
+// (h1, h0, h1), both operand forms of gram_f16_role, with three plain reads; a product lane writes the 32 bytes of its four columns to each plane (two ds_write_b128).  The 8 lanes one ds_write_b128 cycle serves are 32 bytes
 // apart, which would put them on 16 of the 32 banks twice: the two 16-byte halves of a lane's 32 bytes swap places in the lanes
 // piece_swap() names, and the 8 lanes cover the 32 banks once.  A lane group's reads stay a permutation of 128 contiguous bytes
-// (two lane groups share an LDS cycle and the same banks there: see gram_split16_role).
+// (two lane groups share an LDS cycle and the same banks there: see gram_f16_role).
+// WHY h1 IS STORED TWICE (144 KiB as with three bf16 planes, where two planes would take 96): the second copy costs the
+// product wave six LDS stores per node and no vector instruction; the other ways to the second operand form all cost the
+// Gram wave.  Tried with two planes: reading plane h1 twice -- hipcc merges the two reads and copies registers (two v_mov
+// per block and chunk: vector-ALU time, which on this chip is matrix-pipe time); the second read made volatile -- hipcc
+// then gathers every read of a chunk at the loop's end and waits for them in the open (measured: a fit 3 ms SLOWER than
+// on bf16 pieces); a six-register vector per block -- 1 138 registers spilled.  The spare 16 KiB of the CU's LDS have no
+// use here (one workgroup per CU either way; the fp32 tiles of the fallback take 102 KiB).
 constexpr int kPlaneDwords = 512;             // one plane: 256 columns x 2 dwords
 constexpr int kGroupDwords = 3 * kPlaneDwords;
 constexpr int kYGroups = kYRows / 4;
@@ -49,8 +58,8 @@ __device__ __forceinline__ int piece_col(int c) { return 8 * (c >> 2) + 4 * (((c
 
 struct alignas(16) FusedShared {
   union {  // the node tiles (double buffered), in the form the launch's Gram role reads
-    uint32_t pc[2][kYGroups][3][kPlaneDwords];  // bf16 pieces: 2 x 72 KiB
-    float y[2][kYRows][kYStride];               // fp32 (LGNN_GRAM_F32)
+    uint32_t pc[2][kYGroups][3][kPlaneDwords];  // fp16 pieces: 2 x 72 KiB
+    float y[2][kYRows][kYStride];               // fp32 (LGNN_GRAM_F32, or a launch without a usable scale): 2 x 51 KiB
   };
   // hand-off counters (one writer each): ready[p] = nodes whose tile columns product wave p has published, done[g] = nodes
   // Gram wave g has contracted
@@ -144,20 +153,19 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
 using u32x2v = __attribute__((ext_vector_type(2))) uint32_t;
 
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // one v_cvt_pk_bf16_f32 (round to nearest, NaN stays NaN)
-  using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-  const bf16x2 v = {static_cast<__bf16>(lo), static_cast<__bf16>(hi)};
-  return __builtin_bit_cast(uint32_t, v);
-}
-// The three bf16 pieces of two tile values (ya in the low halves, yb in the high halves), each rounded to nearest:
-// q0 = bf16(y), q1 = bf16(y - q0), q2 = bf16(y - q0 - q1) = y - q0 - q1 (see gram_split16_role).  11 vector instructions.
-__device__ __forceinline__ void split_pair(float ya, float yb, uint32_t& q0, uint32_t& q1, uint32_t& q2) {
-  q0 = pk_bf16(ya, yb);
-  asm("" : "+v"(q0));  // (keeps the two values in one cvt: hipcc otherwise converts and widens each on its own)
-  const float r1a = ya - __uint_as_float(q0 << 16), r1b = yb - __uint_as_float(q0 & 0xffff0000u);
-  q1 = pk_bf16(r1a, r1b);
-  asm("" : "+v"(q1));
-  q2 = pk_bf16(r1a - __uint_as_float(q1 << 16), r1b - __uint_as_float(q1 & 0xffff0000u));
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
+// The two fp16 pieces of two scaled tile values (ya in the low halves, yb in the high halves), each rounded to nearest:
+// h0 = fp16(y), h1 = fp16(y - h0) (see gram_f16_role; the difference is exact).  3 vector instructions.
+__device__ __forceinline__ void split_pair(float ya, float yb, uint32_t& h0, uint32_t& h1) {
+  // (the conversion in assembly as well: left to itself hipcc fuses it into the FMA that made y (v_fma_mix), computes every
+  // value twice and keeps W_1's rows, T1 and Y2 alive beside the results -- 95 registers spilled; the pieces are those of the
+  // ROUNDED fp32 value, the one the fp32 tile holds)
+  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h0) : "v"(ya), "v"(yb));
+  // y - h0 with the fp16 piece as an operand of a mixed-precision FMA: widens the piece, subtracts -- exactly -- and rounds
+  // to fp16 (the mode's round to nearest, subnormals kept) in ONE instruction per value.  hipcc does not find the form itself
+  // (it converts, subtracts and packs: three more instructions per pair, on the wave that paces the kernel).
+  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(h1) : "v"(h0), "v"(ya));
+  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(h1) : "v"(h0), "v"(yb));
 }
 
 struct PTables {  // descriptors of what the role reads
@@ -175,13 +183,16 @@ __device__ __forceinline__ void meta_issue(const PTables& tb, int32_t p0, int32_
   bload1(t.om, q, tb.pv);
   bload1(t.w, q, tb.pw);
 }
+// `scale`: the launch's power of two s (GramScale): the weight goes on as w s, so every tile value comes out as s y -- exactly,
+// and at one multiply per chunk and lane.
 template <int YOUNGER>  // vector-memory operations issued after the triples' loads that may still be in flight
-__device__ __forceinline__ void meta_finish(int32_t p0, int32_t p1, int lane, uint32_t row_bytes, uint32_t mask_bytes, PMeta& t) {
+__device__ __forceinline__ void meta_finish(int32_t p0, int32_t p1, int lane, uint32_t row_bytes, uint32_t mask_bytes, float scale,
+                                            PMeta& t) {
   asm volatile("s_waitcnt vmcnt(%3)" : "+v"(t.oc), "+v"(t.om), "+v"(t.w) : "n"(YOUNGER) : "memory");
   const bool in = p0 + lane < p1;
   const uint32_t m = in ? t.oc : 0u, v = in ? t.om : 0u;
   t.oc = m * uint32_t(kCoefRow * 4); t.ob = m * row_bytes; t.om = v * mask_bytes;
-  t.w = in ? t.w : 0u;
+  t.w = in ? __float_as_uint(__uint_as_float(t.w) * scale) : 0u;
 }
 
 struct PLane {        // what a product-wave lane is: class slot / column slot i, path k of a step
@@ -432,7 +443,7 @@ __device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, in
 }
 template <bool LIST, bool NOBG, bool HI>
 __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
-                                             FusedShared& sh, int64_t nn, int64_t cnt, int cg) {
+                                             FusedShared& sh, int64_t nn, int64_t cnt, int cg, float scale, bool f32_tile) {
   const int lane = threadIdx.x & 63;
   const int H = a.H;
   const bool path_wave = 64 * cg < H;  // (H <= 192: the last product wave has no columns)
@@ -468,8 +479,8 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   PMeta mc, mn;
   meta_issue(tb, q0c, q1c, lane, mc);
   meta_issue(tb, q0n, q1n, lane, mn);
-  meta_finish<0>(q0c, q1c, lane, row_bytes, mask_bytes, mc);
-  meta_finish<0>(q0n, q1n, lane, row_bytes, mask_bytes, mn);
+  meta_finish<0>(q0c, q1c, lane, row_bytes, mask_bytes, scale, mc);
+  meta_finish<0>(q0n, q1n, lane, row_bytes, mask_bytes, scale, mn);
   POps A, B;
   p_load<NOBG>(tb, mc, 0, pl, A);
   p_load<NOBG>(tb, mc, 1, pl, B);
@@ -547,7 +558,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       if (node_has && wcol_ok) {
         // Y[n] = W_1 (.) T1 + Y2.  Rows past the launch's classes come out as the zeros they already are (their coefficients
         // and their rows of W_1 are zero): one branch around unconditional 16-byte stores.
-        if (a.gram_f32) {  // the fp32 tile: twelve stores
+        if (f32_tile) {  // the fp32 tile: twelve stores
           float (*ytile)[kYStride] = sh.y[i & 1];
 #pragma unroll
           for (int t = 0; t < 3; ++t)
@@ -563,23 +574,22 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
           uint32_t* __restrict__ grp = &sh.pc[i & 1][wkq][0][0];
 #pragma unroll
           for (int t = 0; t < 3; ++t) {
-            u32x4v pz[3][2];  // [piece y0, y1, y2][column pair]: (rows 0 1 | rows 2 3) of the pair's two columns
+            u32x4v pz[2][2];  // [piece h0, h1][column pair]: (rows 0 1 | rows 2 3) of the pair's two columns
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
               for (int rp = 0; rp < 2; ++rp) {
                 const float ya = w1[t][2 * rp][ct] * t1[t][ct][2 * rp] + y2[t][ct][2 * rp];
                 const float yb = w1[t][2 * rp + 1][ct] * t1[t][ct][2 * rp + 1] + y2[t][ct][2 * rp + 1];
-                uint32_t q0, q1, q2;
-                split_pair(ya, yb, q0, q1, q2);
+                uint32_t q0, q1;
+                split_pair(ya, yb, q0, q1);
                 pz[0][ct >> 1][2 * (ct & 1) + rp] = q0;
                 pz[1][ct >> 1][2 * (ct & 1) + rp] = q1;
-                pz[2][ct >> 1][2 * (ct & 1) + rp] = q2;
               }
             uint32_t* __restrict__ g = grp + 4 * t * kGroupDwords;
-            // planes in the order (y2, y0, y1)
-            *reinterpret_cast<u32x4v*>(g + pc_lo) = pz[2][0];
-            *reinterpret_cast<u32x4v*>(g + pc_hi) = pz[2][1];
+            // planes in the order (h1, h0, h1)
+            *reinterpret_cast<u32x4v*>(g + pc_lo) = pz[1][0];
+            *reinterpret_cast<u32x4v*>(g + pc_hi) = pz[1][1];
             *reinterpret_cast<u32x4v*>(g + kPlaneDwords + pc_lo) = pz[0][0];
             *reinterpret_cast<u32x4v*>(g + kPlaneDwords + pc_hi) = pz[0][1];
             *reinterpret_cast<u32x4v*>(g + 2 * kPlaneDwords + pc_lo) = pz[1][0];
@@ -600,7 +610,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       node_has = false;
     }
     // rotate the chunk stream (the paths issued at the top are older than the 2 NL loads of the last pair's refills)
-    meta_finish<2 * NL>(q0f, q1f, lane, row_bytes, mask_bytes, mf2);
+    meta_finish<2 * NL>(q0f, q1f, lane, row_bytes, mask_bytes, scale, mf2);
     firstc = lastc;
     q0c = q0n; q1c = q1n; lastc = lastn; mc = mn;
     q0n = q0f; q1n = q1f; lastn = lastf; mn = mf2;
@@ -616,6 +626,8 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
 // (measured: its node time = time alone + 155 x 64 cycles; Gram waves idle 30 %).
 // Operand of a k step (4 tile rows) for the 16 columns 32 b + 16 h: lane l holds Y[k0 + (l >> 4)][32 b + 16 h + (l & 15)] -- as
 // A operand (row l & 15, k = l >> 4) and as B operand (k = l >> 4, column l & 15) alike.
+template <int W>  // (the flush both Gram roles share, below)
+__device__ __forceinline__ void gram_flush(const YArgs& a, const f32x4 (&acc)[9][2][2], float inv2, float* __restrict__ scratch);
 template <int W>
 __device__ __forceinline__ void gram16_load(const float* __restrict__ p, float (&x)[8][2]) {
 #pragma unroll
@@ -676,64 +688,51 @@ __device__ __forceinline__ void gram_role(const YArgs& a, const int32_t* __restr
     lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: the MFMAs above consumed them)
     p0 = q0; p1 = q1;
   }
-  // accumulator layout of 16x16x4: column l & 15, rows 4 (l >> 4) + r
-  const int64_t D = a.H;
-  const int li = lane & 15, lq = lane >> 4;
-#pragma unroll
-  for (int s = 0; s < 9; ++s)
-#pragma unroll
-    for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-      for (int hj = 0; hj < 2; ++hj) {
-        if (Tiles256<W>::si[s] == Tiles256<W>::sj[s] && hi > hj) continue;
-        const int64_t jj = Tiles256<W>::sj[s] * 32 + 16 * hj + li;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t ii = Tiles256<W>::si[s] * 32 + 16 * hi + 4 * lq + r;
-          if (ii < D && jj < D) atomicAdd(&scratch[ii * D + jj], acc[s][hi][hj][r]);
-        }
-      }
+  gram_flush<W>(a, acc, 1.f, scratch);  // (accumulator layout of 16x16x4: column l & 15, rows 4 (l >> 4) + r)
 }
 
-// The same Gram on v_mfma_f32_16x16x32_bf16 (the default; LGNN_GRAM_F32=1 runs gram_role above).  Every fp32 tile value y is
-// split into three bf16 pieces, each rounded to nearest:  y0 = bf16(y), y1 = bf16(y - y0), y2 = bf16(y - y0 - y1) = y - y0 - y1
-// (both differences are exact; each piece carries 8 of the 24 significand bits).  A product y z keeps six of the nine piece
-// products, y0 z0 + y0 z1 + y1 z0 + y0 z2 + y1 z1 + y2 z0: the three dropped ones are at most 2^-23 |y z| together and of either
-// sign (fp32 rounding level).  The product waves form the pieces (split_pair) and store them in the layout of FusedShared: this
-// role only reads them.
+// The same Gram on v_mfma_f32_16x16x32_f16 (the default; LGNN_GRAM_F32=1, or a launch without a usable scale, runs gram_role
+// above).  Every SCALED fp32 tile value y' = s cn_j y (GramScale: |y'| <= 2^15) is split into two fp16 pieces, each rounded
+// to nearest:  h0 = fp16(y'), h1 = fp16(y' - h0)  (the difference is exact; each piece carries 11 significand bits, so h0 + h1
+// is y' to 2^-22 |y'| while h1 is a normal fp16, |y'| >= 2^-3 or so, and to 2^-25 absolutely -- half an fp16 subnormal step --
+// below: 2^-40 of the launch's range).  A product y z is ALL FOUR piece products, h0 k0 + h1 k1 + h0 k1 + h1 k0 = (h0 + h1)(k0 +
+// k1): nothing is dropped.  The product waves form the pieces (split_pair) and store them in the layout of FusedShared: this
+// role only reads them.  Why two scales: fp16 has 5 exponent bits, the pieces of a value 2^-12 below the range are short and
+// those 2^-25 below it are gone.  The columns of a tile differ by what W_1's columns differ by (tests run 2^30), so they are
+// normalised one by one, for free (PathScale in paths.h); what is left is the spread over nodes and classes inside a column,
+// where a value far below the column's largest does not matter to the column's sums of squares.
 // WHY THIS SHAPE: the two waves of a SIMD take turns on its matrix pipe instruction by instruction (gram_role's header), so
-// every MFMA of the product wave waits one instruction of this wave.  The 32x32x16 form this role ran on before is 32 cycles
-// long, this one 16 for half the flops: the Gram's matrix cycles stay what they were, the product wave's wait halves.
-// Measured: a full arxiv batch 3.75 -> 3.62 ms, its short last batch 1.70 -> 1.60 ms -- a fifth of what strict
-// alternation would give: the product wave is paced by more than this wave's turns.
+// every MFMA of the product wave waits one instruction of this wave: 16 cycles with the 16x16x32 form, 32 with 32x32x16
+// (a full arxiv batch 3.75 -> 3.62 ms for that alone).
 // Tiles: gram_role's, acc[9][2][2] of 16 x 16 (34 per wave, 136 accumulator registers; lane l holds D[4 (l >> 4) + r][l & 15]).
 // Operands: a lane is (column l & 15 of a 16-column block, K group q = l >> 4); for the 16-row chunk cc lane group q reads the
-// row group 4 cc + q: per 16-column block the 8 bytes of its column from each plane, six registers (y2a y2b y0a y0b y1a y1b;
-// a = rows 0 1 of the group, b = rows 2 3), in two operand forms that overlap:  T = (y2a y2b y0a y0b),  U = (y0a y0b y1a y1b).
-// Per chunk and tile three MFMAs with K = 32 = 4 row groups x (2 pieces x 4 rows):
-//     U[i] x U[j] = y0 z0 + y1 z1,   T[i] x U[j] = y2 z0 + y0 z1,   U[i] x T[j] = y0 z2 + y1 z0.
+// row group 4 cc + q: per 16-column block the 8 bytes of its column from the planes h1, h0 and h1 again, six registers
+// (h1a h1b h0a h0b h1a h1b; a = rows 0 1 of the group, b = rows 2 3), in two operand forms that overlap:
+//     T = (h1a h1b h0a h0b),  U = (h0a h0b h1a h1b).
+// Per chunk and tile two MFMAs with K = 32 = 4 row groups x (2 pieces x 4 rows):
+//     T[i] x T[j] = h1 k1 + h0 k0,   T[i] x U[j] = h1 k0 + h0 k1.
+// (U x U + U x T is the same sum; with THIS pair -- T the only A operand, U a B operand alone -- hipcc keeps the six registers
+// of a block where the reads put them, 8 v_mov per chunk; with U as the A operand it builds operands through scratch memory.)
 // Which K slot a (lane group, register half) is does not matter and is nowhere written down: the instruction's A and B layouts
 // mirror each other (lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15]), and A and B of one
 // lane are filled by the same reads, so slot k of A and slot k of B are the same (tile row, piece) whatever k is.
-// AN ODD NUMBER OF 8-ROW CHUNKS (R = 40: five): the last one is not run as a 16-row chunk of which half is zero rows.  Lane
-// groups 2, 3 read the same two row groups as lane groups 0, 1, and two MFMAs do the work of three:
-//     (U | T) x U = U x U + T x U   (A: U in lane groups 0 1, T in 2 3),      (U | 0) x T = U x T.
-// (Zeroing A alone is enough: a finite B times zero is zero, and a non-finite input gives a non-finite factor anyway.)
-// R = 40 is 3 + 3 + 2 = 8 MFMAs of 16 cycles per tile: 34 x 8 x 16 = 4 352 matrix cycles per node against 27 x 5 x 32 = 4 320 before.
-// ONE operand set (hipcc keeps U in registers of its own, two moves and eight registers per block: 96 beside 136 accumulators,
-// 255 in all -- a second set, or half of one, does not fit): a wave's sub-tiles run in the order GramOrder names, chosen so that
-// its column blocks are used up one after the other; the reads of the NEXT chunk's block go out right behind the last MFMA
-// that reads the block, a sub-tile and a half (300 cycles) or more before their first use.  Behind a node's last chunk those
-// reads fetch the same chunk again (values nobody uses): the body stays straight-line.
-// Inside a sub-tile the order is all U x U, all T x U, all U x T: an accumulator comes round every third or fourth MFMA.
+// AN ODD NUMBER OF 8-ROW CHUNKS (R = 40: five) needs nothing of its own any more: the tile's rows past R are zero pieces (the
+// product waves store all 48 rows, zeros past the launch's classes), so the last 16-row chunk runs as it stands, its two
+// MFMAs per tile being what the bf16 role's special case took.  (One MFMA -- lane groups 2, 3 on the same rows -- would need T
+// x T in lane groups 0, 1 and T x U in 2, 3: B operands from different registers, a select per operand.)
+// R = 40 is 3 x 2 = 6 MFMAs of 16 cycles per tile: 34 x 6 x 16 = 3 264 matrix cycles per node against 4 352 on three bf16 pieces.
+// ONE operand set (96 registers beside 136 accumulators: a second set, or half of one, does not fit): a wave's sub-tiles run
+// in the order GramOrder names, chosen so that its column blocks are used up one after the other; the reads of the NEXT chunk's
+// block go out right behind the last MFMA that reads the block, a sub-tile and a half or more before their first use.  Behind
+// a node's last chunk those reads fetch the same chunk again (values nobody uses): the body stays straight-line.
+// Inside a sub-tile the order is all T x T, all T x U: an accumulator comes round every third or fourth MFMA.
 // Bank conflicts: the 16 lanes of a lane group read 128 contiguous bytes of a plane (permuted by piece_col), but groups and
 // planes are multiples of 256 bytes apart, so the two lane groups that share an LDS cycle (ds_read_b64 serves lanes 0 - 31,
 // then 32 - 63) meet on the same 32 banks: every read is 2-way, 4 LDS cycles instead of 2 -- 36 reads per chunk beside
-// 102 MFMAs of 16 cycles.  (Only a layout with the rows of a group pair side by side could avoid it.)
-// Rounding can take only a value above 3.39e38 to infinity (its square overflows in fp32 anyway); a NaN or an infinity turns
-// into NaN pieces (inf - inf): a non-finite input gives a non-finite factor, as the fp32 role does.
-struct PieceBlk { u32x4v t; u32x2v y1; };  // a 16-column block's pieces of the lane's 4 rows of a chunk, (rows 0 1 | rows 2 3)
-                                            // each: t = (y2, y0) is the form T as it stands, U is its upper half beside y1
+// 68 MFMAs of 16 cycles.  (Only a layout with the rows of a group pair side by side could avoid it.)
+// A NaN or an infinity never gets here: it makes the launch's bound non-finite, and the launch runs the fp32 role.
+struct PieceBlk { u32x4v t; u32x2v h1; };  // a 16-column block's pieces of the lane's 4 rows of a chunk, (rows 0 1 | rows 2 3)
+                                            // each: t = (h1, h0) is the form T as it stands, U is its upper half beside h1
 
 // the order a wave runs its sub-tiles in (indices into Tiles256<W>).  Wave 0: (0,0) (0,2) (0,3) (0,4) (0,5) (0,1) (1,1) (1,2)
 // (1,3); waves 1, 2: the two with the far row block, the 2 x 2 between the pairs, the own pair's; wave 3: (6,6) (1,6) (2,6)
@@ -763,58 +762,32 @@ template <int W> __device__ __forceinline__ constexpr int gram_first_use(int b) 
 __device__ __forceinline__ void piece_load(const uint32_t* __restrict__ tile, int off, int b, PieceBlk (&x)[8][2]) {
   const uint32_t* __restrict__ pe = tile + off;
   const uint32_t* __restrict__ po = tile + (off ^ 4) + 32;
-  const u32x2v e2 = *reinterpret_cast<const u32x2v*>(pe + b * 64), e0 = *reinterpret_cast<const u32x2v*>(pe + kPlaneDwords + b * 64);
-  const u32x2v o2 = *reinterpret_cast<const u32x2v*>(po + b * 64), o0 = *reinterpret_cast<const u32x2v*>(po + kPlaneDwords + b * 64);
-  x[b][0].t = u32x4v{e2[0], e2[1], e0[0], e0[1]};
-  x[b][0].y1 = *reinterpret_cast<const u32x2v*>(pe + 2 * kPlaneDwords + b * 64);
-  x[b][1].t = u32x4v{o2[0], o2[1], o0[0], o0[1]};
-  x[b][1].y1 = *reinterpret_cast<const u32x2v*>(po + 2 * kPlaneDwords + b * 64);
+  const u32x2v e1 = *reinterpret_cast<const u32x2v*>(pe + b * 64), e0 = *reinterpret_cast<const u32x2v*>(pe + kPlaneDwords + b * 64);
+  const u32x2v o1 = *reinterpret_cast<const u32x2v*>(po + b * 64), o0 = *reinterpret_cast<const u32x2v*>(po + kPlaneDwords + b * 64);
+  x[b][0].t = u32x4v{e1[0], e1[1], e0[0], e0[1]};
+  x[b][0].h1 = *reinterpret_cast<const u32x2v*>(pe + 2 * kPlaneDwords + b * 64);
+  x[b][1].t = u32x4v{o1[0], o1[1], o0[0], o0[1]};
+  x[b][1].h1 = *reinterpret_cast<const u32x2v*>(po + 2 * kPlaneDwords + b * 64);
 }
-__device__ __forceinline__ u32x4v piece_u(const PieceBlk& p) { return u32x4v{p.t[2], p.t[3], p.y1[0], p.y1[1]}; }
+__device__ __forceinline__ u32x4v piece_u(const PieceBlk& p) { return u32x4v{p.t[2], p.t[3], p.h1[0], p.h1[1]}; }
 __device__ __forceinline__ u32x4v piece_t(const PieceBlk& p) { return p.t; }
-// A 16-row chunk: 34 x 3 MFMAs, and the next chunk's reads (at `off` of the tile) as the blocks are used up.
+__device__ __forceinline__ f32x4 mfma_f16(u32x4v a, u32x4v b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+// A 16-row chunk: 34 x 2 MFMAs, and the next chunk's reads (at `off` of the tile) as the blocks are used up.
 template <int W>
-__device__ __forceinline__ void piece_chunk16(PieceBlk (&x)[8][2], f32x4 (&acc)[9][2][2], const uint32_t* __restrict__ tile, int off) {
+__device__ __forceinline__ void piece_chunk16(PieceBlk (&x)[8][2], f32x4 (&acc)[9][2][2], const uint32_t* tile, int off) {
 #pragma unroll
   for (int p = 0; p < 9; ++p) {
     const int s = GramOrder<W>::o[p], si = Tiles256<W>::si[s], sj = Tiles256<W>::sj[s];
     // An empty statement that redefines a block's registers where the chunk first uses them: hipcc otherwise forms U (a copy
-    // of y0 beside y1) right behind the reads and waits for them there, with the latency in the open.
+    // of h0 beside h1) right behind the reads and waits for them there, with the latency in the open.
 #pragma unroll
     for (int b = 0; b < 8; ++b)
       if (gram_first_use<W>(b) == p)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(x[b][h].t), "+v"(x[b][h].y1));
-    const u32x4v ua[2] = {piece_u(x[si][0]), piece_u(x[si][1])}, ta[2] = {piece_t(x[si][0]), piece_t(x[si][1])};
-    const u32x4v ub[2] = {piece_u(x[sj][0]), piece_u(x[sj][1])}, tb[2] = {piece_t(x[sj][0]), piece_t(x[sj][1])};
-#pragma unroll
-    for (int f = 0; f < 3; ++f)
-#pragma unroll
-      for (int hi = 0; hi < 2; ++hi)
-#pragma unroll
-        for (int hj = 0; hj < 2; ++hj) {
-          if (si == sj && hi > hj) continue;  // (below the diagonal)
-          acc[s][hi][hj] = mfma_bf16(f == 1 ? ta[hi] : ua[hi], f == 2 ? tb[hj] : ub[hj], acc[s][hi][hj]);
-        }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-      if (gram_last_use<W>(b) == p) piece_load(tile, off, b, x);
-  }
-}
-// The odd last 8-row chunk: 34 x 2 MFMAs (`low`: the lane is of lane group 0 or 1).
-template <int W>
-__device__ __forceinline__ void piece_chunk8(const PieceBlk (&x)[8][2], f32x4 (&acc)[9][2][2], bool low) {
-#pragma unroll
-  for (int p = 0; p < 9; ++p) {
-    const int s = GramOrder<W>::o[p], si = Tiles256<W>::si[s], sj = Tiles256<W>::sj[s];
-    u32x4v a1[2], a2[2];
-#pragma unroll
-    for (int hi = 0; hi < 2; ++hi) {
-      const u32x4v u = piece_u(x[si][hi]), t = piece_t(x[si][hi]);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { a1[hi][j] = low ? u[j] : t[j]; a2[hi][j] = low ? u[j] : 0u; }
-    }
+        for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(x[b][h].t), "+v"(x[b][h].h1));
+    const u32x4v ta[2] = {piece_t(x[si][0]), piece_t(x[si][1])};
     const u32x4v ub[2] = {piece_u(x[sj][0]), piece_u(x[sj][1])}, tb[2] = {piece_t(x[sj][0]), piece_t(x[sj][1])};
 #pragma unroll
     for (int f = 0; f < 2; ++f)
@@ -822,58 +795,22 @@ __device__ __forceinline__ void piece_chunk8(const PieceBlk (&x)[8][2], f32x4 (&
       for (int hi = 0; hi < 2; ++hi)
 #pragma unroll
         for (int hj = 0; hj < 2; ++hj) {
-          if (si == sj && hi > hj) continue;
-          acc[s][hi][hj] = mfma_bf16(f == 0 ? a1[hi] : a2[hi], f == 0 ? ub[hj] : tb[hj], acc[s][hi][hj]);
+          if (si == sj && hi > hj) continue;  // (below the diagonal)
+          acc[s][hi][hj] = mfma_f16(ta[hi], f == 1 ? ub[hj] : tb[hj], acc[s][hi][hj]);
         }
     __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int b = 0; b < 8; ++b)
+      if (gram_last_use<W>(b) == p) piece_load(tile, off, b, x);
   }
 }
-template <int W, bool LIST>
-__device__ __forceinline__ void gram_split16_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
-                                                  FusedShared& sh, int64_t nn, int64_t cnt, float* __restrict__ scratch) {
-  const int lane = threadIdx.x & 63;
-  f32x4 acc[9][2][2];
-#pragma unroll
-  for (int s = 0; s < 9; ++s)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[s][q >> 1][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // chunks of 8 tile rows (rows past R are zero; 8 n8 <= kYRows): n16 pairs of them and, if n8 is odd, the last one alone
-  const int n8 = (a.R + 7) >> 3, n16 = n8 >> 1;
-  const bool odd = n8 & 1;
-  // dword offsets inside a tile (piece_load): of the lane's reads of chunk 0 -- lane group q reads the row group q of a 16-row
-  // chunk, q & 1 of the odd 8-row one -- and the step from the last 16-row chunk to the odd chunk behind it
-  const int gq = lane >> 4;
-  const int start = (n16 > 0 ? gq : gq & 1) * kGroupDwords + piece_col(lane & 15);
-  const int to_odd = (4 - 2 * (gq >> 1)) * kGroupDwords;
-  NodeRanges<LIST> nr;
-  nr.init(pptr, list, a.n0, a.N, nn, cnt);
-  int32_t p0, p1;
-  nr.get(0, p0, p1);
-  for (int64_t i = 0; i < cnt; ++i) {
-    int32_t q0, q1;
-    nr.get(i + 1, q0, q1);
-    // node i's tile: every product wave must have published i + 1 nodes
-    while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
-    if (p1 > p0) {
-      const uint32_t* __restrict__ tile = &sh.pc[i & 1][0][0][0];
-      int off = start;
-      PieceBlk x[8][2];
-#pragma unroll
-      for (int b = 0; b < 8; ++b)
-        if (tiles256_uses<W>(b)) piece_load(tile, off, b, x);
-      __builtin_amdgcn_sched_barrier(0);
-      for (int cc = 0; cc < n16; ++cc) {  // (wave-uniform trip count)
-        off += cc + 1 < n16 ? 4 * kGroupDwords : odd ? to_odd : 0;
-        piece_chunk16<W>(x, acc, tile, off);
-      }
-      if (odd) piece_chunk8<W>(x, acc, gq < 2);
-    }
-    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: LDS operations execute in order)
-    p0 = q0; p1 = q1;
-  }
-  // gram_role's flush; of a diagonal sub-tile only the part on and above the diagonal (the symmetrising pass rewrites the rest).
-  // (The lane's place is worked out anew, from nothing that lives through the node loop: two registers less there.)
+// S += (what a Gram wave holds) * inv2 / (cn_i cn_j): undoes the launch's scale (GramScale; 1 for the fp32 role) and the
+// column normalisation of PathScale.  Of a diagonal sub-tile only the part on and above the diagonal (the symmetrising pass
+// rewrites the rest).  (The lane's place is worked out anew, from nothing that lives through the node loop.)
+template <int W>
+__device__ __forceinline__ void gram_flush(const YArgs& a, const f32x4 (&acc)[9][2][2], float inv2, float* __restrict__ scratch) {
   const int64_t D = a.H;
+  const float* __restrict__ cinv = a.scale + kScaleCinv;
   const int fl = int(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)));
   const int li = fl & 15, lq = (fl >> 4) & 3;
 #pragma unroll
@@ -884,12 +821,74 @@ __device__ __forceinline__ void gram_split16_role(const YArgs& a, const int32_t*
       for (int hj = 0; hj < 2; ++hj) {
         if (Tiles256<W>::si[s] == Tiles256<W>::sj[s] && hi > hj) continue;
         const int64_t jj = Tiles256<W>::sj[s] * 32 + 16 * hj + li;
+        const float cj = inv2 * cinv[jj];  // (jj < 256: inside the block whatever H is)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int64_t ii = Tiles256<W>::si[s] * 32 + 16 * hi + 4 * lq + r;
-          if (ii < D && jj < D && (Tiles256<W>::si[s] != Tiles256<W>::sj[s] || ii <= jj)) atomicAdd(&scratch[ii * D + jj], acc[s][hi][hj][r]);
+          if (ii < D && jj < D && (Tiles256<W>::si[s] != Tiles256<W>::sj[s] || ii <= jj))
+            atomicAdd(&scratch[ii * D + jj], acc[s][hi][hj][r] * cj * cinv[ii]);
         }
       }
+}
+template <int W, bool LIST>
+__device__ __forceinline__ void gram_f16_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
+                                              FusedShared& sh, int64_t nn, int64_t cnt, float inv2, float* __restrict__ scratch) {
+  const int lane = threadIdx.x & 63;
+  f32x4 acc[9][2][2];
+#pragma unroll
+  for (int s = 0; s < 9; ++s)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[s][q >> 1][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int n16 = (a.R + 15) >> 4;  // chunks of 16 tile rows (rows past R are zero pieces; 16 n16 <= kYRows)
+  // dword offset inside a tile (piece_load) of the lane's reads of chunk 0: lane group q reads the row group q of a chunk
+  const int start = (lane >> 4) * kGroupDwords + piece_col(lane & 15);
+  NodeRanges<LIST> nr;
+  nr.init(pptr, list, a.n0, a.N, nn, cnt);
+  int32_t p0, p1;
+  nr.get(0, p0, p1);
+  for (int64_t i = 0; i < cnt; ++i) {
+    int32_t q0, q1;
+    nr.get(i + 1, q0, q1);
+    // node i's tile: every product wave must have published i + 1 nodes
+    while (lds_min4(sh.ready) < int(i) + 1) __builtin_amdgcn_s_sleep(2);
+    if (p1 > p0) {
+      const uint32_t* tile = &sh.pc[i & 1][0][0][0];
+      int off = start;
+      PieceBlk x[8][2];
+#pragma unroll
+      for (int b = 0; b < 8; ++b)
+        if (tiles256_uses<W>(b)) piece_load(tile, off, b, x);
+      __builtin_amdgcn_sched_barrier(0);
+      for (int cc = 0; cc < n16; ++cc) {  // (wave-uniform trip count)
+        off += cc + 1 < n16 ? 4 * kGroupDwords : 0;
+        piece_chunk16<W>(x, acc, tile, off);
+      }
+    }
+    lds_publish(&sh.done[W], int(i) + 1, lane);  // (the tile's reads have returned: LDS operations execute in order)
+    p0 = q0; p1 = q1;
+  }
+  gram_flush<W>(a, acc, inv2, scratch);
+}
+
+// The launch's scale (wave uniform, the same in every wave of every workgroup): s = 2^e with s * bound in [2^14, 2^15) for the
+// bound of PathScale (paths.h), so that every scaled tile value is an fp16 well below 65504 whatever the last bit of the
+// fp32 sums does; inv2 = s^-2 for the flush.  The fp16 role runs for 2^-49 <= bound < 2^78 (biased exponents 78 .. 204), where
+// s (2^-63 .. 2^63) and s^-2 are normal fp32 numbers, the scaled weights w s and alpha pieces stay far inside fp32's range,
+// and a workgroup's sums of s^2 y^2 <= 2^30 cannot overflow; a zero, tiny, huge or non-finite bound (and LGNN_GRAM_F32) gives
+// s = 1 and the fp32 tile and role -- at 2^78 the Gram's entries pass fp32's range themselves.
+struct GramScale { float s, inv2; bool f32; };
+__device__ __forceinline__ GramScale gram_scale(const YArgs& a, const int32_t* __restrict__ pptr) {
+  const float wsum = __int_as_float(pptr[a.N + 1]);  // (the word behind the list's pointers: path_list_reserve)
+  // (PathScale: the smaller of the two triangle inequalities and 2^-12 of the first for the fp32 sums' rounding; `tri` stands
+  // in the sum as it is, so a NaN or an infinity in it stays visible whatever fminf does)
+  const float tri = a.scale[0] * a.scale[1] + a.scale[2];
+  const float bound = wsum * (fminf(tri, a.scale[3] * a.scale[1]) + 0x1p-12f * tri);
+  const uint32_t eb = __builtin_amdgcn_readfirstlane(int((__float_as_uint(bound) >> 23) & 0x1ffu));  // (a sign bit: a NaN's)
+  GramScale g;
+  g.f32 = a.gram_f32 != 0 || eb < 78u || eb > 204u;
+  g.s = g.f32 ? 1.f : __uint_as_float((268u - eb) << 23);
+  g.inv2 = g.f32 ? 1.f : __uint_as_float((2u * eb - 155u) << 23);
+  return g;
 }
 
 // LIST: the node loop runs over a device-side list of the nodes that have a path
@@ -898,7 +897,8 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
                                                              const int32_t* __restrict__ list, float* __restrict__ scratch) {
   __shared__ FusedShared sh;  // ONE LDS object
   if (int64_t(pptr[a.N]) > a.cap) return;  // the path list overflowed its buffer: the enumerating route takes over
-  // the tiles are zero where nobody writes: columns >= H, the odd row out (zero bits are zero pieces)
+  // the tiles are zero where nobody writes: columns >= H (zero bits are zero pieces); the fp32 form is the larger one
+  static_assert(sizeof(sh.pc) >= sizeof(sh.y) && sizeof(sh.pc) % 16 == 0, "the tiles' union");
   for (int q = threadIdx.x; q < int(sizeof(sh.pc) / 16); q += 512) reinterpret_cast<u32x4v*>(&sh.pc[0][0][0][0])[q] = u32x4v{0u, 0u, 0u, 0u};
   if (threadIdx.x < 4) {
     sh.ready[threadIdx.x] = 64 * int(threadIdx.x) < a.H ? 0 : INT32_MAX;  // (H <= 192: the last product wave has no columns)
@@ -910,19 +910,21 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   const int64_t nn = LIST ? int64_t(__builtin_amdgcn_readfirstlane(*a.n_list)) : a.n1 - a.n0;
   const int64_t cnt = nn > int64_t(blockIdx.x) ? (nn - blockIdx.x + stride - 1) / stride : 0;
   // (hardware waves g and g + 4 share a SIMD: one product wave and one Gram wave on each, see the kernel's header)
+  const GramScale gs = gram_scale(a, pptr);
   switch (hw) {
-    // (the Gram role on bf16 pieces unless LGNN_GRAM_F32 asks for the fp32 one; wave-uniform)
-    case 4: if (a.gram_f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
-    case 5: if (a.gram_f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
-    case 6: if (a.gram_f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
-    case 7: if (a.gram_f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_split16_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); break;
+    // (the Gram role on fp16 pieces unless the launch has no usable scale or LGNN_GRAM_F32 asks for the fp32 one; wave-uniform,
+    // and the same choice as the product waves' tile form: both read gs.f32)
+    case 4: if (gs.f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<0, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 5: if (gs.f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<1, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 6: if (gs.f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<2, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 7: if (gs.f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<3, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
     default:
       if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
-        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, nn, cnt, hw);
-        else product_role<LIST, false, true>(a, pptr, list, sh, nn, cnt, hw);
+        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
+        else product_role<LIST, false, true>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
       } else {
-        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, nn, cnt, hw);
-        else product_role<LIST, false, false>(a, pptr, list, sh, nn, cnt, hw);
+        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
+        else product_role<LIST, false, false>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
       }
       break;
   }
@@ -937,6 +939,7 @@ constexpr int64_t kFusedWorkgroups = 256;
 int launch_paths_fused(lgnn_ctx* h, YArgs y, int64_t cb, int64_t ce, float* scratch, hipStream_t s) {
   LGNN_REQUIRE(y.N < (int64_t(1) << 31), "too many nodes for one launch");
   const dim3 grid{unsigned(std::min<int64_t>(y.n1 - y.n0, kFusedWorkgroups))};
+  LGNN_REQUIRE(y.scale != nullptr, "internal: the fused kernel needs its scale block");
   const char* e = getenv("LGNN_GRAM_F32");  // =1: the Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
   y.Y = nullptr; y.gram_f32 = e && atoi(e) != 0 ? 1 : 0;
   for (int64_t c0 = cb; c0 < ce; c0 += kYRows) {
