@@ -302,7 +302,7 @@ class FunctionalLaplace(_GLMLinkMixin, BaseLaplace):
 
     def _star_chunk(self) -> int:
         C = self.n_outputs
-        budget = min(self._K_STAR_BYTES_MAX, int(getattr(getattr(self.backend, "engine", None), "_ws_limit", 1 << 62)))
+        budget = min(self._K_STAR_BYTES_MAX, int(getattr(getattr(self.backend, "engine", None), "workspace_limit", 1 << 62)))
         per_node = self.n_subset * C * (1 if self.independent_outputs else C) * 4  # K_*M of one test node
         return max(1, budget // max(1, per_node))
 

@@ -80,17 +80,16 @@ class DiagLaplace(ParametricLaplace):
 
     def _fit_graph_key(self, train_loader, override, process_group):
         eng = getattr(self.backend, "engine", None)
-        if (not self.fit_graph or not override or eng is None or _dist_info(process_group)[1] != 1
+        # (an engine without ``capture_token`` -- the CPU stand-in of the tests -- captures nothing)
+        if (not self.fit_graph or not override or not hasattr(eng, "capture_token") or _dist_info(process_group)[1] != 1
                 or self.likelihood != "classification" or not isinstance(train_loader, TensorBatchLoader)
-                or getattr(eng, "_timing_on", False) or self._on_phase is not None):
+                or eng.timing_enabled or self._on_phase is not None):
             return None
         ts = (train_loader.indices, train_loader.labels)
         if any((not t.is_cuda) for t in ts):
             return None
         return (id(train_loader), tuple((t.data_ptr(), tuple(t.shape)) for t in ts), getattr(train_loader, "batch_size", None),
-                tuple((p.data_ptr(), tuple(p.shape)) for p in self.params), eng.feature_token() if hasattr(eng, "feature_token")
-                else None, getattr(eng, "_graph_edits", 0), getattr(eng, "_ws_limit", None), float(self.backend.factor),
-                tuple(p for p, _ in eng._param_versions()) if hasattr(eng, "_param_versions") else None)
+                tuple((p.data_ptr(), tuple(p.shape)) for p in self.params), float(self.backend.factor), eng.capture_token())
 
     def _fit_graph_try(self, train_loader, key) -> bool:
         st = self.__dict__.setdefault("_fit_graph_state", {"key": None, "seen": 0, "graph": None, "off": False})

@@ -279,7 +279,7 @@ class _PredictiveMixin(_GLMLinkMixin):
                 or self.likelihood != "classification"):
             return None
         # (a 1-layer model has no hidden layer: no width limit, any activation)
-        if len(eng.dims) == 3 and (eng.dims[1] > 256 or getattr(eng, "_bind_opts", ("relu",))[0] != "relu"):
+        if len(eng.dims) == 3 and (eng.dims[1] > 256 or eng.act != "relu"):
             return None
         ops = self._matrix_free_operands(out_map)
         if ops is None:

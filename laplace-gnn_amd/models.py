@@ -31,7 +31,7 @@ class _TrainForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine, idx, masks, p, *params):
         out = engine.train_forward(idx, masks, p)
-        ctx.engine, ctx.token = engine, engine._train_token
+        ctx.engine, ctx.token = engine, engine.train_token
         ctx.keep = (idx, masks)
         return out
 
@@ -713,7 +713,7 @@ class LoRASTEGCN(GCN):
         eng = self.engine
         N = self.num_nodes
         part = 4 * self.r * N * ((N + 63) // 64)  # lgnn_lora_grad's partials of grad_A
-        limit = getattr(eng, "_ws_limit", None) or (32 << 30)
+        limit = eng.workspace_limit
         if part > limit:
             raise NotImplementedError(f"LoRASTEGCN.adj_backward: {part} bytes of grad_A partials exceed the workspace limit "
                                       f"({limit} bytes)")
