@@ -112,6 +112,12 @@ LGNN_API int lgnn_kfac_last_top(const lgnn_ctx* h);
 /* Which kernel that was: 0 seed_spmm_gram_kernel, 1 top_tiles_kernel (per-node tiles and Grams), 2 top_pairs_kernel (one MFMA
  * K step per sample and per pair of samples that share a node; taken when a host-known bound of the pairs fits the list). */
 LGNN_API int lgnn_kfac_last_top_kernel(const lgnn_ctx* h);
+/* Which MFMAs the last launch of the path route's fused kernel (csrc/paths_fused.hip) ran on: 0 fp32 throughout (LGNN_GRAM_F32=1,
+ * or a launch without a usable scale), 1 the Gram on fp16 pieces and the beta / gamma path products on fp32, 2 those products
+ * on fp16 pieces too (where the launch's scalars pass the rule of PathScale); -1 if the last call did not take that route or
+ * its path list overflowed its buffer, so that the fused kernel did not run.  `scalars` (5 floats, may be null) receives the launch's bound terms amax, w1max, bgmax, vmax, wsum (PathScale in
+ * csrc/paths.h).  Waits for the device: a query for tests and measurements, not for use inside a fit. */
+LGNN_API int lgnn_last_paths_product_role(lgnn_ctx* h, float* scalars);
 /* 1 if the stored adjacency equals its transpose (then forward and backward share one CSR) */
 LGNN_API int lgnn_is_symmetric(const lgnn_ctx* h);
 

@@ -37,6 +37,7 @@ SIGNATURES = {
     "lgnn_kfac_last_route": (_i32, [_vp]),
     "lgnn_kfac_last_top": (_i32, [_vp]),
     "lgnn_kfac_last_top_kernel": (_i32, [_vp]),
+    "lgnn_last_paths_product_role": (_i32, [_vp, _vp]),
     "lgnn_export_adj": (_i32, [_vp, _vp, _vp, _vp]),
     "lgnn_update_adjacency": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "lgnn_adj_to_edge_index": (_i32, [_vp, _vp, C.POINTER(_i64), _vp]),
@@ -140,3 +141,13 @@ def check(rc: int, what: str):
 def ptr_array(ptrs):
     arr = (C.c_void_p * len(ptrs))(*ptrs)
     return arr
+
+
+def last_paths_product_role(handle):
+    """``(role, scalars)`` of the last launch of the path route's fused kernel on the context ``handle`` (``GraphEngine._h``):
+    role 0 fp32 MFMAs throughout, 1 the Gram on fp16 pieces and the beta / gamma path products on fp32, 2 those products on
+    fp16 pieces too, -1 if the last KFAC accumulate did not take that route; scalars = the launch's bound terms ``amax, w1max, bgmax, vmax, wsum`` (PathScale in csrc/paths.h).
+    Waits for the device."""
+    out = (C.c_float * 5)()
+    role = load().lgnn_last_paths_product_role(handle, out)
+    return int(role), dict(zip(("amax", "w1max", "bgmax", "vmax", "wsum"), (float(v) for v in out)))

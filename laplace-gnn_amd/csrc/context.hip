@@ -401,6 +401,17 @@ extern "C" int64_t lgnn_num_long_rows(const lgnn_ctx* h) { return h ? h->n_long 
 extern "C" int lgnn_kfac_last_route(const lgnn_ctx* h) { return h && h->last_route_paths ? 1 : 0; }
 extern "C" int lgnn_kfac_last_top(const lgnn_ctx* h) { return h && h->last_top_kernel != 0 ? 1 : 0; }
 extern "C" int lgnn_kfac_last_top_kernel(const lgnn_ctx* h) { return h ? h->last_top_kernel : 0; }
+// (waits for the device: the role is a word the launch wrote; -1: no launch of paths_fused_kernel so far, or an error)
+extern "C" int lgnn_last_paths_product_role(lgnn_ctx* h, float* scalars) {
+  if (!h || !h->last_route_paths || !h->ws.path_scale.p) return -1;
+  float host[6];
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host, h->ws.path_scale.p, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  if (scalars) memcpy(scalars, host, 5 * sizeof(float));
+  int32_t role;
+  memcpy(&role, &host[5], sizeof(role));  // (-1 where the call's path list overflowed and the fused kernel did not run)
+  return role;
+}
 
 extern "C" int lgnn_bind_model(lgnn_ctx* h, int num_layers, const int64_t* dims, const float* const* weights,
                                const float* const* biases, const float* X, int activation, int likelihood) {

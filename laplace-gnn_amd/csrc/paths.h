@@ -32,13 +32,14 @@ struct YArgs {
   int H, c0, R;
   int cb;                   // first class of the coefficient table's slots (the call's class range starts there)
   int64_t n_coef;           // rows of the coefficient table
-  int unused_;              // (keeps the fields below at their kernel-argument offsets: hipcc merges the argument loads
-                            //  by offset, and shifted by 4 bytes paths_fused_kernel spills more SGPRs)
+  int piece_share_log2;     // K of the piece products' rule (PathScale; path_role_kernel alone reads it).  (The field also keeps
+                            //  those below at their kernel-argument offsets: hipcc merges the argument loads by offset, and
+                            //  shifted by 4 bytes paths_fused_kernel spills more SGPRs)
   int no_bg;                // regression / nothing but the diagonal term: the beta / gamma products vanish
   int gram_f32;             // LGNN_GRAM_F32: paths_fused_kernel's Gram on fp32 MFMAs instead of the fp16 pieces
   const float* scale;       // paths_fused_kernel: the launch's PathScale block (below); W1 and bg are its normalised copies then
 };
-// (the kernels take YArgs by value and hipcc merges the argument loads by offset, see unused_: the layout is part of the kernels)
+// (the kernels take YArgs by value and hipcc merges the argument loads by offset, see piece_share_log2: the layout is part of the kernels)
 static_assert(sizeof(YArgs) == 248 && __builtin_offsetof(YArgs, no_bg) == 228, "YArgs: paths_fused_kernel's argument offsets");
 
 // What the fp16 Gram of paths_fused_kernel needs to know about the size of the tile values (floats; paths.hip fills it per
@@ -58,8 +59,41 @@ static_assert(sizeof(YArgs) == 248 && __builtin_offsetof(YArgs, no_bg) == 228, "
 // exact value is, so the bound it scales by is  wsum * (min(tri, vmax * w1max) + 2^-12 tri):  2^-12 covers 4 096 terms of
 // 2^-24 relative error each, all of one sign.  The maxima are taken on the bit patterns of |x| (unsigned order = numeric
 // order, and a NaN is above everything): a non-finite operand gives a non-finite bound, and such a launch runs the fp32 role.
-constexpr int kScaleCn = 4, kScaleCinv = kScaleCn + 256, kScaleW1 = kScaleCinv + 256;  // offsets: cn [256], 1 / cn [256], W1n [C][H]
-// ([0] amax, [1] w1max, [2] bgmax, [3] vmax as bit patterns)
+constexpr int kScaleCn = 8, kScaleCinv = kScaleCn + 256, kScaleW1 = kScaleCinv + 256;  // offsets: cn [256], 1 / cn [256], W1n [C][H]
+// ([0] amax, [1] w1max, [2] bgmax, [3] vmax as bit patterns; [4] wsum and [5] the role the launch ran, kRole*, written by
+// path_role_kernel for lgnn_last_paths_product_role: nothing on the device reads those two)
+constexpr int kScaleWsum = 4, kScaleRole = 5;
+// everything on fp32 MFMAs; the Gram on fp16 pieces and the beta / gamma products on fp32; those products on fp16 pieces too
+constexpr int kRoleF32 = 0, kRoleGramF16 = 1, kRoleProductsF16 = 2;
+// The beta / gamma products run on fp16 pieces where  min(tri, vmax * w1max) >= 2^-K tri  (below); K per model family, since
+// GraphSAGE's `tri` carries the self half of W_1 as table rows and its ratio lies lower at the same cancellation.
+constexpr int kPieceShareLog2Gcn = 1, kPieceShareLog2Sage = 3;
+// -1 in the role word: the call's path list overflowed its buffer and the fused kernel did not run
+constexpr int kRoleNone = -1;
+// THE PIECE PRODUCTS.  A path's beta term is a_c (mask (.) b_m)[j], a_c = w s (-beta_c^m) (s: the launch's power of two, on the
+// path weight), the gamma term likewise.  fp16 has 5 exponent bits, so both sides are normalised, exactly: table row m by the
+// power of two 2^k_m that puts max_j |bgn[m, j]| in [2^6, 2^7) (kPieceRowLog2), the sample's beta coefficients by 2^-k_m (the
+// g row and the gamma coefficients by a power of their own) -- the product is what it was.  Then
+//     |a'| = |w| s |beta_c^m| 2^-k_m <= s wsum |beta_c^m| max_j |bgn[m, j]| / 2^6 <= s wsum tri / 2^6,
+// and s * bound < 2^15 with bound >= wsum min(tri, vmax w1max) >= wsum 2^-K tri under the rule: |a'| < 2^(9 + K), 2^12 at the
+// most, a sixteenth of fp16's range (it is the product of the two maxima that is bounded, not bgmax alone).  A row of zeros
+// takes zero coefficients, so no large a' ever meets it.  Each operand is two fp16 pieces rounded to nearest (x0 = fp16(x),
+// x1 = fp16(x - x0): 22 bits while x1 is a normal number, i.e. for |x| >= 2^-3, and 2^-25 absolutely below), all four piece
+// products are kept, each is exact in fp32: a term carries about 2^-21 relative error where the fp32 MFMA carries 2^-24,
+// hence the wider rounding share of the bound for this role (2^-9 tri: 4 096 terms of 2^-21).  WHY 2^6 AND NOT 2^13 for the
+// rows: a' is small against its bound (the bound takes every maximum at once); with rows at 2^13 the largest a' of the test
+// shapes is 0.02 .. 0.05, its second piece a subnormal, and B_0 came out five times further from fp64 than on fp32 MFMAs
+// (measured, GraphSAGE 6e-7 against 1e-7); at 2^6 the largest a' is 2 .. 60 and the distance to fp64 is the fp32 role's.
+// THE RULE.  The pieces run only where cancellation between a path's terms is moderate, min(tri, vmax w1max) >= 2^-K tri:
+// where the seed block vanishes a tile value is rounding noise of terms of size `tri`, and 2^-21 of them is eight times the
+// noise of the fp32 products.  K is what a sweep gives per family (tests/test_gpu_path_products_f16.py: W_1, b_1 x 2^k, k = 0
+// .. 20, both splits restated in numpy; the largest ratio at which the restated B_0 leaves a quarter of the suite's two
+// bounds is 0.28 for the GCN, so 2^-1, and 0.10 for GraphSAGE, so 2^-3).
+constexpr int kPieceRowLog2 = 6;
+// What path_bound_kernel leaves in ws.path_bgn for a table of `rows` samples (float offsets): the normalised fp32 table
+// [2 rows][H], the PIECE table [2 rows][H] of packed dwords, the coefficient rows [rows][kCoefRow] that go with the pieces.
+__host__ __device__ __forceinline__ int64_t piece_table_offset(int64_t rows, int64_t H) { return 2 * rows * H; }
+__host__ __device__ __forceinline__ int64_t piece_coef_offset(int64_t rows, int64_t H) { return 4 * rows * H; }
 
 // R, the path list and the node list of a batch as the launches below read them: the workspace's or a cache entry's
 struct PathLists {
@@ -71,6 +105,8 @@ struct PathLists {
 // scratch += B_0 of the classes [cb, ce) over the nodes [y.n0, y.n1), kYRows classes per launch (sets y.c0, y.R, y.gram_f32);
 // on the device a launch returns at once if the path list overflowed y.cap (paths_fused.hip) ...
 int launch_paths_fused(lgnn_ctx* h, YArgs y, int64_t cb, int64_t ce, float* scratch, hipStream_t s);
+// whether a call of launch_paths_fused may run the piece instance at all (not under LGNN_GRAM_F32; read per call)
+bool fused_pieces_possible();
 // ... and this one unless it did: the same sum through class planes in ws.planes_a and the streaming Gram (paths_overflow.hip)
 int launch_paths_overflow(lgnn_ctx* h, YArgs y, int64_t cb, int64_t ce, float* scratch, hipStream_t s);
 

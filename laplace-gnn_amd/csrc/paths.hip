@@ -338,9 +338,24 @@ __global__ __launch_bounds__(256) void path_colscale_kernel(const float* __restr
 // |gamma| over the 64 class slots (16 lanes per kind, 16 bytes per lane), its rows b_r, g_r of the table times cn -- written to
 // bgn, which the fused kernel reads in the table's place -- and their largest entries; the row's entry of `vsum`.  The waves
 // stride over the rows and keep their maxima in registers; a workgroup ends in three atomics at most.  bg == nullptr (regression): no beta / gamma term.
+// A table row's power of two for the piece products from the bit pattern of its largest |entry|: up = 2^k with up * max in
+// [2^kPieceRowLog2, 2 * 2^kPieceRowLog2), k kept in [-126, 126] (both powers normal numbers); down = 2^-k, and zero for a row
+// of zeros.
+struct PieceRow { float up, down; };
+__device__ __forceinline__ PieceRow piece_row(uint32_t max_bits) {
+  const int k = min(max(127 + kPieceRowLog2 - int(max_bits >> 23), -126), 126);
+  return {__uint_as_float(uint32_t(127 + k) << 23), max_bits ? __uint_as_float(uint32_t(127 - k) << 23) : 0.f};
+}
+// x as (x0 | x1 << 16), x0 = fp16(x), x1 = fp16(x - x0), both rounded to nearest (split_pair of paths_fused.hip)
+__device__ __forceinline__ uint32_t piece_pack(float x) {
+  const _Float16 x0 = _Float16(x);
+  const _Float16 x1 = _Float16(x - float(x0));
+  return uint32_t(__builtin_bit_cast(uint16_t, x0)) | uint32_t(__builtin_bit_cast(uint16_t, x1)) << 16;
+}
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
 __global__ __launch_bounds__(256) void path_bound_kernel(const float* __restrict__ coef, int64_t rows, const float* __restrict__ bg,
                                                          float* __restrict__ bgn, int H, const uint32_t* __restrict__ vsum,
-                                                         float* __restrict__ sc) {
+                                                         float* __restrict__ sc, int pieces) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t amax = 0u, xmax = 0u, vmax = 0u;
   f32x4 cn = {0.f, 0.f, 0.f, 0.f};
@@ -357,9 +372,10 @@ __global__ __launch_bounds__(256) void path_bound_kernel(const float* __restrict
     if (bg == nullptr) continue;
     const float be = __uint_as_float(uint32_t(__shfl(int(km), 16))), ga = __uint_as_float(uint32_t(__shfl(int(km), 32)));
     uint32_t bm = 0u, gm = 0u;
+    f32x4 b4 = {0.f, 0.f, 0.f, 0.f}, g4 = b4;
     if (4 * lane < H) {
-      const f32x4 b4 = *reinterpret_cast<const f32x4*>(bg + r * H + 4 * lane) * cn;
-      const f32x4 g4 = *reinterpret_cast<const f32x4*>(bg + (rows + r) * H + 4 * lane) * cn;
+      b4 = *reinterpret_cast<const f32x4*>(bg + r * H + 4 * lane) * cn;
+      g4 = *reinterpret_cast<const f32x4*>(bg + (rows + r) * H + 4 * lane) * cn;
       *reinterpret_cast<f32x4*>(bgn + r * H + 4 * lane) = b4;
       *reinterpret_cast<f32x4*>(bgn + (rows + r) * H + 4 * lane) = g4;
 #pragma unroll
@@ -375,6 +391,19 @@ __global__ __launch_bounds__(256) void path_bound_kernel(const float* __restrict
     }
     // (0 * inf is NaN: a non-finite operand stays visible whatever it meets)
     xmax = max(xmax, __float_as_uint(be * __uint_as_float(bm) + ga * __uint_as_float(gm)) & 0x7fffffffu);
+    if (!pieces) continue;  // (LGNN_GRAM_F32: the call cannot run the piece instance)
+    // The same rows for the fused kernel's piece products (PathScale, "the piece table"): row m times the power of two that
+    // puts its largest entry in [2^6, 2^7), every entry as two fp16 pieces in one dword, and the sample's coefficient row
+    // with -beta / -gamma times the inverse power.  A row of zeros takes zero coefficients (its products are zero).
+    const PieceRow pb = piece_row(bm), pg = piece_row(gm);
+    if (4 * lane < H) {
+      b4 *= pb.up; g4 *= pg.up;
+      uint32_t* __restrict__ pt = reinterpret_cast<uint32_t*>(bgn + piece_table_offset(rows, H));
+      *reinterpret_cast<u32x4*>(pt + r * H + 4 * lane) = u32x4{piece_pack(b4[0]), piece_pack(b4[1]), piece_pack(b4[2]), piece_pack(b4[3])};
+      *reinterpret_cast<u32x4*>(pt + (rows + r) * H + 4 * lane) = u32x4{piece_pack(g4[0]), piece_pack(g4[1]), piece_pack(g4[2]), piece_pack(g4[3])};
+    }
+    const int kind = lane >> 4;  // (alpha | -beta | -gamma | pad)
+    *reinterpret_cast<f32x4*>(bgn + piece_coef_offset(rows, H) + r * kCoefRow + 4 * lane) = cf * (kind == 1 ? pb.down : kind == 2 ? pg.down : 1.f);
   }
   __shared__ uint32_t red[3][4];
   if (lane == 0) { red[0][wave] = amax; red[1][wave] = xmax; red[2][wave] = vmax; }
@@ -534,13 +563,13 @@ static int path_scale_args(lgnn_ctx* h, YArgs& y, const float* W1b, int ld, hipS
   Workspace& ws = h->ws;
   const int64_t C = h->dims[2], H = y.H, rows = y.n_coef;
   LGNN_CALL(ws.path_scale.reserve(size_t(kScaleW1 + C * H) * 4));
-  if (!y.no_bg) LGNN_CALL(ws.path_bgn.reserve(size_t(2 * rows) * H * 4));
+  if (!y.no_bg) LGNN_CALL(ws.path_bgn.reserve(size_t(piece_coef_offset(rows, H) + rows * kCoefRow) * 4));
   float* sc = ws.path_scale.as<float>();
   hipLaunchKernelGGL(path_colscale_kernel, dim3(1), dim3(256), 0, s, y.W1, W1b, ld, int(C), int(H), sc);
   LGNN_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(path_bound_kernel, dim3(unsigned(std::min<int64_t>(cdiv(rows, 4), 1024))), dim3(256), 0, s, y.coef, rows,
                      y.no_bg ? static_cast<const float*>(nullptr) : y.bg, ws.path_bgn.as<float>(), int(H),
-                     ws.path_vsum.as<uint32_t>(), sc);
+                     ws.path_vsum.as<uint32_t>(), sc, fused_pieces_possible() ? 1 : 0);
   LGNN_HIP_CHECK(hipGetLastError());
   y.scale = sc; y.W1 = sc + kScaleW1; y.w1_ld = int(H);
   if (!y.no_bg) y.bg = ws.path_bgn.as<float>();
@@ -655,7 +684,7 @@ int kfac_paths_first_layer(lgnn_ctx* h, const int64_t* idx, int64_t M, int seed_
     LGNN_CALL(launch_top_tiles(h, PathR{pl.rptr, pl.r_m, pl.r_w}, M, cb, ce, top->act_list, top->act_count, top->scratch, s));
   }
   YArgs y = path_args(h, pl, cb, cap, nb, ne);
-  y.W1 = h->W[1]; y.w1_ld = int(H); y.M = M; y.n_coef = M; y.no_bg = no_bg ? 1 : 0;
+  y.W1 = h->W[1]; y.w1_ld = int(H); y.M = M; y.n_coef = M; y.no_bg = no_bg ? 1 : 0; y.piece_share_log2 = kPieceShareLog2Gcn;
   YArgs yf = y;  // (the overflow route keeps W_1 and the table as they are)
   LGNN_CALL(path_scale_args(h, yf, nullptr, int(H), s));
   LGNN_CALL(launch_paths_fused(h, yf, cb, ce, scratch, s));
@@ -712,6 +741,7 @@ int kfac_paths_first_layer_sage(lgnn_ctx* h, const int64_t* idx, int64_t M, int 
   YArgs y = path_args(h, pl, cb, cap, nb, ne);
   y.W1 = h->W[1] + H; y.w1_ld = int(2 * H);  // the neighbour half: the alpha term of the neighbour paths
   y.M = T; y.n_coef = T; y.no_bg = 0;        // (the one-hot alpha paths go through the beta product: never skipped)
+  y.piece_share_log2 = kPieceShareLog2Sage;
   LGNN_CALL(path_scale_args(h, y, h->W[1], int(2 * H), s));
   return launch_paths_fused(h, y, cb, ce, scratch, s);
 }

@@ -7,8 +7,11 @@
 //       classes of the launch.  Per step of FOUR paths: three 16-byte loads of the paths' coefficient rows (A operands: lane
 //       (i, k) = class slot i of path k, the four class tiles of a slot side by side in the table row), two 16-byte loads of
 //       the table rows b_m, g_m (B operands: lane (i, k) = columns 64 cg + 4 i .. + 3 of path k -- the four 16-column MFMA
-//       tiles of the wave interleave the columns, so one load feeds all four), one mask word; 24 v_mfma_f32_16x16x4_f32
-//       (3 class tiles x 4 column tiles x (beta, gamma): 768 cycles) per step and, per PAIR of steps, 12
+//       tiles of the wave interleave the columns, so one load feeds all four), one mask word; for the beta / gamma products
+//       12 v_mfma_f32_16x16x32_f16 per step (3 class tiles x 4 column tiles, both terms and all four products of two fp16
+//       pieces per operand along K: 192 cycles, see PCurH) in the instance most launches run, 24 v_mfma_f32_16x16x4_f32
+//       (768 cycles) in the other (a launch whose terms cancel too far for pieces, the regression likelihood, LGNN_GRAM_F32:
+//       path_role_kernel); and, per PAIR of steps, 12
 //       v_mfma_f32_16x16x32_bf16 for the alpha product of both (192 cycles, exact: the mask is 0 / 1 and the weighted
 //       coefficient goes in as three bf16 pieces along K, see PAlpha).  No LDS staging, no window, no restaging of hubs: the
 //       operands of step s + 1 are in flight while the MFMAs of step s issue, across node boundaries (a node's triples
@@ -115,14 +118,18 @@ struct NodeRanges {
   }
   __device__ __forceinline__ void fill(int64_t b) {
     base = b;
-    const uint32_t ii = uint32_t(b) + (threadIdx.x & 31u);
+    // (an opaque copy of the thread number: as a loop invariant the lane's index would live -- in the product role: in
+    // scratch memory -- from one window to the next, 32 nodes on, for the sake of one v_and)
+    uint32_t tx = threadIdx.x;
+    asm volatile("" : "+v"(tx));
+    const uint32_t ii = uint32_t(b) + (tx & 31u);
     const bool in = int64_t(ii) < cnt;
     const uint32_t k = blockIdx.x + ii * gridDim.x;
     uint32_t node = k;
     if constexpr (LIST)
-      asm volatile("buffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(node) : "v"(in ? k * 4u : 0xfffffff0u), "s"(lrs) : "memory");
-    const uint32_t off = in ? (n0 + node) * 4u + ((threadIdx.x >> 3) & 4u) : 0xfffffff0u;
-    asm volatile("buffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(off), "s"(prs) : "memory");
+      asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(node) : "v"(in ? k * 4u : 0xfffffff0u), "s"(lrs) : "memory");
+    const uint32_t off = in ? (n0 + node) * 4u + ((tx >> 3) & 4u) : 0xfffffff0u;
+    asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(off), "s"(prs) : "memory");
   }
   __device__ __forceinline__ void get(int64_t i, int32_t& p0, int32_t& p1) {
     if (i - base >= 32) fill(i);
@@ -142,12 +149,23 @@ struct NodeRanges {
 // ALUs, so every VALU instruction of either wave of a SIMD is matrix-pipe time lost, not work hidden behind the MFMAs
 // (measured: the product wave's MFMA time and the time of its other instructions add up, with or without the Gram wave) --
 // 64-bit address arithmetic per load was a quarter of this wave's instructions.  An offset past the table's end reads zeros.
-template <int OFF>
+// PAD: five wait states in front of the load, inside the same statement.  A descriptor that hipcc has spilled to a VGPR lane
+// comes back with v_readlane right in front of the statement that uses it, and a vector-memory instruction that reads an SGPR
+// fewer than five wait states after a vector-ALU instruction wrote it reads the OLD value; hipcc pads its own loads and
+// does not look into an assembly statement.  (Measured: with the coefficient table's descriptor reloaded one instruction in
+// front of a step's first load, the no-list instance's B_0 was 0.57 off the oracle at C = 7.)  The FIRST load of every group
+// below is padded -- the reloads of a group's descriptors stand in front of it -- not each one: 5 cycles per step, not 30.
+template <int OFF, bool PAD = false>
 __device__ __forceinline__ void bload4(f32x4& d, uint32_t voff, const i32x4& rsrc) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(d) : "v"(voff), "s"(rsrc), "n"(OFF) : "memory");
+  if constexpr (PAD)
+    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(d) : "v"(voff), "s"(rsrc), "n"(OFF) : "memory");
+  else
+    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen offset:%3" : "=v"(d) : "v"(voff), "s"(rsrc), "n"(OFF) : "memory");
 }
+template <bool PAD = false>
 __device__ __forceinline__ void bload1(uint32_t& d, uint32_t voff, const i32x4& rsrc) {
-  asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rsrc) : "memory");
+  if constexpr (PAD) asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rsrc) : "memory");
+  else asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(d) : "v"(voff), "s"(rsrc) : "memory");
 }
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x4v = __attribute__((ext_vector_type(4))) uint32_t;
@@ -179,7 +197,7 @@ struct PTables {  // descriptors of what the role reads
 struct PMeta { uint32_t oc, ob, om, w; };  // (w: the bits of a float)
 __device__ __forceinline__ void meta_issue(const PTables& tb, int32_t p0, int32_t p1, int lane, PMeta& t) {
   const uint32_t q = uint32_t(max(min(p0 + lane, p1 - 1), 0)) * 4u;
-  bload1(t.oc, q, tb.pm);  // (sample m, node v: turned into offsets in meta_finish)
+  bload1<true>(t.oc, q, tb.pm);  // (sample m, node v: turned into offsets in meta_finish)
   bload1(t.om, q, tb.pv);
   bload1(t.w, q, tb.pw);
 }
@@ -217,7 +235,7 @@ __device__ __forceinline__ void p_load(const PTables& tb, const PMeta& mt, int s
   const uint32_t oc = uint32_t(__shfl(int(mt.oc), src)) + pl.oc;
   const uint32_t om = uint32_t(__shfl(int(mt.om), src)) + pl.om;
   o.w = __uint_as_float(uint32_t(__shfl(int(mt.w), src)));
-  bload4<0>(o.ca[0], oc, tb.coef);
+  bload4<0, true>(o.ca[0], oc, tb.coef);
   if constexpr (!NOBG) {
     const uint32_t ob = uint32_t(__shfl(int(mt.ob), src)) + pl.ob;
     bload4<kCoefStride * 4>(o.ca[1], oc, tb.coef);
@@ -240,6 +258,58 @@ __device__ __forceinline__ void p_wait(POps& o) {
 // A step's beta / gamma MFMA operands: lane (i, k): A[row i][k] = weighted coefficient of class 16 t + i, B[k][col i] = masked
 // table value of the lane's column ct.
 struct PCur { float a1[3], a2[3], bb[4], gg[4]; };
+// The same operands for v_mfma_f32_16x16x32_f16 (the launches path_role() gives the fp16 products, see PathScale in paths.h):
+// both sides as two fp16 pieces, x = x0 + x1 with x0 = fp16(x), x1 = fp16(x - x0) as in split_pair, and ALL FOUR piece
+// products along K.  The instruction's lane (i, q) owns the K slots 8 q .. 8 q + 7, and lane group q is path q of the step, so
+// a lane's eight slots are its own path's
+//   A operand of class tile t:    a0 a0 | a1 a1 | c0 c0 | c1 c1    (a = w s (-beta') of class 16 t + i, c = w s (-gamma'))
+//   B operand of column tile ct:  b0 b1 | b0 b1 | g0 g1 | g0 g1    (the masked dwords of the PIECE table, each one twice)
+// and ONE MFMA per (class tile, column tile) is the step's four paths, both terms: 12 of 16 cycles where the fp32 form takes
+// 24 of 32.  The table's rows come normalised by a power of two per row and the coefficients by its inverse (path_bound_kernel,
+// PathScale): the primes.  The B side's pieces are made once per table row there; a lane's b4 / g4 are the same two 16-byte
+// loads, of packed dwords (b0 | b1 << 16).  ONE operand set (28 registers, what the two fp32 sets take together).
+struct PCurH { u32x4v a[3], b[4]; };
+// a as (a0 | a0 << 16) and (a1 | a1 << 16): 3 vector instructions (in assembly for split_pair's reasons)
+__device__ __forceinline__ void split_twice(float a, uint32_t& h0, uint32_t& h1) {
+  asm("v_cvt_pk_f16_f32 %0, %1, %1" : "=v"(h0) : "v"(a));
+  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(h1) : "v"(h0), "v"(a));
+  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "+v"(h1) : "v"(h0), "v"(a));
+}
+// a step's beta / gamma operands from its landed loads (`bits`: the lane's mask bits from bit 0 on): 6 + 8 vector instructions
+// in the fp32 form, 24 + 16 as pieces
+template <bool HI>
+__device__ __forceinline__ void p_bg(const POps& o, int bits, PCur& c) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    const int tt = HI ? 3 : t;
+    c.a1[t] = (HI && t > 0) ? 0.f : o.w * o.ca[1][tt];
+    c.a2[t] = (HI && t > 0) ? 0.f : o.w * o.ca[2][tt];
+  }
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    const int on = __builtin_amdgcn_sbfe(bits, ct, 1);
+    c.bb[ct] = __uint_as_float(uint32_t(on) & __float_as_uint(o.b4[ct]));
+    c.gg[ct] = __uint_as_float(uint32_t(on) & __float_as_uint(o.g4[ct]));
+  }
+}
+template <bool HI>
+__device__ __forceinline__ void p_bg(const POps& o, int bits, PCurH& c) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t) {
+    if (HI && t > 0) { c.a[t] = u32x4v{0u, 0u, 0u, 0u}; continue; }
+    const int tt = HI ? 3 : t;
+    uint32_t h[4];
+    split_twice(o.w * o.ca[1][tt], h[0], h[1]);
+    split_twice(o.w * o.ca[2][tt], h[2], h[3]);
+    c.a[t] = u32x4v{h[0], h[1], h[2], h[3]};
+  }
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) {
+    const uint32_t on = uint32_t(__builtin_amdgcn_sbfe(bits, ct, 1));
+    const uint32_t b = on & __float_as_uint(o.b4[ct]), g = on & __float_as_uint(o.g4[ct]);
+    c.b[ct] = u32x4v{b, b, g, g};
+  }
+}
 // The alpha product T1 += (w alpha) Mk of a PAIR of steps as v_mfma_f32_16x16x32_bf16, exactly.  Mk is 0 or 1 and a bf16 as it
 // is; a = w alpha is cut into three bf16 pieces by TRUNCATION,
 //   r1 = a - (a & 0xffff0000), r2 = r1 - (r1 & 0xffff0000), pieces = the high halves of a, r1, r2:
@@ -261,8 +331,8 @@ constexpr uint32_t kHiHalves = 0x07060302u;  // v_perm_b32(x, y): y's high half 
 // step).  About 48 vector instructions (each costs the SIMD's matrix pipe its issue cycles, see above): 7 per class tile for
 // the alpha pieces (multiply, two ANDs, two subtractions, two to pack), 13 for the mask -- bit ct of the mask word as 0 / -1
 // with one v_bfe_i32, ANDed with the bf16 ones of its slots --, 6 + 8 for beta / gamma.
-template <bool NOBG, bool HI, bool SB>
-__device__ __forceinline__ void p_xform(const POps& o, const PLane& pl, PCur& c, PAlpha& al, bool bg) {
+template <bool NOBG, bool HI, bool SB, class CUR>
+__device__ __forceinline__ void p_xform(const POps& o, const PLane& pl, CUR& c, PAlpha& al, bool bg) {
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
     const int tt = HI ? 3 : t;
@@ -299,20 +369,7 @@ __device__ __forceinline__ void p_xform(const POps& o, const PLane& pl, PCur& c,
     }
   }
   if constexpr (!NOBG) {
-    if (bg) {  // (wave uniform)
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        const int tt = HI ? 3 : t;
-        c.a1[t] = (HI && t > 0) ? 0.f : o.w * o.ca[1][tt];
-        c.a2[t] = (HI && t > 0) ? 0.f : o.w * o.ca[2][tt];
-      }
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) {
-        const int on = __builtin_amdgcn_sbfe(bits, ct, 1);
-        c.bb[ct] = __uint_as_float(uint32_t(on) & __float_as_uint(o.b4[ct]));
-        c.gg[ct] = __uint_as_float(uint32_t(on) & __float_as_uint(o.g4[ct]));
-      }
-    }
+    if (bg) p_bg<HI>(o, bits, c);  // (wave uniform)
   }
 }
 // an empty statement that reads every register of `c`: keeps the set alive (and out of the other set's registers) up to here
@@ -323,6 +380,7 @@ __device__ __forceinline__ void p_keep(const PCur& c) {
     asm volatile("" :: "v"(c.bb[0]), "v"(c.bb[1]), "v"(c.bb[2]), "v"(c.bb[3]), "v"(c.gg[0]), "v"(c.gg[1]), "v"(c.gg[2]), "v"(c.gg[3]));
   }
 }
+template <bool NOBG> __device__ __forceinline__ void p_keep(const PCurH&) {}  // (one set: nothing to keep apart)
 __device__ __forceinline__ f32x4 mfma_bf16(u32x4v a, u32x4v b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
@@ -350,6 +408,23 @@ __device__ __forceinline__ void p_mfma_first(const PCur& c, f32x4 (&y2)[3][4]) {
   for (int t = 0; t < 3; ++t)
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) y2[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(c.a2[t], c.gg[ct], y2[t][ct], 0, 0, 0);
+}
+// the same on pieces: 12 v_mfma_f32_16x16x32_f16 per step, beta and gamma in one
+__device__ __forceinline__ f32x4 mfma_f16(u32x4v a, u32x4v b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ void p_mfma(const PCurH& c, f32x4 (&y2)[3][4]) {
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) y2[t][ct] = mfma_f16(c.a[t], c.b[ct], y2[t][ct]);
+}
+__device__ __forceinline__ void p_mfma_first(const PCurH& c, f32x4 (&y2)[3][4]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < 3; ++t)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) y2[t][ct] = mfma_f16(c.a[t], c.b[ct], zero);
 }
 // the 12 alpha MFMAs of a pair (v_mfma_f32_16x16x32_bf16)
 template <bool FIRST>
@@ -418,9 +493,9 @@ struct ChunkGen {
 // the 8-pass 16x16x4 -- but nothing there is a guarantee, and hipcc places no s_nop of its own.  Both are excluded by
 // construction now: no branch holds a load, and `s_nop 11` (12 wait states) sits in front of the tile write's first
 // accumulator read on every path.
-template <bool NOBG, bool HI>
-__device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, int sx, const PLane& pl, POps& A, POps& B, PCur& cA,
-                                          PCur& cB, PAlpha& al, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4], bool first, bool half) {
+template <bool NOBG, bool HI, class CUR>
+__device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, int sx, const PLane& pl, POps& A, POps& B, CUR& cA,
+                                          CUR& cB, PAlpha& al, f32x4 (&t1)[3][4], f32x4 (&y2)[3][4], bool first, bool half) {
   constexpr int NL = kStepLoads<NOBG>;
   // A's loads: the NL youngest outstanding may be B's (the first pair of a chunk: B's and the three path loads -- there
   // the count also waits for B's first half, issued a whole pair earlier)
@@ -441,7 +516,9 @@ __device__ __forceinline__ void pair_body(const PTables& tb, const PMeta& mx, in
   if constexpr (!NOBG)
     if (!half) p_mfma(cB, y2);
 }
-template <bool LIST, bool NOBG, bool HI>
+// CUR: the form of the beta / gamma operands, PCur (fp32 MFMAs) or PCurH (fp16 pieces: the tables are then the piece table and
+// the coefficient rows that go with it, which path_bound_kernel leaves behind the normalised fp32 table)
+template <bool LIST, bool NOBG, bool HI, class CUR>
 __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __restrict__ pptr, const int32_t* __restrict__ list,
                                              FusedShared& sh, int64_t nn, int64_t cnt, int cg, float scale, bool f32_tile) {
   const int lane = threadIdx.x & 63;
@@ -459,9 +536,12 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
   pl.mshift = col & 31;
   const uint32_t row_bytes = uint32_t(H) * 4u, mask_bytes = uint32_t(a.mask_words) * 4u;
   PTables tb;
-  tb.coef = make_rsrc(a.coef, uint64_t(a.n_coef) * kCoefRow * 4);
-  tb.b = make_rsrc(a.bg, uint64_t(a.M) * row_bytes);
-  tb.g = make_rsrc(a.bg + a.M * int64_t(H), uint64_t(a.M) * row_bytes);
+  constexpr bool PH = __is_same(CUR, PCurH);
+  static_assert(!(PH && NOBG), "the piece products are the beta / gamma products");
+  const float* __restrict__ tab = PH ? a.bg + piece_table_offset(a.M, H) : a.bg;
+  tb.coef = make_rsrc(PH ? a.bg + piece_coef_offset(a.M, H) : a.coef, uint64_t(a.n_coef) * kCoefRow * 4);
+  tb.b = make_rsrc(tab, uint64_t(a.M) * row_bytes);
+  tb.g = make_rsrc(tab + a.M * int64_t(H), uint64_t(a.M) * row_bytes);
   tb.mask = make_rsrc(a.mask, uint64_t(a.N) * mask_bytes);
   tb.pm = make_rsrc(a.pm, uint64_t(a.cap) * 4);
   tb.pv = make_rsrc(a.pv, uint64_t(a.cap) * 4);
@@ -492,8 +572,11 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) { t1[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f}; y2[t][ct] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   // Two sets of prepared MFMA operands, alternating (p_keep pins them to registers of their own): the next step is prepared
-  // while the MFMAs of the previous one may still be reading theirs.
-  PCur cA = {}, cB = {};
+  // while the MFMAs of the previous one may still be reading theirs.  The pieces have ONE set (cB is cA, p_keep is empty):
+  // the transform of a pair's second step then follows the first step's MFMAs by ordinary register dependency -- the
+  // MFMAs are builtins, hipcc orders the rewrite of their operands behind them.
+  CUR cA = {}, cB_ = {};
+  CUR& cB = PH ? cA : cB_;  // (the pieces: one set)
   // the pair's alpha operands; the fourth register of each (the two empty K slots) stays zero
   PAlpha al;
 #pragma unroll
@@ -524,7 +607,7 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
       mx.oc = more ? mc.oc : mn.oc; mx.ob = more ? mc.ob : mn.ob; mx.om = more ? mc.om : mn.om; mx.w = more ? mc.w : mn.w;
       const int sx = more ? 2 * (j + 1) : 0;
       const bool first = firstc && j == 0, half = !more && 4 * (2 * j + 1) >= kch;  // (wave uniform)
-      pair_body<NOBG, HI>(tb, mx, sx, pl, A, B, cA, cB, al, t1, y2, first, half);
+      pair_body<NOBG, HI, CUR>(tb, mx, sx, pl, A, B, cA, cB, al, t1, y2, first, half);
     }
     if (lastc) {
       // W_1's 48 x 4 values of the lane: twelve 16-byte loads, the YOUNGEST vector-memory operations of the wave from here to
@@ -544,7 +627,10 @@ __device__ __forceinline__ void product_role(const YArgs& a, const int32_t* __re
 #pragma unroll
       for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) bload4<0>(w1[t][r], w1_off + uint32_t(16 * t + r) * w1_row_bytes, w1rs);
+        for (int r = 0; r < 4; ++r) {
+          if (t == 0 && r == 0) bload4<0, true>(w1[t][r], w1_off, w1rs);
+          else bload4<0>(w1[t][r], w1_off + uint32_t(16 * t + r) * w1_row_bytes, w1rs);
+        }
       // tile i & 1 was last read by the Gram of node i - 2: every Gram wave must have counted i - 1 nodes
       if (i >= 2)
         while (lds_min4(sh.done) < int(i) - 1) __builtin_amdgcn_s_sleep(2);
@@ -771,9 +857,6 @@ __device__ __forceinline__ void piece_load(const uint32_t* __restrict__ tile, in
 }
 __device__ __forceinline__ u32x4v piece_u(const PieceBlk& p) { return u32x4v{p.t[2], p.t[3], p.h1[0], p.h1[1]}; }
 __device__ __forceinline__ u32x4v piece_t(const PieceBlk& p) { return p.t; }
-__device__ __forceinline__ f32x4 mfma_f16(u32x4v a, u32x4v b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 // A 16-row chunk: 34 x 2 MFMAs, and the next chunk's reads (at `off` of the tile) as the blocks are used up.
 template <int W>
 __device__ __forceinline__ void piece_chunk16(PieceBlk (&x)[8][2], f32x4 (&acc)[9][2][2], const uint32_t* tile, int off) {
@@ -876,13 +959,16 @@ __device__ __forceinline__ void gram_f16_role(const YArgs& a, const int32_t* __r
 // s (2^-63 .. 2^63) and s^-2 are normal fp32 numbers, the scaled weights w s and alpha pieces stay far inside fp32's range,
 // and a workgroup's sums of s^2 y^2 <= 2^30 cannot overflow; a zero, tiny, huge or non-finite bound (and LGNN_GRAM_F32) gives
 // s = 1 and the fp32 tile and role -- at 2^78 the Gram's entries pass fp32's range themselves.
+// PH: the scale of the instance that runs the beta / gamma products on fp16 pieces (the share of `tri` that stands for the sums'
+// rounding is 2^-9 there, 2^-12 with fp32 products: a piece product carries 2^-21 where the fp32 MFMA carries 2^-24).
 struct GramScale { float s, inv2; bool f32; };
+template <bool PH>
 __device__ __forceinline__ GramScale gram_scale(const YArgs& a, const int32_t* __restrict__ pptr) {
   const float wsum = __int_as_float(pptr[a.N + 1]);  // (the word behind the list's pointers: path_list_reserve)
-  // (PathScale: the smaller of the two triangle inequalities and 2^-12 of the first for the fp32 sums' rounding; `tri` stands
+  // (PathScale: the smaller of the two triangle inequalities and a share of the first for the sums' rounding; `tri` stands
   // in the sum as it is, so a NaN or an infinity in it stays visible whatever fminf does)
   const float tri = a.scale[0] * a.scale[1] + a.scale[2];
-  const float bound = wsum * (fminf(tri, a.scale[3] * a.scale[1]) + 0x1p-12f * tri);
+  const float bound = wsum * (fminf(tri, a.scale[3] * a.scale[1]) + (PH ? 0x1p-9f : 0x1p-12f) * tri);
   const uint32_t eb = __builtin_amdgcn_readfirstlane(int((__float_as_uint(bound) >> 23) & 0x1ffu));  // (a sign bit: a NaN's)
   GramScale g;
   g.f32 = a.gram_f32 != 0 || eb < 78u || eb > 204u;
@@ -891,12 +977,32 @@ __device__ __forceinline__ GramScale gram_scale(const YArgs& a, const int32_t* _
   return g;
 }
 
-// LIST: the node loop runs over a device-side list of the nodes that have a path
-template <bool LIST>
+// The role of a call's launches (kRole*, paths.h), written in front of them into the word of the scale block that both
+// instances of the kernel below read, and that lgnn_last_paths_product_role reports beside the launch's wsum: the products run
+// on pieces where PathScale's rule allows it (a comparison with a NaN is false) and the piece instance's scale is usable.
+// One thread.  -1 where the path list overflowed its buffer (both instances return at once then).  The rule is evaluated here
+// once per call, not in every wave of both instances: each instance's scale then has its role as a constant.
+__global__ void path_role_kernel(YArgs a, const int32_t* __restrict__ pptr, float* __restrict__ sc) {
+  const float tri = a.scale[0] * a.scale[1] + a.scale[2];
+  const bool rule = a.gram_f32 == 0 && a.no_bg == 0 && fminf(tri, a.scale[3] * a.scale[1]) >= ldexpf(tri, -a.piece_share_log2);
+  int role = gram_scale<false>(a, pptr).f32 ? kRoleF32 : kRoleGramF16;
+  if (rule && !gram_scale<true>(a, pptr).f32) role = kRoleProductsF16;
+  if (int64_t(pptr[a.N]) > a.cap) role = kRoleNone;
+  sc[kScaleWsum] = __int_as_float(pptr[a.N + 1]);
+  reinterpret_cast<int32_t*>(sc)[kScaleRole] = role;
+}
+
+// LIST: the node loop runs over a device-side list of the nodes that have a path.  PH: the instance whose product waves run
+// the beta / gamma products on fp16 pieces.  A call launches BOTH instances and the one that path_role_kernel's word does not
+// name returns at once -- two kernels, not two roles in one, so that each instance's registers are allocated for one form of
+// the product role (both forms in one kernel: 256 VGPRs and two of them spilled, 128 / 114 SGPR spills) and the fp32 instance
+// stays the code it was.  (One kernel with the rule as a run-time flag was not tried again after the loads got their pads.)
+template <bool LIST, bool PH>
 __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int32_t* __restrict__ pptr,
                                                              const int32_t* __restrict__ list, float* __restrict__ scratch) {
   __shared__ FusedShared sh;  // ONE LDS object
   if (int64_t(pptr[a.N]) > a.cap) return;  // the path list overflowed its buffer: the enumerating route takes over
+  if ((reinterpret_cast<const int32_t*>(a.scale)[kScaleRole] == kRoleProductsF16) != PH) return;  // (the same in every workgroup)
   // the tiles are zero where nobody writes: columns >= H (zero bits are zero pieces); the fp32 form is the larger one
   static_assert(sizeof(sh.pc) >= sizeof(sh.y) && sizeof(sh.pc) % 16 == 0, "the tiles' union");
   for (int q = threadIdx.x; q < int(sizeof(sh.pc) / 16); q += 512) reinterpret_cast<u32x4v*>(&sh.pc[0][0][0][0])[q] = u32x4v{0u, 0u, 0u, 0u};
@@ -910,21 +1016,24 @@ __global__ __launch_bounds__(512, 2) void paths_fused_kernel(YArgs a, const int3
   const int64_t nn = LIST ? int64_t(__builtin_amdgcn_readfirstlane(*a.n_list)) : a.n1 - a.n0;
   const int64_t cnt = nn > int64_t(blockIdx.x) ? (nn - blockIdx.x + stride - 1) / stride : 0;
   // (hardware waves g and g + 4 share a SIMD: one product wave and one Gram wave on each, see the kernel's header)
-  const GramScale gs = gram_scale(a, pptr);
+  const GramScale gs = gram_scale<PH>(a, pptr);
   switch (hw) {
     // (the Gram role on fp16 pieces unless the launch has no usable scale or LGNN_GRAM_F32 asks for the fp32 one; wave-uniform,
     // and the same choice as the product waves' tile form: both read gs.f32)
-    case 4: if (gs.f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<0, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
-    case 5: if (gs.f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<1, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
-    case 6: if (gs.f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<2, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
-    case 7: if (gs.f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<3, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 4: if (!PH && gs.f32) gram_role<0, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<0, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 5: if (!PH && gs.f32) gram_role<1, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<1, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 6: if (!PH && gs.f32) gram_role<2, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<2, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
+    case 7: if (!PH && gs.f32) gram_role<3, LIST>(a, pptr, list, sh, nn, cnt, scratch); else gram_f16_role<3, LIST>(a, pptr, list, sh, nn, cnt, gs.inv2, scratch); break;
     default:
-      if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
-        if (a.no_bg) product_role<LIST, true, true>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
-        else product_role<LIST, false, true>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
+      if constexpr (PH) {  // (never under no_bg, never with the fp32 tile)
+        if (a.c0 != a.cb) product_role<LIST, false, true, PCurH>(a, pptr, list, sh, nn, cnt, hw, gs.s, false);
+        else product_role<LIST, false, false, PCurH>(a, pptr, list, sh, nn, cnt, hw, gs.s, false);
+      } else if (a.c0 != a.cb) {  // classes cb + 48 ..: the fourth tile of the coefficient slots
+        if (a.no_bg) product_role<LIST, true, true, PCur>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
+        else product_role<LIST, false, true, PCur>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
       } else {
-        if (a.no_bg) product_role<LIST, true, false>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
-        else product_role<LIST, false, false>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
+        if (a.no_bg) product_role<LIST, true, false, PCur>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
+        else product_role<LIST, false, false, PCur>(a, pptr, list, sh, nn, cnt, hw, gs.s, gs.f32);
       }
       break;
   }
@@ -936,18 +1045,29 @@ constexpr int64_t kFusedWorkgroups = 256;
 
 }  // namespace
 
+bool fused_pieces_possible() {
+  const char* e = getenv("LGNN_GRAM_F32");  // =1: the Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
+  return !(e && atoi(e) != 0);
+}
+
 int launch_paths_fused(lgnn_ctx* h, YArgs y, int64_t cb, int64_t ce, float* scratch, hipStream_t s) {
   LGNN_REQUIRE(y.N < (int64_t(1) << 31), "too many nodes for one launch");
   const dim3 grid{unsigned(std::min<int64_t>(y.n1 - y.n0, kFusedWorkgroups))};
   LGNN_REQUIRE(y.scale != nullptr, "internal: the fused kernel needs its scale block");
-  const char* e = getenv("LGNN_GRAM_F32");  // =1: the Gram role on fp32 MFMAs (the A/B arm and fallback); read per call
-  y.Y = nullptr; y.gram_f32 = e && atoi(e) != 0 ? 1 : 0;
+  y.Y = nullptr; y.gram_f32 = fused_pieces_possible() ? 0 : 1;
+  hipLaunchKernelGGL(path_role_kernel, dim3(1), dim3(1), 0, s, y, y.pptr, const_cast<float*>(y.scale));
+  LGNN_HIP_CHECK(hipGetLastError());
   for (int64_t c0 = cb; c0 < ce; c0 += kYRows) {
     y.c0 = int(c0); y.R = int(std::min<int64_t>(kYRows, ce - c0));
     if (h->timing) LGNN_CALL(record_event(h, s));  // dominant kernel of the KFAC path (bench.py roofline)
-    if (y.list) hipLaunchKernelGGL(paths_fused_kernel<true>, grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
-    else hipLaunchKernelGGL(paths_fused_kernel<false>, grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    if (y.list) hipLaunchKernelGGL((paths_fused_kernel<true, false>), grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
+    else hipLaunchKernelGGL((paths_fused_kernel<false, false>), grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
     LGNN_HIP_CHECK(hipGetLastError());
+    if (!y.no_bg && !y.gram_f32) {  // (the piece instance can only be named without either)
+      if (y.list) hipLaunchKernelGGL((paths_fused_kernel<true, true>), grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
+      else hipLaunchKernelGGL((paths_fused_kernel<false, true>), grid, dim3(512), 0, s, y, y.pptr, y.list, scratch);
+      LGNN_HIP_CHECK(hipGetLastError());
+    }
     if (h->timing) { LGNN_CALL(record_event(h, s)); h->ev_planes += y.R; }
   }
   return 0;
