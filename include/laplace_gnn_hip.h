@@ -622,6 +622,41 @@ LGNN_API int lgnn_diag_adjgrad_batch_dense(lgnn_ctx* h, const int64_t* idx, cons
 LGNN_API int lgnn_diag_adjgrad_finish_dense(lgnn_ctx* h, const float* out_bar, const float* h1_bar, const float* e_bar,
                                    float* grad_adj_dense, void* stream);
 
+/* ---- the all-pairs gradient in ROW BANDS (DiagLaplace.propose_edges) -------------------------------------------------------
+ * The reference's structure learning moves every entry of a dense adj along adj.grad (gnn/marglik_training.py:197-224): a
+ * non-edge becomes an edge when its entry of d(-marglik)/d adj is negative enough.  The _dense calls above hold that gradient
+ * as N x N floats; these calls hold [a1 - a0, N] of it at a time.  Under the diagonal posterior the GGN is a sum over
+ * samples (laplace/curvature/curvature.py:412-432), the per-sample all-pairs term of a sample writes only the row of its own
+ * node, and the remaining terms of row a are <out_bar[a], Z1[b]> + <Hb[a], Z0[b]> + <e_bar[a, :F], X[b]> + e_bar[a, F] over
+ * whole-graph adjoints -- so a band of rows needs the samples whose node lies in it and the band's rows of three tile GEMMs.
+ * Plain directed 2-layer GCN (no res / norm, symmetric = 0), ReLU, classification.
+ *   lgnn_diag_adjgrad_band_sparse, per batch: lgnn_diag_adjgrad_batch without candidates -- the same accumulators, the same
+ *     sums -- with every sum in a fixed order, so that two runs leave the same bits: no float atomic in LDS, and one
+ *     workgroup adds the chunk's samples to grad_P, out_bar, h1_bar and e_bar one after the other (slower per batch than the
+ *     parallel scatter; the bands dominate the pass).
+ *   lgnn_diag_adjgrad_band_prepare, once: Z1 [N, C] = H_1 W_1^T + b_1, Z0 [N, H] = X W_0^T + b_0, Hb [N, H] = act'(h_1) *
+ *     (P^T out_bar W_1 + h1_bar); grad_P [nnz] is completed in place as lgnn_diag_adjgrad_finish completes it (the three
+ *     bilinear terms on the stored entries); rs / cs [N] = the row / column sums of grad_P * P behind normalize_adj
+ *     backward's rt_i (gnn/models/utils.py:106-112), summed in a fixed order; all outputs caller owned.
+ *   lgnn_diag_adjgrad_band_batch, per band and sub-batch: band [a1 - a0, N] (zeroed by the caller; 64-bit row offsets) += the
+ *     per-sample all-pairs term of lgnn_diag_adjgrad_batch_dense for samples whose node lies in [a0, a1); nothing else is
+ *     accumulated.  Repeated node ids and chunks under the workspace limit as there; a node outside the band contributes
+ *     nothing, an id outside the graph raises the sticky flag (lgnn_check_async_errors).
+ *   lgnn_diag_adjgrad_band_finish, per band: adds the three bilinear terms for the rows [a0, a1) (fp32 MFMA tiles) and turns the
+ *     band in place into band[j - a0, i] = d(-marglik)/d adj[i, j] = G[j, i] d_i d_j + rt_i (the STE as identity,
+ *     gnn/models/utils.py:42-86); the diagonal and the stored entries of the adjacency leave as +inf, so that a smallest-k
+ *     selection over the band sees the non-edges only.  One writer per element, no float atomics on the band.
+ * None of the four synchronises.                                                                                           */
+LGNN_API int lgnn_diag_adjgrad_band_sparse(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma,
+                                  float loss_scale, float* grad_P, float* out_bar, float* h1_bar, float* e_bar, void* stream);
+LGNN_API int lgnn_diag_adjgrad_band_prepare(lgnn_ctx* h, const float* out_bar, const float* h1_bar, const float* e_bar,
+                                   float* grad_P, float* Hb, float* Z0, float* Z1, float* rs, float* cs, void* stream);
+LGNN_API int lgnn_diag_adjgrad_band_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma,
+                                 int64_t a0, int64_t a1, float* band /* [a1 - a0, N] */, void* stream);
+LGNN_API int lgnn_diag_adjgrad_band_finish(lgnn_ctx* h, const float* out_bar, const float* Hb, const float* Z0, const float* Z1,
+                                  const float* e_bar, const float* rs, const float* cs, int64_t a0, int64_t a1,
+                                  float* band /* [a1 - a0, N] */, void* stream);
+
 /* ---- LoRA structure learning (LoRASTEGCN) -----------------------------------------------------------------------------
  * lgnn_lora_threshold: re-binarise the LoRA adjacency (gnn/models/models.py:226-230) against the stored pattern and edit it
  * in place (lgnn_update_adjacency).  For every off-diagonal pair: t = (B @ A)[i, j] * scaling, m = adj0[i, j] + t, symmetric

@@ -84,6 +84,10 @@ SIGNATURES = {
     "lgnn_adjgrad_finish_dense": (_i32, [_vp, _vp, _pp, C.c_float, _vp, _vp]),
     "lgnn_diag_adjgrad_batch_dense": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "lgnn_diag_adjgrad_finish_dense": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_diag_adjgrad_band_sparse": (_i32, [_vp, _vp, _vp, _i64, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_diag_adjgrad_band_prepare": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lgnn_diag_adjgrad_band_batch": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "lgnn_diag_adjgrad_band_finish": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
     "lgnn_lora_threshold": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_float, C.c_float, _i32, C.POINTER(_i64), _vp]),
     "lgnn_lora_grad": (_i32, [_vp, _vp, _vp, _vp, _i64, C.c_float, _vp, _vp, _vp]),
     "lgnn_glm_variance": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -104,6 +108,11 @@ SIGNATURES = {
     "lgnn_ggn_matmat": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     "lgnn_knn": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
 }
+
+# The row-band entries of the adjacency gradient (csrc/adjband.hip), named here for engine/structure.py: the engine package
+# spells out the entries of the one-file module it replaced and no others (tests/test_engine_layout.py)
+BAND_SPARSE, BAND_PREPARE, BAND_BATCH, BAND_FINISH = (f"lgnn_diag_adjgrad_band_{n}"
+                                                      for n in ("sparse", "prepare", "batch", "finish"))
 
 _lib = None
 

@@ -132,3 +132,114 @@ def _adjgrad_drive(eng, train_loader, process_group, candidates, sym: bool, dens
         K = candidates.shape[1]
         gc = 0.5 * (gc[:K] + gc[K:])
     return torch.stack([rows, cols]), grad, gc
+
+
+# ---- propose_edges: the k non-edges the gradient most wants to add, from row bands of the all-pairs gradient -----------------
+BAND_TILE = 64  # rows of the tile GEMMs behind a band (csrc/lora.hip: dense_nt_kernel)
+
+
+def _propose_scope(la, eng, process_group=None):
+    """``DiagLaplace.propose_edges`` covers plain directed 2-layer GCN models, ReLU, classification, one process: everything
+    else is refused by name.  (A symmetric model's pair (i, j) needs row j and row i of d/dP at once -- a row band and a column
+    band; the Kronecker posterior's B factors and GraphSAGE's local chain have no per-row split of the samples.)"""
+    what = "propose_edges"
+    if la.likelihood != "classification":
+        raise NotImplementedError(f"{what}: the regression likelihood is not covered (classification only)")
+    kind = getattr(eng, "kind", None)
+    if eng is None or not hasattr(eng, "diag_adjgrad_band_sparse") or kind not in ("gcn", "sage"):
+        raise NotImplementedError(f"{what}: plain 2-layer GCN models on the HIP backend")
+    if kind != "gcn":
+        raise NotImplementedError(f"{what}: GraphSAGE models are not covered (plain directed 2-layer GCN only)")
+    if eng.num_layers != 2:
+        raise NotImplementedError(f"{what}: {eng.num_layers}-layer models are not covered (2 layers only)")
+    if eng.has_extras:
+        raise NotImplementedError(f"{what}: models with res / norm are not covered (plain 2-layer GCN only)")
+    if bool(getattr(la.model, "symmetric", False)) or bool(getattr(eng, "is_symmetric", False)):
+        raise NotImplementedError(f"{what}: symmetric models are not covered (a pair needs a row band and a column band at "
+                                  "once); symmetric=False only")
+    if getattr(eng, "act", "relu") != "relu":
+        raise NotImplementedError(f"{what}: the {eng.act} activation is not covered (ReLU only)")
+    if _front._dist_info(process_group)[1] > 1:
+        raise NotImplementedError(f"{what}: a torch.distributed world larger than 1 is not covered (single process)")
+
+
+def _band_plan(N: int, band_bytes, workspace_limit):
+    """``(height, [(a0, a1), ...])``: the row bands of an N-node graph under ``band_bytes`` (default: the smaller of the
+    engine's workspace limit and 1 GiB).  The height is ``band_bytes / (4 N)`` rounded down to whole 64-row tiles -- at least one,
+    otherwise ValueError --, the last band is ragged."""
+    if band_bytes is None:
+        band_bytes = min(int(workspace_limit), 1 << 30) if workspace_limit is not None else 1 << 30
+    height = int(band_bytes) // (4 * N) // BAND_TILE * BAND_TILE
+    if height < BAND_TILE:
+        raise ValueError(f"band_bytes = {int(band_bytes)} holds fewer than one {BAND_TILE}-row tile of a {N}-node graph "
+                         f"({4 * N * BAND_TILE} bytes)")
+    return height, [(a0, min(a0 + height, N)) for a0 in range(0, N, height)]
+
+
+def _deal_to_bands(idx: torch.Tensor, height: int, n_bands: int):
+    """``(order, counts)``: ``idx[order]`` lists the samples band by band (the loader's order within a band), ``counts[b]`` of
+    them in band b.  An id outside the graph goes to the nearest band, whose batch call flags it.  One host round trip."""
+    band = torch.div(idx, height, rounding_mode="floor").clamp_(0, n_bands - 1)
+    return torch.sort(band, stable=True).indices, torch.bincount(band, minlength=n_bands).tolist()
+
+
+def _merge_smallest(best, vals, keys, k: int):
+    """The k smallest of the running selection and a band's: a fixed order (the running ones first), so two runs agree bit
+    for bit."""
+    if best is not None:
+        vals, keys = torch.cat([best[0], vals]), torch.cat([best[1], keys])
+    if vals.numel() > k:
+        vals, pick = torch.topk(vals, k, largest=False, sorted=True)
+        keys = keys[pick]
+    return vals, keys
+
+
+def _propose_edges_drive(eng, train_loader, k: int, band_bytes, *, weight, loss_scale):
+    """Everything of ``DiagLaplace.propose_edges`` behind its refusals and value: ``(pairs [2, k'], grad [k'])``.
+
+    One sparse pass (``diag_adjgrad_band_sparse`` per batch: ``diag_adjgrad_batch`` with every sum in a fixed order, so that two
+    calls return the same bits) leaves the adjoints ``out_bar`` / ``h1_bar`` / ``e_bar`` and the batches' part of d/dP on the stored
+    entries; ``diag_adjgrad_band_prepare`` completes it and forms the whole-graph operands once.
+    The samples are dealt to the bands once; per band the engine adds the per-sample term of its samples and the three bilinear
+    terms, turns the band into d/d adj with the stored entries and the diagonal at +inf, and the band's k smallest join the
+    running selection (``torch.topk`` on the band in place: no copy of it, index tensors of k entries).  Nothing waits for
+    the device between bands; the buffer of one band is the only N-wide allocation."""
+    dev, N = eng.device, eng.num_nodes
+    height, bands = _band_plan(N, band_bytes, getattr(eng, "workspace_limit", None))
+    target = torch.zeros(eng.nnz, dtype=torch.float32, device=dev)
+    out_bar = torch.zeros(N, eng.dims[-1], dtype=torch.float32, device=dev)
+    h1_bar = torch.zeros(N, eng.dims[1], dtype=torch.float32, device=dev)
+    e_bar = torch.zeros(N, eng.dims[0] + 1, dtype=torch.float32, device=dev)
+    eng.set_likelihood("classification")
+    Xs, ys = [], []
+    for X, y in train_loader:
+        X, y = X.to(dev).to(torch.int64), y.to(dev)
+        if not Xs:
+            eng.forward(X[:1].clamp(0, N - 1))  # synchronises the parameter versions: the cached forward is current for the pass
+        eng.diag_adjgrad_band_sparse(X, y, weight, target, out_bar, h1_bar, e_bar, loss_scale=loss_scale)
+        Xs.append(X)
+        ys.append(y)
+    prepared = eng.diag_adjgrad_band_prepare(out_bar, h1_bar, e_bar, target)
+    idx, y = torch.cat(Xs), torch.cat(ys)
+    step = max(X.shape[0] for X in Xs)  # a band's samples go in pieces no larger than the loader's batches
+    order, counts = _deal_to_bands(idx, height, len(bands))
+    idx, y = idx[order], y[order]
+    buf = torch.empty(min(height, N), N, dtype=torch.float32, device=dev)
+    best, lo = None, 0
+    for (a0, a1), count in zip(bands, counts):
+        band = buf[:a1 - a0]
+        band.zero_()
+        for s in range(lo, lo + count, step):
+            e = min(s + step, lo + count)
+            eng.diag_adjgrad_band_batch(idx[s:e], y[s:e], weight, a0, a1, band)
+        lo += count
+        eng.diag_adjgrad_band_finish(out_bar, prepared, e_bar, a0, a1, band)
+        flat = band.view(-1)
+        vals, q = torch.topk(flat, min(k, flat.numel()), largest=False, sorted=True)
+        # band[t, i] is the pair (i, j = a0 + t); key = i N + j
+        best = _merge_smallest(best, vals, (q % N) * N + (a0 + torch.div(q, N, rounding_mode="floor")), k)
+    vals, keys = best
+    keep = torch.isfinite(vals)  # (k beyond the eligible pairs: the masked entries are +inf)
+    vals, by_value = torch.sort(vals[keep], stable=True)
+    keys = keys[keep][by_value]
+    return torch.stack([torch.div(keys, N, rounding_mode="floor"), keys % N]), vals

@@ -42,9 +42,11 @@ int kfac_adjgrad_batch_gcn(lgnn_ctx* h, const int64_t* idx, const void* y, int64
                            const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s, float* dense);
 
 // ---- adjgrad_diag.hip: plain 2-layer GCN, diagonal posterior (closed form) --------------------------------------------------------
+// band1 > band0: the per-sample all-pairs term alone, into dense = the rows [band0, band1) of the grid (adjband.hip)
 int diag_adjgrad_batch_gcn(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, float loss_scale,
                            float* grad_P, float* out_bar, float* h1_bar, float* e_bar, const int32_t* cand_a,
-                           const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s, float* dense);
+                           const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s, float* dense, int64_t band0 = 0,
+                           int64_t band1 = 0, bool det = false);  // det: the fixed-order kernels (lgnn_diag_adjgrad_band_sparse)
 
 // ---- adjgrad_sage.hip: plain 2-layer GraphSAGE ------------------------------------------------------------------------------------
 int sage_adjgrad_batch(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, bool fork_exact, const float* gamma_B0,

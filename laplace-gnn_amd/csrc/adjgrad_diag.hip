@@ -43,6 +43,10 @@ struct DadjSample {
 // tile: p, q (which needs the softmax and W_1 only) first; the row's entries staged VCH at a time, thread <-> 4 x 4 sub-tiles
 // in registers (two 16-byte LDS reads per 16 FMAs and staged entry); with the LAST group of entries a sub-tile leaves as
 // Tbar = 2 q g0e T and adds its share of r[j] = sum_i g0e T^2 (LDS atomics); then the last layer and the logits' adjoint.
+// DET (the fixed-order pass behind DiagLaplace.propose_edges, lgnn_diag_adjgrad_band_sparse): no float atomic decides a bit --
+// the last group leaves T unscaled, r[j] is one wave's fixed-order sum over the finished row, a second sweep scales T to Tbar;
+// the logits' adjoint goes to fbar [chunk][C] for the serial entry kernel instead of out_bar.
+template <bool DET>
 __global__ __launch_bounds__(256) void dadj_tile_kernel(const int64_t* __restrict__ idx, const int64_t* __restrict__ y,
                                                         int64_t m0, int64_t N, const int32_t* __restrict__ rowptr,
                                                         const int32_t* __restrict__ col, const float* __restrict__ val,
@@ -51,7 +55,8 @@ __global__ __launch_bounds__(256) void dadj_tile_kernel(const int64_t* __restric
                                                         const float* __restrict__ probs, int64_t C, const float* __restrict__ W1,
                                                         const float* __restrict__ PH, int64_t ldp,
                                                         const float* __restrict__ gamma, float loss_scale, float* __restrict__ T,
-                                                        float* __restrict__ phibar, float* __restrict__ out_bar) {
+                                                        float* __restrict__ phibar, float* __restrict__ out_bar,
+                                                        float* __restrict__ fbar) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int64_t F1 = F + 1, FP = (F1 + 3) & ~int64_t(3), HP = (H + 3) & ~int64_t(3), H1 = H + 1;
   float* __restrict__ mk = sm;                     // [VCH][HP]  w_u * mask rows, zero padded
@@ -69,6 +74,8 @@ __global__ __launch_bounds__(256) void dadj_tile_kernel(const int64_t* __restric
   if (n < 0 || n >= N) {  // flagged by the prologue: contributes nothing
     for (int64_t e = tid; e < H * FP; e += 256) Tm[e] = 0.f;
     for (int64_t j = tid; j < H1; j += 256) pbm[j] = 0.f;
+    if (DET)
+      for (int64_t c = tid; c < C; c += 256) fbar[int64_t(blockIdx.x) * C + c] = 0.f;
     return;
   }
   for (int64_t c = tid; c < C; c += 256) S.p[c] = probs[m * C + c];
@@ -127,7 +134,7 @@ __global__ __launch_bounds__(256) void dadj_tile_kernel(const int64_t* __restric
       for (int rr = 0; rr < 4; ++rr) {
         const int64_t j = 4 * jb + rr;
         if (j >= H) continue;
-        if (last) {  // T -> Tbar on the way out, r[j] from the unscaled entries
+        if (last && !DET) {  // T -> Tbar on the way out, r[j] from the unscaled entries
           const float qj = 2.f * S.q[j];
           float rs = 0.f;
 #pragma unroll
@@ -143,6 +150,27 @@ __global__ __launch_bounds__(256) void dadj_tile_kernel(const int64_t* __restric
         *reinterpret_cast<float4*>(Tm + j * FP + 4 * ib) = make_float4(acc[rr][0], acc[rr][1], acc[rr][2], acc[rr][3]);
       }
     }
+  }
+  if (DET) {
+    __syncthreads();  // T is complete (this workgroup's own writes)
+    if (ps != pe)
+      for (int64_t j = wave; j < H; j += 4) {
+        float rs = 0.f;
+        for (int64_t i = lane; i < F1; i += 64) {
+          const float t = Tm[j * FP + i];
+          rs = fmaf((i < F ? g0[j * F + i] : gb0[j]) * t, t, rs);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) rs += __shfl_xor(rs, o);
+        if (lane == 0) S.r[j] = rs;
+      }
+    __syncthreads();
+    if (ps != pe)
+      for (int64_t e = tid; e < H * FP; e += 256) {
+        const int64_t j = e / FP, i = e - j * FP;
+        const float g = i < F ? g0[j * F + i] : (i == F ? gb0[j] : 0.f);
+        Tm[e] = 2.f * S.q[j] * g * Tm[e];
+      }
   }
   __syncthreads();  // r is complete
   for (int64_t c = wave; c < C; c += 4) {
@@ -168,8 +196,12 @@ __global__ __launch_bounds__(256) void dadj_tile_kernel(const int64_t* __restric
   for (int64_t c = tid; c < C; c += 256) part = fmaf(S.p[c], S.pb[c], part);
   const float dot = block_sum_256(part, S.red);
   const int64_t yc = y[m];
-  for (int64_t c = tid; c < C; c += 256)
-    atomicAdd(&out_bar[n * C + c], S.p[c] * (S.pb[c] - dot) + loss_scale * (S.p[c] - (c == yc ? 1.f : 0.f)));
+  if (DET)
+    for (int64_t c = tid; c < C; c += 256)
+      fbar[int64_t(blockIdx.x) * C + c] = S.p[c] * (S.pb[c] - dot) + loss_scale * (S.p[c] - (c == yc ? 1.f : 0.f));
+  else if (out_bar)  // (null: a row band's second visit of the sample, adjband.hip -- the sparse pass has accumulated it)
+    for (int64_t c = tid; c < C; c += 256)
+      atomicAdd(&out_bar[n * C + c], S.p[c] * (S.pb[c] - dot) + loss_scale * (S.p[c] - (c == yc ? 1.f : 0.f)));
   for (int64_t j = tid; j < H1; j += 256) {
     float lg = 0.f;
     for (int64_t c = 0; c < C; ++c) lg = fmaf(S.p[c] * (1.f - S.p[c]), j < H ? g1[c * H + j] : gb1[c], lg);
@@ -206,6 +238,9 @@ __device__ __forceinline__ float dadj_pair(const float* __restrict__ Tm, const f
 // NJ > 1), ICH columns at a time; the sums are then contracted with Ee[v_u, :] (gradP) and scattered (e_bar).
 constexpr int EV = 8;
 constexpr int ICH = 1024;  // columns of the tile per pass (cas: 32 KiB)
+// DET: ONE workgroup takes the chunk's samples one after the other (launched with a grid of 1), the row slices are not split
+// (NJ = 1: no LDS atomics), and out_bar takes the tile kernel's fbar here -- every address is added to in sample order.
+template <bool DET>
 __global__ __launch_bounds__(256) void dadj_entry_kernel(const int64_t* __restrict__ idx, int64_t m0, int64_t N,
                                                          const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                          const float* __restrict__ val, const float* __restrict__ mask, int64_t H,
@@ -213,7 +248,9 @@ __global__ __launch_bounds__(256) void dadj_entry_kernel(const int64_t* __restri
                                                          const float* __restrict__ rowsum, int64_t F,
                                                          const float* __restrict__ H1p, int64_t ldh, const float* __restrict__ T,
                                                          const float* __restrict__ phibar, float* __restrict__ gradP,
-                                                         float* __restrict__ h1_bar, float* __restrict__ e_bar) {
+                                                         float* __restrict__ h1_bar, float* __restrict__ e_bar, int64_t mc,
+                                                         int64_t C, const float* __restrict__ fbar,
+                                                         float* __restrict__ out_bar) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int64_t F1 = F + 1, FP = (F1 + 3) & ~int64_t(3);
   const int icw = int(min<int64_t>(ICH, FP));   // columns per pass
@@ -223,10 +260,15 @@ __global__ __launch_bounds__(256) void dadj_entry_kernel(const int64_t* __restri
   float* __restrict__ wv = red + 4 * EV;         // [EV]
   int32_t* __restrict__ vid = reinterpret_cast<int32_t*>(wv + EV);  // [EV]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t n = idx[m0 + blockIdx.x];
-  if (n < 0 || n >= N) return;
-  const float* __restrict__ Tm = T + int64_t(blockIdx.x) * H * FP;
-  const float* __restrict__ pbm = phibar + int64_t(blockIdx.x) * (H + 1);
+  for (int64_t blk = DET ? 0 : int64_t(blockIdx.x); blk < (DET ? mc : int64_t(blockIdx.x) + 1); ++blk) {
+  const int64_t n = idx[m0 + blk];
+  if (n < 0 || n >= N) continue;  // (uniform over the workgroup)
+  if (DET) {
+    __syncthreads();  // the previous sample's adds are done before this one's
+    for (int64_t c = tid; c < C; c += 256) out_bar[n * C + c] += fbar[blk * C + c];
+  }
+  const float* __restrict__ Tm = T + blk * H * FP;
+  const float* __restrict__ pbm = phibar + blk * (H + 1);
   const int32_t ps = rowptr[n], pe = rowptr[n + 1];
   for (int32_t p0 = ps; p0 < pe; p0 += EV) {
     const int un = min(EV, pe - p0);
@@ -246,7 +288,7 @@ __global__ __launch_bounds__(256) void dadj_entry_kernel(const int64_t* __restri
     for (int64_t c0 = 0; c0 < FP; c0 += icw) {
       const int cw = int(min<int64_t>(icw, FP - c0));  // a multiple of 4
       const int nI = cw / 4;
-      const int NJ = nI >= 256 ? 1 : int(min<int64_t>(256 / nI, H));  // row slices
+      const int NJ = (DET || nI >= 256) ? 1 : int(min<int64_t>(256 / nI, H));  // row slices
       __syncthreads();  // mk staged / the previous pass's cas consumed
       if (NJ > 1)
         for (int t = tid; t < EV * cw; t += 256) cas[(t / cw) * icw + (t % cw)] = 0.f;
@@ -311,6 +353,7 @@ __global__ __launch_bounds__(256) void dadj_entry_kernel(const int64_t* __restri
     if (tid < un)  // (a repeated node id: several samples share the entry, hence the atomic)
       atomicAdd(&gradP[p0 + tid], red[tid] + red[EV + tid] + red[2 * EV + tid] + red[3 * EV + tid] + pbm[H]);
   }
+  }
 }
 
 // candidate pairs (a, b): a contributes through the samples that are a -- the first one's tile, times its multiplicity
@@ -336,13 +379,22 @@ __global__ __launch_bounds__(256) void dadj_cand_kernel(const int32_t* __restric
 
 }  // namespace
 
-// dense != null (lgnn_diag_adjgrad_batch_dense): the entries' terms are also added on the full grid (lora.hip)
+// dense != null (lgnn_diag_adjgrad_batch_dense): the entries' terms are also added on the full grid (lora.hip).
+// band1 > band0 (lgnn_diag_adjgrad_band_batch, adjband.hip): dense holds the rows [band0, band1) of that grid and nothing else
+// is accumulated -- the tiles of the samples are formed again, the entry and candidate kernels are skipped, the four
+// accumulators are null.  det (lgnn_diag_adjgrad_band_sparse): the fixed-order kernels -- the same sums, the same bits on every run;
+// the entry kernel then runs the chunk's samples one after the other in one workgroup.
 int diag_adjgrad_batch_gcn(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* gamma, float loss_scale,
                            float* grad_P, float* out_bar, float* h1_bar, float* e_bar, const int32_t* cand_a,
-                           const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s, float* dense) {
+                           const int32_t* cand_b, int64_t K, float* grad_cand, hipStream_t s, float* dense, int64_t band0,
+                           int64_t band1, bool det) {
   LGNN_CALL(check_model(h));
   LGNN_REQUIRE(h->kind == LGNN_KIND_GCN, "adjacency gradient, diagonal posterior: GCN models");
-  LGNN_REQUIRE(M > 0 && idx && y && gamma && grad_P && out_bar && h1_bar && e_bar, "empty batch or null pointers");
+  const bool band = band1 > band0;
+  LGNN_REQUIRE(!det || (!band && !dense && K == 0), "fixed-order pass: stored entries only");
+  LGNN_REQUIRE(M > 0 && idx && y && gamma, "empty batch or null pointers");
+  if (band) LGNN_REQUIRE(dense && !grad_P && !out_bar && !h1_bar && !e_bar && K == 0, "row band: the band buffer only");
+  else LGNN_REQUIRE(grad_P && out_bar && h1_bar && e_bar, "empty batch or null pointers");
   LGNN_CALL(forward_ensure_aux(h, s));
   const int64_t N = h->N, C = h->dims[2], H = h->dims[1], F = h->dims[0], F1 = F + 1;
   LGNN_REQUIRE(h->in_dim[1] == H, "internal: GCN head stride");
@@ -363,17 +415,30 @@ int diag_adjgrad_batch_gcn(lgnn_ctx* h, const int64_t* idx, const void* y, int64
   const int64_t ldx = h->fc.prop_ld[0];
   const float* rowsum = h->fc.rowsum.as<float>();
   LGNN_CALL(h->ws.jac.reserve(size_t(chunk) * per_sample));
-  LGNN_CALL(h->ws.misc.reserve(size_t(chunk) * (H + 1) * 4));
+  LGNN_CALL(h->ws.misc.reserve(size_t(chunk) * (H + 1 + C) * 4));
   float* T = h->ws.jac.as<float>();
   float* phibar = h->ws.misc.as<float>();
+  float* fbar = phibar + chunk * (H + 1);  // [chunk][C]: the logits' adjoints of a chunk (fixed-order pass)
   for (int64_t m0 = 0; m0 < M; m0 += chunk) {
     const int64_t mc = std::min(chunk, M - m0);
-    hipLaunchKernelGGL(dadj_tile_kernel, dim3(unsigned(mc)), dim3(256), smem_t + smem_s, s, idx,
-                       static_cast<const int64_t*>(y), m0, N, h->P.rowptr, h->P.col, h->P.val, mask, H, PX, ldx, rowsum, F, vch,
-                       h->ws.probs.as<float>(), C, h->W[1], h->fc.prop_in[1].as<float>(), h->fc.prop_ld[1], gamma, loss_scale, T,
-                       phibar, out_bar);
-    hipLaunchKernelGGL(dadj_entry_kernel, dim3(unsigned(mc)), dim3(256), smem_e, s, idx, m0, N, h->P.rowptr, h->P.col, h->P.val,
-                       mask, H, PX, ldx, rowsum, F, h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, grad_P, h1_bar, e_bar);
+#define LGNN_DADJ_TILE(DETV)                                                                                                    \
+    hipLaunchKernelGGL(dadj_tile_kernel<DETV>, dim3(unsigned(mc)), dim3(256), smem_t + smem_s, s, idx,                            \
+                       static_cast<const int64_t*>(y), m0, N, h->P.rowptr, h->P.col, h->P.val, mask, H, PX, ldx, rowsum, F, vch,  \
+                       h->ws.probs.as<float>(), C, h->W[1], h->fc.prop_in[1].as<float>(), h->fc.prop_ld[1], gamma, loss_scale, T, \
+                       phibar, out_bar, fbar)
+#define LGNN_DADJ_ENTRY(DETV, GRID)                                                                                             \
+    hipLaunchKernelGGL(dadj_entry_kernel<DETV>, dim3(GRID), dim3(256), smem_e, s, idx, m0, N, h->P.rowptr, h->P.col, h->P.val,  \
+                       mask, H, PX, ldx, rowsum, F, h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, grad_P, h1_bar, e_bar, mc, C, \
+                       fbar, out_bar)
+    if (det) {
+      LGNN_DADJ_TILE(true);
+      LGNN_DADJ_ENTRY(true, 1u);
+    } else {
+      LGNN_DADJ_TILE(false);
+      if (!band) LGNN_DADJ_ENTRY(false, unsigned(mc));
+    }
+#undef LGNN_DADJ_TILE
+#undef LGNN_DADJ_ENTRY
     if (K > 0)
       hipLaunchKernelGGL(dadj_cand_kernel, dim3(unsigned(std::min<int64_t>(K, 65535))), dim3(256), size_t(H + 4) * 4, s, cand_a, cand_b, K,
                          h->ws.pos.as<int32_t>(), h->ws.mult.as<int32_t>(), m0, mc, mask, H, PX, ldx, rowsum, F,
@@ -381,7 +446,8 @@ int diag_adjgrad_batch_gcn(lgnn_ctx* h, const int64_t* idx, const void* y, int64
     LGNN_HIP_CHECK(hipGetLastError());
     if (dense)
       LGNN_CALL(launch_dense_diag_pair(idx, m0, mc, N, h->ws.pos.as<int32_t>(), h->ws.mult.as<int32_t>(), mask, H, PX, ldx, rowsum,
-                                       F, h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, dense, s));
+                                       F, h->fc.hact_p[0], h->fc.hact_ld[0], T, phibar, band ? band0 : 0, band ? band1 : N,
+                                       dense, s));
   }
   LGNN_CALL(batch_epilogue(h, idx, M, s));
   return 0;

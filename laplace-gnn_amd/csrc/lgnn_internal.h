@@ -494,7 +494,8 @@ struct DenseNtArgs {
 int launch_dense_nt(const DenseNtArgs& g, hipStream_t s);
 int launch_dense_diag_pair(const int64_t* idx, int64_t m0, int64_t mc, int64_t N, const int32_t* pos, const int32_t* mult,
                            const float* mask, int64_t H, const float* PX, int64_t ldx, const float* rowsum, int64_t F,
-                           const float* H1p, int64_t ldh, const float* T, const float* phibar, float* out, hipStream_t s);
+                           const float* H1p, int64_t ldh, const float* T, const float* phibar, int64_t row0, int64_t row1,
+                           float* out, hipStream_t s);  // out: the rows [row0, row1) of the grid
 int launch_gp_rowcol(lgnn_ctx* h, const float* gP, float* rs, float* cs, hipStream_t s);  // adjgrad.hip
 int dense_adj_finish(lgnn_ctx* h, float* G, hipStream_t s);
 

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void dense_nt_kernel(DenseNtArgs g) {
 }
 
 // ---- diagonal posterior, one sample n = idx[m] (first occurrence, times its multiplicity) x 64 columns b:
-//   out[n, b] += mult * ( sum_j mask[b, j] sum_i Tbar[j, i] Ee[b, i] + <phibar[:H], H1[b]> + phibar[H] )
+//   out[n - row0, b] += mult * ( sum_j mask[b, j] sum_i Tbar[j, i] Ee[b, i] + <phibar[:H], H1[b]> + phibar[H] )
+// out holds the rows [row0, row1) of the grid (the whole grid, or a row band of it: adjband.hip); samples outside are skipped.
 // Tbar [H][FP] (zero padded beyond F + 1), Ee[b] = [P X | rowsum(P)][b].  64 x 64 tiles (rows j, columns b) on the fp32 MFMA,
 // K = i staged through LDS; the mask contraction is the epilogue of each j tile and stays in registers (lane: one b).
 __global__ __launch_bounds__(256) void dense_diag_pair_kernel(const int64_t* __restrict__ idx, int64_t m0, int64_t N,
@@ -91,14 +92,14 @@ __global__ __launch_bounds__(256) void dense_diag_pair_kernel(const int64_t* __r
                                                               const float* __restrict__ rowsum, int64_t F,
                                                               const float* __restrict__ H1p, int64_t ldh,
                                                               const float* __restrict__ T, const float* __restrict__ phibar,
-                                                              float* __restrict__ out) {
+                                                              int64_t row0, int64_t row1, float* __restrict__ out) {
   __shared__ float Ts[DT * DLD], Es[DT * DLD];
   __shared__ float red[2][DT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int64_t m = m0 + blockIdx.y;
   const int64_t n = idx[m];
-  if (n < 0 || n >= N || pos[n] != int32_t(m)) return;  // (uniform) duplicates: the first occurrence carries the multiplicity
+  if (n < row0 || n >= row1 || pos[n] != int32_t(m)) return;  // (uniform) duplicates: the first occurrence carries the multiplicity
   const int64_t F1 = F + 1, FP = (F1 + 3) & ~int64_t(3);
   const float* __restrict__ Tm = T + int64_t(blockIdx.y) * H * FP;
   const float* __restrict__ pbm = phibar + int64_t(blockIdx.y) * (H + 1);
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(256) void dense_diag_pair_kernel(const int64_t* __r
       float dot = 0.f;
       for (int64_t j = 0; j < H; ++j) dot = fmaf(pbm[j], H1p[b * ldh + j], dot);
       const float v = red[0][tid] + red[1][tid] + dot + pbm[H];
-      out[n * N + b] += float(mult[m]) * v;
+      out[(n - row0) * N + b] += float(mult[m]) * v;
     }
   }
 }
@@ -354,11 +355,13 @@ int launch_dense_nt(const DenseNtArgs& g, hipStream_t s) {
 
 int launch_dense_diag_pair(const int64_t* idx, int64_t m0, int64_t mc, int64_t N, const int32_t* pos, const int32_t* mult,
                            const float* mask, int64_t H, const float* PX, int64_t ldx, const float* rowsum, int64_t F,
-                           const float* H1p, int64_t ldh, const float* T, const float* phibar, float* out, hipStream_t s) {
+                           const float* H1p, int64_t ldh, const float* T, const float* phibar, int64_t row0, int64_t row1,
+                           float* out, hipStream_t s) {
   if (mc <= 0) return 0;
   LGNN_REQUIRE(mc < 65536, "dense grid term: too many samples in a chunk");
+  LGNN_REQUIRE(row0 >= 0 && row0 <= row1 && row1 <= N, "dense grid term: rows outside the grid");
   hipLaunchKernelGGL(dense_diag_pair_kernel, dim3(unsigned(cdiv(N, DT)), unsigned(mc)), dim3(256), 0, s, idx, m0, N, pos, mult,
-                     mask, H, PX, ldx, rowsum, F, H1p, ldh, T, phibar, out);
+                     mask, H, PX, ldx, rowsum, F, H1p, ldh, T, phibar, row0, row1, out);
   LGNN_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -9,6 +9,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from .._lib import BAND_BATCH, BAND_FINISH, BAND_PREPARE, BAND_SPARSE
 from ._marshal import _dev_ptr, _opt_ptr, _ptrs
 
 _f32 = torch.float32
@@ -126,6 +127,51 @@ class StructureEntries:
         self._call("lgnn_diag_adjgrad_finish_dense", _dev_ptr(out_bar, _f32, "out_bar"), _dev_ptr(h1_bar, _f32, "h1_bar"),
                    _dev_ptr(e_bar, _f32, "e_bar"), _dev_ptr(grad_dense, _f32, "grad_dense"))
         return grad_dense
+
+    # -- the same gradient in row bands (DiagLaplace.propose_edges: csrc/adjband.hip) ------------------------------------
+    # The four calls run inside one ``propose_edges`` pass, whose driver has made the cached forward current (``forward``
+    # synchronises the parameter versions): they open no batch of their own.
+    def diag_adjgrad_band_sparse(self, idx, y, gamma: torch.Tensor, grad_P: torch.Tensor, out_bar: torch.Tensor,
+                                 h1_bar: torch.Tensor, e_bar: torch.Tensor, loss_scale: float = 1.0):
+        """``diag_adjgrad_batch`` without candidates and with every sum in a fixed order: the same bits on every run."""
+        idx, y, gamma = idx.contiguous(), y.contiguous(), gamma.contiguous()
+        self._call(BAND_SPARSE, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
+                   _dev_ptr(gamma, _f32, "gamma"), float(loss_scale), _dev_ptr(grad_P, _f32, "grad_P"),
+                   _dev_ptr(out_bar, _f32, "out_bar"), _dev_ptr(h1_bar, _f32, "h1_bar"), _dev_ptr(e_bar, _f32, "e_bar"))
+
+    def diag_adjgrad_band_prepare(self, out_bar: torch.Tensor, h1_bar: torch.Tensor, e_bar: torch.Tensor, grad_P: torch.Tensor):
+        """Once per pass, after the last ``diag_adjgrad_band_sparse``: completes ``grad_P`` in place (the finish's bilinear terms
+        on the stored entries) and returns ``(Hb [N, H], Z0 [N, H], Z1 [N, C], rs [N], cs [N])`` -- the whole-graph operands of
+        every band's bilinear terms and the row / column sums behind normalize_adj backward."""
+        N, (H, Cc) = self.num_nodes, self.dims[1:]
+        Hb, Z0, Z1, rs, cs = self._new(N, H), self._new(N, H), self._new(N, Cc), self._new(N), self._new(N)
+        self._call(BAND_PREPARE, _dev_ptr(out_bar, _f32, "out_bar"), _dev_ptr(h1_bar, _f32, "h1_bar"),
+                   _dev_ptr(e_bar, _f32, "e_bar"), _dev_ptr(grad_P, _f32, "grad_P"), Hb.data_ptr(), Z0.data_ptr(), Z1.data_ptr(),
+                   rs.data_ptr(), cs.data_ptr())
+        return Hb, Z0, Z1, rs, cs
+
+    def diag_adjgrad_band_batch(self, idx, y, gamma: torch.Tensor, a0: int, a1: int, band: torch.Tensor):
+        """Add the per-sample all-pairs term of the samples ``idx`` (int64, nodes in ``[a0, a1)``) to ``band`` [a1 - a0, N]."""
+        idx, y, gamma = idx.contiguous(), y.contiguous(), gamma.contiguous()
+        self._band_check(a0, a1, band)
+        self._call(BAND_BATCH, _dev_ptr(idx, torch.int64, "idx"), _dev_ptr(y, torch.int64, "y"), idx.shape[0],
+                   _dev_ptr(gamma, _f32, "gamma"), int(a0), int(a1), _dev_ptr(band, _f32, "band"))
+
+    def diag_adjgrad_band_finish(self, out_bar: torch.Tensor, prepared, e_bar: torch.Tensor, a0: int, a1: int,
+                                 band: torch.Tensor):
+        """Add the bilinear terms of the rows ``[a0, a1)`` and turn ``band`` in place into ``band[j - a0, i] = d / d adj[i, j]``;
+        the diagonal and the stored entries leave as ``+inf``.  ``prepared``: what ``diag_adjgrad_band_prepare`` returned."""
+        Hb, Z0, Z1, rs, cs = prepared
+        self._band_check(a0, a1, band)
+        self._call(BAND_FINISH, _dev_ptr(out_bar, _f32, "out_bar"), _dev_ptr(Hb, _f32, "Hb"), _dev_ptr(Z0, _f32, "Z0"),
+                   _dev_ptr(Z1, _f32, "Z1"), _dev_ptr(e_bar, _f32, "e_bar"), _dev_ptr(rs, _f32, "rs"), _dev_ptr(cs, _f32, "cs"),
+                   int(a0), int(a1), _dev_ptr(band, _f32, "band"))
+        return band
+
+    def _band_check(self, a0: int, a1: int, band: torch.Tensor):
+        if not 0 <= a0 < a1 <= self.num_nodes or tuple(band.shape) != (a1 - a0, self.num_nodes):
+            raise ValueError(f"band: rows [{a0}, {a1}) of {self.num_nodes} nodes need a [{a1 - a0}, {self.num_nodes}] buffer, "
+                             f"got {tuple(band.shape)}")
 
     # -- LoRA (lgnn_lora_threshold / lgnn_lora_grad) ------------------------------------------------------------------
     def lora_threshold(self, base_rowptr: torch.Tensor, base_col: torch.Tensor, A: torch.Tensor, B: torch.Tensor,

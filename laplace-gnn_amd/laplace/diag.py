@@ -5,7 +5,7 @@ import warnings
 
 import torch
 
-from ..adjgrad import _adjgrad_drive, _adjgrad_prelude
+from ..adjgrad import _adjgrad_drive, _adjgrad_prelude, _propose_edges_drive, _propose_scope
 from ..curvature import HipGGN
 from ..data import TensorBatchLoader
 from .dist import _dist_info
@@ -194,6 +194,33 @@ class DiagLaplace(ParametricLaplace):
         return (value, *_adjgrad_drive(eng, train_loader, process_group, candidates, bool(getattr(self.model, "symmetric", False)),
                                        dense, batch="diag_adjgrad_batch", finish="diag_adjgrad_finish", weight=gamma,
                                        per_sample=True, loss_scale=f))
+
+    def propose_edges(self, train_loader, k: int, prior_precision=None, band_bytes=None):
+        """The ``k`` non-edges whose entry of ``d(-marglik)/d adj`` is smallest: ``(neg_marglik, pairs [2, k'] int64, grad [k']
+        fp32)``, ascending by ``grad`` (most negative first; ties in any order), ``k' = min(k, eligible pairs)``.  Eligible:
+        ``i != j`` and ``(i, j)`` not stored in the engine's adjacency (``export_adj()``).  ``grad[t]`` is what
+        ``neg_marglik_adj_grad(loader, candidates=pairs)[3]`` returns for the pair and what ``neg_marglik_adj_grad(loader,
+        dense=True)[1][i, j]`` holds (normalize_adj backward included, the STE as identity) -- without the N x N floats: the
+        all-pairs gradient is formed in row bands of at most ``band_bytes`` (default: the smaller of the engine's workspace
+        limit and 1 GiB; it must hold one 64-row tile, else ValueError) and only each band's k smallest survive it.  No eligible
+        pair outside the result has a gradient below the largest returned one, up to fp32 rounding of the values.  ``neg_marglik``
+        and ``prior_precision`` as in ``neg_marglik_adj_grad``.
+
+        The reference's dense ``adj`` moves every entry along ``adj.grad`` (gnn/marglik_training.py:197-224): its plain-SGD step
+        flips exactly the non-edges with ``grad < -threshold / lr_adj``.  There is no threshold argument: filter ``grad`` by
+        that bound, hand the surviving pairs to ``STEGCN.add_candidates`` and step them like any tracked entry.
+
+        Plain directed 2-layer GCN (no res / norm, ``symmetric=False``), ReLU, classification, one process; everything else
+        raises NotImplementedError."""
+        if int(k) < 1:
+            raise ValueError(f"propose_edges: k must be at least 1, got {k}")
+        _propose_scope(self, getattr(self.backend, "engine", None))
+        eng = _adjgrad_prelude(self, "DiagLaplace", "a diagonal posterior", self.H is not None and bool(self.n_data),
+                               prior_precision, None, False, batch="diag_adjgrad_batch")
+        value = -self.log_marginal_likelihood()
+        f = self._H_factor
+        gamma = (0.5 * f / self.posterior_precision).to(torch.float32).contiguous()
+        return (value, *_propose_edges_drive(eng, train_loader, int(k), band_bytes, weight=gamma, loss_scale=f))
 
     def _scale_samples(self, eps):  # laplace/baselaplace.py:1912-1919: samples * posterior_scale
         return eps * (1.0 / self.posterior_precision.sqrt()).reshape(1, -1)

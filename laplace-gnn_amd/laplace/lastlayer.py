@@ -34,6 +34,9 @@ class _LastLayerHead:
     def neg_marglik_adj_grad(self, *args, **kwargs):
         raise NotImplementedError("adjacency gradient: posteriors over all weights (KronLaplace, DiagLaplace, FullLaplace)")
 
+    def propose_edges(self, *args, **kwargs):
+        raise NotImplementedError("propose_edges: the diagonal posterior over all weights (DiagLaplace)")
+
     def _ll_variance(self, phi, s, diagonal_output: bool):
         raise NotImplementedError
 

@@ -107,6 +107,10 @@ class SubnetLaplace(ParametricLaplace):
         raise NotImplementedError("adjacency gradient under a subnetwork posterior is not implemented "
                                   "(KronLaplace, DiagLaplace and FullLaplace over all weights offer it)")
 
+    def propose_edges(self, *args, **kwargs):
+        raise NotImplementedError("propose_edges under a subnetwork posterior is not implemented (DiagLaplace over all weights "
+                                  "offers it)")
+
 
 class FullSubnetLaplace(SubnetLaplace, FullLaplace):
     """Dense ``S x S`` posterior precision over the subnetwork (laplace/subnetlaplace.py:175-199).  With the HIP backend only

@@ -318,6 +318,8 @@ class _TrackedAdjacency:
     whether pairs ``(i, i)`` may be tracked (GraphSAGE: the diagonal is a learnable entry) or are dropped (GCN: the forward
     overwrites it)."""
     _track_diagonal = False
+    _train_pair_grad = 0.1  # ``grad_adj_mask`` between two training nodes under ``train_masked_update`` (STEGCN's soft mask)
+    _is_train = None  # bool [N] of ``train_nodes``, kept for ``add_candidates`` (set by ``_train_pair_mask``)
 
     def _track(self, candidates):
         """Registers ``adj_index`` and ``adj`` from the model's ``edge_index`` buffer and the candidate pairs."""
@@ -348,7 +350,43 @@ class _TrackedAdjacency:
         """bool [n]: the tracked pair joins two training nodes (gnn/models/utils.py:19-22)."""
         is_train = torch.zeros(self.num_nodes, dtype=torch.bool)
         is_train[torch.as_tensor(train_nodes).cpu().to(torch.int64)] = True
+        self._is_train = is_train
         return is_train[self.adj_index[0]] & is_train[self.adj_index[1]]
+
+    @torch.no_grad()
+    def add_candidates(self, pairs) -> int:
+        """Track the listed pairs ``[2, K]`` that are not tracked yet, with value 0 (implicit non-edges become explicit ones):
+        ``adj_index`` / ``adj`` grow, existing values and the row-major order are kept, pairs ``(i, i)`` are dropped where the
+        diagonal is not tracked (GCN), a symmetric model tracks both orientations, and ``grad_adj_mask`` is rebuilt under
+        ``train_masked_update``.  Returns the number of entries added.  ``adj`` becomes a NEW ``nn.Parameter`` (without a
+        ``.grad``): the caller rebuilds ``adj_optimizer`` over it.  With ``DiagLaplace.propose_edges`` the loop at scale reads
+
+            la.fit(loader); _, pairs, grad = la.propose_edges(loader, k)
+            model.add_candidates(pairs[:, grad < -threshold / lr_adj]); adj_optimizer = SGD([model.adj], lr_adj)
+            model.adj_backward(la, loader); adj_optimizer.step(); model.apply_adj()"""
+        N, dev = self.num_nodes, self.adj.device
+        pairs = torch.as_tensor(pairs).to(dev, torch.int64).reshape(2, -1)
+        if pairs.numel() and bool(((pairs < 0) | (pairs >= N)).any()):
+            raise ValueError(f"candidate pairs must index nodes in [0, {N})")
+        k = pairs[0] * N + pairs[1]
+        if self.symmetric:
+            k = torch.cat([k, pairs[1] * N + pairs[0]])
+        if not self._track_diagonal:
+            k = k[(k // N) != (k % N)]
+        keys = self._keys().to(dev)
+        k = torch.unique(k)
+        k = k[~torch.isin(k, keys)]
+        if not k.numel():
+            return 0
+        keys, order = torch.sort(torch.cat([keys, k]))
+        vals = torch.cat([self.adj.detach(), torch.zeros(k.numel(), dtype=self.adj.dtype, device=dev)])[order]
+        self.adj_index = torch.stack([keys // N, keys % N])
+        self.adj = nn.Parameter(vals)
+        if self.train_masked_update:
+            is_train = self._is_train.to(dev)
+            both = is_train[self.adj_index[0]] & is_train[self.adj_index[1]]
+            self.grad_adj_mask = torch.where(both, self._train_pair_grad, 1.0).to(vals.dtype)
+        return int(k.numel())
 
     def _keys(self) -> torch.Tensor:
         return self.adj_index[0] * self.num_nodes + self.adj_index[1]
@@ -511,6 +549,7 @@ class STEGraphSAGE(_TrackedAdjacency, GraphSAGE):
     as in the reference (its sampling line is commented out, models.py:174-177).  Plain 2-layer models only: ``sign_grad=True``,
     ``res=True``, a ``norm`` and other depths are refused here, as the adjacency gradient refuses them."""
     _track_diagonal = True
+    _train_pair_grad = 0.0  # the hard mask of ``train_adj_mask``
 
     def __init__(self, in_channels, hidden_channels, out_channels, num_layers, X, init_adj, num_sampled_nodes_per_hop=None,
                  dropout_p: float = 0.5, act="relu", act_kwargs=None, threshold: float = 0.5, train_masked_update: bool = False,
