@@ -503,6 +503,27 @@ LGNN_API int lgnn_jvp_block(lgnn_ctx* h, const int64_t* idx, int64_t M, const fl
 LGNN_API int lgnn_ggn_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* V /* [k, P] */, int64_t k,
                              int flags, float* G /* [k, P] */, float* loss_out, void* stream);
 
+/* ---- exact Hessian of the loss: what it adds to the GGN, as a block product --------------------------------------------
+ * CurvlinopsHessian (laplace/curvature/curvlinops.py:182-187) multiplies with the Hessian of the summed loss by double backward
+ * (curvlinops/hessian.py).  That matrix is H = sum_n J_n^T Lambda_n J_n + R with R = sum_n sum_c r_nc grad^2 f_nc, r_n =
+ * softmax(f_n) - onehot(y_n) (regression: r_n = f_n - y_n; GGN + R is then the interface's factor 0.5 times the Hessian of
+ * MSELoss(sum)).  lgnn_ggn_matmat is the first term; this entry is the second:
+ *   lgnn_hessian_resid_matmat: G [k, P]: G[i, :] += R V[i, :]   (directions and parameters laid out as in lgnn_ggn_matmat)
+ * Plain 1- and 2-layer GCN / GraphSAGE (relu or tanh, no res / norm, both likelihoods) only: every other model is refused with
+ * "exact Hessian: closed-form models only" -- its second derivatives are not in chunks of Jacobian rows.  One layer: R = 0, G is
+ * left untouched.  Two layers, in lgnn_ggn_matmat's notation with D2 = act''(s) (0 for ReLU, -2 tanh(s) D for tanh), S [N, C]
+ * the residual rows added at the batch's nodes (a repeated id adds) and G = P^T S (GraphSAGE: Gs = S, Gn = P^T S against W1 =
+ * [W1a | W1b]), per direction (dW0, db0, dW1, db1):
+ *   dS = in0 [dW0 | db0]^T,  E = D . dS,  T = (G dW1) . D + (G W1) . D2 . dS,
+ *   (RV)_W1 = G^T E,  [(RV)_W0 | (RV)_b0] = T^T in0,  (RV)_b1 = 0
+ * on the batch's needed rows: G as a gather over P^T's rows, G W1 once per call, dS and G dW1 on v_mfma_f32_32x32x2_f32 with
+ * the elementwise step in registers, the two outer products in slabs added in slab order.  Only the residual rows, G, G W1, E, T
+ * ([rows, H] per direction), the slab partials and G reach memory; the directions go in chunks under the workspace limit.  No
+ * float atomics: two calls on the same input return the same bits.  An invalid id or label contributes zero and raises the
+ * sticky flag (lgnn_check_async_errors).  Enqueues only.  With kernel timing enabled: one event pair per chunk.              */
+LGNN_API int lgnn_hessian_resid_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* V /* [k, P] */,
+                                       int64_t k, float* G /* [k, P] */, void* stream);
+
 /* ---- gradient of the negative log marginal likelihood w.r.t. the adjacency ("next" row 8(f)-4) --------------
  * Replaces what autograd does for ``neg_marglik.backward()`` into ``model.adj`` (gnn/marglik_training.py:197-216):
  * back through KronDecomposed.logdet / log_marginal_likelihood (laplace/utils/matrix.py:371-394,

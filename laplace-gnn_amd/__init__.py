@@ -6,7 +6,7 @@ kernels behind a C ABI (``include/laplace_gnn_hip.h``), a ``laplace.curvature``-
 backend class and the thin ``Laplace`` front that drives it.
 """
 from . import _lib  # noqa: F401
-from .curvature import HipCurvatureInterface, HipEF, HipGGN  # noqa: F401
+from .curvature import HipCurvatureInterface, HipEF, HipGGN, HipHessian  # noqa: F401
 from .data import TensorBatchLoader, batches_of_rank, units_of_rank  # noqa: F401
 from .engine import GraphEngine  # noqa: F401
 from .knn import get_knn_graph, knn, knn_candidates, knn_graph  # noqa: F401
@@ -22,7 +22,7 @@ from .models import GCN, STEGCN, GraphSAGE, LoRASTEGCN, STEGraphSAGE  # noqa: F4
 
 __all__ = ["BaseLaplace", "DiagLLLaplace", "DiagLaplace", "DiagSubnetLaplace", "FullLLLaplace", "FullLaplace",
            "FullSubnetLaplace", "FunctionalLaplace", "GCN", "GraphEngine", "GraphSAGE", "HipCurvatureInterface", "HipEF",
-           "HipGGN", "Kron", "KronDecomposed", "KronLLLaplace", "KronLaplace", "Laplace", "LargestMagnitudeSubnetMask",
+           "HipGGN", "HipHessian", "Kron", "KronDecomposed", "KronLLLaplace", "KronLaplace", "Laplace", "LargestMagnitudeSubnetMask",
            "LargestVarianceDiagLaplaceSubnetMask", "LastLayerSubnetMask", "LoRASTEGCN", "LowRankLaplace",
            "ModuleNameSubnetMask", "ParamNameSubnetMask", "ParametricLaplace", "RandomSubnetMask", "STEGCN", "STEGraphSAGE",
            "SubnetLaplace", "SubnetMask", "TensorBatchLoader", "all_reduce_flat_", "batches_of_rank", "get_knn_graph", "knn", "knn_candidates",

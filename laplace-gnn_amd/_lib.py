@@ -106,6 +106,7 @@ SIGNATURES = {
     "lgnn_block_gram": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "lgnn_jvp_block": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "lgnn_ggn_matmat": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "lgnn_hessian_resid_matmat": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     "lgnn_knn": (_i32, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, C.POINTER(_i64), _vp]),
 }
 
@@ -113,6 +114,8 @@ SIGNATURES = {
 # spells out the entries of the one-file module it replaced and no others (tests/test_engine_layout.py)
 BAND_SPARSE, BAND_PREPARE, BAND_BATCH, BAND_FINISH = (f"lgnn_diag_adjgrad_band_{n}"
                                                       for n in ("sparse", "prepare", "batch", "finish"))
+# ... and the exact Hessian's residual product (csrc/hessmat.hip), for engine/matfree.py
+HESSIAN_RESID_MATMAT = "lgnn_hessian_resid_matmat"
 
 _lib = None
 

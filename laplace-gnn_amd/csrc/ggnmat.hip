@@ -39,6 +39,7 @@
 // lgnn_block_gram: A B^T of two blocks of directions through the same NT GEMM -- the Gram and Rayleigh-Ritz matrices of the
 // eigensolver (lowrank.py), bit-reproducible and exactly symmetric for A == B.
 #include "closedform.h"
+#include "ggn_struct.h"
 #include "lgnn_internal.h"
 
 #include <climits>
@@ -238,22 +239,6 @@ __global__ __launch_bounds__(1024) void ggn_bias_kernel(const float* __restrict_
   }
 }
 
-struct TnArgs {
-  const float* A; int64_t a_ld, a_ds;   // A[i * a_ds + t * a_ld + a]: qbar [kc][rcap][Cz] or w [kc][M][C]
-  int64_t acols;                         // its columns
-  int mode;                              // 0: At = A's tile;  1: At[t][h] = D[row_t][h] sum_cz A[t][cz] W1z[cz][h]
-  const float* W1; int64_t ld1, C, H;    // mode 1
-  const float* dact;
-  const float* B; int64_t b_ld, bcols;   // B[row * b_ld + b]: in0 or h
-  const float* in0; int64_t ldk, Fp;     // the bias column in0[row * ldk + Fp] (bias_off >= 0)
-  const int32_t* rows; const int32_t* count;
-  int64_t adim;                          // output rows: H (mode 1) or acols
-  int64_t ooff, old, amod, ashift;       // output element (a, b) at ooff + (a % amod) * old + (a / amod) * ashift + b
-  int64_t bias_off;                      // -1: none; else element a of sum_t At[t][a] bcol[t] at bias_off + a
-  float* part; int64_t P, kc;            // part[(slab * kc + i) * P + ...]
-  int btiles;
-};
-
 // 16 consecutive floats of a row into registers (zero where the row is absent or the column is past `cols`)
 __device__ __forceinline__ void tn_fetch(float (&v)[16], const float* __restrict__ src, int64_t c0, int64_t cols, bool ok) {
 #pragma unroll
@@ -314,7 +299,9 @@ __global__ __launch_bounds__(256) void ggn_tn_kernel(TnArgs g) {
     const int64_t t0 = tile * SBM;
     const bool rok = r_cur >= 0;
     float pb[16];
-    tn_fetch(pb, g.B + int64_t(rok ? r_cur : 0) * g.b_ld, b0 + sk, g.bcols, rok);
+    const float* __restrict__ bp = g.b_listed ? g.B + i * g.b_ds + (rok ? t0 + srow : 0) * g.b_ld
+                                              : g.B + int64_t(rok ? r_cur : 0) * g.b_ld;
+    tn_fetch(pb, bp, b0 + sk, g.bcols, rok);
     const float bc = (rok && bias) ? g.in0[int64_t(r_cur) * g.ldk + g.Fp] : 0.f;
     __syncthreads();  // the previous tile's products have read At / Bt / bcol / rid
     if ((tid & 3) == 0) {
@@ -400,12 +387,6 @@ __global__ __launch_bounds__(256) void ggn_place_kernel(const float* __restrict_
   out[mc * k + i0 + i] = U[t];
 }
 
-// the shapes and operands both structured drivers read (sampled.hip's parameter layout)
-struct StructModel {
-  bool two, sage;
-  int64_t N, Fp, H, C, Cz, ld1, off1, offb, P, rcap;
-};
-
 int struct_model(lgnn_ctx* h, int64_t M, StructModel& m) {
   m.two = h->L == 2; m.sage = h->kind == LGNN_KIND_SAGE;
   m.N = h->N; m.Fp = h->in_dim[0]; m.H = h->dims[1]; m.C = h->dims[h->L];
@@ -448,12 +429,13 @@ int struct_forward(lgnn_ctx* h, const StructModel& m, const int64_t* idx, int64_
 }
 
 // directions per chunk: q, qbar, u, w and the slab partials under half the workspace limit
-constexpr int kMaxSlabs = 16;
 int64_t struct_chunk(const lgnn_ctx* h, const StructModel& m, int64_t M, int64_t k, bool with_transpose) {
   int64_t per_dir = M * m.C * 4 + (m.two ? m.rcap * m.Cz * 4 : 0);
   if (with_transpose) per_dir = 2 * per_dir + int64_t(kMaxSlabs) * m.P * 4;
   return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(k, 32768), h->ws_limit / 2 / per_dir));
 }
+
+}  // namespace
 
 int struct_prepare(lgnn_ctx* h, const int64_t* idx, int64_t M, StructModel& m, hipStream_t s) {
   LGNN_CALL(forward_ensure_aux(h, s));
@@ -462,6 +444,34 @@ int struct_prepare(lgnn_ctx* h, const int64_t* idx, int64_t M, StructModel& m, h
   LGNN_CALL(sampled_needed_rows(h, idx, M, s));
   return 0;
 }
+
+int struct_slabs(const StructModel& m, int64_t kc, int64_t tiles) {
+  return int(std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kMaxSlabs, cdiv(m.rcap, SBM)), cdiv(1024, kc * tiles))));
+}
+
+int launch_ggn_qbar(lgnn_ctx* h, const StructModel& m, const float* w, int64_t M, int64_t kc, float* qbar, hipStream_t s) {
+  const int64_t bound = kc * m.rcap * m.Cz;
+  hipLaunchKernelGGL(ggn_qbar_kernel, dim3(unsigned(std::min<int64_t>(cdiv(bound, 256), int64_t(1) << 20))), dim3(256), 0, s, w,
+                     M, m.C, m.Cz, m.sage ? 1 : 0, h->ws.pos.as<int32_t>(), h->ws.mult.as<int32_t>(), h->PT.rowptr, h->PT.col,
+                     h->PT.val, h->sf.rows.as<int32_t>(), h->sf.count.as<int32_t>(), m.rcap, kc, qbar);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_ggn_tn(const TnArgs& t, int nslab, int64_t atiles, hipStream_t s) {
+  hipLaunchKernelGGL(ggn_tn_kernel, dim3(unsigned(nslab), unsigned(t.kc), unsigned(atiles * t.btiles)), dim3(256), 0, s, t);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_ggn_finish(const float* part, int nslab, int64_t per, float* G, hipStream_t s) {
+  hipLaunchKernelGGL(ggn_finish_kernel, dim3(unsigned(std::min<int64_t>(cdiv(per, 256), 8192))), dim3(256), 0, s, part, nslab,
+                     per, G);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+namespace {
 
 int jvp_block_structured(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* V, int64_t k, float* out, hipStream_t s) {
   StructModel m;

@@ -186,6 +186,9 @@ struct Workspace {
   // ... and of its structured route: q and qbar [kc][|R|][Cz] (u and w [kc][M][C] share ggn_u / ggn_wt), the slab partials
   // [slabs][kc][P]
   DevBuf ggn_q, ggn_qbar, ggn_part;
+  // exact Hessian's residual product (hessmat.hip; it shares ggn_wt for the residual rows and ggn_part): G [|R|][Cz], G W1
+  // [|R|][H], and E, T [kc][|R|][H]
+  DevBuf hess_g, hess_gw1, hess_e, hess_t;
   // per-sample GraphSAGE adjacency gradient (adjgrad_sage.hip): the candidates' rows sorted (int32 [K]) with their positions
   // in the caller's list (int32 [K]; cand_iota: the unsorted positions), the sort's scratch, and the slice of every row
   // (int32 [N + 1])
@@ -204,6 +207,7 @@ struct Workspace {
     f(gp_tab_a); f(gp_tab_b); f(gp_phi_a); f(gp_phi_b); f(gp_g); f(gp_kt); f(gp_s); f(gp_wpair); f(gp_part); f(gp_jac_a);
     f(gp_jac_b); f(cov_phit_a); f(cov_phit_b); f(cov_phis); f(cov_t2); f(cov_va); f(cov_vb); f(cov_add); f(cov_small);
     f(cov_scr); f(ggn_jac); f(ggn_u); f(ggn_wt); f(ggn_tmp); f(ggn_q); f(ggn_qbar); f(ggn_part);
+    f(hess_g); f(hess_gw1); f(hess_e); f(hess_t);
     f(cand_rows); f(cand_ord); f(cand_iota); f(cand_tmp); f(cand_ptr);
   }
 };
@@ -708,6 +712,10 @@ int launch_nt_gemm(lgnn_ctx* h, const NtProblem& p, hipStream_t s);
 int jvp_block(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* V, int64_t k, float* out, hipStream_t s);
 int ggn_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* V, int64_t k, int flags, float* G,
                float* loss_out, hipStream_t s);
+// ---- hessmat.hip ------------------------------------------------------------------------
+// G [k, P] += R V^T, R = sum_n sum_c r_nc grad^2 f_nc: what the exact Hessian of the loss adds to the GGN (closed-form models)
+int hessian_resid_matmat(lgnn_ctx* h, const int64_t* idx, const void* y, int64_t M, const float* V, int64_t k, float* G,
+                         hipStream_t s);
 // ---- sampled.hip ------------------------------------------------------------------------
 // out [S, M, C] = the logits (flags & LGNN_SAMPLED_SOFTMAX: their softmax) of S parameter vectors theta [S, n_params] at idx
 int sampled_forward(lgnn_ctx* h, const int64_t* idx, int64_t M, const float* theta, int64_t S, uint32_t flags, float* out,
@@ -735,6 +743,7 @@ constexpr int SBM = 64, SBH = 64, SBK = 64, SLDT = SBK + 1, SLDH = SBH + 1, SZW 
 //   z_i[r] = (D[r] . (in0[r] [dW0 | db0]^T)) W1^T + h[r] dW1^T
 struct FwdArgs {
   static constexpr bool linearised = true;
+  static constexpr bool hessian = false;
   const float* in0; int64_t ldk;
   const int32_t* rows; const int32_t* count;
   const float* theta; int64_t P;    // the chunk's first direction, floats between directions
@@ -744,6 +753,22 @@ struct FwdArgs {
   float* z; int64_t rcap;           // z[(i * rcap + t) * Cz + c]   (1 layer: u[(i * rcap + m) * H + c])
 };
 int launch_first_layer(const FwdArgs& a, bool two, int64_t ndir, hipStream_t s);
+// Its second-derivative instance (hessmat.hip, 2-layer models): theta is a block of directions, dS = in0 [dW0 | db0]^T, and
+//   E_i[t] = D . dS     T_i[t] = (G[t] dW1) . D + GW1[t] . D2 . dS     (D2 = act''(s): 0 for ReLU, -2 h D for tanh)
+// for the listed rows t; G dW1 runs on the same MFMA step while dS waits in its accumulators.  Nothing but E and T is written.
+struct HessArgs {
+  static constexpr bool linearised = false;
+  static constexpr bool hessian = true;
+  const float* in0; int64_t ldk;
+  const int32_t* rows; const int32_t* count;
+  const float* theta; int64_t P;
+  int64_t Fp, H;
+  const float* dact; const float* h1; int64_t h1_ld; int act;
+  const float* G; const float* GW1;                   // G [rcap, Cz], GW1 [rcap, H], rows listed like `rows`
+  int64_t ld1, off1, C, Cz;                           // dW1 of a direction at theta_i + off1, row stride ld1
+  float* E; float* T; int64_t rcap;                   // [(i * rcap + t) * H + j]
+};
+int launch_first_layer(const HessArgs& a, int64_t ndir, hipStream_t s);
 // ---- fulladj.hip ------------------------------------------------------------------------
 // full posterior: Kn [mc][C][C] = (J_m Gamma) J_m^T (zeroed here, float atomics) and R [mc * C, P] = 2 Lambda_m (J_m Gamma) of a
 // chunk's Jacobian rows J [mc * C, P]; Lambda_m from the softmax of logits [N, C] at idx[m]; C <= 127

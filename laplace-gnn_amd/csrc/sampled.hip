@@ -79,6 +79,7 @@ __global__ void sampled_batch_rows_kernel(const int64_t* __restrict__ idx, int64
 
 struct HiddenArgs {
   static constexpr bool linearised = false;
+  static constexpr bool hessian = false;
   const float* in0; int64_t ldk;
   const int32_t* rows; const int32_t* count;
   const float* theta; int64_t P;   // the chunk's first sample, floats between samples
@@ -91,15 +92,19 @@ struct HiddenArgs {
 // (b).  grid: (workers over the row tiles, samples of the chunk, windows of SZW columns of z).  Two argument structs, one
 // text: HiddenArgs writes act(.) into the hidden tile and multiplies it with the sample's own W1_s; FwdArgs (the GGN's
 // forward product, ggnmat.hip) writes D . (.) instead, multiplies it with the bound W1, and then runs h dW1^T over the same
-// accumulators.
+// accumulators.  HessArgs (the exact Hessian's residual product, hessmat.hip) keeps the first product in its accumulators, runs
+// G dW1 for the same 64 x 64 tile on a second one, and writes E and T from registers: no hidden tile, no z.
+// (The HessArgs instance asks for two waves per SIMD, the forward instances' occupancy: left alone it takes 251 + 16 registers.)
 template <class Args, bool ONE>
-__global__ __launch_bounds__(256) void first_layer_kernel(Args g) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Args::hessian ? 2 : 1))) void first_layer_kernel(Args g) {
   constexpr bool LIN = Args::linearised;
+  constexpr bool HESS = Args::hessian;
+  static_assert(!(HESS && ONE), "one-layer models have no second derivative");
   // As / Bs (the first product's K stage) and Ws (W1's tile) are never live at the same time: one region
   __shared__ float stage[SZW * SLDH];
   __shared__ float Hs[SBM * SLDH];
   __shared__ float bcol[SBM];
-  __shared__ int rid[LIN && !ONE ? SBM : 1];  // LIN: the tile rows' node ids, for D and h
+  __shared__ int rid[(LIN || HESS) && !ONE ? SBM : 1];  // LIN / HESS: the tile rows' node ids, for D and h
   float* As = stage;
   float* Bs = stage + SBM * SLDT;
   float* Ws = stage;
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(256) void first_layer_kernel(Args g) {
     // what the bias is multiplied with: rowsum(P) (GCN) or 1 (GraphSAGE); 0 for padding rows and invalid ids (a zero row)
     if ((tid & 3) == 0) {
       bcol[srow] = arow < 0 ? 0.f : ap[g.Fp];
-      if constexpr (LIN && !ONE) rid[srow] = int(arow);
+      if constexpr ((LIN || HESS) && !ONE) rid[srow] = int(arow);
     }
     f32x16 zacc[2];
 #pragma unroll
@@ -165,7 +170,44 @@ __global__ __launch_bounds__(256) void first_layer_kernel(Args g) {
       // bias in registers: this lane's column of the tile, the rows' bias columns from LDS
       const int64_t jb = j0 + wc * 32 + l31;
       const float bias = jb < g.H ? th[g.H * g.Fp + jb] : 0.f;
-      if constexpr (ONE) {
+      if constexpr (HESS) {
+        // gd = G[t0 .. t0 + 64) dW1z[:, j0 .. j0 + 64): the class columns in chunks of 64 through the K stage's two tiles
+        f32x16 gd;
+        acc_zero(gd);
+        for (int64_t cz0 = 0; cz0 < g.Cz; cz0 += SBK) {
+          __syncthreads();  // every wave has read the stage before
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int64_t c = cz0 + sk + e;
+            As[srow * SLDT + sk + e] = (arow >= 0 && c < g.Cz) ? g.G[(t0 + srow) * g.Cz + c] : 0.f;
+          }
+#pragma unroll 1
+          for (int cz = wave; cz < SBK; cz += 4) {  // Bs[h][cz] = dW1z[cz0 + cz][j0 + h], lanes along h
+            const int64_t c = cz0 + cz, hh = j0 + lane;
+            const int64_t half = c >= g.C ? 1 : 0;  // (Cz <= 2 C: no division)
+            float v = 0.f;
+            if (c < g.Cz && hh < g.H) v = th[g.off1 + (c - half * g.C) * g.ld1 + half * g.H + hh];
+            Bs[lane * SLDT + cz] = v;
+          }
+          __syncthreads();
+          tile_nt_step<SBK, SLDT>(As, wr * 32, Bs, wc * 32, lane, gd);
+        }
+        const bool curved = g.act != LGNN_ACT_RELU;  // (uniform: the ReLU run reads neither h nor G W1)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = acc_row(wr * 32, lane, r);
+          const int64_t t = t0 + row;
+          const int rr = rid[row];
+          if (t >= cnt || rr < 0 || jb >= g.H) continue;
+          const float ds = fmaf(bcol[row], bias, acc[r]);
+          const float d = g.dact[int64_t(rr) * g.H + jb];
+          float tv = gd[r] * d;
+          if (curved) tv = fmaf(g.GW1[t * g.H + jb] * (-2.f * g.h1[int64_t(rr) * g.h1_ld + jb] * d), ds, tv);
+          const int64_t o = (int64_t(blockIdx.y) * g.rcap + t) * g.H + jb;
+          g.E[o] = d * ds;
+          g.T[o] = tv;
+        }
+      } else if constexpr (ONE) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int row = acc_row(wr * 32, lane, r);
@@ -216,7 +258,7 @@ __global__ __launch_bounds__(256) void first_layer_kernel(Args g) {
         // (the next tile of the hidden width starts with a barrier before it writes the regions again)
       }
     }
-    if constexpr (!ONE) {
+    if constexpr (!ONE && !HESS) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int64_t c = zw0 + (wc + 2 * i) * 32 + l31;
@@ -348,6 +390,13 @@ int sampled_needed_rows(lgnn_ctx* h, const int64_t* idx, int64_t M, hipStream_t 
 }
 
 int launch_first_layer(const FwdArgs& a, bool two, int64_t ndir, hipStream_t s) { return launch_first_layer_t(a, two, ndir, s); }
+
+int launch_first_layer(const HessArgs& a, int64_t ndir, hipStream_t s) {
+  const dim3 grid(unsigned(std::min<int64_t>(cdiv(a.rcap, SBM), 512)), unsigned(ndir), 1u);
+  hipLaunchKernelGGL((first_layer_kernel<HessArgs, false>), grid, dim3(256), 0, s, a);
+  LGNN_HIP_CHECK(hipGetLastError());
+  return 0;
+}
 
 int launch_sampled_gather(const GatherArgs& g, hipStream_t s) {
   LGNN_REQUIRE(cdiv(g.ns * g.M, 4) < (int64_t(1) << 31), "too many (sample, node) pairs per chunk");

@@ -473,6 +473,99 @@ class HipGGN(HipCurvatureInterface):
         return res.eigenvectors, res.eigenvalues, state["loss"]
 
 
+class HipHessian(HipCurvatureInterface):
+    """Exact Hessian of the loss; the counterpart of ``CurvlinopsHessian`` (laplace/curvature/curvlinops.py:182-187, which
+    builds ``full`` from curvlinops' HessianLinearOperator): ``H = sum_n J_n^T Lambda_n J_n + R``, the GGN of ``HipGGN`` plus
+    the residual term ``R = sum_n sum_c r_nc grad^2 f_nc`` of ``lgnn_hessian_resid_matmat`` (csrc/hessmat.hip).  Plain 1- and
+    2-layer GCN / GraphSAGE; the library refuses the others.  The matrix is indefinite away from a minimum of the loss.
+    Like the reference's class it has ``full`` only -- no ``kron``, no ``diag``; ``jacobians``, ``gradients`` and the predictive
+    entries are the interface's."""
+
+    def __init__(self, model, likelihood, last_layer: bool = False, subnetwork_indices=None, dict_key_x: str = "input_ids",
+                 dict_key_y: str = "labels", stochastic: bool = False, **kwargs):
+        if last_layer:
+            raise NotImplementedError("HipHessian with last_layer=True is not implemented: the last layer is linear in its "
+                                      "weights, so its exact Hessian is the GGN -- use HipGGN")
+        if stochastic:
+            raise NotImplementedError("HipHessian with stochastic=True is not implemented: the exact Hessian has no "
+                                      "Monte-Carlo form")
+        super().__init__(model, likelihood, False, subnetwork_indices, dict_key_x, dict_key_y, stochastic=False, **kwargs)
+
+    def _refuse_subnetwork(self):
+        raise NotImplementedError("subnetwork_indices with the exact Hessian (HipHessian) is not implemented: HipGGN only")
+
+    def kron(self, *args, **kwargs):
+        raise NotImplementedError("HipHessian has no kron: the exact Hessian has no Kronecker form, and the reference's "
+                                  "CurvlinopsHessian has none either (full only)")
+
+    def diag(self, *args, **kwargs):
+        raise NotImplementedError("HipHessian has no diag: the reference's CurvlinopsHessian has none either (full only)")
+
+    # The in-place routes of the front (KronLaplace asks for ``_kron_fisher_type`` before it calls ``kron_accumulate_``) and the
+    # GGN-only in-place entries: refused like ``kron`` / ``diag``.  CurvlinopsHessian._kron_fisher_type raises likewise
+    # (laplace/curvature/curvlinops.py:38-40).
+    @property
+    def _kron_fisher_type(self) -> str:
+        raise NotImplementedError("HipHessian has no kron (no Kronecker form of the exact Hessian; the reference's "
+                                  "CurvlinopsHessian has none either): hessian_structure='full' only")
+
+    def kron_accumulate_(self, *args, **kwargs):
+        raise NotImplementedError("HipHessian has no kron_accumulate_: the factors are the GGN's -- HipGGN only")
+
+    def diag_accumulate_(self, *args, **kwargs):
+        raise NotImplementedError("HipHessian has no diag_accumulate_: the diagonal is the GGN's -- HipGGN only")
+
+    def full_accumulate_(self, *args, **kwargs):
+        raise NotImplementedError("HipHessian has no full_accumulate_: the in-place entry is the last-layer GGN's -- HipGGN only")
+
+    def ggn_matmat(self, *args, **kwargs):
+        raise NotImplementedError("ggn_matmat is a product with the GGN: HipGGN only (HipHessian offers hessian_matmat)")
+
+    def eig_lowrank(self, *args, **kwargs):
+        raise NotImplementedError("eig_lowrank is not implemented for HipHessian: the block iteration (lowrank.py) assumes a "
+                                  "positive semi-definite operator, the exact Hessian is indefinite -- HipGGN only")
+
+    def hessian_matmat(self, loader_or_batches, V: torch.Tensor):
+        """``(V @ H [k, P], loss)`` for the exact Hessian ``H`` of all batches ``(X, y)`` of a loader (or any iterable of them),
+        never formed: per batch the GGN product and then the residual product into the same block.  Loss and H carry ``factor``
+        the way ``full`` applies it."""
+        eng = self.engine
+        eng.set_likelihood(self.likelihood)
+        V = V.detach().to(eng.device, torch.float32).contiguous()
+        G = torch.zeros_like(V)
+        loss = torch.zeros(1, dtype=torch.float32, device=eng.device)
+        for X, y in loader_or_batches:
+            X, y = X.to(eng.device), y.to(eng.device)
+            eng.ggn_matmat_(G, loss, X, y, V)
+            eng.hessian_resid_matmat_(G, X, y, V)
+        if self.likelihood != "regression" and self.factor != 1.0:
+            G = self.factor * G
+        return G, self.factor * loss[0]
+
+    RESID_BLOCK = 256  # identity directions per residual product in ``full`` (the library chunks them under the workspace limit)
+
+    def full(self, x: torch.Tensor, y: torch.Tensor, **kwargs: Any):
+        """``(factor * loss, H [P, P])``: the GGN of ``lgnn_full_accumulate`` plus the residual product on identity blocks of
+        ``RESID_BLOCK`` directions, whose rows go straight into ``H``.  Not symmetrised (the reference does not).  ``factor`` is
+        applied as ``hessian_matmat`` applies it.  Regression: ``sum J^T J + R`` is ``factor`` times the Hessian of
+        ``MSELoss(sum)``, what CurvlinopsInterface.full returns as ``self.factor * H``."""
+        loss, H = self._full_all_weights(x, y)
+        eng = self.engine
+        P, kb = eng.n_params, int(self.RESID_BLOCK)
+        scale = 1.0 if self.likelihood == "regression" else self.factor  # (what ``_full_all_weights`` put on the GGN)
+        for i0 in range(0, P, kb):
+            k = min(kb, P - i0)
+            V = torch.zeros(k, P, dtype=torch.float32, device=eng.device)
+            V[:, i0:i0 + k].fill_diagonal_(1.0)
+            if scale == 1.0:
+                eng.hessian_resid_matmat_(H[i0:i0 + k], x, y, V)
+            else:
+                R = torch.zeros_like(V)
+                eng.hessian_resid_matmat_(R, x, y, V)
+                H[i0:i0 + k] += scale * R
+        return loss, H
+
+
 class HipEF(HipCurvatureInterface):
     """Empirical Fisher backend; the counterpart of ``CurvlinopsEF`` / ``EFInterface`` (laplace/curvature/curvlinops.py:
     170-179, laplace/curvature/curvature.py:435-504): KFAC with FisherType.EMPIRICAL, ``diag = factor * sum_n G_n^2``,

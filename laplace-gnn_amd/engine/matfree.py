@@ -1,11 +1,13 @@
 """The matrix-free entries of ``GraphEngine``: products with the Jacobian that never write it where the model has a closed
 form.  Behind them: csrc/gpkernel.hip (``gp_kernel``, ``gp_jvp``), ggnmat.hip (``jvp_block``, ``block_gram``,
-``ggn_matmat_``), predictive.hip (``glm_variance*``), glmcov.hip (``glm_covariance``) and sampled.hip (``sampled_forward``)."""
+``ggn_matmat_``), hessmat.hip (``hessian_resid_matmat_``), predictive.hip (``glm_variance*``), glmcov.hip (``glm_covariance``)
+and sampled.hip (``sampled_forward``)."""
 from __future__ import annotations
 
 import torch
 
 from .. import _lib
+from .._lib import HESSIAN_RESID_MATMAT
 from ._marshal import _dev_ptr, _opt_ptr, _ptrs
 
 _f32 = torch.float32
@@ -111,6 +113,19 @@ class MatrixFreeEntries:
         y, yp = self._labels(y, M)
         self._call("lgnn_ggn_matmat", ip, yp, M, V.data_ptr(), V.shape[0], _lib.GGN_FROM_JACOBIANS if from_jacobians else 0,
                    _dev_ptr(G, _f32, "G"), loss_buf.data_ptr())
+
+    def hessian_resid_matmat_(self, G: torch.Tensor, idx, y, V: torch.Tensor):
+        """``G[i, :] += R V[i, :]`` with ``R = sum_n sum_c r_nc grad^2 f_nc`` (r = softmax(f) - onehot(y); regression f - y): what
+        the exact Hessian of the loss adds to the GGN (csrc/hessmat.hip).  Plain 1- and 2-layer models; the library refuses
+        the others.  It opens no batch of its own: it runs right after ``ggn_matmat_`` on the same batch, which has
+        synchronised the parameter versions, and marshals ``idx`` / ``y`` itself."""
+        V = self._directions(V)
+        if tuple(G.shape) != tuple(V.shape) or not G.is_contiguous():
+            raise ValueError(f"G must be contiguous [{V.shape[0]}, {V.shape[1]}], got {tuple(G.shape)}")
+        idx = idx.contiguous()
+        y, yp = self._labels(y, idx.shape[0])
+        self._call(HESSIAN_RESID_MATMAT, _dev_ptr(idx, torch.int64, "idx"), yp, idx.shape[0], V.data_ptr(), V.shape[0],
+                   _dev_ptr(G, _f32, "G"))
 
     # -- matrix-free GLM predictive (csrc/predictive.hip) ------------------------------------------------------------
     def glm_variance(self, idx: torch.Tensor, S0, S1, kappa, QA0=None, QB0=None, QA1=None, QB1sq=None, out_map=None):

@@ -4,6 +4,7 @@ from torch import nn
 from torch.distributions.multivariate_normal import _precision_to_scale_tril
 
 from ..adjgrad import _adjgrad_drive, _adjgrad_prelude
+from ..curvature import HipHessian
 from .fit import Accumulator, ParametricLaplace
 
 
@@ -77,7 +78,11 @@ class FullLaplace(ParametricLaplace):
         ``DiagLaplace.neg_marglik_adj_grad``.  1-layer GCN, 2-layer GCN (STEGCN, also with res / norm) and plain 2-layer GraphSAGE,
         classification.  ``d(1/2 logdet(f H + Delta))/dH = Gamma = (f / 2) (f H + Delta)^-1`` is held fixed; it is built once per
         call in fp64 (as ``posterior_scale``) and handed to the device in fp32.  The GGN is a sum over samples, so the ranks of a
-        job split every batch by samples.  ``dense=True`` (LoRA) stays on the Kronecker and diagonal posteriors."""
+        job split every batch by samples.  ``dense=True`` (LoRA) stays on the Kronecker and diagonal posteriors.  The gradient
+        differentiates the GGN: a fit on the exact Hessian (``backend=HipHessian``) is refused."""
+        if isinstance(self._backend_cls, type) and issubclass(self._backend_cls, HipHessian):
+            raise NotImplementedError("neg_marglik_adj_grad differentiates the GGN; a posterior fitted with backend=HipHessian "
+                                      "(the exact Hessian) has no adjacency gradient: fit with HipGGN")
         eng = _adjgrad_prelude(self, "FullLaplace", "the full posterior", self.H is not None and bool(self.n_data),
                                prior_precision, candidates, dense, batch="full_adjgrad_batch", dense_offered=False, depth=True)
         value = -self.log_marginal_likelihood()
